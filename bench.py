@@ -13,9 +13,17 @@ and decodes its own 32 rows; there is no data-path collective (SURVEY.md section
 
 Prints ONE JSON line on rank 0. `roofline` describes the hipGraph-captured frame step (the unit the
 AR loop launches): algorithmic bytes = distinct weight bytes + KV bytes read, over the average
-frame-step duration measured with HIP events on the engine's stream. `cpu_baseline` times the oracle
-(oracle/, a C restatement -- kind "port") on the host cores for a bounded sample of the same
-workload (rank 0, N = 1 only).
+frame-step duration measured with HIP events on the engine's stream.
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds the measurements
+that take runs of their own, after the timed region: `streaming` (one batch with the waveform streamed
+while tokens are generated) and `cpu_baseline` (the oracle -- oracle/, a C restatement, kind "port" --
+on the host cores for a bounded sample of the same workload); rank 0, N = 1 only.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as float32 .npy files
+(rank 0's rows): codes [rows, frames, 16], audio [rows, samples] (24 kHz PCM), and per row the
+frame count, sample count and status. Ragged rows are padded (codes -1, audio 0). When all of it
+exceeds DUMP_BUDGET_BYTES, audio keeps a fixed seeded sample of rows, named in audio_rows.npy.
 """
 from __future__ import annotations
 
@@ -34,6 +42,7 @@ sys.path.insert(0, os.path.join(ROOT, "swift-qwen3-tts_amd"))
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA peak (16x the 157.3 TFLOP/s fp32 matrix rate, MI355X_MICROARCH.md)
 FRAME_SECONDS = 0.08   # 1 codec frame = 1920 samples @ 24 kHz
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files together
 
 
 def kernel_sources_sha16() -> str:
@@ -147,6 +156,32 @@ def cpu_baseline(ckpt: str, preset: str, n_text: int, n_instruct: int, frames: i
                       f"AR {t1 - t0:.1f}s + codec {t2 - t1:.1f}s; MLX-CPU reference unavailable offline"}
 
 
+def dump_outputs(out_dir: str, results) -> None:
+    """The arrays a caller of generate_batch / generate_batch_end receives, as float32 .npy files (module docstring)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(results)
+    frames = np.array([r.codes.shape[0] for r in results], np.int64)
+    audios = [np.asarray(getattr(r, "audio", np.zeros(0, np.float32)), np.float32) for r in results]
+    samples = np.array([a.size for a in audios], np.int64)
+    codes = np.full((n, int(frames.max(initial=0)), 16), -1.0, np.float32)
+    for i, r in enumerate(results):
+        codes[i, :frames[i]] = r.codes
+    small = {"codes": codes, "frames": frames.astype(np.float32), "samples": samples.astype(np.float32),
+             "status": np.array([getattr(r, "status", 0) for r in results], np.float32)}
+    row_bytes = 4 * int(samples.max(initial=0))
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in small.values()) - 4 * n - 1024  # 1024: the .npy headers
+    rows = np.arange(n)
+    if row_bytes and n * row_bytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(n, max(room // row_bytes, 0), replace=False))
+    audio = np.zeros((rows.size, row_bytes // 4), np.float32)
+    for j, i in enumerate(rows):
+        audio[j, :samples[i]] = audios[i]
+    small["audio"] = audio
+    small["audio_rows"] = rows.astype(np.float32)
+    for name, a in small.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -163,9 +198,15 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay (profiling)")
     ap.add_argument("--streams", type=int, default=0, help="lanes per GPU (0 = engine default)")
     ap.add_argument("--no-pipeline", action="store_true", help="one batch at a time (no codec / AR overlap between steps)")
-    ap.add_argument("--no-streaming", action="store_true", help="skip the streamed-audio batch behind the timed region (profiling runs)")
+    ap.add_argument("--no-streaming", action="store_true", help="with --full: skip the streamed-audio batch behind the timed region (profiling runs)")
     ap.add_argument("--codec-cus", type=int, default=0, help="q3tts_load_opts.codec_overlap_cus (0 = engine default, -1 = no mask)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need, after the timed region: streaming and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's codes and audio (rank 0's rows) to DIR/*.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -292,9 +333,11 @@ def main():
     frame_steps = 0
     kv_bytes = 0
     frames_done = 0
+    last = None  # what the last timed step returned (--dump-outputs)
 
     def account(res):
-        nonlocal dec_ms, pre_ms, codec_ms, fe_ms, frame_steps, kv_bytes, frames_done, launches
+        nonlocal dec_ms, pre_ms, codec_ms, fe_ms, frame_steps, kv_bytes, frames_done, launches, last
+        last = res
         tm = model.last_timing()  # timing of the job that just ended
         launches = max(launches, getattr(tm, "launches_per_frame_step", 0))
         pre_ms += tm.prefill_ms
@@ -337,6 +380,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     value = frames_done / elapsed
     # memory-side bytes per frame step from the PMC passes committed under profiles/ (default workload only); the file
     # names the kernel sources it was measured on, and a figure from other sources is not reported
@@ -424,7 +469,7 @@ def main():
                            "narrow_stages_hbm": codec_hbm, "hbm_peak_gbs": HBM_PEAK_GBS,
                            "ms": codec_solo_ms, "measured": "one batch alone (last warm-up step)" if solo else "overlapped steps"},
     }
-    if world == 1 and not clone and not args.no_streaming and not dry:
+    if args.full and world == 1 and not clone and not args.no_streaming and not dry:
         # row f1, outside the timed region: one batch with the waveform streamed while the tokens are generated (16-frame
         # chunks, 32 frames of left context, 4 of look-ahead) -- when does the first audio reach the host?
         sk = dict(gen_kw, audio_chunk_frames=16, audio_window_frames=32, audio_lookahead_frames=4)
@@ -437,7 +482,7 @@ def main():
                             "one_shot_latency_ms": latency_ms, "chunk_frames": 16, "window_frames": 32, "lookahead_frames": 4,
                             "note": "time from the request to the first 16 frames (1.28 s) of audio of all rows on the host; "
                                     "the exact (one-shot) mode delivers everything after one_shot_latency_ms"}
-    if world == 1 and not args.no_cpu_baseline and not dry:
+    if args.full and world == 1 and not args.no_cpu_baseline and not dry:
         out["cpu_baseline"] = cpu_baseline(ckpt, args.preset, args.n_text, n_instruct, args.cpu_frames)
     if dist is not None:
         dist.destroy_process_group()

@@ -244,6 +244,25 @@ q3tts_status q3tts_generate_begin(q3tts_model* m, const q3tts_request* reqs, int
                                   q3tts_job** job);
 q3tts_status q3tts_generate_end(q3tts_model* m, q3tts_job* job, q3tts_result* results);
 
+/* Continuous batching (new: the reference has no batches, Qwen3.swift:847-936 generates one utterance at a time). Runs
+ * n_reqs requests (any number >= 1) with at most `slots` rows in flight, 1 <= slots <= max_batch: a slot whose row finishes
+ * (EOS or its max_tokens cap) takes the next request in index order, so rows of different lengths do not wait for the
+ * longest one of a batch. results[i] (n_reqs entries, freed with q3tts_result_free) is bit-identical in codes, pcm,
+ * n_frames, n_samples and status to what q3tts_generate returns for reqs[i] with row_base = sampling->row_base + i: request
+ * i draws from random stream (seed, row_base + i), whatever slot or lane serves it.
+ * Events, per request with request_index = i: TOKEN*, INFO, AUDIO. A request's INFO and AUDIO fire as soon as its audio is
+ * decoded, which can be before later requests have started; the interleaving across requests is unspecified.
+ * Every request is checked before any GPU work (prompt length, max_tokens <= max_frames, speaker, route, RoPE range). Refused
+ * with Q3TTS_ERR_INVALID_INPUT, the engine staying usable: slots outside 1..max_batch, a voice-clone request (ref_audio !=
+ * NULL), audio_chunk_frames > 0, a q3tts_generate_begin job outstanding on the handle. force_frames keeps its meaning.
+ * A request whose first token is EOS fails alone (GENERATION_FAILED), as does a row whose decode leaves the fp16 range even
+ * on the fp32 re-decode (AUDIO_DECODING_FAILED); the others are delivered.
+ * q3tts_last_timing afterwards: frame_steps = frame-step replays, prefill_ms = sum of all admission prefills, codec_ms = sum
+ * of the decode batches, rows = n_reqs. A request's q3tts_gen_info times run from its admission to its retirement (the burst
+ * boundary at which its finished row was seen), not over the whole call. */
+q3tts_status q3tts_generate_queued(q3tts_model* m, const q3tts_request* reqs, int32_t n_reqs, int32_t slots,
+                                   const q3tts_sampling* sampling, q3tts_event_cb cb, void* user, q3tts_result* results);
+
 /* Qwen3TTSSpeechTokenizer.decode (Models/SpeechTokenizer.swift:823-836): codes
  * [batch][max_frames][num_code_groups] -> pcm [batch][max_frames*1920] (caller-allocated),
  * audio_lengths[batch] = count(code0 > 0) * 1920. n_frames[b] <= max_frames are the valid rows. Every code of a valid row is

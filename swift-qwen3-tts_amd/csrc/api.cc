@@ -218,6 +218,21 @@ q3tts_status q3tts_generate(q3tts_model* m, const q3tts_request* reqs, int32_t n
     });
 }
 
+q3tts_status q3tts_generate_queued(q3tts_model* m, const q3tts_request* reqs, int32_t n_reqs, int32_t slots,
+                                   const q3tts_sampling* sampling, q3tts_event_cb cb, void* user, q3tts_result* results) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && reqs && results, 3, "Invalid input: null argument");
+        q3tts_sampling sp;
+        if (sampling) sp = *sampling;
+        else q3tts_default_sampling(&sp);
+        std::memset(results, 0, sizeof(q3tts_result) * size_t(n_reqs > 0 ? n_reqs : 0));
+        m->eng->generate_queued(reqs, n_reqs, slots, sp, cb, user, results);
+        for (int i = 0; i < n_reqs; ++i)
+            if (results[i].status == Q3TTS_ERR_GENERATION_FAILED)
+                m->eng->last_error = "Generation failed: No tokens generated";  // Qwen3.swift:940
+    });
+}
+
 struct q3tts_job {
     int slot = -1;
     int n = 0;

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <deque>
 #include <thread>
 
 #include "codec.h"
@@ -114,6 +115,8 @@ Engine::~Engine() {
         for (int32_t* p : J.st_codes) std::free(p);
     }
     for (auto& g : graphs_) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : qgraphs_) (void)hipGraphExecDestroy(g.second);
+    if (qws_) (void)hipFree(qws_);
     codec_.reset();
     fe_.reset();
     for (auto& L : fe_lanes_) {
@@ -432,6 +435,7 @@ void Engine::enqueue_frame_body(int B, const DebugOpts* dbg) {
         sa.next_x = m_->has_cp_proj ? cp_x_ : cp_x2_; sa.next_ss = m_->has_cp_proj ? nullptr : cp_ss2_;
     }
     sa.logits_dump = (dbg && dbg->talker_logits) ? tl_dump_ : nullptr; sa.dump_ld = V; sa.dump_off = 0;
+    sa.row_key = frame_row_key_;
     if (pair) {
         other([&] { launch_sampler(sa, st_); });
         int ss_count = 1;
@@ -490,6 +494,7 @@ void Engine::enqueue_frame_body(int B, const DebugOpts* dbg) {
             sc.emb_ss = m_->cp_pss[size_t(i)]; sc.nss = CH / 16; sc.next_ss = cp_.ss_a; sc.next_ss_ld = Mp_;
         }
         sc.logits_dump = (dbg && dbg->cp_logits) ? cl_dump_ : nullptr; sc.dump_ld = (groups - 1) * Vc; sc.dump_off = i * Vc;
+        sc.row_key = frame_row_key_;
         if (i == groups - 2 && Vc <= 2048) {  // the frame's last draw carries its row's end-of-frame job (Qwen3.swift:919-935; row_jobs.h)
             other([&] { launch_sampler_with_frame_end(sc, fe, st_); });
             fe_done = true;
@@ -640,8 +645,10 @@ void Engine::enqueue_frame(int B, const DebugOpts* dbg) {
 }
 
 hipGraphExec_t Engine::frame_graph(int B) {
-    auto it = graphs_.find(B);
-    if (it != graphs_.end()) return it->second;
+    // a queued frame step keys its samplers on row_key_ (frame_row_key_ set): a capture of its own
+    std::map<int, hipGraphExec_t>& graphs = frame_row_key_ ? qgraphs_ : graphs_;
+    auto it = graphs.find(B);
+    if (it != graphs.end()) return it->second;
     hipGraph_t g = nullptr;
     Q3_HIP(hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal));
     try {
@@ -655,7 +662,7 @@ hipGraphExec_t Engine::frame_graph(int B) {
     hipGraphExec_t ge = nullptr;
     Q3_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
     Q3_HIP(hipGraphDestroy(g));
-    graphs_[B] = ge;
+    graphs[B] = ge;
     return ge;
 }
 
@@ -772,7 +779,8 @@ void Engine::project_rows(const std::vector<int32_t>& ids, int rows) {
     }
 }
 
-void Engine::assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vector<int>& n_prompt, std::vector<int>& n_trailing) {
+void Engine::assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vector<int>& n_prompt, std::vector<int>& n_trailing,
+                              const std::vector<int>* trailing_rows) {
     const ModelConfig& cfg = m_->cfg;
     const TalkerConfig& t = cfg.talker;
     const int H = t.hidden_size;
@@ -797,6 +805,7 @@ void Engine::assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vec
     n_trailing.assign(size_t(n), 0);
     for (int b = 0; b < n; ++b) {
         const auto& r = reqs[size_t(b)];
+        const int trow = trailing_rows ? (*trailing_rows)[size_t(b)] : b;
         const int bos = tts_off[size_t(b)], eos = bos + 1, pad = bos + 2;
         std::vector<int> cp_ids;  // codec prefix, Qwen3.swift:322-359 / 527-561
         if (r.language_id < 0) cp_ids = {t.codec_nothink_id, t.codec_think_bos_id, t.codec_think_eos_id};
@@ -827,7 +836,7 @@ void Engine::assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vec
             n_prompt[size_t(b)] = p;
             ta.push_back(pad);  // trailing text is just tts_pad (:579)
             tb.push_back(-1);
-            td.push_back(b * Tcap_);
+            td.push_back(trow * Tcap_);
             n_trailing[size_t(b)] = 1;
             continue;
         }
@@ -842,7 +851,7 @@ void Engine::assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vec
         auto pusht = [&](int a) {
             ta.push_back(a);
             tb.push_back(-1);
-            td.push_back(b * Tcap_ + q);
+            td.push_back(trow * Tcap_ + q);
             ++q;
         };
         if (tl - 5 > 4)  // Qwen3.swift:394-406
@@ -1066,6 +1075,42 @@ void Engine::debug_prepare_inputs(const q3tts_request& req, uint16_t* input_embe
     *n_trailing = nt[0];
 }
 
+// Prefill of n right-aligned prompts: positions 0 .. Pmax-2 through the talker's layers into the pages `block_table` names, then
+// the last position loaded into w.h / w.ss_a (the first frame step consumes it). begin() runs it on the frame step's own
+// activations and arrays; a queued admission on a sub-batch's (run_queued), so that the rows in flight keep theirs.
+void Engine::enqueue_prefill(Stream& w, int n, int Pmax, const int32_t* block_table, int32_t* kv_len, const int32_t* n_prompt,
+                             uint8_t* active) {
+    const int H = m_->cfg.talker.hidden_size;
+    PrefillLoadArgs pl{};
+    pl.prompt = prompt_; pl.n_prompt = n_prompt; pl.Pmax = Pcap_; pl.H = H; pl.B = n; pl.h = w.h; pl.hMB = Mp_ / 16;
+    pl.ss_out = w.ss_a; pl.active = active;
+    // prompt_ rows are laid out with stride Pcap_; right alignment is relative to the longest prompt.
+    // Positions 0 .. Pmax-2 go through the decode kernels C at a time (C * n <= Mp_ activation rows: the GEMMs stream
+    // the weights once per chunk instead of once per position); rows whose prompt is shorter start inside a chunk.
+    const int P1 = Pmax - 1;  // positions before the one the first frame step consumes
+    int C = std::max(1, std::min(16, Mp_ / n));
+    const int S = (P1 + C - 1) / C;
+    for (int s = 0; s < S; ++s) {
+        // element p of row b in chunk s is prompt position r = s*C - S*C + (n_prompt[b] - 1) + p
+        const int r_base = s * C - S * C - 1;
+        if (C == 1) {
+            pl.step = s + (Pcap_ - Pmax);
+            launch_prefill_load(pl, st_);
+            enqueue_layers(m_->talker, w, n, kpool_, vpool_, kv_layer_stride_, block_table, max_pages_, kv_len, active, 1, -1, 1, nullptr, 0);
+            launch_advance_len(kv_len, active, n, st_);
+        } else {
+            PrefillLoadArgs pc = pl;
+            pc.step = r_base;
+            launch_prefill_chunk_load(pc, C, st_);
+            enqueue_layers(m_->talker, w, n, kpool_, vpool_, kv_layer_stride_, block_table, max_pages_, kv_len, nullptr, 1, -1,
+                           C, n_prompt, r_base);
+            launch_advance_len_chunk(kv_len, n_prompt, r_base, C, n, st_);
+        }
+    }
+    pl.step = (Pmax - 1) + (Pcap_ - Pmax);  // the last prompt position: consumed by the first frame step
+    launch_prefill_load(pl, st_);
+}
+
 // ------------------------------------------------------------------------------------------------
 // generate
 // ------------------------------------------------------------------------------------------------
@@ -1087,7 +1132,7 @@ hipStream_t Engine::codec_stream(bool overlapped) {
 int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const DebugOpts* dbg,
                   bool overlapped) {
     const TalkerConfig& t = m_->cfg.talker;
-    const int H = t.hidden_size, V = t.vocab_size, Vc = t.cp.vocab_size, groups = t.num_code_groups;
+    const int V = t.vocab_size, Vc = t.cp.vocab_size, groups = t.num_code_groups;
     Q3_HIP(hipSetDevice(m_->device));  // lanes run on their own host threads
     Q3_CHECK(n >= 1 && n <= Bm_, 3, "Invalid input: batch size must be between 1 and max_batch");
     Q3_CHECK(groups == 16, 3, "Invalid input: num_code_groups must be 16");
@@ -1169,36 +1214,7 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
 
     // ---- prefill: positions 0 .. Pmax-2 of the right-aligned prompts, then load the last one ----
     Q3_HIP(hipEventRecord(ev_[0], st_));
-    PrefillLoadArgs pl{};
-    pl.prompt = prompt_; pl.n_prompt = n_prompt_; pl.Pmax = Pcap_; pl.H = H; pl.B = n; pl.h = tk_.h; pl.hMB = Mp_ / 16;
-    pl.ss_out = tk_.ss_a; pl.active = active_;
-    // prompt_ rows are laid out with stride Pcap_; right alignment is relative to the longest prompt.
-    // Positions 0 .. Pmax-2 go through the decode kernels C at a time (C * n <= Mp_ activation rows: the GEMMs stream
-    // the weights once per chunk instead of once per position); rows whose prompt is shorter start inside a chunk.
-    {
-        const int P1 = Pmax - 1;  // positions before the one the first frame step consumes
-        int C = std::max(1, std::min(16, Mp_ / n));
-        const int S = (P1 + C - 1) / C;
-        for (int s = 0; s < S; ++s) {
-            // element p of row b in chunk s is prompt position r = s*C - S*C + (n_prompt[b] - 1) + p
-            const int r_base = s * C - S * C - 1;
-            if (C == 1) {
-                pl.step = s + (Pcap_ - Pmax);
-                launch_prefill_load(pl, st_);
-                enqueue_talker_step(n, false);
-                launch_advance_len(kv_len_, active_, n, st_);
-            } else {
-                PrefillLoadArgs pc = pl;
-                pc.step = r_base;
-                launch_prefill_chunk_load(pc, C, st_);
-                enqueue_layers(m_->talker, tk_, n, kpool_, vpool_, kv_layer_stride_, block_table_, max_pages_, kv_len_, nullptr, 1, -1,
-                               C, n_prompt_, r_base);
-                launch_advance_len_chunk(kv_len_, n_prompt_, r_base, C, n, st_);
-            }
-        }
-        pl.step = (Pmax - 1) + (Pcap_ - Pmax);  // the last prompt position: consumed by the first frame step
-        launch_prefill_load(pl, st_);
-    }
+    enqueue_prefill(tk_, n, Pmax, block_table_, kv_len_, n_prompt_, active_);
     Q3_HIP(hipEventRecord(ev_[1], st_));
 
     // ---- streamed decode (row f1): chunks of the waveform leave while the loop below is still producing tokens ----
@@ -1472,6 +1488,8 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     }
     J.t_start = t_start;
     J.t_done = 0;
+    J.req_index.clear();  // (a queued call's decode batches used the slot with request indices of their own)
+    J.row_span.clear();
     J.cb = cb;
     J.user = user;
     J.request_base = request_base;
@@ -1736,13 +1754,17 @@ void Engine::end(int job, q3tts_result* results) {
         J.timing.first_audio_ms = ms;
     }
     timing = J.timing;
-    const double total = (J.t_done > 0 ? J.t_done : now_s()) - J.t_start;
+    const double job_total = (J.t_done > 0 ? J.t_done : now_s()) - J.t_start;
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
+    // a queued decode batch: row b is request req_index[b], timed from its admission to its retirement
+    auto out = [&](int b) -> q3tts_result& { return results[J.req_index.empty() ? b : J.req_index[size_t(b)]]; };
+    auto ev_index = [&](int b) { return J.request_base + (J.req_index.empty() ? b : J.req_index[size_t(b)]); };
     for (int b = 0; b < n; ++b) {
-        q3tts_result& r = results[b];
+        q3tts_result& r = out(b);
         std::memset(&r, 0, sizeof(r));
         const int F = J.frames[size_t(b)];
+        const double total = J.row_span.empty() ? job_total : J.row_span[size_t(b)];
         r.info.prompt_token_count = J.target_tokens[size_t(b)];  // tokens of `text` (Qwen3+Streaming.swift:106)
         r.info.generation_token_count = F;
         r.info.prefill_time = 0;  // hard-coded in the reference (Qwen3+Streaming.swift:112)
@@ -1773,19 +1795,390 @@ void Engine::end(int job, q3tts_result* results) {
         std::unique_lock<std::mutex> lk;
         if (cb_mutex) lk = std::unique_lock<std::mutex>(*cb_mutex);
         for (int b = 0; b < n; ++b) {
-            if (results[b].status != Q3TTS_OK) continue;
+            if (out(b).status != Q3TTS_OK) continue;
             q3tts_event ev{};
             ev.kind = Q3TTS_EVENT_INFO;
-            ev.request_index = J.request_base + b;
-            ev.info = &results[b].info;
+            ev.request_index = ev_index(b);
+            ev.info = &out(b).info;
             J.cb(J.user, &ev);
             ev.kind = Q3TTS_EVENT_AUDIO;
             ev.info = nullptr;
-            ev.pcm = results[b].pcm;
-            ev.n_samples = results[b].n_samples;
+            ev.pcm = out(b).pcm;
+            ev.n_samples = out(b).n_samples;
             J.cb(J.user, &ev);
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// continuous batching (q3tts_generate_queued)
+// ------------------------------------------------------------------------------------------------
+bool Engine::job_outstanding() const {
+    for (const auto& J : jobs_)
+        if (J.busy) return true;
+    return false;
+}
+
+// resolve() plus every limit a request would otherwise hit inside the slot loop, on the host: the lengths are the ones
+// assemble_prompts produces for a request that is not a voice clone (those are refused here)
+ResolvedRequest Engine::check_queued(const q3tts_request& r, const q3tts_sampling& sp) const {
+    const TalkerConfig& t = m_->cfg.talker;
+    Q3_CHECK(r.ref_audio == nullptr, 3, "Invalid input: voice-clone requests (ref_audio) are not supported by q3tts_generate_queued");
+    ResolvedRequest o = resolve(r, sp);
+    Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");  // Qwen3.swift:799-801
+    Q3_CHECK(o.max_frames <= Fcap_, 3, "Invalid input: max_tokens exceeds the configured max_frames");
+    Q3_CHECK(o.language_id < t.vocab_size && o.speaker_token < t.vocab_size, 3, "Invalid input: codec prefix id out of range");
+    const int nc = (o.language_id < 0 ? 3 : 4) + (o.speaker_token >= 0 ? 1 : 0) + 2;  // codec prefix (Qwen3.swift:322-359)
+    const int np = int(o.instruct_ids.size()) + 3 + nc;                                // instruct, role, prefix, first text token
+    Q3_CHECK(np <= Pcap_, 3, "Invalid input: prompt longer than max_prompt");
+    const int tl = int(o.text_ids.size());
+    const int nt = (tl - 5 > 4 ? tl - 9 : 0) + 1;                                      // trailing text + tts_eos (:394-406)
+    Q3_CHECK(nt <= Tcap_, 3, "Invalid input: text longer than max_prompt");
+    Q3_CHECK(np + o.max_frames + 1 <= m_->talker.max_pos, 3, "Invalid input: sequence longer than the RoPE table");
+    return o;
+}
+
+void Engine::ensure_queue_ws() {
+    if (qws_) return;
+    const TalkerConfig& t = m_->cfg.talker;
+    const int H = t.hidden_size, qd = t.num_attention_heads * kHeadDim, kd = t.num_key_value_heads * kHeadDim;
+    uint8_t* base = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        Bump b{base};
+        // the talker's activations of a prefill: tk_'s shapes without the head's logits
+        qk_.ld_qkv = qd + 2 * kd;
+        qk_.ld_act = m_->talker.max_inter_p;
+        qk_.ld_logits = 0;
+        qk_.h = b.take<uint16_t>(size_t(Mp_) * H);
+        qk_.xn = b.take<uint16_t>(size_t(Mp_) * H);
+        qk_.ss_a = b.take<float>(size_t(H / 16) * Mp_);
+        qk_.ss_b = b.take<float>(size_t(H / 16) * Mp_);
+        qk_.qkv = b.take<uint16_t>(size_t(Mp_) * qk_.ld_qkv);
+        qk_.ao = b.take<uint16_t>(size_t(Mp_) * qd);
+        qk_.act = b.take<uint16_t>(size_t(Mp_) * qk_.ld_act);
+        qk_.logits = nullptr;
+        q_bt_ = b.take<int32_t>(size_t(Bm_) * max_pages_);
+        q_kv_len_ = b.take<int32_t>(size_t(Bm_));
+        q_n_prompt_ = b.take<int32_t>(size_t(Bm_));
+        q_desc_ = b.take<AdmitDesc>(size_t(Bm_));
+        row_key_ = b.take<uint32_t>(size_t(Bm_));
+        q_active_ = b.take<uint8_t>(size_t(Bm_));
+        if (!pass) {
+            const size_t bytes = align_up(b.off, 256);
+            Q3_HIP(hipMalloc(reinterpret_cast<void**>(&base), bytes));
+            Q3_HIP(hipMemset(base, 0, bytes));
+        }
+    }
+    qws_ = base;
+}
+
+std::vector<int> Engine::admit(const std::vector<ResolvedRequest>& rr, const std::vector<int>& slots, const std::vector<uint32_t>& keys) {
+    const int k = int(rr.size());
+    std::vector<int> np, nt;
+    assemble_prompts(rr, np, nt, &slots);  // prompt_ rows 0..k-1; trailing text into the slots' rows (synchronises st_)
+    int Pmax = 0;
+    for (int p : np) Pmax = std::max(Pmax, p);
+    // the sub-batch's arrays: block table (its slots' pages), cache lengths 0, prompt lengths, admission descriptors
+    const size_t nbt = size_t(k) * max_pages_;
+    q_host_.assign(nbt + 2 * size_t(k) + 4 * size_t(k), 0);
+    int32_t* hbt = q_host_.data();
+    int32_t* hnp = hbt + nbt + k;
+    AdmitDesc* hd = reinterpret_cast<AdmitDesc*>(hbt + nbt + 2 * size_t(k));
+    for (int j = 0; j < k; ++j) {
+        const int s = slots[size_t(j)];
+        for (int i = 0; i < max_pages_; ++i) hbt[size_t(j) * max_pages_ + i] = s * max_pages_ + i;
+        hnp[j] = np[size_t(j)];
+        hd[j] = AdmitDesc{s, nt[size_t(j)], rr[size_t(j)].max_frames, keys[size_t(j)]};
+    }
+    Q3_HIP(hipMemcpyAsync(q_bt_, hbt, nbt * 4, hipMemcpyHostToDevice, st_));
+    Q3_HIP(hipMemcpyAsync(q_kv_len_, hbt + nbt, size_t(k) * 4, hipMemcpyHostToDevice, st_));
+    Q3_HIP(hipMemcpyAsync(q_n_prompt_, hnp, size_t(k) * 4, hipMemcpyHostToDevice, st_));
+    Q3_HIP(hipMemcpyAsync(q_desc_, hd, size_t(k) * sizeof(AdmitDesc), hipMemcpyHostToDevice, st_));
+    Q3_HIP(hipEventRecord(ev_[0], st_));
+    enqueue_prefill(qk_, k, Pmax, q_bt_, q_kv_len_, q_n_prompt_, q_active_);
+    AdmitArgs a{};
+    a.desc = q_desc_; a.src_h = qk_.h; a.srcMB = Mp_ / 16; a.src_ss = qk_.ss_a; a.src_kv_len = q_kv_len_; a.src_n_prompt = q_n_prompt_;
+    a.h = tk_.h; a.hMB = Mp_ / 16; a.ss = tk_.ss_a;
+    a.H = m_->cfg.talker.hidden_size; a.V = m_->cfg.talker.vocab_size; a.Fmax = Fcap_; a.slots = Bm_;
+    a.kv_len = kv_len_; a.n_prompt = n_prompt_; a.n_trailing = n_trailing_; a.max_frames = max_frames_; a.n_frames = n_frames_;
+    a.cp_len = cp_len_; a.trailing_idx = trailing_idx_; a.cur_codes = cur_codes_; a.codes = codes_; a.row_key = row_key_;
+    a.finished = finished_; a.active = active_; a.seen = seen_;
+    launch_admit_rows(a, k, st_);
+    Q3_HIP(hipEventRecord(ev_[1], st_));
+    return np;
+}
+
+// The slot loop. Slot s owns KV pages [s * max_pages_, (s + 1) * max_pages_) for the whole call. Every burst boundary:
+//   retire   rows whose finished flag is up: codes copied to the host, slot freed; their decode waits for the codec stream
+//   admit    free slots take the next requests (in request order), prefilled as a sub-batch of their own (admit())
+//   burst    frame steps of all `slots` rows, ending no later than the frame at which the first running row reaches its cap
+// and, while the burst runs, a decode batch that has landed is delivered (INFO / AUDIO, results) and, the codec stream being
+// idle, every retired row waiting is decoded in one batch beside the frame loop (the confined stream of a pipelined job).
+void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_event_cb cb, void* user) {
+    const TalkerConfig& t = m_->cfg.talker;
+    Q3_HIP(hipSetDevice(m_->device));
+    Q3_CHECK(S >= 1 && S <= Bm_, 3, "Invalid input: slots must be between 1 and max_batch");
+    Q3_CHECK(!job_outstanding(), 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
+    ensure_queue_ws();
+    const double t_call = now_s();
+    // every slot starts empty: finished, inactive, an empty cache in its own pages
+    std::vector<int32_t> bt(size_t(S) * max_pages_);
+    for (size_t i = 0; i < bt.size(); ++i) bt[i] = int32_t(i);
+    Q3_HIP(hipMemcpyAsync(block_table_, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, st_));
+    for (int32_t* p : {kv_len_, cp_len_, n_frames_, max_frames_, trailing_idx_, n_trailing_, n_prompt_})
+        Q3_HIP(hipMemsetAsync(p, 0, size_t(S) * 4, st_));
+    Q3_HIP(hipMemsetAsync(row_key_, 0, size_t(S) * 4, st_));
+    Q3_HIP(hipMemsetAsync(active_, 0, size_t(S), st_));
+    Q3_HIP(hipMemsetAsync(finished_, 1, size_t(S), st_));
+    SamplingParams sph{sp.temperature, sp.top_k, sp.top_p, sp.repetition_penalty, sp.seed, 0u, sp.force_frames > 0 ? 1 : 0};
+    Q3_HIP(hipMemcpyAsync(sp_dev_, &sph, sizeof(sph), hipMemcpyHostToDevice, st_));
+    if (!cp_tables_ && m_->has_cp_proj && !std::getenv("Q3TTS_NO_PROJ_TABLES")) build_cp_proj_tables();
+    struct KeyScope {
+        Engine* e;
+        ~KeyScope() { e->frame_row_key_ = nullptr; }
+    } key_scope{this};
+    frame_row_key_ = row_key_;  // the samplers of every frame step below key on the slots' request indices
+    hipGraphExec_t ge = opts_.use_graph ? frame_graph(S) : nullptr;
+    Q3_HIP(hipStreamSynchronize(st_));
+
+    struct Slot {
+        int req = -1;       // request in this slot, -1: empty
+        int since = 0;      // frame steps since its admission
+        int reported = 0;   // TOKEN events delivered
+        int np = 0;
+        double t0 = 0;      // admission (host clock)
+    };
+    std::vector<Slot> sl((size_t)(S));
+    struct Retired {
+        int req, frames;
+        double span;
+        std::vector<int32_t> codes;  // [frames][16]
+    };
+    std::deque<Retired> waiting;  // retired, decode not started
+    int dec = -1;                 // job slot of the decode batch in flight (all are free: no begin job is outstanding)
+    struct DecodeGuard {          // an exception leaves no job slot behind
+        Engine* e;
+        int* dec;
+        ~DecodeGuard() {
+            if (*dec < 0) return;
+            Job& J = e->jobs_[*dec];
+            (void)hipEventSynchronize(J.ev_codec[1]);
+            {
+                std::unique_lock<std::mutex> lk(e->stage_mu_);
+                e->stage_cv_.wait(lk, [&] { return J.stage != 1; });
+            }
+            for (float* p : J.st_pcm) std::free(p);
+            for (int32_t* p : J.st_codes) std::free(p);
+            J.st_pcm.clear();
+            J.st_codes.clear();
+            J.busy = false;
+        }
+    } dec_guard{this, &dec};
+    double codec_ms = 0;
+    auto deliver = [&](bool wait) {  // end(): results[i] and INFO / AUDIO of every row of the batch (fp32 re-decode included)
+        if (!wait) {
+            std::lock_guard<std::mutex> lk(stage_mu_);
+            if (jobs_[dec].stage == 1) return;  // the staging thread has not copied it out yet
+        }
+        const int j = dec;
+        dec = -1;
+        end(j, q.results);
+        codec_ms += timing.codec_ms;
+    };
+    auto decode = [&](bool overlapped) {  // every waiting row (up to max_batch) in one decode on the codec stream
+        Job& J = jobs_[0];
+        const int R = std::min(int(waiting.size()), Bm_);
+        J.n = R;
+        J.up = codec_->upsample();
+        J.frames.assign(size_t(R), 0);
+        J.ref_T.assign(size_t(R), 0);
+        J.target_tokens.assign(size_t(R), 0);
+        J.ref_code0.assign(size_t(R), {});
+        J.req_index.assign(size_t(R), 0);
+        J.row_span.assign(size_t(R), 0);
+        J.codes_host.assign(size_t(R) * Fcap_ * 16, 0);
+        std::vector<int> dframes((size_t)(R), 0);
+        int Fdec = 0;
+        for (int b = 0; b < R; ++b) {
+            const Retired& w = waiting[size_t(b)];
+            J.frames[size_t(b)] = w.frames;
+            J.target_tokens[size_t(b)] = (*q.reqs)[size_t(w.req)].target_token_count;
+            J.req_index[size_t(b)] = w.req;
+            J.row_span[size_t(b)] = w.span;
+            std::copy(w.codes.begin(), w.codes.end(), J.codes_host.begin() + ptrdiff_t(size_t(b) * Fcap_ * 16));
+            dframes[size_t(b)] = w.frames;
+            Fdec = std::max(Fdec, w.frames);
+        }
+        waiting.erase(waiting.begin(), waiting.begin() + R);
+        J.Fdec = Fdec;
+        J.decoded = false;
+        J.streamed = false;
+        J.n_chunks = 0;
+        J.chunk_frames = 0;
+        J.chunks_fired = 0;
+        J.t_first_audio = 0;
+        J.held_from.assign(size_t(R), -1);
+        std::memset(J.nf_host, 0, size_t(Bm_) * 4);
+        hipStream_t cst = codec_stream(overlapped);
+        Q3_HIP(hipEventRecord(J.ev_codec[0], cst));
+        if (Fdec > 0) {
+            const size_t need = size_t(R) * Fdec * 16, floats = size_t(R) * Fdec * J.up;
+            if (need > J.dec_codes_cap) {
+                if (J.dec_codes) Q3_HIP(hipFree(J.dec_codes));
+                J.dec_codes = nullptr;
+                Q3_HIP(hipMalloc(reinterpret_cast<void**>(&J.dec_codes), need * 4));
+                J.dec_codes_cap = need;
+            }
+            if (floats > J.pcm_host_cap) {
+                if (J.pcm_host) Q3_HIP(hipHostFree(J.pcm_host));
+                J.pcm_host = nullptr;
+                Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&J.pcm_host), floats * 4, hipHostMallocDefault));
+                J.pcm_host_cap = floats;
+            }
+            Q3_HIP(hipMemcpy2DAsync(J.dec_codes, size_t(Fdec) * 64, J.codes_host.data(), size_t(Fcap_) * 64, size_t(Fdec) * 64, size_t(R),
+                                    hipMemcpyHostToDevice, cst));
+            float* pcm_dev = nullptr;
+            codec_->decode(J.dec_codes, Fdec, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, J.nf_host);
+            Q3_HIP(hipMemcpyAsync(J.pcm_host, pcm_dev, floats * 4, hipMemcpyDeviceToHost, cst));
+            J.decoded = true;
+        }
+        Q3_HIP(hipEventRecord(J.ev_codec[1], cst));
+        J.timing = q3tts_timing{};
+        J.t_start = t_call;
+        J.t_done = 0;
+        J.cb = cb;
+        J.user = user;
+        J.request_base = 0;
+        J.seq = job_seq_++;
+        J.busy = true;
+        dec = 0;
+        compute_cuts(J);
+        std::lock_guard<std::mutex> lk(stage_mu_);
+        J.stage_err.clear();
+        J.stage = J.decoded ? 1 : 0;  // copied out by the staging thread while the frame loop goes on
+        if (J.stage == 1) {
+            if (!stager_.joinable()) stager_ = std::thread([this] { staging_loop(); });
+            stage_cv_.notify_all();
+        }
+    };
+
+    const int burst_frames = std::max(1, max_inflight_frames / 2);
+    std::vector<int32_t> h_nframes((size_t)(S), 0);
+    std::vector<uint8_t> h_fin((size_t)(S), 0);
+    const int64_t per_tok = int64_t(t.num_hidden_layers) * t.num_key_value_heads * kHeadDim * 2 * 2;
+    int64_t kvb = 0;
+    int launched = 0, served = 0;
+    bool drained = false;
+    double prefill_ms = 0;
+    Q3_HIP(hipEventRecord(ev_[2], st_));
+    for (;;) {
+        // ---- admission: free slots in slot order take the next requests in request order ----
+        std::vector<ResolvedRequest> ar;
+        std::vector<int> as, ai;
+        std::vector<uint32_t> ak;
+        for (int s = 0; s < S && !drained; ++s) {
+            if (sl[size_t(s)].req >= 0) continue;
+            const int i = q.next.fetch_add(1);
+            if (i >= q.n) {
+                drained = true;
+                break;
+            }
+            ar.push_back((*q.reqs)[size_t(i)]);
+            as.push_back(s);
+            ai.push_back(i);
+            ak.push_back(q.row_base + uint32_t(i));  // request i draws what q3tts_generate draws with row_base + i
+        }
+        const bool admitted = !ar.empty();
+        if (admitted) {
+            const std::vector<int> np = admit(ar, as, ak);
+            const double now = now_s();
+            for (size_t j = 0; j < as.size(); ++j) {
+                Slot& x = sl[size_t(as[j])];
+                x = Slot{};
+                x.req = ai[j];
+                x.np = np[j];
+                x.t0 = now;
+            }
+            served += int(ar.size());
+        }
+        // ---- burst: no longer than the first running row's remaining frames (its cap ends it on time) ----
+        int running = 0, burst = burst_frames;
+        for (const Slot& x : sl)
+            if (x.req >= 0) {
+                ++running;
+                burst = std::min(burst, (*q.reqs)[size_t(x.req)].max_frames - x.since);
+            }
+        if (running == 0) break;
+        burst = std::max(burst, 1);
+        for (int f = 0; f < burst; ++f) {
+            if (ge) Q3_HIP(hipGraphLaunch(ge, st_));
+            else enqueue_frame(S, nullptr);
+        }
+        launched += burst;
+        Q3_HIP(hipMemcpyAsync(h_nframes.data(), n_frames_, size_t(S) * 4, hipMemcpyDeviceToHost, st_));
+        Q3_HIP(hipMemcpyAsync(h_fin.data(), finished_, size_t(S), hipMemcpyDeviceToHost, st_));
+        Q3_HIP(hipEventRecord(burst_ev_[0], st_));
+        // ---- while the burst runs: deliver the decode batch that has landed, start the next one ----
+        if (dec >= 0) deliver(false);
+        if (dec < 0 && !waiting.empty()) decode(true);
+        Q3_HIP(hipEventSynchronize(burst_ev_[0]));
+        if (admitted) {
+            float ms = 0;
+            Q3_HIP(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
+            prefill_ms += ms;
+        }
+        // ---- TOKEN events (generation order), retirement ----
+        bool any_retired = false;
+        const double now = now_s();
+        for (int s = 0; s < S; ++s) {
+            Slot& x = sl[size_t(s)];
+            if (x.req < 0) continue;
+            x.since += burst;
+            const int nf = h_nframes[size_t(s)];
+            if (cb && nf > x.reported) {
+                std::vector<int32_t> tmp((size_t)(nf - x.reported) * 16);
+                Q3_HIP(hipMemcpy(tmp.data(), codes_ + (size_t(s) * Fcap_ + x.reported) * 16, tmp.size() * 4, hipMemcpyDeviceToHost));
+                std::unique_lock<std::mutex> lk;
+                if (cb_mutex) lk = std::unique_lock<std::mutex>(*cb_mutex);
+                for (int f = 0; f < nf - x.reported; ++f) {
+                    q3tts_event ev{};
+                    ev.kind = Q3TTS_EVENT_TOKEN;
+                    ev.request_index = x.req;
+                    ev.token = tmp[size_t(f) * 16];
+                    cb(user, &ev);
+                }
+                x.reported = nf;
+            }
+            if (!h_fin[size_t(s)]) continue;
+            // copied out before the slot's next admission resets its row (stream order on st_)
+            waiting.push_back(Retired{x.req, nf, now - x.t0, std::vector<int32_t>((size_t)(nf) * 16)});
+            if (nf > 0)
+                Q3_HIP(hipMemcpyAsync(waiting.back().codes.data(), codes_ + size_t(s) * Fcap_ * 16, size_t(nf) * 64, hipMemcpyDeviceToHost, st_));
+            for (int f = 0; f < nf; ++f) kvb += int64_t(x.np - 1 + f) * per_tok;
+            x = Slot{};
+            any_retired = true;
+        }
+        if (any_retired) Q3_HIP(hipStreamSynchronize(st_));
+    }
+    Q3_HIP(hipEventRecord(ev_[3], st_));
+    Q3_HIP(hipStreamSynchronize(st_));
+    // ---- the last decode batches: nothing overlaps them any more ----
+    while (dec >= 0 || !waiting.empty()) {
+        if (dec >= 0) deliver(true);
+        else decode(false);
+    }
+    q3tts_timing tm{};
+    float loop_ms = 0;
+    Q3_HIP(hipEventElapsedTime(&loop_ms, ev_[2], ev_[3]));
+    tm.prefill_ms = prefill_ms;
+    tm.decode_ms = std::max(0.0, double(loop_ms) - prefill_ms);
+    tm.codec_ms = codec_ms;
+    tm.frame_steps = launched;
+    tm.rows = served;
+    tm.kv_bytes_read = kvb;
+    auto fl = frame_launches_.find(S);
+    tm.launches_per_frame_step = fl == frame_launches_.end() ? 0 : fl->second;
+    timing = tm;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2131,6 +2524,74 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
         timing.rows += t.rows;
         timing.kv_bytes_read += t.kv_bytes_read;
     }
+}
+
+void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
+                                  q3tts_result* results) {
+    Q3_CHECK(n >= 1, 3, "Invalid input: n_reqs must be at least 1");
+    Q3_CHECK(slots >= 1 && slots <= opts_.max_batch, 3, "Invalid input: slots must be between 1 and max_batch");
+    Q3_CHECK(sp.audio_chunk_frames == 0, 3,
+             "Invalid input: audio_chunk_frames is not supported by q3tts_generate_queued (each request's audio is delivered whole)");
+    bool outstanding = false;
+    for (const auto& p : parked_) outstanding = outstanding || p.busy;
+    for (const auto& l : lanes_) outstanding = outstanding || l->job_outstanding();
+    Q3_CHECK(!outstanding, 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
+    Q3_CHECK(model_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
+    // every request is checked before any GPU work: a bad one late in the queue must not fail after the others were delivered
+    std::vector<ResolvedRequest> rr;
+    rr.reserve(size_t(n));
+    for (int i = 0; i < n; ++i) {
+        try {
+            rr.push_back(lanes_[0]->check_queued(reqs[i], sp));
+        } catch (const Error& e) {
+            throw Error(e.status, std::string(e.what()) + " (request " + std::to_string(i) + ")");
+        }
+    }
+    QueueShared q;
+    q.reqs = &rr;
+    q.n = n;
+    q.row_base = sp.row_base;
+    q.results = results;
+    // each lane runs a slot pool of its own; all of them take requests from the one queue
+    const int L = int(lanes_.size());
+    std::vector<int> pool((size_t)(L));
+    for (int i = 0; i < L; ++i) pool[size_t(i)] = slots / L + (i < slots % L ? 1 : 0);
+    std::vector<std::string> errs((size_t)(L));
+    std::vector<int> codes((size_t)(L), 0);
+    auto run = [&](int i) {
+        if (pool[size_t(i)] == 0) return;
+        try {
+            lanes_[size_t(i)]->run_queued(q, pool[size_t(i)], sp, cb, user);
+        } catch (const Error& ex) {
+            errs[size_t(i)] = ex.what();
+            codes[size_t(i)] = ex.status;
+        } catch (const std::exception& ex) {
+            errs[size_t(i)] = ex.what();
+            codes[size_t(i)] = 7;
+        }
+    };
+    if (L == 1 || slots == 1) {
+        for (int i = 0; i < L; ++i) run(i);
+    } else {
+        std::vector<std::thread> th;
+        for (int i = 0; i < L; ++i) th.emplace_back(run, i);
+        for (auto& t : th) t.join();
+    }
+    for (int i = 0; i < L; ++i)
+        if (codes[size_t(i)]) throw Error(codes[size_t(i)], errs[size_t(i)]);
+    // lanes run concurrently: spans are maxima; volumes (frame-step replays, prefills, decodes, bytes) are sums
+    timing = q3tts_timing{};
+    for (int i = 0; i < L; ++i) {
+        if (pool[size_t(i)] == 0) continue;
+        const q3tts_timing& t = lanes_[size_t(i)]->timing;
+        timing.prefill_ms += t.prefill_ms;
+        timing.decode_ms = std::max(timing.decode_ms, t.decode_ms);
+        timing.codec_ms += t.codec_ms;
+        timing.frame_steps += t.frame_steps;
+        timing.launches_per_frame_step = std::max(timing.launches_per_frame_step, t.launches_per_frame_step);
+        timing.kv_bytes_read += t.kv_bytes_read;
+    }
+    timing.rows = n;
 }
 
 }  // namespace q3

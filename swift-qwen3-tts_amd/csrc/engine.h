@@ -5,6 +5,7 @@
 // :943-961) with batching added: rows are independent sequences with their own KV pages,
 // repetition sets and RNG streams.
 #pragma once
+#include <atomic>
 #include <map>
 #include <memory>
 #include <condition_variable>
@@ -46,6 +47,16 @@ struct ResolvedRequest {
 class CodecRunner;
 class VoiceFrontEnd;
 
+// One q3tts_generate_queued call as the lanes see it: the resolved requests and the index of the next one to admit, which
+// every lane's slot pool takes from (a request's random stream is keyed by its index, so which lane serves it does not matter).
+struct QueueShared {
+    const std::vector<ResolvedRequest>* reqs = nullptr;
+    int n = 0;
+    std::atomic<int> next{0};
+    uint32_t row_base = 0;
+    q3tts_result* results = nullptr;
+};
+
 class Engine {
   public:
     // One lane: a slice of the batch with its own stream, workspace, KV pool and frame graph.
@@ -67,6 +78,13 @@ class Engine {
     int begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const DebugOpts* dbg,
               bool overlapped);  // overlapped: another batch's AR loop is expected to run beside this one's decode
     void end(int job, q3tts_result* results);
+    bool job_outstanding() const;
+    // Continuous batching (q3tts_generate_queued). check_queued resolves one request and applies every limit the slot loop
+    // would hit (prompt, trailing text, max_frames, RoPE range) on the host, before any GPU work. run_queued keeps `slots`
+    // rows in flight: at each burst boundary finished rows are retired (codes copied out, decode queued on the codec stream
+    // beside the frame loop) and their slots take the next requests of `q`, prefilled as a sub-batch of their own.
+    ResolvedRequest check_queued(const q3tts_request& r, const q3tts_sampling& sp) const;
+    void run_queued(QueueShared& q, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
     void debug_prepare_inputs(const q3tts_request& req, uint16_t* input_embeds, int cap_prompt, int* n_prompt,
                               uint16_t* trailing, int cap_trailing, int* n_trailing, uint16_t* tts_pad);
     void debug_sample(const uint16_t* logits, int rows, int V, const q3tts_sampling& sp, const uint8_t* seen,
@@ -144,6 +162,8 @@ class Engine {
         uint64_t seq = 0;                 // begin order
         int n = 0, Fdec = 0, up = 0;
         std::vector<int> frames, ref_T, target_tokens, n_prompt;
+        std::vector<int> req_index;   // queued decode batch: row b is request req_index[b] (results / events); empty: row b
+        std::vector<double> row_span; // queued decode batch: admission -> retirement of row b (generate_time); empty: the job's
         std::vector<std::vector<int32_t>> ref_code0;  // first code row of each reference (valid-length count)
         std::vector<int32_t> codes_host;  // [n][Fcap][16]
         int32_t* dec_codes = nullptr;     // device [n][Fdec][16]: what the decoder reads (reference ++ generated for clone rows)
@@ -247,8 +267,14 @@ class Engine {
 
     void alloc_workspace();
     ResolvedRequest resolve(const q3tts_request& r, const q3tts_sampling& sp) const;
-    // builds prompt_/trailing_/tts_pad_ for rows [0,n); fills host-side lengths
-    void assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vector<int>& n_prompt, std::vector<int>& n_trailing);
+    // builds prompt_/trailing_/tts_pad_ for rows [0,n); fills host-side lengths. trailing_rows: row of trailing_ that
+    // request b's trailing text goes to (queued admission: its slot); nullptr: row b
+    void assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vector<int>& n_prompt, std::vector<int>& n_trailing,
+                          const std::vector<int>* trailing_rows = nullptr);
+    // positions 0 .. Pmax-2 of n right-aligned prompts (prompt_ rows 0..n-1) through the talker into the pages of `block_table`,
+    // then the last position loaded into w.h / w.ss_a
+    void enqueue_prefill(Stream& w, int n, int Pmax, const int32_t* block_table, int32_t* kv_len, const int32_t* n_prompt,
+                         uint8_t* active);
     void project_rows(const std::vector<int32_t>& ids, int rows);  // ids -> proj_out_[rows][H]
     void enqueue_layers(const StackW& s, Stream& w, int B, uint16_t* kpool, uint16_t* vpool, size_t layer_stride,
                         const int32_t* block_table, int max_pages, const int32_t* kv_len, const uint8_t* active,
@@ -257,6 +283,19 @@ class Engine {
     void enqueue_cp_pass(int B, bool from_talker, int head, int cp_pos, bool projected = false);  // head: lm_head index or -1; cp_pos: tokens already cached
     void enqueue_frame(int B, const DebugOpts* dbg);
     hipGraphExec_t frame_graph(int B);
+    // ---- continuous batching (run_queued) ----
+    const uint32_t* frame_row_key_ = nullptr;  // non-null while a queued frame step is enqueued: the samplers key on it
+    std::map<int, hipGraphExec_t> qgraphs_;   // frame_graph() while frame_row_key_ is set, keyed by slot count
+    uint8_t* qws_ = nullptr;  // allocated at the first queued call
+    Stream qk_{};             // activations of an admission's prefill (the frame step's tk_ carries the running rows)
+    int32_t *q_bt_ = nullptr, *q_kv_len_ = nullptr, *q_n_prompt_ = nullptr;  // the admitted sub-batch
+    uint8_t* q_active_ = nullptr;
+    AdmitDesc* q_desc_ = nullptr;
+    uint32_t* row_key_ = nullptr;  // [max_batch] random key of every slot
+    std::vector<int32_t> q_host_;  // staging of the sub-batch's arrays (alive until the next boundary's sync)
+    void ensure_queue_ws();
+    // prompts, prefill and admit_rows_kernel for requests rr into `slots` (random keys `keys`); returns their prompt lengths
+    std::vector<int> admit(const std::vector<ResolvedRequest>& rr, const std::vector<int>& slots, const std::vector<uint32_t>& keys);
     GemmArgs gemm_args(const LinearW& L, const uint16_t* x, int M) const;
 };
 
@@ -277,6 +316,9 @@ class EngineGroup {
     // Two-deep pipeline (Engine::begin / end). With more than one lane a job runs to completion inside begin.
     int begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, bool more_follows);
     void end(int job, q3tts_result* results);
+    // q3tts_generate_queued: every request checked up front; `slots` rows split over the lanes, one shared queue
+    void generate_queued(const q3tts_request* reqs, int n, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
+                         q3tts_result* results);
     std::string last_error;
     q3tts_timing timing{};
     std::vector<std::string> speakers;

@@ -203,6 +203,7 @@ struct SamplerArgs {
     int B;
     uint16_t* logits_dump;   // [B][forced_frames][dump_ld] (tests) or nullptr
     int dump_ld, dump_off;
+    const uint32_t* row_key; // [B] random stream of row b (queued slots: the request's global index), or nullptr: sp->row0 + b
 };
 void launch_sampler(const SamplerArgs& a, hipStream_t st);
 // The frame's last draw with its row's end-of-frame job riding along (kernels/row_jobs.h frame_end_job): the sampler is that
@@ -238,6 +239,31 @@ void launch_stamp(unsigned long long* acc, unsigned long long* last, int k, hipS
 // chunked prefill: C positions per row per step; a.step carries r_base (prompt index of element 0 = r_base + n_prompt[b])
 void launch_prefill_chunk_load(const PrefillLoadArgs& a, int C, hipStream_t st);
 void launch_advance_len_chunk(int32_t* kv_len, const int32_t* n_prompt, int r_base, int C, int B, hipStream_t st);
+
+// Continuous batching (Engine::run_queued): row j of a prefilled sub-batch moves into frame-step row (slot) desc[j].slot --
+// its last prompt position's input row and that row's sum of squares, its cache length and lengths, its random key -- and
+// the slot's per-row loop state is reset (frame count, predictor cache length, trailing-text index, codes in flight,
+// repetition flags, code history; finished = 0, active = 1). One workgroup per admitted row.
+struct AdmitDesc {
+    int32_t slot, n_trailing, max_frames;
+    uint32_t row_key;
+};
+struct AdmitArgs {
+    const AdmitDesc* desc;     // [k]
+    const uint16_t* src_h;     // fragment-major, row j: the sub-batch's loaded last prompt position
+    int srcMB;
+    const float* src_ss;       // [k] its sum of squares (first partial of the first layer's norm)
+    const int32_t* src_kv_len; // [k] tokens the prefill cached
+    const int32_t* src_n_prompt;
+    uint16_t* h;               // frame step: fragment-major next talker input (tk_.h)
+    int hMB;
+    float* ss;                 // [slots] (tk_.ss_a)
+    int H, V, Fmax, slots;
+    int32_t *kv_len, *n_prompt, *n_trailing, *max_frames, *n_frames, *cp_len, *trailing_idx, *cur_codes, *codes;
+    uint32_t* row_key;
+    uint8_t *finished, *active, *seen;
+};
+void launch_admit_rows(const AdmitArgs& a, int k, hipStream_t st);
 
 
 // prompt assembly (Qwen3.swift:371-406, 505-510): dst[dst_row[i]] = proj[a[i]] when b[i] == -1, else

@@ -160,6 +160,36 @@ __global__ void advance_len_chunk_kernel(int32_t* kv_len, const int32_t* n_promp
     kv_len[b] += C - p0;
 }
 
+// Continuous batching: row j of the prefilled sub-batch takes slot desc[j].slot of the frame step (kernels.h AdmitArgs).
+// Only that slot's row of every array is written: the rows in flight around it carry their state across this launch.
+__global__ __launch_bounds__(256) void admit_rows_kernel(AdmitArgs a) {
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const AdmitDesc d = a.desc[j];
+    const int s = d.slot;
+    if (s < 0 || s >= a.slots) return;
+    for (int i = tid; i < a.H / 8; i += 256)
+        *reinterpret_cast<uint4*>(a.h + act_tiled_offset(s, 8 * i, a.hMB)) =
+            *reinterpret_cast<const uint4*>(a.src_h + act_tiled_offset(j, 8 * i, a.srcMB));
+    uint8_t* seen = a.seen + (size_t)s * a.V;
+    for (int i = tid; i < a.V; i += 256) seen[i] = 0;
+    int32_t* codes = a.codes + (size_t)s * a.Fmax * 16;
+    for (int i = tid; i < a.Fmax * 16; i += 256) codes[i] = 0;
+    if (tid < 16) a.cur_codes[(size_t)s * 16 + tid] = 0;
+    if (tid == 0) {
+        a.ss[s] = a.src_ss[j];
+        a.kv_len[s] = a.src_kv_len[j];
+        a.n_prompt[s] = a.src_n_prompt[j];
+        a.n_trailing[s] = d.n_trailing;
+        a.max_frames[s] = d.max_frames;
+        a.row_key[s] = d.row_key;
+        a.n_frames[s] = 0;
+        a.cp_len[s] = 0;
+        a.trailing_idx[s] = 0;
+        a.finished[s] = 0;
+        a.active[s] = 1;
+    }
+}
+
 // Diagnostics (Q3TTS_FRAME_STAMPS=1): slot[k] accumulates the time between this stamp and the previous one of the same
 // frame step, so that the phases of a REPLAYED graph can be timed (a tracing profiler perturbs a chain of 5 us launches).
 __global__ void stamp_kernel(unsigned long long* acc, unsigned long long* last, int k) {
@@ -251,6 +281,10 @@ void launch_stamp(unsigned long long* acc, unsigned long long* last, int k, hipS
 }
 void launch_advance_len(int32_t* kv_len, const uint8_t* active, int B, hipStream_t st) {
     hipLaunchKernelGGL(advance_len_kernel, dim3(1), dim3(64), 0, st, kv_len, active, B);
+}
+void launch_admit_rows(const AdmitArgs& a, int k, hipStream_t st) {
+    if (k <= 0) return;
+    hipLaunchKernelGGL(admit_rows_kernel, dim3(k), dim3(256), 0, st, a);
 }
 void launch_frame_end(const FrameEndArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(frame_end_kernel, dim3(a.B), dim3(256), 0, st, a);

@@ -194,6 +194,10 @@ __device__ __forceinline__ void sampler_body(const SamplerArgs& a, const FrameEn
     // (read from an address that is always valid, with the other operands: under a branch on the pointer this byte was a
     // memory round trip of its own behind them)
     const uint8_t gate_raw = *(a.advance_gate ? a.advance_gate + b : a.finished + b);
+    // the row's random stream: a queued slot's key (the request's global index), else row0 + b (same always-valid-address
+    // form as the gate above: the key arrives with the other operands instead of behind a branch)
+    const uint32_t key_raw = *(a.row_key ? a.row_key + b : reinterpret_cast<const uint32_t*>(a.n_frames) + b);
+    const uint32_t row_key = a.row_key ? key_raw : sp.row0 + (uint32_t)b;
     const bool gate = a.advance_gate ? (gate_raw != 0) : true;
     if (tid < 256) {  // both radix levels' histograms, zeroed under the loads
         hist[0][tid] = 0;
@@ -392,7 +396,7 @@ __device__ __forceinline__ void sampler_body(const SamplerArgs& a, const FrameEn
         Best x{-INFINITY, 0x7fffffff};
         for (int q = tid; q < ns; q += kThreads) {
             const int i = (int)sortbuf[q];
-            const float v = rbf(sval[q] * invt) + gumbel_noise(sp.seed, sp.row0 + (uint32_t)b, draw, (uint32_t)i);
+            const float v = rbf(sval[q] * invt) + gumbel_noise(sp.seed, row_key, draw, (uint32_t)i);
             x = better(x, Best{v, i});
         }
         Best r = block_argmax<kThreads>(x, scratch);

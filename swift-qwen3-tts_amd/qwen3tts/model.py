@@ -259,6 +259,25 @@ class Qwen3TTSModel:
         del keep
         return self._collect(st, res, len(reqs))
 
+    def generate_queued(self, reqs: Sequence[GenerationRequest], slots: Optional[int] = None, temperature: float = 0.9,
+                        top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.05, seed: int = 0,
+                        force_frames: int = 0, on_event: Optional[Callable[[int, str, object], None]] = None,
+                        audio_chunk_frames: int = 0, audio_window_frames: int = 0, audio_lookahead_frames: int = 4,
+                        row_base: int = 0) -> List[GenerationResult]:
+        """Continuous batching (q3tts_generate_queued): any number of requests with at most `slots` rows in flight (default
+        max_batch); a finished row's slot takes the next request. Result i is bit-identical to generate_batch([reqs[i]],
+        row_base=row_base + i). Events as generate_batch's, except that a request's ("info", ...) / ("audio", ...) arrive as
+        soon as its audio is decoded. Voice-clone requests and audio_chunk_frames > 0 are refused."""
+        arr, keep = self._marshal(reqs)
+        s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
+                           audio_window_frames, audio_lookahead_frames, row_base)
+        cb = self._event_cb(on_event)
+        res = (L.Result * len(reqs))()
+        n_slots = int(self.info.max_batch) if slots is None else int(slots)
+        st = self._lib.q3tts_generate_queued(self._h, arr, len(reqs), n_slots, C.byref(s), cb, None, res)
+        del keep
+        return self._collect(st, res, len(reqs))
+
     @staticmethod
     def _event_cb(on_event):
         if not on_event:

@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Continuous batching against static batches.
+
+  python tools/queued_bench.py [--preset 1.7b] [--slots 32] [--requests 256]
+
+Two workloads on bench.py's synthetic checkpoint and request builder:
+  ragged   max_tokens uniform in 50..400 (seeded), temperature 0.9, seed 1234: rows end at their caps (or EOS) at different frames
+  uniform  force_frames = 200: every row has the same length, so continuous batching can only lose (admission costs)
+and two paths for each:
+  static   pipelined q3tts_generate_begin / _end batches of `slots` requests in request order, row_base = first request's index
+  queued   one q3tts_generate_queued call with `slots` rows in flight
+Prints, per run, frames/s (generated frames over the wall time of the whole workload, codec decode included), frame steps,
+prefill and codec milliseconds, and whether every request's codes and PCM are bit-identical between the two paths.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "swift-qwen3-tts_amd"))
+
+import bench  # noqa: E402  (checkpoint synthesis and request builder of the headline benchmark)
+
+
+def run_static(model, reqs, slots, kw):
+    """Pipelined begin / end batches in request order (bench.py's pipeline): the next batch's frame loop overlaps the decode
+    of the one before."""
+    out, steps, pre, codec = [], 0, 0.0, 0.0
+    batches = [(lo, reqs[lo:lo + slots]) for lo in range(0, len(reqs), slots)]
+    t0 = time.perf_counter()
+    job = model.generate_batch_begin(batches[0][1], row_base=batches[0][0], more_follows=len(batches) > 1, **kw)
+    for k in range(len(batches)):
+        nxt = None
+        if k + 1 < len(batches):
+            lo, b = batches[k + 1]
+            nxt = model.generate_batch_begin(b, row_base=lo, more_follows=k + 2 < len(batches), **kw)
+        out += model.generate_batch_end(job)
+        tm = model.last_timing()
+        steps += tm.frame_steps
+        pre += tm.prefill_ms
+        codec += tm.codec_ms
+        job = nxt
+    return out, time.perf_counter() - t0, steps, pre, codec
+
+
+def run_queued(model, reqs, slots, kw):
+    t0 = time.perf_counter()
+    out = model.generate_queued(reqs, slots=slots, **kw)
+    dt = time.perf_counter() - t0
+    tm = model.last_timing()
+    return out, dt, tm.frame_steps, tm.prefill_ms, tm.codec_ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--preset", default="1.7b")
+    ap.add_argument("--slots", type=int, default=32)
+    ap.add_argument("--requests", type=int, default=256)
+    ap.add_argument("--n-text", type=int, default=32)
+    args = ap.parse_args()
+    from qwen3tts import Qwen3TTSModel
+
+    ckpt = bench.ensure_checkpoint(args.preset, 0, None)
+    model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=128)
+    n_instruct = 16 if args.preset == "1.7b" else 0
+    base = bench.build_requests(args.preset, 0, args.requests, args.n_text, n_instruct)
+    rng = np.random.default_rng(1234)
+    caps = rng.integers(50, 401, size=args.requests)
+    ragged = []
+    for r, c in zip(base, caps):
+        # max_tokens is the cap; target_token_count only lifts the max(75, 6 x target) floor above it (Qwen3.swift:822-823)
+        ragged.append(type(r)(r.text_ids, 100, r.instruct_ids, r.speaker, r.language, int(c)))
+    sampling = dict(temperature=0.9, top_k=50, top_p=1.0, repetition_penalty=1.05, seed=1234)
+    workloads = [("ragged", ragged, dict(sampling)), ("uniform", base, dict(sampling, force_frames=200))]
+
+    # warm-up: both frame graphs captured, projected tables built, codec scratch grown
+    warm = [type(r)(r.text_ids, r.target_token_count, r.instruct_ids, r.speaker, r.language, 8) for r in base[:2 * args.slots]]
+    run_static(model, warm, args.slots, sampling)
+    run_queued(model, warm, args.slots, sampling)
+
+    print(f"# {args.preset} bf16, {args.requests} requests, slots {args.slots}; frames/s = generated frames / wall time (codec included)")
+    for name, reqs, kw in workloads:
+        res = {}
+        for path, fn in (("static", run_static), ("queued", run_queued)):
+            out, dt, steps, pre, codec = fn(model, reqs, args.slots, kw)
+            frames = sum(int(r.codes.shape[0]) for r in out)
+            res[path] = (out, dt, steps, frames)
+            print(f"{name:8s} {path:6s} frames {frames:7d}  wall {dt:8.3f} s  frames/s {frames / dt:9.1f}  frame_steps {steps:6d}  "
+                  f"prefill {pre:8.1f} ms  codec {codec:8.1f} ms  failed {sum(1 for r in out if r.status != 0)}", flush=True)
+        (a, da, sa, fa), (b, db, sb, fb) = res["static"], res["queued"]
+        same = all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio) for x, y in zip(a, b))
+        print(f"{name:8s} bit-identical codes + pcm, all {len(a)} requests: {same}   queued / static: frame_steps {sb / sa:.3f}  "
+              f"frames/s {(fb / db) / (fa / da):.3f}", flush=True)
+    model.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 namespace q3 {
 
@@ -68,6 +69,46 @@ inline size_t act_tiled_offset(int m, int k, int MBL) {
     return (((size_t(k >> 7) * MBL + (m >> 4)) * 4 + ((k >> 3) & 3)) * 64 + (((k >> 5) & 3) * 16 + (m & 15))) * 8 + (k & 7);
 }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// An owned device (hipMalloc) or pinned host (hipHostMalloc) buffer of T. grow(n) reallocates only when n exceeds the
+// capacity and keeps nothing of the old contents; it does not synchronise: a caller whose old buffer a stream may still
+// read synchronises that stream first.
+template <class T, bool Pinned>
+class HipBuf {
+  public:
+    HipBuf() = default;
+    HipBuf(HipBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    HipBuf& operator=(HipBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
+    HipBuf(const HipBuf&) = delete;
+    HipBuf& operator=(const HipBuf&) = delete;
+    ~HipBuf() { release(); }
+    T* grow(size_t n) {
+        if (n > cap_) {
+            release();
+            void* p = nullptr;
+            if constexpr (Pinned) Q3_HIP(hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault));
+            else Q3_HIP(hipMalloc(&p, n * sizeof(T)));
+            p_ = static_cast<T*>(p);
+            cap_ = n;
+        }
+        return p_;
+    }
+    size_t capacity() const { return cap_; }
+    operator T*() const { return p_; }
+
+  private:
+    void release() {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+};
+template <class T>
+using DevBuf = HipBuf<T, false>;
+template <class T>
+using PinnedBuf = HipBuf<T, true>;
 
 }  // namespace q3
 

@@ -37,6 +37,16 @@ struct Bump {
         return p;
     }
 };
+// one AUDIO_CHUNK event: n samples at pcm, sample `offset` of the request's audio (the caller holds Engine::cb_lock)
+void audio_chunk(q3tts_event_cb cb, void* user, int request_index, const float* pcm, int64_t n, int64_t offset) {
+    q3tts_event ev{};
+    ev.kind = Q3TTS_EVENT_AUDIO_CHUNK;
+    ev.request_index = request_index;
+    ev.pcm = pcm;
+    ev.n_samples = n;
+    ev.sample_offset = offset;
+    cb(user, &ev);
+}
 }  // namespace
 
 Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opts) {
@@ -72,8 +82,7 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
         for (auto& e : J.ev_codec) Q3_HIP(hipEventCreate(&e));
         Q3_HIP(hipEventCreate(&J.ev_begin));
         Q3_HIP(hipEventCreate(&J.ev_first_audio));
-        Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&J.nf_host), size_t(std::max(opts.max_batch, 1)) * 4, hipHostMallocDefault));
-        std::memset(J.nf_host, 0, size_t(std::max(opts.max_batch, 1)) * 4);
+        std::memset(J.nf_host.grow(size_t(std::max(opts.max_batch, 1))), 0, size_t(std::max(opts.max_batch, 1)) * 4);
     }
     for (auto& e : ev_) Q3_HIP(hipEventCreate(&e));
     for (auto& e : burst_ev_) Q3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -110,10 +119,6 @@ Engine::~Engine() {
         stage_cv_.notify_all();
         stager_.join();
     }
-    for (auto& J : jobs_) {  // rows staged for a job that was never ended
-        for (float* p : J.st_pcm) std::free(p);
-        for (int32_t* p : J.st_codes) std::free(p);
-    }
     for (auto& g : graphs_) (void)hipGraphExecDestroy(g.second);
     for (auto& g : qgraphs_) (void)hipGraphExecDestroy(g.second);
     if (qws_) (void)hipFree(qws_);
@@ -121,21 +126,14 @@ Engine::~Engine() {
     fe_.reset();
     for (auto& L : fe_lanes_) {
         L.fe.reset();
-        if (L.spk) (void)hipFree(L.spk);
         if (L.done) (void)hipEventDestroy(L.done);
         if (L.st) (void)hipStreamDestroy(L.st);
     }
-    for (void* p : {(void*)ref_audio_dev_, (void*)ref_codes_dev_, (void*)extra_, (void*)spk_f32_})
-        if (p) (void)hipFree(p);
     for (auto& J : jobs_) {
         for (auto& e : J.chunk_done)
             if (e) (void)hipEventDestroy(e);
-        if (J.dec_codes) (void)hipFree(J.dec_codes);
-        if (J.pcm_host) (void)hipHostFree(J.pcm_host);
         for (auto& e : J.ev_codec)
             if (e) (void)hipEventDestroy(e);
-        if (J.nf_host) (void)hipHostFree(J.nf_host);
-        if (J.nf_chunk_host) (void)hipHostFree(J.nf_chunk_host);
         if (J.ev_begin) (void)hipEventDestroy(J.ev_begin);
         if (J.ev_first_audio) (void)hipEventDestroy(J.ev_first_audio);
     }
@@ -168,7 +166,9 @@ Engine::~Engine() {
 // each of passes 1..14. The projection of a table row does not depend on anything else, so it is taken once per row at
 // load -- by the very GEMM kernel the frame step would have launched, Mp_ codes at a time, so the rows (and their per-tile sums
 // of squares for the next norm prologue) are bit-identical to projecting at run time -- and the frame step loses 14 launches.
+// The tables are cut from the weights, which may arrive after load (weights_from_broadcast): first use, not load.
 void Engine::build_cp_proj_tables() {
+    if (cp_tables_ || !m_->has_cp_proj || std::getenv("Q3TTS_NO_PROJ_TABLES")) return;
     const TalkerConfig& t = m_->cfg.talker;
     const int H = t.hidden_size, CH = m_->cp.hidden, MBL = Mp_ / 16, Vc = t.cp.vocab_size, nss = CH / 16;
     const int ntab = t.num_code_groups - 2;  // embeddings 0..13 feed passes 1..14; the last code feeds nothing
@@ -877,12 +877,9 @@ void Engine::assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vec
 }
 
 const float* Engine::upload_audio(const float* audio, int64_t n) {
-    if (size_t(n) > ref_audio_cap_) {
+    if (size_t(n) > ref_audio_dev_.capacity()) {
         Q3_HIP(hipStreamSynchronize(st_));
-        if (ref_audio_dev_) Q3_HIP(hipFree(ref_audio_dev_));
-        ref_audio_dev_ = nullptr;
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&ref_audio_dev_), size_t(n) * 4));
-        ref_audio_cap_ = size_t(n);
+        ref_audio_dev_.grow(size_t(n));
     }
     Q3_HIP(hipMemcpyAsync(ref_audio_dev_, audio, size_t(n) * 4, hipMemcpyHostToDevice, st_));
     return ref_audio_dev_;
@@ -902,18 +899,8 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
         total_codes += size_t(16) * r.ref_T;
         total_rows += size_t(1) + r.ref_T;
     }
-    if (total_codes > ref_codes_cap_) {
-        if (ref_codes_dev_) Q3_HIP(hipFree(ref_codes_dev_));
-        ref_codes_dev_ = nullptr;
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&ref_codes_dev_), total_codes * 4));
-        ref_codes_cap_ = total_codes;
-    }
-    if (total_rows > extra_cap_) {
-        if (extra_) Q3_HIP(hipFree(extra_));
-        extra_ = nullptr;
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&extra_), total_rows * H * 2));
-        extra_cap_ = total_rows;
-    }
+    ref_codes_dev_.grow(total_codes);
+    extra_.grow(total_rows * H);
     int n_clone = 0;
     for (auto& r : reqs) n_clone += r.clone ? 1 : 0;
     const int K = std::min(4, n_clone);
@@ -922,19 +909,16 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
         Q3_HIP(hipStreamCreateWithFlags(&L.st, hipStreamNonBlocking));
         Q3_HIP(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
         L.fe = std::make_unique<VoiceFrontEnd>(*m_, L.st);
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&L.spk), size_t(H) * 4));
+        L.spk.grow(size_t(H));
         fe_lanes_.push_back(std::move(L));
     }
     // every clip zero-padded to the longest one: the (causal) codec encoder then runs ONCE over all of them
     int64_t S_max = 0;
     for (auto& r : reqs)
         if (r.clone) S_max = std::max<int64_t>(S_max, r.n_ref_samples);
-    if (size_t(S_max) * n_clone > ref_audio_cap_) {
+    if (size_t(S_max) * n_clone > ref_audio_dev_.capacity()) {
         Q3_HIP(hipStreamSynchronize(st_));
-        if (ref_audio_dev_) Q3_HIP(hipFree(ref_audio_dev_));
-        ref_audio_dev_ = nullptr;
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&ref_audio_dev_), size_t(S_max) * n_clone * 4));
-        ref_audio_cap_ = size_t(S_max) * n_clone;
+        ref_audio_dev_.grow(size_t(S_max) * n_clone);
     }
     Q3_HIP(hipMemsetAsync(ref_audio_dev_, 0, size_t(S_max) * n_clone * 4, st_));
     std::vector<int64_t> valid, offs;  // samples per clip, offset of its codes
@@ -988,12 +972,7 @@ int Engine::codec_encode(const float* audio, int64_t n_samples, int32_t* codes, 
     Q3_CHECK(audio && n_samples > 0, 3, "Invalid input: empty audio");
     const int T = fe_->encoded_frames(n_samples);
     Q3_CHECK(T <= cap_frames, 3, "Invalid input: output buffer too small for the encoded frames");
-    if (size_t(16) * T > ref_codes_cap_) {
-        if (ref_codes_dev_) Q3_HIP(hipFree(ref_codes_dev_));
-        ref_codes_dev_ = nullptr;
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&ref_codes_dev_), size_t(16) * T * 4));
-        ref_codes_cap_ = size_t(16) * T;
-    }
+    ref_codes_dev_.grow(size_t(16) * T);
     const float* a = upload_audio(audio, n_samples);
     Q3_HIP(hipEventRecord(ev_fe_[0], st_));
     fe_->encode(a, n_samples, ref_codes_dev_);
@@ -1012,7 +991,7 @@ void Engine::speaker_embedding(const float* audio, int64_t n_samples, float* out
     Q3_CHECK(audio && n_samples > 0, 3, "Invalid input: empty audio");
     const int D = m_->speaker.enc_dim;
     Q3_CHECK(cap >= D, 3, "Invalid input: output buffer too small for the speaker embedding");
-    if (!spk_f32_) Q3_HIP(hipMalloc(reinterpret_cast<void**>(&spk_f32_), size_t(m_->cfg.talker.hidden_size) * 4));
+    spk_f32_.grow(size_t(m_->cfg.talker.hidden_size));
     const float* a = upload_audio(audio, n_samples);
     Q3_HIP(hipEventRecord(ev_fe_[0], st_));
     fe_->speaker_embedding(a, n_samples, spk_f32_);
@@ -1036,17 +1015,12 @@ void Engine::debug_frontend_stage(const float* audio, int64_t n_samples, const c
     for (const char* s : kSpeaker) is_spk = is_spk || cap_s.name == s;
     if (is_spk) {
         Q3_CHECK(m_->has_speaker_encoder, 1, "Model not initialized: Speaker encoder not available for this model");
-        if (!spk_f32_) Q3_HIP(hipMalloc(reinterpret_cast<void**>(&spk_f32_), size_t(m_->cfg.talker.hidden_size) * 4));
+        spk_f32_.grow(size_t(m_->cfg.talker.hidden_size));
         fe_->speaker_embedding(a, n_samples, spk_f32_, &cap_s);
     } else {
         Q3_CHECK(m_->has_codec_encoder, 1, "Model not initialized: Speech tokenizer encoder not available");
         const int Tq = fe_->encoded_frames(n_samples);
-        if (size_t(16) * Tq > ref_codes_cap_) {
-            if (ref_codes_dev_) Q3_HIP(hipFree(ref_codes_dev_));
-            ref_codes_dev_ = nullptr;
-            Q3_HIP(hipMalloc(reinterpret_cast<void**>(&ref_codes_dev_), size_t(16) * Tq * 4));
-            ref_codes_cap_ = size_t(16) * Tq;
-        }
+        ref_codes_dev_.grow(size_t(16) * Tq);
         fe_->encode(a, n_samples, ref_codes_dev_, &cap_s);
     }
     Q3_HIP(hipStreamSynchronize(st_));
@@ -1129,13 +1103,90 @@ hipStream_t Engine::codec_stream(bool overlapped) {
     return want;
 }
 
+// A streamed decode (row f1): chunks of the waveform leave while the frame loop is still producing tokens.
+struct Engine::StreamedDecode {
+    Engine& e;
+    Job& J;
+    const bool on;
+    hipStream_t sst = nullptr;
+    std::vector<int> avail;    // frames of row b the decoder may read
+    std::vector<uint8_t> fin;  // row b has all of its frames
+    int copied = 0;            // frames [0, copied) of every row are in J.dec_codes
+
+    StreamedDecode(Engine& eng, Job& job, bool streamed, const q3tts_sampling& sp, q3tts_event_cb cb, void* user)
+        : e(eng), J(job), on(streamed), avail(size_t(job.n), 0), fin(size_t(job.n), 0) {
+        if (!on) return;
+        J.Fdec = e.Fcap_;  // row stride of the job's code and PCM buffers: the final lengths are not known yet
+        J.cb = cb;         // fire_chunks delivers from inside the frame loop
+        J.user = user;
+        J.request_base = e.request_base;
+        J.dec_codes.grow(size_t(J.n) * e.Fcap_ * 16);
+        J.pcm_host.grow(size_t(J.n) * e.Fcap_ * J.up);
+        J.clear_chunk_flags(e.Fcap_);
+        // the decode runs beside this batch's own frame loop: the confined stream, like a decode beside the next batch's
+        sst = e.codec_stream(true);
+        CodecRunner::StreamCfg cfg;
+        cfg.rows = J.n; cfg.chunk_frames = sp.audio_chunk_frames; cfg.window = sp.audio_window_frames;
+        cfg.lookahead = std::max(0, sp.audio_lookahead_frames); cfg.max_frames = e.Fcap_;
+        Q3_HIP(hipEventRecord(J.ev_codec[0], sst));
+        e.codec_->stream_open(cfg);
+        J.streamed = true;
+    }
+    ~StreamedDecode() {  // an exception must not leave the runner's stream open
+        if (on && e.codec_->streaming()) e.codec_->stream_close();
+    }
+    // frames [0, upto) of every row exist on the device once the copy below has run: hand them to the decoder, which issues
+    // every chunk that avail / fin now allow
+    void feed(int upto) {
+        if (!on) return;
+        if (upto > copied) {
+            Q3_HIP(hipMemcpy2DAsync(J.dec_codes + size_t(copied) * 16, size_t(e.Fcap_) * 64, e.codes_ + size_t(copied) * 16,
+                                    size_t(e.Fcap_) * 64, size_t(upto - copied) * 64, size_t(J.n), hipMemcpyDeviceToDevice, e.st_));
+            copied = upto;
+            Q3_HIP(hipEventRecord(e.ev_[3], e.st_));
+            Q3_HIP(hipStreamWaitEvent(sst, e.ev_[3], 0));
+        }
+        const int before = J.n_chunks;
+        J.n_chunks = e.codec_->stream_push(J.dec_codes, e.Fcap_, avail.data(), fin.data(), J.pcm_host, size_t(e.Fcap_) * J.up,
+                                           J.chunk_done, J.nf_chunk_host);
+        if (before == 0 && J.n_chunks > 0) Q3_HIP(hipEventRecord(J.ev_first_audio, sst));  // behind chunk 0's copy to the host
+    }
+};
+
 int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const DebugOpts* dbg,
                   bool overlapped) {
-    const TalkerConfig& t = m_->cfg.talker;
-    const int V = t.vocab_size, Vc = t.cp.vocab_size, groups = t.num_code_groups;
     Q3_HIP(hipSetDevice(m_->device));  // lanes run on their own host threads
+    std::vector<ResolvedRequest> rr;
+    double t_start = 0;
+    const int slot = open_job(reqs, n, sp, dbg, rr, t_start);
+    bool any_clone = false;
+    for (auto& r : rr) any_clone = any_clone || r.clone;
+    Q3_HIP(hipEventRecord(ev_fe_[0], st_));
+    if (any_clone) prepare_clone_rows(rr);  // codec encoder + speaker encoder, once per request (Qwen3.swift:443, :524)
+    Q3_HIP(hipEventRecord(ev_fe_[1], st_));
+    std::vector<int> np, nt;
+    assemble_prompts(rr, np, nt);
+    const int Pmax = reserve_rows(rr, np, nt, sp);
+    if (dbg) debug_buffers(n, *dbg);
+    // ---- prefill: positions 0 .. Pmax-2 of the right-aligned prompts, then load the last one ----
+    Q3_HIP(hipEventRecord(ev_[0], st_));
+    enqueue_prefill(tk_, n, Pmax, block_table_, kv_len_, n_prompt_, active_);
+    Q3_HIP(hipEventRecord(ev_[1], st_));
+    Job& J = jobs_[slot];
+    J.reset(n, codec_->upsample());
+    J.chunk_frames = sp.audio_chunk_frames;
+    StreamedDecode sd(*this, J, sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && !any_clone && !dbg, sp, cb, user);
+    const int launched = frame_loop(J, rr, sp, cb, user, dbg, sd);
+    hand_off(J, rr, sd, launched, overlapped);
+    job_timing(J, np, launched);
+    publish_job(J, cb, user, request_base, t_start, overlapped);  // a pipelined job: its rows are copied out while the next batch runs
+    return slot;
+}
+
+int Engine::open_job(const q3tts_request* reqs, int n, const q3tts_sampling& sp, const DebugOpts* dbg, std::vector<ResolvedRequest>& rr,
+                     double& t_start) {
     Q3_CHECK(n >= 1 && n <= Bm_, 3, "Invalid input: batch size must be between 1 and max_batch");
-    Q3_CHECK(groups == 16, 3, "Invalid input: num_code_groups must be 16");
+    Q3_CHECK(m_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
     Q3_CHECK(sp.audio_chunk_frames >= 0, 3, "Invalid input: audio_chunk_frames must not be negative");
     if (sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && m_->has_codec)  // before any GPU work (the stream would refuse it later)
         Q3_CHECK(sp.audio_chunk_frames >= codec_->hist_frames(), 3,
@@ -1144,29 +1195,23 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     for (int i = 0; i < kJobSlots; ++i)
         if (!jobs_[i].busy && slot < 0) slot = i;
     Q3_CHECK(slot >= 0, 3, "Invalid input: two jobs are already outstanding (q3tts_generate_end must be called first)");
-    const double t_start = now_s();
+    t_start = now_s();
     Q3_HIP(hipEventRecord(jobs_[slot].ev_begin, st_));
-    std::vector<ResolvedRequest> rr;
     for (int i = 0; i < n; ++i) rr.push_back(resolve(reqs[i], sp));
     if (dbg)
         for (auto& r : rr) r.max_frames = dbg->frames;
     for (auto& r : rr) Q3_CHECK(r.max_frames <= Fcap_, 3, "Invalid input: max_tokens exceeds the configured max_frames");
     if (m_->has_codec == false)
         throw Error(1, "Model not initialized: Speech tokenizer not loaded");  // Qwen3.swift:799-801
+    return slot;
+}
 
-    bool any_clone = false;
-    for (auto& r : rr) any_clone = any_clone || r.clone;
-    Q3_HIP(hipEventRecord(ev_fe_[0], st_));
-    if (any_clone) prepare_clone_rows(rr);  // codec encoder + speaker encoder, once per request (Qwen3.swift:443, :524)
-    Q3_HIP(hipEventRecord(ev_fe_[1], st_));
-
-    std::vector<int> np, nt;
-    assemble_prompts(rr, np, nt);
+int Engine::reserve_rows(const std::vector<ResolvedRequest>& rr, const std::vector<int>& np, const std::vector<int>& nt,
+                         const q3tts_sampling& sp) {
+    const int n = int(rr.size());
     int Pmax = 0;
     for (int p : np) Pmax = std::max(Pmax, p);
-
-    // ---- per-row state ----
-    std::vector<int32_t> bt((size_t)(n) * max_pages_, 0), zeros((size_t)(n), 0), maxf((size_t)(n)), ntr((size_t)(n)), npr((size_t)(n));
+    std::vector<int32_t> bt((size_t)(n) * max_pages_, 0), maxf((size_t)(n)), ntr((size_t)(n)), npr((size_t)(n));
     int next_page = 0;
     for (int b = 0; b < n; ++b) {
         const int need = ceil_div(np[size_t(b)] + rr[size_t(b)].max_frames + 1, kPageTokens);
@@ -1185,122 +1230,44 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     for (int32_t* p : {kv_len_, cp_len_, n_frames_, trailing_idx_}) Q3_HIP(hipMemsetAsync(p, 0, size_t(n) * 4, st_));
     Q3_HIP(hipMemsetAsync(active_, 0, size_t(n), st_));
     Q3_HIP(hipMemsetAsync(finished_, 0, size_t(n), st_));
-    Q3_HIP(hipMemsetAsync(seen_, 0, size_t(n) * V, st_));
+    Q3_HIP(hipMemsetAsync(seen_, 0, size_t(n) * m_->cfg.talker.vocab_size, st_));
     Q3_HIP(hipMemsetAsync(codes_, 0, size_t(n) * Fcap_ * 16 * 4, st_));
-    SamplingParams sph{sp.temperature, sp.top_k, sp.top_p, sp.repetition_penalty, sp.seed, row_offset + sp.row_base, sp.force_frames > 0 ? 1 : 0};
-    Q3_HIP(hipMemcpyAsync(sp_dev_, &sph, sizeof(sph), hipMemcpyHostToDevice, st_));
-    int frames_cap = 0;
-    for (int f : maxf) frames_cap = std::max(frames_cap, f);
-    if (dbg) {
-        for (void* p : {(void*)forced_dev_, (void*)sampled_dev_, (void*)tl_dump_, (void*)cl_dump_})
-            if (p) (void)hipFree(p);
-        forced_dev_ = sampled_dev_ = nullptr;
-        tl_dump_ = cl_dump_ = nullptr;
-        const size_t nf = size_t(n) * dbg->frames;
-        if (dbg->forced_codes) {
-            // teacher-forced codes are fed back as rows of the codec / predictor embedding tables
-            for (size_t i = 0; i < nf * 16; ++i) {
-                const int32_t c = dbg->forced_codes[i];
-                Q3_CHECK(c >= 0 && c < ((i & 15) == 0 ? V : Vc), 3, "Invalid input: forced code outside its vocabulary");
-            }
-            Q3_HIP(hipMalloc(reinterpret_cast<void**>(&forced_dev_), nf * 16 * 4));
-            Q3_HIP(hipMemcpy(forced_dev_, dbg->forced_codes, nf * 16 * 4, hipMemcpyHostToDevice));
+    upload_sampling(sp, row_offset + sp.row_base);
+    return Pmax;
+}
+
+void Engine::debug_buffers(int n, const DebugOpts& dbg) {
+    const TalkerConfig& t = m_->cfg.talker;
+    const int V = t.vocab_size, Vc = t.cp.vocab_size;
+    for (void* p : {(void*)forced_dev_, (void*)sampled_dev_, (void*)tl_dump_, (void*)cl_dump_})
+        if (p) (void)hipFree(p);
+    forced_dev_ = sampled_dev_ = nullptr;
+    tl_dump_ = cl_dump_ = nullptr;
+    const size_t nf = size_t(n) * dbg.frames;
+    if (dbg.forced_codes) {
+        // teacher-forced codes are fed back as rows of the codec / predictor embedding tables
+        for (size_t i = 0; i < nf * 16; ++i) {
+            const int32_t c = dbg.forced_codes[i];
+            Q3_CHECK(c >= 0 && c < ((i & 15) == 0 ? V : Vc), 3, "Invalid input: forced code outside its vocabulary");
         }
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&sampled_dev_), nf * 16 * 4));
-        Q3_HIP(hipMemset(sampled_dev_, 0xff, nf * 16 * 4));
-        if (dbg->talker_logits) Q3_HIP(hipMalloc(reinterpret_cast<void**>(&tl_dump_), nf * V * 2));
-        if (dbg->cp_logits) Q3_HIP(hipMalloc(reinterpret_cast<void**>(&cl_dump_), nf * (groups - 1) * Vc * 2));
+        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&forced_dev_), nf * 16 * 4));
+        Q3_HIP(hipMemcpy(forced_dev_, dbg.forced_codes, nf * 16 * 4, hipMemcpyHostToDevice));
     }
+    Q3_HIP(hipMalloc(reinterpret_cast<void**>(&sampled_dev_), nf * 16 * 4));
+    Q3_HIP(hipMemset(sampled_dev_, 0xff, nf * 16 * 4));
+    if (dbg.talker_logits) Q3_HIP(hipMalloc(reinterpret_cast<void**>(&tl_dump_), nf * V * 2));
+    if (dbg.cp_logits) Q3_HIP(hipMalloc(reinterpret_cast<void**>(&cl_dump_), nf * (t.num_code_groups - 1) * Vc * 2));
+}
 
-    // ---- prefill: positions 0 .. Pmax-2 of the right-aligned prompts, then load the last one ----
-    Q3_HIP(hipEventRecord(ev_[0], st_));
-    enqueue_prefill(tk_, n, Pmax, block_table_, kv_len_, n_prompt_, active_);
-    Q3_HIP(hipEventRecord(ev_[1], st_));
-
-    // ---- streamed decode (row f1): chunks of the waveform leave while the loop below is still producing tokens ----
-    Job& J = jobs_[slot];
-    const bool streamed = sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && !any_clone && !dbg && m_->has_codec;
-    hipStream_t sst = nullptr;
-    std::vector<int> s_avail((size_t)(n), 0);
-    std::vector<uint8_t> s_final((size_t)(n), 0);
-    std::memset(J.nf_host, 0, size_t(Bm_) * 4);
-    J.streamed = false;
-    // the rows' non-finite flags behind every chunk of a decode in pieces (fire_chunks holds a row back from its first flagged chunk)
-    auto chunk_flags = [&](int frames_cap) {
-        const size_t slots = size_t(ceil_div(frames_cap, sp.audio_chunk_frames) + 1) * size_t(n);
-        if (slots > J.nf_chunk_cap) {
-            if (J.nf_chunk_host) Q3_HIP(hipHostFree(J.nf_chunk_host));
-            J.nf_chunk_host = nullptr;
-            J.nf_chunk_cap = 0;
-            Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&J.nf_chunk_host), slots * 4, hipHostMallocDefault));
-            J.nf_chunk_cap = slots;
-        }
-        std::memset(J.nf_chunk_host, 0, slots * 4);
-    };
-    J.held_from.assign(size_t(n), -1);
-    J.chunks_fired = 0;
-    J.t_first_audio = 0;
-    J.n_chunks = 0;
-    if (streamed) {
-        J.n = n;
-        J.up = codec_->upsample();
-        J.Fdec = Fcap_;  // row stride of the job's code and PCM buffers: the final lengths are not known yet
-        J.chunk_frames = sp.audio_chunk_frames;
-        J.cb = cb;
-        J.user = user;
-        J.request_base = request_base;
-        const size_t need = size_t(n) * Fcap_ * 16, floats = size_t(n) * Fcap_ * J.up;
-        if (need > J.dec_codes_cap) {
-            if (J.dec_codes) Q3_HIP(hipFree(J.dec_codes));
-            J.dec_codes = nullptr;
-            Q3_HIP(hipMalloc(reinterpret_cast<void**>(&J.dec_codes), need * 4));
-            J.dec_codes_cap = need;
-        }
-        if (floats > J.pcm_host_cap) {
-            if (J.pcm_host) Q3_HIP(hipHostFree(J.pcm_host));
-            J.pcm_host = nullptr;
-            Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&J.pcm_host), floats * 4, hipHostMallocDefault));
-            J.pcm_host_cap = floats;
-        }
-        chunk_flags(Fcap_);
-        // the decode runs beside this batch's own frame loop: the confined stream, like a decode beside the next batch's
-        sst = codec_stream(true);
-        CodecRunner::StreamCfg cfg;
-        cfg.rows = n; cfg.chunk_frames = sp.audio_chunk_frames; cfg.window = sp.audio_window_frames;
-        cfg.lookahead = std::max(0, sp.audio_lookahead_frames); cfg.max_frames = Fcap_;
-        Q3_HIP(hipEventRecord(J.ev_codec[0], sst));
-        codec_->stream_open(cfg);
-        J.streamed = true;
-    }
-    struct StreamGuard {  // an exception below must not leave the runner's stream open
-        CodecRunner* c;
-        bool on;
-        ~StreamGuard() { if (on && c->streaming()) c->stream_close(); }
-    } stream_guard{codec_.get(), streamed};
-    // frames [0, upto) of every row exist on the device once the copy below has run: hand them to the decoder, which
-    // issues every chunk that s_avail / s_final now allow
-    int s_copied = 0;
-    auto stream_feed = [&](int upto) {
-        if (!streamed) return;
-        if (upto > s_copied) {
-            Q3_HIP(hipMemcpy2DAsync(J.dec_codes + size_t(s_copied) * 16, size_t(Fcap_) * 64, codes_ + size_t(s_copied) * 16,
-                                    size_t(Fcap_) * 64, size_t(upto - s_copied) * 64, size_t(n), hipMemcpyDeviceToDevice, st_));
-            s_copied = upto;
-            Q3_HIP(hipEventRecord(ev_[3], st_));
-            Q3_HIP(hipStreamWaitEvent(sst, ev_[3], 0));
-        }
-        const int before = J.n_chunks;
-        J.n_chunks = codec_->stream_push(J.dec_codes, Fcap_, s_avail.data(), s_final.data(), J.pcm_host, size_t(Fcap_) * J.up, J.chunk_done,
-                                         J.nf_chunk_host);
-        if (before == 0 && J.n_chunks > 0) Q3_HIP(hipEventRecord(J.ev_first_audio, sst));  // behind chunk 0's copy to the host
-    };
-
-    // ---- frame loop ----
+int Engine::frame_loop(Job& J, const std::vector<ResolvedRequest>& rr, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
+                       const DebugOpts* dbg, StreamedDecode& sd) {
+    const int n = J.n;
     const bool use_graph = opts_.use_graph && !dbg;
-    // the tables are cut from the weights, which may arrive after load (weights_from_broadcast): first use, not load
-    if (!cp_tables_ && m_->has_cp_proj && !std::getenv("Q3TTS_NO_PROJ_TABLES")) build_cp_proj_tables();
+    build_cp_proj_tables();
     hipGraphExec_t ge = use_graph ? frame_graph(n) : nullptr;
-    std::vector<int32_t> h_nframes((size_t)(n), 0), h_codes;
+    int frames_cap = 0;
+    for (auto& r : rr) frames_cap = std::max(frames_cap, r.max_frames);
+    std::vector<int32_t> h_nframes((size_t)(n), 0);
     std::vector<uint8_t> h_fin((size_t)(n), 0);
     std::vector<int> reported((size_t)(n), 0);
     int launched = 0;
@@ -1315,7 +1282,7 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     while (!done && launched < frames_cap) {
         if (bursts >= 2) Q3_HIP(hipEventSynchronize(ring[bursts & 1]));  // burst (bursts-2) has drained
         int burst = std::min(burst_frames, frames_cap - launched);
-        if (streamed) {
+        if (sd.on) {
             // a burst ends where the next chunk becomes decodable (its frames + the lookahead), so the chunk is issued behind
             // exactly the frames it needs instead of behind the rest of a full burst (first audio 139 -> 115 ms at 1.7B / batch 32)
             const int need = std::min(frames_cap, (J.n_chunks + 1) * sp.audio_chunk_frames + std::max(0, sp.audio_lookahead_frames));
@@ -1333,93 +1300,73 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
         Q3_HIP(hipEventRecord(ring[bursts & 1], st_));
         ++bursts;
         if (fixed_len && !cb) {
-            if (streamed) {  // every row has exactly `launched` frames (nothing ends early)
-                for (int b = 0; b < n; ++b) s_avail[size_t(b)] = std::min(launched, maxf[size_t(b)]);
-                stream_feed(launched);
+            if (sd.on) {  // every row has exactly `launched` frames (nothing ends early)
+                for (int b = 0; b < n; ++b) sd.avail[size_t(b)] = std::min(launched, rr[size_t(b)].max_frames);
+                sd.feed(launched);
             }
             continue;
         }
         Q3_HIP(hipEventSynchronize(ring[(bursts - 1) & 1]));
         done = true;
         for (int b = 0; b < n; ++b) done = done && h_fin[size_t(b)];
-        if (streamed) {
+        if (sd.on) {
             for (int b = 0; b < n; ++b) {
-                s_avail[size_t(b)] = h_nframes[size_t(b)];
-                s_final[size_t(b)] = h_fin[size_t(b)];
+                sd.avail[size_t(b)] = h_nframes[size_t(b)];
+                sd.fin[size_t(b)] = h_fin[size_t(b)];
             }
-            stream_feed(launched);
-            fire_chunks(J, J.n_chunks, &s_avail, false);  // what has already landed on the host, without waiting
+            sd.feed(launched);
+            fire_chunks(J, J.n_chunks, &sd.avail, false);  // what has already landed on the host, without waiting
         }
-        if (cb) {  // .token events in generation order (Qwen3+Streaming.swift:24-27)
-            for (int b = 0; b < n; ++b) {
-                const int nf = h_nframes[size_t(b)];
-                if (nf > reported[size_t(b)]) {
-                    std::vector<int32_t> tmp((size_t)(nf - reported[size_t(b)]) * 16);
-                    Q3_HIP(hipMemcpy(tmp.data(), codes_ + (size_t(b) * Fcap_ + reported[size_t(b)]) * 16, tmp.size() * 4,
-                                     hipMemcpyDeviceToHost));
-                    std::unique_lock<std::mutex> lk;
-                    if (cb_mutex) lk = std::unique_lock<std::mutex>(*cb_mutex);
-                    for (int f = 0; f < nf - reported[size_t(b)]; ++f) {
-                        q3tts_event ev{};
-                        ev.kind = Q3TTS_EVENT_TOKEN;
-                        ev.request_index = request_base + b;
-                        ev.token = tmp[size_t(f) * 16];
-                        cb(user, &ev);
-                    }
-                    reported[size_t(b)] = nf;
-                }
-            }
-        }
+        if (cb)  // .token events in generation order (Qwen3+Streaming.swift:24-27)
+            for (int b = 0; b < n; ++b) emit_tokens(cb, user, b, request_base + b, h_nframes[size_t(b)], reported[size_t(b)]);
     }
     Q3_HIP(hipEventRecord(ev_[2], st_));
     Q3_HIP(hipMemcpyAsync(h_nframes.data(), n_frames_, size_t(n) * 4, hipMemcpyDeviceToHost, st_));
     Q3_HIP(hipStreamSynchronize(st_));
     if (dbg) {
+        const TalkerConfig& t = m_->cfg.talker;
         const size_t nf = size_t(n) * dbg->frames;
         if (dbg->sampled) Q3_HIP(hipMemcpy(dbg->sampled, sampled_dev_, nf * 16 * 4, hipMemcpyDeviceToHost));
-        if (dbg->talker_logits) Q3_HIP(hipMemcpy(dbg->talker_logits, tl_dump_, nf * V * 2, hipMemcpyDeviceToHost));
-        if (dbg->cp_logits) Q3_HIP(hipMemcpy(dbg->cp_logits, cl_dump_, nf * (groups - 1) * Vc * 2, hipMemcpyDeviceToHost));
+        if (dbg->talker_logits) Q3_HIP(hipMemcpy(dbg->talker_logits, tl_dump_, nf * t.vocab_size * 2, hipMemcpyDeviceToHost));
+        if (dbg->cp_logits)
+            Q3_HIP(hipMemcpy(dbg->cp_logits, cl_dump_, nf * (t.num_code_groups - 1) * t.cp.vocab_size * 2, hipMemcpyDeviceToHost));
     }
+    J.frames.assign(h_nframes.begin(), h_nframes.end());
+    return launched;
+}
 
-    // ---- hand the codes to the codec decoder (Qwen3.swift:943-961) on its own stream ----
-    J.n = n;
-    J.up = codec_->upsample();
-    J.frames.assign(size_t(n), 0);
-    J.ref_T.assign(size_t(n), 0);
-    J.target_tokens.assign(size_t(n), 0);
-    J.ref_code0.assign(size_t(n), {});
+// ---- hand the codes to the codec decoder (Qwen3.swift:943-961) on its own stream ----
+void Engine::hand_off(Job& J, const std::vector<ResolvedRequest>& rr, StreamedDecode& sd, int launched, bool overlapped) {
+    const int n = J.n;
+    bool any_clone = false;
     std::vector<int> dframes((size_t)(n), 0);  // frames the decoder sees per row: [reference ++] generated (:1176-1186)
     int Fdec = 0;
     for (int b = 0; b < n; ++b) {
-        const int F = h_nframes[size_t(b)];
-        J.frames[size_t(b)] = F;
+        const int F = J.frames[size_t(b)];
+        any_clone = any_clone || rr[size_t(b)].clone;
         J.ref_T[size_t(b)] = rr[size_t(b)].clone ? rr[size_t(b)].ref_T : 0;
         J.target_tokens[size_t(b)] = rr[size_t(b)].target_token_count;
         dframes[size_t(b)] = F > 0 ? F + J.ref_T[size_t(b)] : 0;
         Fdec = std::max(Fdec, dframes[size_t(b)]);
     }
-    J.Fdec = streamed ? Fcap_ : Fdec;
+    J.Fdec = sd.on ? Fcap_ : Fdec;
     J.codes_host.resize(size_t(n) * Fcap_ * 16);
     Q3_HIP(hipMemcpyAsync(J.codes_host.data(), codes_, J.codes_host.size() * 4, hipMemcpyDeviceToHost, st_));
-    if (streamed) {  // the remaining chunks: every row is final now
+    if (sd.on) {  // the remaining chunks: every row is final now
         for (int b = 0; b < n; ++b) {
-            s_avail[size_t(b)] = J.frames[size_t(b)];
-            s_final[size_t(b)] = 1;
+            sd.avail[size_t(b)] = J.frames[size_t(b)];
+            sd.fin[size_t(b)] = 1;
         }
-        stream_feed(launched);
+        sd.feed(launched);
         codec_->stream_close(J.nf_host);
         Q3_HIP(hipStreamSynchronize(st_));
-        Q3_HIP(hipEventRecord(J.ev_codec[1], sst));
+        Q3_HIP(hipEventRecord(J.ev_codec[1], sd.sst));
         J.decoded = Fdec > 0;
-    } else if (Fdec > 0) {
+        return;
+    }
+    if (Fdec > 0) {
         // The decoder reads a copy owned by the job: the next begin() overwrites codes_ while this decode may still run.
-        const size_t need = size_t(n) * Fdec * 16;
-        if (need > J.dec_codes_cap) {
-            if (J.dec_codes) Q3_HIP(hipFree(J.dec_codes));
-            J.dec_codes = nullptr;
-            Q3_HIP(hipMalloc(reinterpret_cast<void**>(&J.dec_codes), need * 4));
-            J.dec_codes_cap = need;
-        }
+        J.dec_codes.grow(size_t(n) * Fdec * 16);
         if (any_clone) {
             for (int b = 0; b < n; ++b) {
                 const auto& r = rr[size_t(b)];
@@ -1437,35 +1384,37 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
                                     hipMemcpyDeviceToDevice, st_));
         }
     }
-    if (!streamed) {
     Q3_HIP(hipStreamSynchronize(st_));  // everything of this call on st_ is done; only the decode is still to come
+    start_decode(J, dframes, overlapped, nullptr);
+}
+
+void Engine::start_decode(Job& J, const std::vector<int>& dframes, bool overlapped, const int32_t* codes_host) {
     hipStream_t cst = codec_stream(overlapped);
     Q3_HIP(hipEventRecord(J.ev_codec[0], cst));
-    J.decoded = false;
-    J.n_chunks = 0;
-    J.chunk_frames = sp.audio_chunk_frames > 0 ? sp.audio_chunk_frames : 0;
-    if (Fdec > 0) {
-        const size_t floats = size_t(n) * Fdec * J.up;
-        if (floats > J.pcm_host_cap) {
-            if (J.pcm_host) Q3_HIP(hipHostFree(J.pcm_host));
-            J.pcm_host = nullptr;
-            Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&J.pcm_host), floats * 4, hipHostMallocDefault));
-            J.pcm_host_cap = floats;
+    if (J.Fdec > 0) {
+        const size_t floats = size_t(J.n) * J.Fdec * J.up;
+        J.pcm_host.grow(floats);
+        if (codes_host) {
+            J.dec_codes.grow(size_t(J.n) * J.Fdec * 16);
+            Q3_HIP(hipMemcpy2DAsync(J.dec_codes, size_t(J.Fdec) * 64, codes_host, size_t(Fcap_) * 64, size_t(J.Fdec) * 64, size_t(J.n),
+                                    hipMemcpyHostToDevice, cst));
         }
         if (J.chunk_frames > 0) {
             // pre-transformer once over all frames, then the causal tail chunk by chunk (codec.h decode_chunked)
-            chunk_flags(Fdec);
-            J.n_chunks = codec_->decode_chunked(J.dec_codes, Fdec, dframes, J.chunk_frames, J.pcm_host, J.chunk_done, J.nf_host, J.nf_chunk_host);
+            J.clear_chunk_flags(J.Fdec);
+            J.n_chunks = codec_->decode_chunked(J.dec_codes, J.Fdec, dframes, J.chunk_frames, J.pcm_host, J.chunk_done, J.nf_host,
+                                                J.nf_chunk_host);
         } else {
             float* pcm_dev = nullptr;
-            codec_->decode(J.dec_codes, Fdec, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, J.nf_host);
+            codec_->decode(J.dec_codes, J.Fdec, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, J.nf_host);
             Q3_HIP(hipMemcpyAsync(J.pcm_host, pcm_dev, floats * 4, hipMemcpyDeviceToHost, cst));
         }
         J.decoded = true;
     }
     Q3_HIP(hipEventRecord(J.ev_codec[1], cst));
-    }
-    J.timing = q3tts_timing{};
+}
+
+void Engine::job_timing(Job& J, const std::vector<int>& np, int launched) {
     float ms = 0;
     Q3_HIP(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
     J.timing.prefill_ms = ms;
@@ -1474,38 +1423,97 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     Q3_HIP(hipEventElapsedTime(&ms, ev_fe_[0], ev_fe_[1]));
     J.timing.frontend_ms = ms;
     J.timing.frame_steps = launched;
-    {
-        auto fl = frame_launches_.find(n);
-        J.timing.launches_per_frame_step = fl == frame_launches_.end() ? 0 : fl->second;
-    }
-    J.timing.rows = n;
-    {
-        int64_t kvb = 0;
-        const int64_t per_tok = int64_t(t.num_hidden_layers) * t.num_key_value_heads * kHeadDim * 2 * 2;
-        for (int b = 0; b < n; ++b)
-            for (int f = 0; f < J.frames[size_t(b)]; ++f) kvb += int64_t(np[size_t(b)] - 1 + f) * per_tok;
-        J.timing.kv_bytes_read = kvb;
-    }
-    J.t_start = t_start;
-    J.t_done = 0;
-    J.req_index.clear();  // (a queued call's decode batches used the slot with request indices of their own)
-    J.row_span.clear();
+    J.timing.launches_per_frame_step = launches_per_step(J.n);
+    J.timing.rows = J.n;
+    for (int b = 0; b < J.n; ++b) J.timing.kv_bytes_read += kv_bytes(np[size_t(b)], J.frames[size_t(b)]);
+}
+
+void Engine::publish_job(Job& J, q3tts_event_cb cb, void* user, int req_base, double t_start, bool stage) {
     J.cb = cb;
     J.user = user;
-    J.request_base = request_base;
+    J.request_base = req_base;
+    J.t_start = t_start;
     J.seq = job_seq_++;
     J.busy = true;
     compute_cuts(J);
-    {
-        std::lock_guard<std::mutex> lk(stage_mu_);
-        J.stage_err.clear();
-        J.stage = (overlapped && J.decoded) ? 1 : 0;  // a pipelined job: its rows are copied out while the next batch runs
-        if (J.stage == 1) {
-            if (!stager_.joinable()) stager_ = std::thread([this] { staging_loop(); });
-            stage_cv_.notify_all();
-        }
+    std::lock_guard<std::mutex> lk(stage_mu_);
+    J.stage_err.clear();
+    J.stage = (stage && J.decoded) ? 1 : 0;
+    if (J.stage == 1) {
+        if (!stager_.joinable()) stager_ = std::thread([this] { staging_loop(); });
+        stage_cv_.notify_all();
     }
-    return slot;
+}
+
+void Engine::release_job(Job& J) {
+    {   // a staging thread may still be copying into the rows
+        std::unique_lock<std::mutex> lk(stage_mu_);
+        stage_cv_.wait(lk, [&] { return J.stage != 1; });
+    }
+    J.st_pcm.clear();  // frees every row not handed over to a result
+    J.st_codes.clear();
+    J.busy = false;
+}
+
+void Engine::Job::reset(int rows, int upsample) {
+    n = rows;
+    up = upsample;
+    Fdec = 0;
+    frames.assign(size_t(n), 0);
+    ref_T.assign(size_t(n), 0);
+    target_tokens.assign(size_t(n), 0);
+    ref_code0.assign(size_t(n), {});
+    req_index.clear();  // (a queued call's decode batches used the slot with request indices of their own)
+    row_span.clear();
+    held_from.assign(size_t(n), -1);
+    std::memset(nf_host, 0, nf_host.capacity() * 4);
+    n_chunks = chunk_frames = chunks_fired = 0;
+    streamed = decoded = false;
+    t_first_audio = t_done = 0;
+    timing = q3tts_timing{};
+}
+
+// the rows' non-finite flags behind every chunk of a decode in pieces (fire_chunks holds a row back from its first flagged chunk)
+void Engine::Job::clear_chunk_flags(int frames) {
+    const size_t slots = size_t(ceil_div(frames, chunk_frames) + 1) * size_t(n);
+    std::memset(nf_chunk_host.grow(slots), 0, slots * 4);
+}
+
+void Engine::upload_sampling(const q3tts_sampling& sp, uint32_t row0) {
+    SamplingParams sph{sp.temperature, sp.top_k, sp.top_p, sp.repetition_penalty, sp.seed, row0, sp.force_frames > 0 ? 1 : 0};
+    Q3_HIP(hipMemcpyAsync(sp_dev_, &sph, sizeof(sph), hipMemcpyHostToDevice, st_));
+}
+
+int64_t Engine::kv_bytes(int n_prompt, int frames) const {
+    const TalkerConfig& t = m_->cfg.talker;
+    const int64_t per_tok = int64_t(t.num_hidden_layers) * t.num_key_value_heads * kHeadDim * 2 * 2;
+    int64_t kvb = 0;
+    for (int f = 0; f < frames; ++f) kvb += int64_t(n_prompt - 1 + f) * per_tok;
+    return kvb;
+}
+
+int Engine::launches_per_step(int B) const {
+    auto fl = frame_launches_.find(B);
+    return fl == frame_launches_.end() ? 0 : fl->second;
+}
+
+std::unique_lock<std::mutex> Engine::cb_lock() {
+    return cb_mutex ? std::unique_lock<std::mutex>(*cb_mutex) : std::unique_lock<std::mutex>();
+}
+
+void Engine::emit_tokens(q3tts_event_cb cb, void* user, int row, int request, int nf, int& reported) {
+    if (nf <= reported) return;
+    std::vector<int32_t> tmp((size_t)(nf - reported) * 16);
+    Q3_HIP(hipMemcpy(tmp.data(), codes_ + (size_t(row) * Fcap_ + reported) * 16, tmp.size() * 4, hipMemcpyDeviceToHost));
+    std::unique_lock<std::mutex> lk = cb_lock();
+    for (int f = 0; f < nf - reported; ++f) {
+        q3tts_event ev{};
+        ev.kind = Q3TTS_EVENT_TOKEN;
+        ev.request_index = request;
+        ev.token = tmp[size_t(f) * 16];
+        cb(user, &ev);
+    }
+    reported = nf;
 }
 
 // samples [cut, cut + ns) of row b's decoded stream are its audio: audioLengths = count(code0 > 0) * 1920, trimmed when
@@ -1557,21 +1565,14 @@ void Engine::fire_chunks(Job& J, int upto, const std::vector<int>* known, bool w
                 if (J.held_from[size_t(b)] < 0 && J.nf_chunk_host[size_t(k) * n + b]) J.held_from[size_t(b)] = k;
         if (!J.cb) continue;
         const int64_t c0 = int64_t(k) * J.chunk_frames * up, c1 = std::min<int64_t>(int64_t(J.Fdec), int64_t(k + 1) * J.chunk_frames) * up;
-        std::unique_lock<std::mutex> lk;
-        if (cb_mutex) lk = std::unique_lock<std::mutex>(*cb_mutex);
+        std::unique_lock<std::mutex> lk = cb_lock();
         for (int b = 0; b < n; ++b) {
             if (J.held_from[size_t(b)] >= 0) continue;
             const int64_t cut = known ? 0 : J.row_cut[size_t(b)];
             const int64_t len = known ? int64_t((*known)[size_t(b)]) * up : J.row_ns[size_t(b)];
             const int64_t lo = std::max(c0, cut), hi = std::min(c1, cut + len);
             if (hi <= lo) continue;
-            q3tts_event ev{};
-            ev.kind = Q3TTS_EVENT_AUDIO_CHUNK;
-            ev.request_index = J.request_base + b;
-            ev.pcm = J.pcm_host + size_t(b) * J.Fdec * up + lo;
-            ev.n_samples = hi - lo;
-            ev.sample_offset = lo - cut;
-            J.cb(J.user, &ev);
+            audio_chunk(J.cb, J.user, J.request_base + b, J.pcm_host + size_t(b) * J.Fdec * up + lo, hi - lo, lo - cut);
         }
     }
 }
@@ -1582,17 +1583,19 @@ void Engine::stage_rows(Job& J) {
     J.t_done = now_s();  // the job's own completion, not the moment end() happens to be called (a pipelined job's end()
                          // comes after the NEXT batch's whole frame loop)
     const int n = J.n;
-    J.st_pcm.assign(size_t(n), nullptr);
-    J.st_codes.assign(size_t(n), nullptr);
+    J.st_pcm.clear();
+    J.st_pcm.resize(size_t(n));
+    J.st_codes.clear();
+    J.st_codes.resize(size_t(n));
     for (int b = 0; b < n; ++b) {
         const int F = J.frames[size_t(b)];
         if (F == 0 || !J.decoded) continue;
         const int64_t ns = J.row_ns[size_t(b)];
-        J.st_codes[size_t(b)] = static_cast<int32_t*>(std::malloc(size_t(F) * 16 * 4));
-        J.st_pcm[size_t(b)] = static_cast<float*>(std::malloc(std::max<size_t>(size_t(ns) * 4, 4)));
+        J.st_codes[size_t(b)].reset(static_cast<int32_t*>(std::malloc(size_t(F) * 16 * 4)));
+        J.st_pcm[size_t(b)].reset(static_cast<float*>(std::malloc(std::max<size_t>(size_t(ns) * 4, 4))));
         Q3_CHECK(J.st_codes[size_t(b)] && J.st_pcm[size_t(b)], 5, "out of host memory for the results");
-        std::memcpy(J.st_codes[size_t(b)], J.codes_host.data() + size_t(b) * Fcap_ * 16, size_t(F) * 16 * 4);
-        std::memcpy(J.st_pcm[size_t(b)], J.pcm_host + size_t(b) * J.Fdec * J.up + J.row_cut[size_t(b)], size_t(ns) * 4);
+        std::memcpy(J.st_codes[size_t(b)].get(), J.codes_host.data() + size_t(b) * Fcap_ * 16, size_t(F) * 16 * 4);
+        std::memcpy(J.st_pcm[size_t(b)].get(), J.pcm_host + size_t(b) * J.Fdec * J.up + J.row_cut[size_t(b)], size_t(ns) * 4);
     }
 }
 
@@ -1645,60 +1648,42 @@ std::vector<int> Engine::redo_rows_fp32(Job& J) {
         Fd = std::max(Fd, dframes[size_t(i)]);
     }
     hipStream_t cst = codec_stream(false);
-    int32_t* dcodes = nullptr;
-    int32_t* nf = nullptr;
-    float* hpcm = nullptr;
-    auto cleanup = [&] {
-        if (dcodes) (void)hipFree(dcodes);
-        if (nf) (void)hipHostFree(nf);
-        if (hpcm) (void)hipHostFree(hpcm);
-    };
-    try {
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&dcodes), size_t(R) * Fd * 64));
-        Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&nf), size_t(R) * 4, hipHostMallocDefault));
-        Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&hpcm), size_t(R) * Fd * up * 4, hipHostMallocDefault));
-        std::memset(nf, 0, size_t(R) * 4);
-        // the codes the first decode read: the job's own device copy ([reference ++] generated; row stride J.Fdec frames)
-        for (int i = 0; i < R; ++i)
-            Q3_HIP(hipMemcpyAsync(dcodes + size_t(i) * Fd * 16, J.dec_codes + size_t(rows[size_t(i)]) * J.Fdec * 16,
-                                  size_t(dframes[size_t(i)]) * 64, hipMemcpyDeviceToDevice, cst));
-        float* pcm_dev = nullptr;
-        codec_->decode(dcodes, Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
-        Q3_HIP(hipMemcpyAsync(hpcm, pcm_dev, size_t(R) * Fd * up * 4, hipMemcpyDeviceToHost, cst));
-        Q3_HIP(hipStreamSynchronize(cst));
-        for (int i = 0; i < R; ++i) {
-            const int b = rows[size_t(i)];
-            if (nf[i]) {
-                bad.push_back(b);
-                continue;
-            }
-            // decoded-stream coordinates: sample p of the decode is sample p - cut of the row's audio; chunk k covers
-            // [k * step, (k + 1) * step). Chunks below `held` have been delivered from the first decode and stay as they are.
-            const int64_t cut = J.row_cut[size_t(b)], ns = J.row_ns[size_t(b)], step = int64_t(std::max(J.chunk_frames, 1)) * up;
-            const int held = J.n_chunks > 0 ? std::max(0, J.held_from[size_t(b)]) : 0;
-            const int64_t from = J.n_chunks > 0 ? std::min(ns, std::max<int64_t>(0, int64_t(held) * step - cut)) : 0;
-            std::memcpy(J.st_pcm[size_t(b)] + from, hpcm + size_t(i) * Fd * up + cut + from, size_t(ns - from) * 4);
-            if (J.cb && J.n_chunks > 0) {  // the pieces fire_chunks held back
-                std::unique_lock<std::mutex> lk;
-                if (cb_mutex) lk = std::unique_lock<std::mutex>(*cb_mutex);
-                for (int k = held; k < J.n_chunks; ++k) {
-                    const int64_t lo = std::max(int64_t(k) * step, cut), hi = std::min(int64_t(k + 1) * step, cut + ns);
-                    if (hi <= lo) continue;
-                    q3tts_event ev{};
-                    ev.kind = Q3TTS_EVENT_AUDIO_CHUNK;
-                    ev.request_index = J.request_base + b;
-                    ev.pcm = J.st_pcm[size_t(b)] + (lo - cut);
-                    ev.n_samples = hi - lo;
-                    ev.sample_offset = lo - cut;
-                    J.cb(J.user, &ev);
-                }
+    DevBuf<int32_t> dcodes;
+    PinnedBuf<int32_t> nf;
+    PinnedBuf<float> hpcm;
+    dcodes.grow(size_t(R) * Fd * 16);
+    nf.grow(size_t(R));
+    hpcm.grow(size_t(R) * Fd * up);
+    std::memset(nf, 0, size_t(R) * 4);
+    // the codes the first decode read: the job's own device copy ([reference ++] generated; row stride J.Fdec frames)
+    for (int i = 0; i < R; ++i)
+        Q3_HIP(hipMemcpyAsync(dcodes + size_t(i) * Fd * 16, J.dec_codes + size_t(rows[size_t(i)]) * J.Fdec * 16,
+                              size_t(dframes[size_t(i)]) * 64, hipMemcpyDeviceToDevice, cst));
+    float* pcm_dev = nullptr;
+    codec_->decode(dcodes, Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
+    Q3_HIP(hipMemcpyAsync(hpcm, pcm_dev, size_t(R) * Fd * up * 4, hipMemcpyDeviceToHost, cst));
+    Q3_HIP(hipStreamSynchronize(cst));
+    for (int i = 0; i < R; ++i) {
+        const int b = rows[size_t(i)];
+        if (nf[i]) {
+            bad.push_back(b);
+            continue;
+        }
+        // decoded-stream coordinates: sample p of the decode is sample p - cut of the row's audio; chunk k covers
+        // [k * step, (k + 1) * step). Chunks below `held` have been delivered from the first decode and stay as they are.
+        const int64_t cut = J.row_cut[size_t(b)], ns = J.row_ns[size_t(b)], step = int64_t(std::max(J.chunk_frames, 1)) * up;
+        const int held = J.n_chunks > 0 ? std::max(0, J.held_from[size_t(b)]) : 0;
+        const int64_t from = J.n_chunks > 0 ? std::min(ns, std::max<int64_t>(0, int64_t(held) * step - cut)) : 0;
+        float* pcm = J.st_pcm[size_t(b)].get();
+        std::memcpy(pcm + from, hpcm + size_t(i) * Fd * up + cut + from, size_t(ns - from) * 4);
+        if (J.cb && J.n_chunks > 0) {  // the pieces fire_chunks held back
+            std::unique_lock<std::mutex> lk = cb_lock();
+            for (int k = held; k < J.n_chunks; ++k) {
+                const int64_t lo = std::max(int64_t(k) * step, cut), hi = std::min(int64_t(k + 1) * step, cut + ns);
+                if (hi > lo) audio_chunk(J.cb, J.user, J.request_base + b, pcm + (lo - cut), hi - lo, lo - cut);
             }
         }
-    } catch (...) {
-        cleanup();
-        throw;
     }
-    cleanup();
     return bad;
 }
 
@@ -1711,20 +1696,7 @@ void Engine::end(int job, q3tts_result* results) {
     struct Release {
         Engine* e;
         Job* j;
-        bool handed_over = false;
-        ~Release() {
-            if (!handed_over) {
-                {   // a staging thread may still be copying into the vectors
-                    std::unique_lock<std::mutex> lk(e->stage_mu_);
-                    e->stage_cv_.wait(lk, [&] { return j->stage != 1; });
-                }
-                for (float* p : j->st_pcm) std::free(p);
-                for (int32_t* p : j->st_codes) std::free(p);
-            }
-            j->st_pcm.clear();
-            j->st_codes.clear();
-            j->busy = false;
-        }
+        ~Release() { e->release_job(*j); }
     } release{this, &J};
     Q3_HIP(hipSetDevice(m_->device));
     const int n = J.n;
@@ -1778,22 +1750,16 @@ void Engine::end(int job, q3tts_result* results) {
         if (std::find(still_bad.begin(), still_bad.end(), b) != still_bad.end()) {  // never hand out a waveform with holes in it
             r.status = Q3TTS_ERR_AUDIO_DECODING_FAILED;
             last_error = kCodecRangeMsg;
-            std::free(J.st_pcm[size_t(b)]);
-            std::free(J.st_codes[size_t(b)]);
-            J.st_pcm[size_t(b)] = nullptr;
-            J.st_codes[size_t(b)] = nullptr;
             continue;
         }
         r.n_frames = F;
-        r.codes = J.st_codes[size_t(b)];  // ownership passes to the result (q3tts_result_free)
+        r.codes = J.st_codes[size_t(b)].release();  // ownership passes to the result (q3tts_result_free)
         r.n_samples = row_ns[size_t(b)];
-        r.pcm = J.st_pcm[size_t(b)];
+        r.pcm = J.st_pcm[size_t(b)].release();
         r.status = Q3TTS_OK;
     }
-    release.handed_over = true;
     if (J.cb) {
-        std::unique_lock<std::mutex> lk;
-        if (cb_mutex) lk = std::unique_lock<std::mutex>(*cb_mutex);
+        std::unique_lock<std::mutex> lk = cb_lock();
         for (int b = 0; b < n; ++b) {
             if (out(b).status != Q3TTS_OK) continue;
             q3tts_event ev{};
@@ -1872,8 +1838,24 @@ void Engine::ensure_queue_ws() {
     qws_ = base;
 }
 
-std::vector<int> Engine::admit(const std::vector<ResolvedRequest>& rr, const std::vector<int>& slots, const std::vector<uint32_t>& keys) {
+int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained) {
+    std::vector<ResolvedRequest> rr;
+    std::vector<int> slots, idx;
+    std::vector<uint32_t> keys;
+    for (int s = 0; s < int(sl.size()) && !drained; ++s) {
+        if (sl[size_t(s)].req >= 0) continue;
+        const int i = q.next.fetch_add(1);
+        if (i >= q.n) {
+            drained = true;
+            break;
+        }
+        rr.push_back((*q.reqs)[size_t(i)]);
+        slots.push_back(s);
+        idx.push_back(i);
+        keys.push_back(q.row_base + uint32_t(i));  // request i draws what q3tts_generate draws with row_base + i
+    }
     const int k = int(rr.size());
+    if (k == 0) return 0;
     std::vector<int> np, nt;
     assemble_prompts(rr, np, nt, &slots);  // prompt_ rows 0..k-1; trailing text into the slots' rows (synchronises st_)
     int Pmax = 0;
@@ -1905,7 +1887,9 @@ std::vector<int> Engine::admit(const std::vector<ResolvedRequest>& rr, const std
     a.finished = finished_; a.active = active_; a.seen = seen_;
     launch_admit_rows(a, k, st_);
     Q3_HIP(hipEventRecord(ev_[1], st_));
-    return np;
+    const double now = now_s();
+    for (int j = 0; j < k; ++j) sl[size_t(slots[size_t(j)])] = QSlot{idx[size_t(j)], 0, 0, np[size_t(j)], now};
+    return k;
 }
 
 // The slot loop. Slot s owns KV pages [s * max_pages_, (s + 1) * max_pages_) for the whole call. Every burst boundary:
@@ -1915,7 +1899,6 @@ std::vector<int> Engine::admit(const std::vector<ResolvedRequest>& rr, const std
 // and, while the burst runs, a decode batch that has landed is delivered (INFO / AUDIO, results) and, the codec stream being
 // idle, every retired row waiting is decoded in one batch beside the frame loop (the confined stream of a pipelined job).
 void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_event_cb cb, void* user) {
-    const TalkerConfig& t = m_->cfg.talker;
     Q3_HIP(hipSetDevice(m_->device));
     Q3_CHECK(S >= 1 && S <= Bm_, 3, "Invalid input: slots must be between 1 and max_batch");
     Q3_CHECK(!job_outstanding(), 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
@@ -1930,9 +1913,8 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     Q3_HIP(hipMemsetAsync(row_key_, 0, size_t(S) * 4, st_));
     Q3_HIP(hipMemsetAsync(active_, 0, size_t(S), st_));
     Q3_HIP(hipMemsetAsync(finished_, 1, size_t(S), st_));
-    SamplingParams sph{sp.temperature, sp.top_k, sp.top_p, sp.repetition_penalty, sp.seed, 0u, sp.force_frames > 0 ? 1 : 0};
-    Q3_HIP(hipMemcpyAsync(sp_dev_, &sph, sizeof(sph), hipMemcpyHostToDevice, st_));
-    if (!cp_tables_ && m_->has_cp_proj && !std::getenv("Q3TTS_NO_PROJ_TABLES")) build_cp_proj_tables();
+    upload_sampling(sp, 0u);
+    build_cp_proj_tables();
     struct KeyScope {
         Engine* e;
         ~KeyScope() { e->frame_row_key_ = nullptr; }
@@ -1941,14 +1923,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     hipGraphExec_t ge = opts_.use_graph ? frame_graph(S) : nullptr;
     Q3_HIP(hipStreamSynchronize(st_));
 
-    struct Slot {
-        int req = -1;       // request in this slot, -1: empty
-        int since = 0;      // frame steps since its admission
-        int reported = 0;   // TOKEN events delivered
-        int np = 0;
-        double t0 = 0;      // admission (host clock)
-    };
-    std::vector<Slot> sl((size_t)(S));
+    std::vector<QSlot> sl((size_t)(S));
     struct Retired {
         int req, frames;
         double span;
@@ -1961,17 +1936,8 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         int* dec;
         ~DecodeGuard() {
             if (*dec < 0) return;
-            Job& J = e->jobs_[*dec];
-            (void)hipEventSynchronize(J.ev_codec[1]);
-            {
-                std::unique_lock<std::mutex> lk(e->stage_mu_);
-                e->stage_cv_.wait(lk, [&] { return J.stage != 1; });
-            }
-            for (float* p : J.st_pcm) std::free(p);
-            for (int32_t* p : J.st_codes) std::free(p);
-            J.st_pcm.clear();
-            J.st_codes.clear();
-            J.busy = false;
+            (void)hipEventSynchronize(e->jobs_[*dec].ev_codec[1]);
+            e->release_job(e->jobs_[*dec]);
         }
     } dec_guard{this, &dec};
     double codec_ms = 0;
@@ -1988,17 +1954,10 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     auto decode = [&](bool overlapped) {  // every waiting row (up to max_batch) in one decode on the codec stream
         Job& J = jobs_[0];
         const int R = std::min(int(waiting.size()), Bm_);
-        J.n = R;
-        J.up = codec_->upsample();
-        J.frames.assign(size_t(R), 0);
-        J.ref_T.assign(size_t(R), 0);
-        J.target_tokens.assign(size_t(R), 0);
-        J.ref_code0.assign(size_t(R), {});
+        J.reset(R, codec_->upsample());
         J.req_index.assign(size_t(R), 0);
         J.row_span.assign(size_t(R), 0);
         J.codes_host.assign(size_t(R) * Fcap_ * 16, 0);
-        std::vector<int> dframes((size_t)(R), 0);
-        int Fdec = 0;
         for (int b = 0; b < R; ++b) {
             const Retired& w = waiting[size_t(b)];
             J.frames[size_t(b)] = w.frames;
@@ -2006,66 +1965,17 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             J.req_index[size_t(b)] = w.req;
             J.row_span[size_t(b)] = w.span;
             std::copy(w.codes.begin(), w.codes.end(), J.codes_host.begin() + ptrdiff_t(size_t(b) * Fcap_ * 16));
-            dframes[size_t(b)] = w.frames;
-            Fdec = std::max(Fdec, w.frames);
+            J.Fdec = std::max(J.Fdec, w.frames);
         }
         waiting.erase(waiting.begin(), waiting.begin() + R);
-        J.Fdec = Fdec;
-        J.decoded = false;
-        J.streamed = false;
-        J.n_chunks = 0;
-        J.chunk_frames = 0;
-        J.chunks_fired = 0;
-        J.t_first_audio = 0;
-        J.held_from.assign(size_t(R), -1);
-        std::memset(J.nf_host, 0, size_t(Bm_) * 4);
-        hipStream_t cst = codec_stream(overlapped);
-        Q3_HIP(hipEventRecord(J.ev_codec[0], cst));
-        if (Fdec > 0) {
-            const size_t need = size_t(R) * Fdec * 16, floats = size_t(R) * Fdec * J.up;
-            if (need > J.dec_codes_cap) {
-                if (J.dec_codes) Q3_HIP(hipFree(J.dec_codes));
-                J.dec_codes = nullptr;
-                Q3_HIP(hipMalloc(reinterpret_cast<void**>(&J.dec_codes), need * 4));
-                J.dec_codes_cap = need;
-            }
-            if (floats > J.pcm_host_cap) {
-                if (J.pcm_host) Q3_HIP(hipHostFree(J.pcm_host));
-                J.pcm_host = nullptr;
-                Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&J.pcm_host), floats * 4, hipHostMallocDefault));
-                J.pcm_host_cap = floats;
-            }
-            Q3_HIP(hipMemcpy2DAsync(J.dec_codes, size_t(Fdec) * 64, J.codes_host.data(), size_t(Fcap_) * 64, size_t(Fdec) * 64, size_t(R),
-                                    hipMemcpyHostToDevice, cst));
-            float* pcm_dev = nullptr;
-            codec_->decode(J.dec_codes, Fdec, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, J.nf_host);
-            Q3_HIP(hipMemcpyAsync(J.pcm_host, pcm_dev, floats * 4, hipMemcpyDeviceToHost, cst));
-            J.decoded = true;
-        }
-        Q3_HIP(hipEventRecord(J.ev_codec[1], cst));
-        J.timing = q3tts_timing{};
-        J.t_start = t_call;
-        J.t_done = 0;
-        J.cb = cb;
-        J.user = user;
-        J.request_base = 0;
-        J.seq = job_seq_++;
-        J.busy = true;
+        start_decode(J, J.frames, overlapped, J.codes_host.data());
         dec = 0;
-        compute_cuts(J);
-        std::lock_guard<std::mutex> lk(stage_mu_);
-        J.stage_err.clear();
-        J.stage = J.decoded ? 1 : 0;  // copied out by the staging thread while the frame loop goes on
-        if (J.stage == 1) {
-            if (!stager_.joinable()) stager_ = std::thread([this] { staging_loop(); });
-            stage_cv_.notify_all();
-        }
+        publish_job(J, cb, user, 0, t_call, true);  // copied out by the staging thread while the frame loop goes on
     };
 
     const int burst_frames = std::max(1, max_inflight_frames / 2);
     std::vector<int32_t> h_nframes((size_t)(S), 0);
     std::vector<uint8_t> h_fin((size_t)(S), 0);
-    const int64_t per_tok = int64_t(t.num_hidden_layers) * t.num_key_value_heads * kHeadDim * 2 * 2;
     int64_t kvb = 0;
     int launched = 0, served = 0;
     bool drained = false;
@@ -2073,37 +1983,11 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     Q3_HIP(hipEventRecord(ev_[2], st_));
     for (;;) {
         // ---- admission: free slots in slot order take the next requests in request order ----
-        std::vector<ResolvedRequest> ar;
-        std::vector<int> as, ai;
-        std::vector<uint32_t> ak;
-        for (int s = 0; s < S && !drained; ++s) {
-            if (sl[size_t(s)].req >= 0) continue;
-            const int i = q.next.fetch_add(1);
-            if (i >= q.n) {
-                drained = true;
-                break;
-            }
-            ar.push_back((*q.reqs)[size_t(i)]);
-            as.push_back(s);
-            ai.push_back(i);
-            ak.push_back(q.row_base + uint32_t(i));  // request i draws what q3tts_generate draws with row_base + i
-        }
-        const bool admitted = !ar.empty();
-        if (admitted) {
-            const std::vector<int> np = admit(ar, as, ak);
-            const double now = now_s();
-            for (size_t j = 0; j < as.size(); ++j) {
-                Slot& x = sl[size_t(as[j])];
-                x = Slot{};
-                x.req = ai[j];
-                x.np = np[j];
-                x.t0 = now;
-            }
-            served += int(ar.size());
-        }
+        const int admitted = admit(q, sl, drained);
+        served += admitted;
         // ---- burst: no longer than the first running row's remaining frames (its cap ends it on time) ----
         int running = 0, burst = burst_frames;
-        for (const Slot& x : sl)
+        for (const QSlot& x : sl)
             if (x.req >= 0) {
                 ++running;
                 burst = std::min(burst, (*q.reqs)[size_t(x.req)].max_frames - x.since);
@@ -2131,31 +2015,18 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         bool any_retired = false;
         const double now = now_s();
         for (int s = 0; s < S; ++s) {
-            Slot& x = sl[size_t(s)];
+            QSlot& x = sl[size_t(s)];
             if (x.req < 0) continue;
             x.since += burst;
             const int nf = h_nframes[size_t(s)];
-            if (cb && nf > x.reported) {
-                std::vector<int32_t> tmp((size_t)(nf - x.reported) * 16);
-                Q3_HIP(hipMemcpy(tmp.data(), codes_ + (size_t(s) * Fcap_ + x.reported) * 16, tmp.size() * 4, hipMemcpyDeviceToHost));
-                std::unique_lock<std::mutex> lk;
-                if (cb_mutex) lk = std::unique_lock<std::mutex>(*cb_mutex);
-                for (int f = 0; f < nf - x.reported; ++f) {
-                    q3tts_event ev{};
-                    ev.kind = Q3TTS_EVENT_TOKEN;
-                    ev.request_index = x.req;
-                    ev.token = tmp[size_t(f) * 16];
-                    cb(user, &ev);
-                }
-                x.reported = nf;
-            }
+            if (cb) emit_tokens(cb, user, s, x.req, nf, x.reported);
             if (!h_fin[size_t(s)]) continue;
             // copied out before the slot's next admission resets its row (stream order on st_)
             waiting.push_back(Retired{x.req, nf, now - x.t0, std::vector<int32_t>((size_t)(nf) * 16)});
             if (nf > 0)
                 Q3_HIP(hipMemcpyAsync(waiting.back().codes.data(), codes_ + size_t(s) * Fcap_ * 16, size_t(nf) * 64, hipMemcpyDeviceToHost, st_));
-            for (int f = 0; f < nf; ++f) kvb += int64_t(x.np - 1 + f) * per_tok;
-            x = Slot{};
+            kvb += kv_bytes(x.np, nf);
+            x = QSlot{};
             any_retired = true;
         }
         if (any_retired) Q3_HIP(hipStreamSynchronize(st_));
@@ -2176,8 +2047,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     tm.frame_steps = launched;
     tm.rows = served;
     tm.kv_bytes_read = kvb;
-    auto fl = frame_launches_.find(S);
-    tm.launches_per_frame_step = fl == frame_launches_.end() ? 0 : fl->second;
+    tm.launches_per_frame_step = launches_per_step(S);
     timing = tm;
 }
 
@@ -2271,49 +2141,31 @@ void Engine::codec_decode(const int32_t* codes, const int32_t* n_frames, int bat
         Fmax = std::max(Fmax, n_frames[b]);
     }
     check_caller_codes(m_->codec, codes, n_frames, batch, max_frames);
-    int32_t* dcodes = nullptr;
-    Q3_HIP(hipMalloc(reinterpret_cast<void**>(&dcodes), size_t(batch) * max_frames * 16 * 4));
+    DevBuf<int32_t> dcodes;
+    dcodes.grow(size_t(batch) * max_frames * 16);
     Q3_HIP(hipMemcpy(dcodes, codes, size_t(batch) * max_frames * 16 * 4, hipMemcpyHostToDevice));
     float* pcm_dev = nullptr;
     hipStream_t cst = codec_stream(false);
-    int32_t* nf = nullptr;  // pinned: rows whose waveform came out non-finite
-    Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&nf), size_t(batch) * 4, hipHostMallocDefault));
+    PinnedBuf<int32_t> nf;  // rows whose waveform came out non-finite
+    nf.grow(size_t(batch));
     std::memset(nf, 0, size_t(batch) * 4);
     Q3_HIP(hipEventRecord(ev_[2], cst));
-    try {
-        if (Fmax > 0) codec_->decode(dcodes, max_frames, frames, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf);
-    } catch (...) {
-        (void)hipFree(dcodes);
-        (void)hipHostFree(nf);
-        throw;
-    }
+    if (Fmax > 0) codec_->decode(dcodes, max_frames, frames, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf);
     Q3_HIP(hipEventRecord(ev_[3], cst));
     Q3_HIP(hipStreamSynchronize(cst));
-    {
-        bool bad = false;
+    bool bad = false;
+    for (int b = 0; b < batch; ++b) bad = bad || nf[b] != 0;
+    if (bad && !codec_->fp32_convs()) {
+        // an activation left the fp16 range of the default kernels: the whole call once more on the fp32 matrix cores (the
+        // reference's range; redo_rows_fp32 does the same for rows of a generate call)
+        std::memset(nf, 0, size_t(batch) * 4);
+        codec_->decode(dcodes, max_frames, frames, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
+        Q3_HIP(hipEventRecord(ev_[3], cst));
+        Q3_HIP(hipStreamSynchronize(cst));
+        bad = false;
         for (int b = 0; b < batch; ++b) bad = bad || nf[b] != 0;
-        if (bad && !codec_->fp32_convs()) {
-            // an activation left the fp16 range of the default kernels: the whole call once more on the fp32 matrix cores (the
-            // reference's range; redo_rows_fp32 does the same for rows of a generate call)
-            std::memset(nf, 0, size_t(batch) * 4);
-            try {
-                codec_->decode(dcodes, max_frames, frames, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
-                Q3_HIP(hipEventRecord(ev_[3], cst));
-                Q3_HIP(hipStreamSynchronize(cst));
-            } catch (...) {
-                (void)hipFree(dcodes);
-                (void)hipHostFree(nf);
-                throw;
-            }
-            bad = false;
-            for (int b = 0; b < batch; ++b) bad = bad || nf[b] != 0;
-        }
-        (void)hipHostFree(nf);
-        if (bad) {
-            (void)hipFree(dcodes);
-            throw Error(4, kCodecRangeMsg);
-        }
     }
+    if (bad) throw Error(4, kCodecRangeMsg);
     float ms = 0;
     Q3_HIP(hipEventElapsedTime(&ms, ev_[2], ev_[3]));
     timing.codec_ms = ms;
@@ -2326,7 +2178,6 @@ void Engine::codec_decode(const int32_t* codes, const int32_t* n_frames, int bat
         for (int f = 0; f < F; ++f) valid += codes[(size_t(b) * max_frames + f) * 16] > 0 ? 1 : 0;
         audio_lengths[b] = int64_t(valid) * up;  // SpeechTokenizer.swift:831-833
     }
-    (void)hipFree(dcodes);
 }
 
 void Engine::codec_decode_streamed(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, int chunk_frames, int window,
@@ -2334,76 +2185,64 @@ void Engine::codec_decode_streamed(const int32_t* codes, const int32_t* n_frames
     Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");
     Q3_CHECK(batch >= 1 && max_frames >= 1 && chunk_frames >= 1, 3, "Invalid input: empty codec batch");
     const int up = codec_->upsample();
-    int32_t* dcodes = nullptr;
-    float* hpcm = nullptr;
-    std::vector<hipEvent_t> done;
-    auto cleanup = [&] {
-        for (auto e : done) (void)hipEventDestroy(e);
-        if (dcodes) (void)hipFree(dcodes);
-        if (hpcm) (void)hipHostFree(hpcm);
-    };
+    DevBuf<int32_t> dcodes;
+    PinnedBuf<float> hpcm;
+    struct Events {  // chunk_done of stream_push
+        std::vector<hipEvent_t> v;
+        ~Events() {
+            for (auto e : v) (void)hipEventDestroy(e);
+        }
+    } done;
+    dcodes.grow(size_t(batch) * max_frames * 16);
+    Q3_HIP(hipMemcpy(dcodes, codes, size_t(batch) * max_frames * 16 * 4, hipMemcpyHostToDevice));
+    hpcm.grow(size_t(batch) * max_frames * up);
+    std::memset(hpcm, 0, size_t(batch) * max_frames * up * 4);
+    std::vector<int> avail((size_t)(batch));
+    std::vector<uint8_t> fin((size_t)(batch), 1);
+    int Fmax = 0;
+    for (int b = 0; b < batch; ++b) {
+        Q3_CHECK(n_frames[b] >= 0 && n_frames[b] <= max_frames, 3, "Invalid input: n_frames out of range");
+        avail[size_t(b)] = n_frames[b];
+        Fmax = std::max(Fmax, n_frames[b]);
+    }
+    check_caller_codes(m_->codec, codes, n_frames, batch, max_frames);
+    hipStream_t cst = codec_stream(false);
+    CodecRunner::StreamCfg cfg;
+    cfg.rows = batch; cfg.chunk_frames = chunk_frames; cfg.window = window; cfg.lookahead = lookahead; cfg.max_frames = std::max(Fmax, 1);
+    codec_->stream_open(cfg);
     try {
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&dcodes), size_t(batch) * max_frames * 16 * 4));
-        Q3_HIP(hipMemcpy(dcodes, codes, size_t(batch) * max_frames * 16 * 4, hipMemcpyHostToDevice));
-        Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&hpcm), size_t(batch) * max_frames * up * 4, hipHostMallocDefault));
-        std::memset(hpcm, 0, size_t(batch) * max_frames * up * 4);
-        std::vector<int> avail((size_t)(batch));
-        std::vector<uint8_t> fin((size_t)(batch), 1);
-        int Fmax = 0;
-        for (int b = 0; b < batch; ++b) {
-            Q3_CHECK(n_frames[b] >= 0 && n_frames[b] <= max_frames, 3, "Invalid input: n_frames out of range");
-            avail[size_t(b)] = n_frames[b];
-            Fmax = std::max(Fmax, n_frames[b]);
-        }
-        check_caller_codes(m_->codec, codes, n_frames, batch, max_frames);
-        hipStream_t cst = codec_stream(false);
-        CodecRunner::StreamCfg cfg;
-        cfg.rows = batch; cfg.chunk_frames = chunk_frames; cfg.window = window; cfg.lookahead = lookahead; cfg.max_frames = std::max(Fmax, 1);
-        codec_->stream_open(cfg);
-        try {
-            // as a stream would deliver them: frames become available chunk by chunk (window >= 0); all at once otherwise
-            if (window >= 0) {
-                std::vector<uint8_t> notyet((size_t)(batch), 0);
-                for (int have = chunk_frames; have < Fmax + chunk_frames + lookahead; have += chunk_frames) {
-                    std::vector<int> a((size_t)(batch));
-                    for (int b = 0; b < batch; ++b) {
-                        a[size_t(b)] = std::min(avail[size_t(b)], have);
-                        notyet[size_t(b)] = a[size_t(b)] == avail[size_t(b)] ? 1 : 0;
-                    }
-                    codec_->stream_push(dcodes, max_frames, a.data(), notyet.data(), hpcm, size_t(max_frames) * up, done);
+        // as a stream would deliver them: frames become available chunk by chunk (window >= 0); all at once otherwise
+        if (window >= 0) {
+            std::vector<uint8_t> notyet((size_t)(batch), 0);
+            for (int have = chunk_frames; have < Fmax + chunk_frames + lookahead; have += chunk_frames) {
+                std::vector<int> a((size_t)(batch));
+                for (int b = 0; b < batch; ++b) {
+                    a[size_t(b)] = std::min(avail[size_t(b)], have);
+                    notyet[size_t(b)] = a[size_t(b)] == avail[size_t(b)] ? 1 : 0;
                 }
+                codec_->stream_push(dcodes, max_frames, a.data(), notyet.data(), hpcm, size_t(max_frames) * up, done.v);
             }
-            codec_->stream_push(dcodes, max_frames, avail.data(), fin.data(), hpcm, size_t(max_frames) * up, done);
-        } catch (...) {
-            codec_->stream_close();
-            throw;
         }
-        codec_->stream_close();
-        Q3_HIP(hipStreamSynchronize(cst));
-        for (int b = 0; b < batch; ++b)
-            std::memcpy(pcm + size_t(b) * max_frames * up, hpcm + size_t(b) * max_frames * up, size_t(n_frames[b]) * up * 4);
+        codec_->stream_push(dcodes, max_frames, avail.data(), fin.data(), hpcm, size_t(max_frames) * up, done.v);
     } catch (...) {
-        cleanup();
+        codec_->stream_close();
         throw;
     }
-    cleanup();
+    codec_->stream_close();
+    Q3_HIP(hipStreamSynchronize(cst));
+    for (int b = 0; b < batch; ++b)
+        std::memcpy(pcm + size_t(b) * max_frames * up, hpcm + size_t(b) * max_frames * up, size_t(n_frames[b]) * up * 4);
 }
 
 void Engine::debug_codec_stage(const int32_t* codes, int n_frames, const char* stage, float* out, int64_t cap, int* T, int* C) {
     Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");
-    int32_t* dcodes = nullptr;
-    Q3_HIP(hipMalloc(reinterpret_cast<void**>(&dcodes), size_t(n_frames) * 16 * 4));
+    DevBuf<int32_t> dcodes;
+    dcodes.grow(size_t(n_frames) * 16);
     Q3_HIP(hipMemcpy(dcodes, codes, size_t(n_frames) * 16 * 4, hipMemcpyHostToDevice));
     std::vector<float> so;
     float* pcm_dev = nullptr;
     (void)codec_stream(false);
-    try {
-        codec_->decode(dcodes, n_frames, {n_frames}, &pcm_dev, stage, &so, T, C);
-    } catch (...) {
-        (void)hipFree(dcodes);
-        throw;
-    }
-    (void)hipFree(dcodes);
+    codec_->decode(dcodes, n_frames, {n_frames}, &pcm_dev, stage, &so, T, C);
     Q3_CHECK(int64_t(so.size()) <= cap, 3, "debug_codec_stage: output buffer too small");
     std::memcpy(out, so.data(), so.size() * 4);
 }
@@ -2461,36 +2300,13 @@ void EngineGroup::end(int job, q3tts_result* results) {
     parked_[job].busy = false;
 }
 
-void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                           q3tts_result* results, const DebugOpts* dbg) {
-    Q3_CHECK(n >= 1 && n <= opts_.max_batch, 3, "Invalid input: batch size must be between 1 and max_batch");
-    const int L = int(lanes_.size());
-    // contiguous split: lane i takes rows [lo_i, hi_i)
-    std::vector<int> lo((size_t)(L + 1), 0);
-    const int per = n / L, rem = n % L;
-    for (int i = 0; i < L; ++i) lo[size_t(i) + 1] = lo[size_t(i)] + per + (i < rem ? 1 : 0);
+template <class F>
+void EngineGroup::run_lanes(int L, bool serial, F&& fn) {
     std::vector<std::string> errs((size_t)(L));
     std::vector<int> codes((size_t)(L), 0);
     auto run = [&](int i) {
-        const int a = lo[size_t(i)], b = lo[size_t(i) + 1];
-        if (b <= a) return;
-        Engine& e = *lanes_[size_t(i)];
-        e.row_offset = uint32_t(a);
-        e.request_base = a;
         try {
-            DebugOpts d;
-            const DebugOpts* dp = nullptr;
-            if (dbg) {  // slice the per-row debug arrays
-                const TalkerConfig& t = model_->cfg.talker;
-                d = *dbg;
-                const size_t fr = size_t(dbg->frames);
-                if (d.forced_codes) d.forced_codes += size_t(a) * fr * 16;
-                if (d.sampled) d.sampled += size_t(a) * fr * 16;
-                if (d.talker_logits) d.talker_logits += size_t(a) * fr * t.vocab_size;
-                if (d.cp_logits) d.cp_logits += size_t(a) * fr * (t.num_code_groups - 1) * t.cp.vocab_size;
-                dp = &d;
-            }
-            e.generate(reqs + a, b - a, sp, cb, user, results + a, dp);
+            fn(i);
         } catch (const Error& ex) {
             errs[size_t(i)] = ex.what();
             codes[size_t(i)] = ex.status;
@@ -2499,9 +2315,8 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
             codes[size_t(i)] = 7;
         }
     };
-    if (L == 1 || n == 1) {
-        run(0);
-        for (int i = 1; i < L; ++i) run(i);
+    if (serial) {
+        for (int i = 0; i < L; ++i) run(i);
     } else {
         std::vector<std::thread> th;
         for (int i = 0; i < L; ++i) th.emplace_back(run, i);
@@ -2509,6 +2324,36 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
     }
     for (int i = 0; i < L; ++i)
         if (codes[size_t(i)]) throw Error(codes[size_t(i)], errs[size_t(i)]);
+}
+
+void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
+                           q3tts_result* results, const DebugOpts* dbg) {
+    Q3_CHECK(n >= 1 && n <= opts_.max_batch, 3, "Invalid input: batch size must be between 1 and max_batch");
+    const int L = int(lanes_.size());
+    // contiguous split: lane i takes rows [lo_i, hi_i)
+    std::vector<int> lo((size_t)(L + 1), 0);
+    const int per = n / L, rem = n % L;
+    for (int i = 0; i < L; ++i) lo[size_t(i) + 1] = lo[size_t(i)] + per + (i < rem ? 1 : 0);
+    run_lanes(L, L == 1 || n == 1, [&](int i) {
+        const int a = lo[size_t(i)], b = lo[size_t(i) + 1];
+        if (b <= a) return;
+        Engine& e = *lanes_[size_t(i)];
+        e.row_offset = uint32_t(a);
+        e.request_base = a;
+        DebugOpts d;
+        const DebugOpts* dp = nullptr;
+        if (dbg) {  // slice the per-row debug arrays
+            const TalkerConfig& t = model_->cfg.talker;
+            d = *dbg;
+            const size_t fr = size_t(dbg->frames);
+            if (d.forced_codes) d.forced_codes += size_t(a) * fr * 16;
+            if (d.sampled) d.sampled += size_t(a) * fr * 16;
+            if (d.talker_logits) d.talker_logits += size_t(a) * fr * t.vocab_size;
+            if (d.cp_logits) d.cp_logits += size_t(a) * fr * (t.num_code_groups - 1) * t.cp.vocab_size;
+            dp = &d;
+        }
+        e.generate(reqs + a, b - a, sp, cb, user, results + a, dp);
+    });
     // aggregate timing: lanes run concurrently, so spans are maxima and volumes are sums
     timing = q3tts_timing{};
     for (int i = 0; i < L; ++i) {
@@ -2556,29 +2401,9 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     const int L = int(lanes_.size());
     std::vector<int> pool((size_t)(L));
     for (int i = 0; i < L; ++i) pool[size_t(i)] = slots / L + (i < slots % L ? 1 : 0);
-    std::vector<std::string> errs((size_t)(L));
-    std::vector<int> codes((size_t)(L), 0);
-    auto run = [&](int i) {
-        if (pool[size_t(i)] == 0) return;
-        try {
-            lanes_[size_t(i)]->run_queued(q, pool[size_t(i)], sp, cb, user);
-        } catch (const Error& ex) {
-            errs[size_t(i)] = ex.what();
-            codes[size_t(i)] = ex.status;
-        } catch (const std::exception& ex) {
-            errs[size_t(i)] = ex.what();
-            codes[size_t(i)] = 7;
-        }
-    };
-    if (L == 1 || slots == 1) {
-        for (int i = 0; i < L; ++i) run(i);
-    } else {
-        std::vector<std::thread> th;
-        for (int i = 0; i < L; ++i) th.emplace_back(run, i);
-        for (auto& t : th) t.join();
-    }
-    for (int i = 0; i < L; ++i)
-        if (codes[size_t(i)]) throw Error(codes[size_t(i)], errs[size_t(i)]);
+    run_lanes(L, L == 1 || slots == 1, [&](int i) {
+        if (pool[size_t(i)] > 0) lanes_[size_t(i)]->run_queued(q, pool[size_t(i)], sp, cb, user);
+    });
     // lanes run concurrently: spans are maxima; volumes (frame-step replays, prefills, decodes, bytes) are sums
     timing = q3tts_timing{};
     for (int i = 0; i < L; ++i) {

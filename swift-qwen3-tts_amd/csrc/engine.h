@@ -6,6 +6,7 @@
 // repetition sets and RNG streams.
 #pragma once
 #include <atomic>
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <condition_variable>
@@ -46,6 +47,12 @@ struct ResolvedRequest {
 
 class CodecRunner;
 class VoiceFrontEnd;
+
+struct FreeDeleter {
+    void operator()(void* p) const { std::free(p); }
+};
+template <class T>
+using MallocPtr = std::unique_ptr<T, FreeDeleter>;  // std::malloc'd host memory
 
 // One q3tts_generate_queued call as the lanes see it: the resolved requests and the index of the next one to admit, which
 // every lane's slot pool takes from (a request's random stream is keyed by its index, so which lane serves it does not matter).
@@ -166,14 +173,11 @@ class Engine {
         std::vector<double> row_span; // queued decode batch: admission -> retirement of row b (generate_time); empty: the job's
         std::vector<std::vector<int32_t>> ref_code0;  // first code row of each reference (valid-length count)
         std::vector<int32_t> codes_host;  // [n][Fcap][16]
-        int32_t* dec_codes = nullptr;     // device [n][Fdec][16]: what the decoder reads (reference ++ generated for clone rows)
-        size_t dec_codes_cap = 0;
-        float* pcm_host = nullptr;        // pinned [n][Fdec * up]
-        size_t pcm_host_cap = 0;
+        DevBuf<int32_t> dec_codes;        // [n][Fdec][16]: what the decoder reads (reference ++ generated for clone rows)
+        PinnedBuf<float> pcm_host;        // [n][Fdec * up]
         hipEvent_t ev_codec[2] = {nullptr, nullptr};
-        int32_t* nf_host = nullptr;  // pinned [max_batch]: rows whose waveform came out non-finite (CodecRunner::decode)
-        int32_t* nf_chunk_host = nullptr;  // pinned [chunks][n]: the same flags behind every chunk of a streamed job
-        size_t nf_chunk_cap = 0;
+        PinnedBuf<int32_t> nf_host;        // [max_batch]: rows whose waveform came out non-finite (CodecRunner::decode)
+        PinnedBuf<int32_t> nf_chunk_host;  // [chunks][n]: the same flags behind every chunk of a decode in pieces
         std::vector<int> held_from;  // streamed job: first chunk of row b that is held back for the fp32 re-decode (-1: none)
         hipEvent_t ev_begin = nullptr, ev_first_audio = nullptr;  // request in / first streamed chunk on the host
         std::vector<hipEvent_t> chunk_done;  // chunked decode (audio_chunk_frames > 0): one per chunk, behind its copy
@@ -191,14 +195,25 @@ class Engine {
         // the decode has finished -- by the staging thread for a pipelined job (so that end() hands over pointers while
         // the next batch's frame loop keeps the device busy), inside end() otherwise
         std::vector<int64_t> row_cut, row_ns;
-        std::vector<float*> st_pcm;
-        std::vector<int32_t*> st_codes;
+        std::vector<MallocPtr<float>> st_pcm;  // std::malloc'd: a result's buffers until q3tts_result_free
+        std::vector<MallocPtr<int32_t>> st_codes;
         int stage = 0;  // 0: not staged, 1: queued for the staging thread, 2: staged, 3: staging failed (stage_err)
         std::string stage_err;
+        void reset(int rows, int upsample);  // every per-batch field, before a batch takes the slot
+        void clear_chunk_flags(int frames);  // nf_chunk_host for a decode of `frames` frames in chunks of chunk_frames
     } jobs_[kJobSlots];
+    // a job's codec decode on the codec stream (ev_codec[0], decode -- in chunks when J.chunk_frames > 0 --, PCM to pcm_host,
+    // ev_codec[1]); codes_host: [n][Fcap][16] copied in on that stream first; nullptr: J.dec_codes holds the codes already
+    void start_decode(Job& J, const std::vector<int>& dframes, bool overlapped, const int32_t* codes_host);
+    // the job is outstanding: cuts, then handed to the staging thread when `stage` and there is PCM to copy
+    void publish_job(Job& J, q3tts_event_cb cb, void* user, int request_base, double t_start, bool stage);
+    void release_job(Job& J);  // waits for the staging thread, frees the rows not handed over, frees the slot
     void compute_cuts(Job& J);
     // AUDIO_CHUNK events of chunks [J.chunks_fired, upto); rows are clipped to known[b] frames (their final length when known)
     void fire_chunks(Job& J, int upto, const std::vector<int>* known, bool wait);
+    std::unique_lock<std::mutex> cb_lock();  // held while events are delivered: callbacks of all lanes are serialised
+    // TOKEN events of frames [reported, nf) of row `row` of codes_ (request `request`), in generation order
+    void emit_tokens(q3tts_event_cb cb, void* user, int row, int request, int nf, int& reported);
     void stage_rows(Job& J);   // waits for the decode, then copies; throws
     // rows whose waveform left the fp16 range of the default codec kernels are decoded again on the fp32 matrix cores
     // (the reference's range) before end() hands them out; returns the rows that are non-finite even then
@@ -246,20 +261,17 @@ class Engine {
     std::unique_ptr<CodecRunner> codec_;
     std::unique_ptr<VoiceFrontEnd> fe_;
     // voice-clone scratch (grown on demand)
-    float* ref_audio_dev_ = nullptr;
-    size_t ref_audio_cap_ = 0;
-    int32_t* ref_codes_dev_ = nullptr;
-    size_t ref_codes_cap_ = 0;
-    uint16_t* extra_ = nullptr;  // [rows][H] bf16: speaker x-vectors and reference-frame embedding sums
-    size_t extra_cap_ = 0;
-    float* spk_f32_ = nullptr;
+    DevBuf<float> ref_audio_dev_;
+    DevBuf<int32_t> ref_codes_dev_;
+    DevBuf<uint16_t> extra_;  // [rows][H] bf16: speaker x-vectors and reference-frame embedding sums
+    DevBuf<float> spk_f32_;
     // Clone rows are independent and their front-end kernels are small: a few of them run side by side, each on its
     // own stream with its own scratch.
     struct FeLane {
         hipStream_t st = nullptr;
         hipEvent_t done = nullptr;
         std::unique_ptr<VoiceFrontEnd> fe;
-        float* spk = nullptr;
+        DevBuf<float> spk;
     };
     std::vector<FeLane> fe_lanes_;
     const float* upload_audio(const float* audio, int64_t n);
@@ -267,6 +279,23 @@ class Engine {
 
     void alloc_workspace();
     ResolvedRequest resolve(const q3tts_request& r, const q3tts_sampling& sp) const;
+    // ---- the steps of begin() ----
+    // input checks, a free job slot (returned; ev_begin recorded), the resolved requests
+    int open_job(const q3tts_request* reqs, int n, const q3tts_sampling& sp, const DebugOpts* dbg, std::vector<ResolvedRequest>& rr,
+                 double& t_start);
+    // block table, per-row limits and lengths, cleared per-row state, sampling parameters; returns the longest prompt
+    int reserve_rows(const std::vector<ResolvedRequest>& rr, const std::vector<int>& np, const std::vector<int>& nt,
+                     const q3tts_sampling& sp);
+    void debug_buffers(int n, const DebugOpts& dbg);
+    struct StreamedDecode;
+    // the bursts of frame steps with their TOKEN events and streamed chunks; fills J.frames, returns the frame steps
+    int frame_loop(Job& J, const std::vector<ResolvedRequest>& rr, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
+                   const DebugOpts* dbg, StreamedDecode& sd);
+    void hand_off(Job& J, const std::vector<ResolvedRequest>& rr, StreamedDecode& sd, int launched, bool overlapped);
+    void job_timing(Job& J, const std::vector<int>& np, int launched);
+    void upload_sampling(const q3tts_sampling& sp, uint32_t row0);  // sp_dev_ on st_
+    int64_t kv_bytes(int n_prompt, int frames) const;  // talker KV bytes the frame steps of one row read
+    int launches_per_step(int B) const;
     // builds prompt_/trailing_/tts_pad_ for rows [0,n); fills host-side lengths. trailing_rows: row of trailing_ that
     // request b's trailing text goes to (queued admission: its slot); nullptr: row b
     void assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vector<int>& n_prompt, std::vector<int>& n_trailing,
@@ -294,8 +323,16 @@ class Engine {
     uint32_t* row_key_ = nullptr;  // [max_batch] random key of every slot
     std::vector<int32_t> q_host_;  // staging of the sub-batch's arrays (alive until the next boundary's sync)
     void ensure_queue_ws();
-    // prompts, prefill and admit_rows_kernel for requests rr into `slots` (random keys `keys`); returns their prompt lengths
-    std::vector<int> admit(const std::vector<ResolvedRequest>& rr, const std::vector<int>& slots, const std::vector<uint32_t>& keys);
+    struct QSlot {
+        int req = -1;      // request in this slot, -1: empty
+        int since = 0;     // frame steps since its admission
+        int reported = 0;  // TOKEN events delivered
+        int np = 0;
+        double t0 = 0;     // admission (host clock)
+    };
+    // free slots of `sl` in slot order take the next requests of q (prompts, prefill and admit_rows_kernel as a sub-batch of
+    // their own); returns how many were admitted, sets `drained` once q is empty
+    int admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained);
     GemmArgs gemm_args(const LinearW& L, const uint16_t* x, int M) const;
 };
 
@@ -324,6 +361,9 @@ class EngineGroup {
     std::vector<std::string> speakers;
 
   private:
+    // fn(i) for lanes 0..L-1, each on a thread of its own unless `serial`; then the first failed lane's Error is rethrown
+    template <class F>
+    static void run_lanes(int L, bool serial, F&& fn);
     struct Parked {  // lanes > 1: finished results waiting for end()
         bool busy = false;
         std::vector<q3tts_result> results;

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 
 #include "codec_kernels.h"
@@ -20,40 +21,26 @@ CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs) : m_(m
     Q3_CHECK(m.cfg.codec.head_dim == 64, 6, "codec transformer head_dim must be 64");
     const char* e = std::getenv("Q3TTS_CODEC_FP32");  // tests switch per model load without touching the load options
     fp32_mfma_ = fp32_convs || (e && e[0] == '1');
-    Q3_HIP(hipMalloc(reinterpret_cast<void**>(&nf_dev_), size_t(kMaxRows) * 4));
-    Q3_HIP(hipMemset(nf_dev_, 0, size_t(kMaxRows) * 4));
+    Q3_HIP(hipMemset(nf_dev_.grow(kMaxRows), 0, size_t(kMaxRows) * 4));
     const char* nf = std::getenv("Q3TTS_CODEC_NO_FUSE");
     no_fuse_ = nf && nf[0] == '1';
     const char* nh = std::getenv("Q3TTS_CODEC_NO_F16");  // float16 checkpoints through the up-cast two-plane path (comparisons)
     no_h1_ = nh && nh[0] == '1';
 }
 
-CodecRunner::~CodecRunner() {
-    if (buf_) (void)hipFree(buf_);
-    if (lens_dev_) (void)hipFree(lens_dev_);
-    if (lens_host_) (void)hipHostFree(lens_host_);
-    if (nf_dev_) (void)hipFree(nf_dev_);
-    if (stream_.arena) (void)hipFree(stream_.arena);
-    if (stream_.lens_host) (void)hipHostFree(stream_.lens_host);
-    if (stream_.lens_dev) (void)hipFree(stream_.lens_dev);
-}
-
-void CodecRunner::ensure(size_t bytes) {
-    if (bytes <= buf_bytes_) return;
-    if (buf_) Q3_HIP(hipFree(buf_));
-    buf_ = nullptr;
-    buf_bytes_ = 0;
-    Q3_HIP(hipMalloc(reinterpret_cast<void**>(&buf_), bytes));
-    buf_bytes_ = bytes;
+// floats per frame of the widest tensor in front of the tail (RVQ, pre_conv, pre-transformer and its latent result)
+size_t CodecRunner::front_floats_per_frame() const {
+    const CodecDecoderConfig& dc = m_.cfg.codec;
+    size_t pf = std::max<size_t>(size_t(2) * m_.codec.inner, size_t(dc.codebook_dim));
+    pf = std::max(pf, size_t(3) * dc.num_attention_heads * 64);
+    pf = std::max(pf, size_t(2) * dc.intermediate_size);
+    return std::max(pf, size_t(dc.latent_dim));
 }
 
 // floats per frame of the largest intermediate tensor
 size_t CodecRunner::floats_per_frame() const {
     const CodecDecoderConfig& dc = m_.cfg.codec;
-    const CodecW& w = m_.codec;
-    size_t per_frame = std::max<size_t>(size_t(2) * w.inner, size_t(dc.codebook_dim));
-    per_frame = std::max(per_frame, size_t(3) * dc.num_attention_heads * 64);
-    per_frame = std::max(per_frame, size_t(2) * dc.intermediate_size);
+    size_t per_frame = front_floats_per_frame();
     int ppf = 1;
     for (int r : dc.upsampling_ratios) {
         ppf *= r;
@@ -90,16 +77,9 @@ int CodecRunner::tail_context_frames() const {
 }
 
 void CodecRunner::upload_lens(const int32_t* lens, int n) {
-    if (lens_cap_ < n) {
-        Q3_HIP(hipStreamSynchronize(st_));
-        if (lens_dev_) Q3_HIP(hipFree(lens_dev_));
-        if (lens_host_) Q3_HIP(hipHostFree(lens_host_));
-        lens_dev_ = nullptr;
-        lens_host_ = nullptr;
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&lens_dev_), size_t(n) * 4));
-        Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&lens_host_), size_t(n) * 4, hipHostMallocDefault));
-        lens_cap_ = n;
-    }
+    if (size_t(n) > lens_dev_.capacity()) Q3_HIP(hipStreamSynchronize(st_));  // the pair about to be freed may still be read
+    lens_dev_.grow(size_t(n));
+    lens_host_.grow(size_t(n));
     // the pinned staging copy may still feed the previous call's transfer
     Q3_HIP(hipStreamSynchronize(st_));
     std::memcpy(lens_host_, lens, size_t(n) * 4);
@@ -109,25 +89,22 @@ void CodecRunner::upload_lens(const int32_t* lens, int n) {
 // `post`: also (or, with out == nullptr, only) write SnakeBeta_post(result) to out2 for the next conv
 void CodecRunner::conv(const Pass& ps, const ConvW& cw, const float* x, int Tmax, int ppf, float* out, const SnakeW* sn,
                        const float* res, int act, const SnakeW* post, float* out2) {
-    if (stream_.dry) return;
-    ConvGemmArgs a{};
-    // streamed decode: Tmax counts the allocation's rows (history margin + chunk); row 0 of the chunk sits behind the margin
-    const int64_t m_in = int64_t(ps.hist_frames) * ppf * cw.Cin, m_out = int64_t(ps.hist_frames) * ppf * cw.N;
-    x += m_in;
-    if (out) out += m_out;
-    if (res) res += m_out;
-    if (out2) out2 += m_out;
-    a.hist = ps.hist_frames * ppf;
-    a.x = x; a.ldx = cw.Cin; a.x_bstride = int64_t(Tmax) * cw.Cin;
-    a.w = cw.w; a.bias = cw.bias; a.scale = cw.scale;
-    if (!fp32_mfma_) { a.wh = cw.wh; a.wsc = cw.wsc; }
-    a.res = res; a.ldr = cw.N; a.res_bstride = int64_t(Tmax) * cw.N;
-    a.out = out; a.ldo = cw.N; a.out_bstride = int64_t(Tmax) * cw.N;
-    a.snake_ea = sn ? sn->ea : nullptr; a.snake_ib = sn ? sn->ib : nullptr;
-    if (post) { a.out2 = out2; a.post_ea = post->ea; a.post_ib = post->ib; a.post_C = post->C; }
-    a.frames = ps.fr; a.ppf = ppf; a.Tmax = Tmax; a.B = ps.nb;
-    a.Cin = cw.Cin; a.N = cw.N; a.K = cw.K; a.dil = cw.dil; a.act = act;
-    launch_conv_gemm(a, st_);
+    launch([&] {
+        ConvGemmArgs a{};
+        // streamed decode: Tmax counts the allocation's rows (history margin + chunk); row 0 of the chunk sits behind the margin
+        const int64_t m_in = int64_t(ps.hist_frames) * ppf * cw.Cin, m_out = int64_t(ps.hist_frames) * ppf * cw.N;
+        a.hist = ps.hist_frames * ppf;
+        a.x = x + m_in; a.ldx = cw.Cin; a.x_bstride = int64_t(Tmax) * cw.Cin;
+        a.w = cw.w; a.bias = cw.bias; a.scale = cw.scale;
+        if (!fp32_mfma_) { a.wh = cw.wh; a.wsc = cw.wsc; }
+        a.res = res ? res + m_out : nullptr; a.ldr = cw.N; a.res_bstride = int64_t(Tmax) * cw.N;
+        a.out = out ? out + m_out : nullptr; a.ldo = cw.N; a.out_bstride = int64_t(Tmax) * cw.N;
+        a.snake_ea = sn ? sn->ea : nullptr; a.snake_ib = sn ? sn->ib : nullptr;
+        if (post) { a.out2 = out2 + m_out; a.post_ea = post->ea; a.post_ib = post->ib; a.post_C = post->C; }
+        a.frames = ps.fr; a.ppf = ppf; a.Tmax = Tmax; a.B = ps.nb;
+        a.Cin = cw.Cin; a.N = cw.N; a.K = cw.K; a.dil = cw.dil; a.act = act;
+        launch_conv_gemm(a, st_);
+    });
 }
 
 void CodecRunner::capture(const Pass& ps, const char* name, const float* t, int T, int C) {
@@ -176,115 +153,28 @@ void CodecRunner::run_front(const Pass& ps, const int32_t* codes, int code_strid
     capture(ps, "pre_transformer", bufs[0], T, w.t_out.N);
 }
 
-// Steps 5-7 (:767-781): the causal tail. In: bufs[0] = [nb][T][latent] with fr[b] valid frames per row; out: pcm
-// [nb][T * upsample] (row stride T * upsample).
-void CodecRunner::run_tail(const Pass& ps, int Tframes, float* const* bufs, float* pcm) {
-    const CodecDecoderConfig& dc = m_.cfg.codec;
-    const CodecW& w = m_.codec;
-    const int nb = ps.nb;
-    const int32_t* fr = ps.fr;
-    int T = Tframes, ppf = 1;
-    int cur = 0;
-    // 5. upsample stages: transposed conv (k = stride) + ConvNeXt (:767-775)
-    for (size_t i = 0; i < w.ups.size(); ++i) {
-        const auto& U = w.ups[i];
-        const int C = U.tconv.N / U.stride;
-        float *h = bufs[cur], *y = bufs[(cur + 1) & 3], *t1 = bufs[(cur + 2) & 3], *t2 = bufs[(cur + 3) & 3];
-        conv(ps, U.tconv, h, T, ppf, y, nullptr, nullptr, 0);  // [T][s*C] == [T*s][C]
-        T *= U.stride;
-        ppf *= U.stride;
-        launch_dwconv_ln(y, U.dw_w, U.dw_b, U.ln_w, U.ln_b, 1e-6f, C, fr, ppf, T, nb, t1, st_);
-        conv(ps, U.pw1, t1, T, ppf, t2, nullptr, nullptr, 1);
-        conv(ps, U.pw2, t2, T, ppf, y, nullptr, y, 0);  // y = y + gamma * (pwconv2(...) + b)  (:396-400)
-        cur = (cur + 1) & 3;
-        capture(ps, ("upsample" + std::to_string(i)).c_str(), bufs[cur], T, C);
-    }
-    // 6. MainDecoder (:681-690). Every SnakeBeta sits in front of a conv; it is evaluated in the epilogue of the
-    // conv that PRODUCES the tensor (one sinf per element) and the activated copy is what the next conv stages.
-    const size_t nblk = w.blocks.size();
-    if (w.f16_main && !fp32_mfma_ && !no_h1_) {  // a float16 speech tokenizer: the reference computes this part in float16
-        run_main_h1(ps, T, ppf, cur, bufs, pcm);
-        return;
-    }
-    {
-        float *y = bufs[(cur + 1) & 3], *ys = bufs[(cur + 2) & 3];
-        conv(ps, w.init_conv, bufs[cur], T, ppf, y, nullptr, nullptr, 0, nblk ? &w.blocks[0].snake : nullptr, ys);
-        cur = (cur + 1) & 3;  // bufs[cur] = init_conv output, bufs[cur + 1] = snake_0 of it
-        capture(ps, "init_conv", bufs[cur], T, w.init_conv.N);
-    }
-    for (size_t i = 0; i < nblk; ++i) {
-        const auto& Bk = w.blocks[i];
-        // in: bufs[cur + 1] = snake_i(previous stage). y (raw residual stream), ya = act1(y) / next snake(y), t1 = act2(conv1)
-        float *hs = bufs[(cur + 1) & 3], *y = bufs[(cur + 2) & 3], *ya = bufs[(cur + 3) & 3], *t1 = bufs[cur];
-        const SnakeW* after = i + 1 < nblk ? &w.blocks[i + 1].snake : nullptr;
-        bool fused = !fp32_mfma_ && !no_fuse_ && resunit_supported(Bk.Cout, Bk.res[0].conv1.K, 9);
-        for (int j = 0; j < 3; ++j)
-            fused = fused && Bk.res[j].conv1.wh && Bk.res[j].conv2.whp &&
-                    Bk.res[j].conv1.N == Bk.Cout && Bk.res[j].conv2.K == 1 &&
-                    resunit_supported(Bk.Cout, Bk.res[j].conv1.K, Bk.res[j].conv1.dil);
-        if (fused) {
-            // narrow blocks: each residual unit is one launch, y ping-pongs between two buffers (codec_conv.hip)
-            conv(ps, Bk.tconv, hs, T, ppf, y, nullptr, nullptr, 0);  // snake (already applied by the producer) -> transposed conv
-            T *= Bk.stride;
-            ppf *= Bk.stride;
-            float *yin = y, *yout = t1;
-            for (int j = 0; j < 3; ++j) {
-                ResUnitArgs r{};
-                r.y = yin; r.out = yout;
-                if (j == 2 && after) { r.out2 = hs; r.post_ea = after->ea; r.post_ib = after->ib; }
-                r.b1 = Bk.res[j].conv1.bias; r.b2 = Bk.res[j].conv2.bias;
-                r.w1h = Bk.res[j].conv1.wh; r.w2ph = Bk.res[j].conv2.whp; r.wsc1 = Bk.res[j].conv1.wsc; r.wsc2 = Bk.res[j].conv2.wsc;
-                r.ea1 = Bk.res[j].act1.ea; r.ib1 = Bk.res[j].act1.ib; r.ea2 = Bk.res[j].act2.ea; r.ib2 = Bk.res[j].act2.ib;
-                r.frames = fr; r.ppf = ppf; r.Tmax = T; r.B = nb; r.C = Bk.Cout; r.K = Bk.res[j].conv1.K; r.dil = Bk.res[j].conv1.dil;
-                launch_resunit(r, st_);
-                std::swap(yin, yout);
-            }
-            // three units: the result sits in t1 = bufs[cur], its activated copy (if any) in hs = bufs[cur + 1]
-            capture(ps, ("block" + std::to_string(i)).c_str(), bufs[cur], T, Bk.Cout);
-            continue;
-        }
-        conv(ps, Bk.tconv, hs, T, ppf, y, nullptr, nullptr, 0, &Bk.res[0].act1, ya);  // snake -> transposed conv (:474-475)
-        T *= Bk.stride;
-        ppf *= Bk.stride;
-        for (int j = 0; j < 3; ++j) {  // DecoderResidualUnit (:430-437): y += conv2(act2(conv1(act1(y))))
-            conv(ps, Bk.res[j].conv1, ya, T, ppf, nullptr, nullptr, nullptr, 0, &Bk.res[j].act2, t1);
-            const SnakeW* next = j < 2 ? &Bk.res[j + 1].act1 : after;
-            conv(ps, Bk.res[j].conv2, t1, T, ppf, y, nullptr, y, 0, next, ya);
-        }
-        cur = (cur + 2) & 3;  // bufs[cur] = y, bufs[cur + 1] = next block's snake of it
-        capture(ps, ("block" + std::to_string(i)).c_str(), bufs[cur], T, Bk.Cout);
-    }
-    // 7. outSnake -> outConv -> clip (:687-688, :781)
-    launch_out_conv(bufs[cur], w.out_C, w.out_snake.ea, w.out_snake.ib, w.out_w, w.out_b, fr, ppf, T, nb,
-                    pcm, st_, 0, nf_dev_ + ps.row0);
-    Q3_CHECK(T == Tframes * up_, 7, "internal error: codec upsampling mismatch");
-    (void)dc;
-}
-
 // ---- float16 speech tokenizers ("lite" checkpoints, docs/paper.tex:207): the MainDecoder as the reference computes it ----
 void CodecRunner::conv_h1(const Pass& ps, const ConvW& cw, const void* x, bool x_f32, int Tmax, int ppf, uint16_t* out, const uint16_t* res,
                           const SnakeW* post, uint16_t* out2) {
-    if (stream_.dry) return;
-    Q3_CHECK(cw.w1 != nullptr, 7, "internal error: float16 decoder without its one-plane weights");
-    ConvH1Args a{};
-    // streamed decode (as conv()): Tmax counts the allocation's rows, row 0 of the chunk sits behind the history margin
-    const int64_t m_in = int64_t(ps.hist_frames) * ppf * cw.Cin, m_out = int64_t(ps.hist_frames) * ppf * cw.N;
-    x = x_f32 ? static_cast<const void*>(static_cast<const float*>(x) + m_in) : static_cast<const void*>(static_cast<const uint16_t*>(x) + m_in);
-    if (out) out += m_out;
-    if (res) res += m_out;
-    if (out2) out2 += m_out;
-    a.hist = ps.hist_frames * ppf;
-    a.x = x; a.x_f32 = x_f32 ? 1 : 0; a.ldx = cw.Cin; a.x_bstride = int64_t(Tmax) * cw.Cin;
-    a.w1 = cw.w1; a.bias = cw.bias;
-    a.res = res; a.ldr = cw.N; a.res_bstride = int64_t(Tmax) * cw.N;
-    a.out = out; a.ldo = cw.N; a.out_bstride = int64_t(Tmax) * cw.N;
-    if (post) { a.out2 = out2; a.post_ea = post->ea16; a.post_ib = post->ib16; a.post_C = post->C; }
-    a.frames = ps.fr; a.ppf = ppf; a.Tmax = Tmax; a.B = ps.nb;
-    a.Cin = cw.Cin; a.N = cw.N; a.K = cw.K; a.dil = cw.dil;
-    launch_conv_gemm_h1(a, st_);
+    launch([&] {
+        Q3_CHECK(cw.w1 != nullptr, 7, "internal error: float16 decoder without its one-plane weights");
+        ConvH1Args a{};
+        // streamed decode (as conv()): Tmax counts the allocation's rows, row 0 of the chunk sits behind the history margin
+        const int64_t m_in = int64_t(ps.hist_frames) * ppf * cw.Cin, m_out = int64_t(ps.hist_frames) * ppf * cw.N;
+        a.hist = ps.hist_frames * ppf;
+        a.x = x_f32 ? static_cast<const void*>(static_cast<const float*>(x) + m_in) : static_cast<const void*>(static_cast<const uint16_t*>(x) + m_in);
+        a.x_f32 = x_f32 ? 1 : 0; a.ldx = cw.Cin; a.x_bstride = int64_t(Tmax) * cw.Cin;
+        a.w1 = cw.w1; a.bias = cw.bias;
+        a.res = res ? res + m_out : nullptr; a.ldr = cw.N; a.res_bstride = int64_t(Tmax) * cw.N;
+        a.out = out ? out + m_out : nullptr; a.ldo = cw.N; a.out_bstride = int64_t(Tmax) * cw.N;
+        if (post) { a.out2 = out2 + m_out; a.post_ea = post->ea16; a.post_ib = post->ib16; a.post_C = post->C; }
+        a.frames = ps.fr; a.ppf = ppf; a.Tmax = Tmax; a.B = ps.nb;
+        a.Cin = cw.Cin; a.N = cw.N; a.K = cw.K; a.dil = cw.dil;
+        launch_conv_gemm_h1(a, st_);
+    });
 }
 
-void CodecRunner::capture_h(const Pass& ps, const char* name, const uint16_t* t, int T, int C) {
+void CodecRunner::capture(const Pass& ps, const char* name, const uint16_t* t, int T, int C) {
     if (!ps.stage_out || *ps.stage != name) return;
     Q3_HIP(hipStreamSynchronize(st_));
     std::vector<uint16_t> h(size_t(ps.nb) * T * C);
@@ -299,132 +189,197 @@ void CodecRunner::capture_h(const Pass& ps, const char* name, const uint16_t* t,
     if (ps.stage_C) *ps.stage_C = C;
 }
 
-// initConv -> four DecoderBlocks -> outSnake -> outConv -> clip (SpeechTokenizer.swift:681-690, 781) on float16 tensors. The launch
-// structure is the unfused two-plane path's (run_tail): every SnakeBeta is evaluated in the epilogue of the conv that produces
-// the tensor; y is the residual stream, ya / t1 / hs the activated copies the next conv reads.
-void CodecRunner::run_main_h1(const Pass& ps, int T, int ppf, int cur, float* const* bufs, float* pcm) {
-    const CodecW& w = m_.codec;
-    const size_t nblk = w.blocks.size();
-    auto H = [&](int i) { return reinterpret_cast<uint16_t*>(bufs[i & 3]); };
-    {
-        uint16_t *y = H(cur + 1), *ys = H(cur + 2);
-        conv_h1(ps, w.init_conv, bufs[cur], true, T, ppf, y, nullptr, nblk ? &w.blocks[0].snake : nullptr, ys);
-        cur = (cur + 1) & 3;  // H(cur) = initConv output, H(cur + 1) = snake_0 of it
-        capture_h(ps, "init_conv", H(cur), T, w.init_conv.N);
-    }
-    for (size_t i = 0; i < nblk; ++i) {
-        const auto& Bk = w.blocks[i];
-        uint16_t *hs = H(cur + 1), *y = H(cur + 2), *ya = H(cur + 3), *t1 = H(cur);
-        const SnakeW* after = i + 1 < nblk ? &w.blocks[i + 1].snake : nullptr;
-        bool fused = !no_fuse_ && resunit_h1_supported(Bk.Cout, Bk.res[0].conv1.K, 9);
-        for (int j = 0; j < 3; ++j)
-            fused = fused && Bk.res[j].conv1.w1 && Bk.res[j].conv2.w1p && Bk.res[j].conv1.N == Bk.Cout && Bk.res[j].conv2.K == 1 &&
-                    resunit_h1_supported(Bk.Cout, Bk.res[j].conv1.K, Bk.res[j].conv1.dil);
-        if (fused) {
-            // narrow blocks: each residual unit is one launch (resunit_h1_kernel), y ping-pongs between two buffers
-            conv_h1(ps, Bk.tconv, hs, false, T, ppf, y, nullptr, nullptr, nullptr);  // snake (applied by the producer) -> transposed conv
-            T *= Bk.stride;
-            ppf *= Bk.stride;
-            uint16_t *yin = y, *yout = t1;
-            for (int j = 0; j < 3; ++j) {
-                ResUnitH1Args r{};
-                r.y = yin; r.out = yout;
-                if (j == 2 && after) { r.out2 = hs; r.post_ea = after->ea16; r.post_ib = after->ib16; }
-                r.b1 = Bk.res[j].conv1.bias; r.b2 = Bk.res[j].conv2.bias;
-                r.w1 = Bk.res[j].conv1.w1; r.w2p = Bk.res[j].conv2.w1p;
-                r.ea1 = Bk.res[j].act1.ea16; r.ib1 = Bk.res[j].act1.ib16; r.ea2 = Bk.res[j].act2.ea16; r.ib2 = Bk.res[j].act2.ib16;
-                r.frames = ps.fr; r.ppf = ppf; r.Tmax = T; r.B = ps.nb; r.C = Bk.Cout; r.dil = Bk.res[j].conv1.dil;
-                launch_resunit_h1(r, st_);
-                std::swap(yin, yout);
-            }
-            // three units: the result sits in t1 = H(cur), its activated copy (if any) in hs = H(cur + 1)
-            capture_h(ps, ("block" + std::to_string(i)).c_str(), H(cur), T, Bk.Cout);
-            continue;
-        }
-        conv_h1(ps, Bk.tconv, hs, false, T, ppf, y, nullptr, &Bk.res[0].act1, ya);  // snake -> transposed conv (:474-475)
-        T *= Bk.stride;
-        ppf *= Bk.stride;
-        for (int j = 0; j < 3; ++j) {  // DecoderResidualUnit (:430-437): y += conv2(act2(conv1(act1(y))))
-            conv_h1(ps, Bk.res[j].conv1, ya, false, T, ppf, nullptr, nullptr, &Bk.res[j].act2, t1);
-            const SnakeW* next = j < 2 ? &Bk.res[j + 1].act1 : after;
-            conv_h1(ps, Bk.res[j].conv2, t1, false, T, ppf, y, y, next, ya);  // (the last unit leaves the NEXT block's snake in ya)
-        }
-        cur = (cur + 2) & 3;  // H(cur) = y, H(cur + 1) = the next block's snake of it
-        capture_h(ps, ("block" + std::to_string(i)).c_str(), H(cur), T, Bk.Cout);
-    }
-    launch_out_conv_h1(H(cur), w.out_C, w.out_snake.ea16, w.out_snake.ib16, w.out_w, w.out_b, ps.fr, ppf, T, ps.nb, pcm, st_, nf_dev_ + ps.row0);
-    Q3_CHECK(ppf == up_, 7, "internal error: codec upsampling mismatch");
+// Narrow blocks: each DecoderResidualUnit is one launch (codec_conv.hip resunit_h2_kernel, codec_conv_h1.hip resunit_h1_kernel).
+bool CodecRunner::fused_block(const CodecW::Block& Bk, float) const {
+    bool fused = !fp32_mfma_ && !no_fuse_ && resunit_supported(Bk.Cout, Bk.res[0].conv1.K, 9);
+    for (const auto& R : Bk.res)
+        fused = fused && R.conv1.wh && R.conv2.whp && R.conv1.N == Bk.Cout && R.conv2.K == 1 && resunit_supported(Bk.Cout, R.conv1.K, R.conv1.dil);
+    return fused;
+}
+bool CodecRunner::fused_block(const CodecW::Block& Bk, uint16_t) const {
+    bool fused = !no_fuse_ && resunit_h1_supported(Bk.Cout, Bk.res[0].conv1.K, 9);
+    for (const auto& R : Bk.res)
+        fused = fused && R.conv1.w1 && R.conv2.w1p && R.conv1.N == Bk.Cout && R.conv2.K == 1 && resunit_h1_supported(Bk.Cout, R.conv1.K, R.conv1.dil);
+    return fused;
 }
 
-// run_main_h1 over one chunk of a stream (run_tail_stream's rules: every tensor in its own persistent buffer of hist + chunk frames
-// per row, float16 here, the ones a k7 / transposed conv reads back carrying the previous chunk's last frames in their margin).
-// in: h32 = the last ConvNeXt stage's fp32 output (stream layout, history kept by the caller's sbuf).
-void CodecRunner::run_main_h1_stream(const Pass& ps, const float* h32, int T, int ppf, float* pcm) {
+void CodecRunner::resunit(const Pass& ps, const CodecW::Res& R, int C, int Tmax, int ppf, const float* y, float* out, float* out2,
+                          const SnakeW* after) {
+    launch([&] {
+        const size_t m = size_t(ps.hist_frames) * ppf * C;
+        ResUnitArgs r{};
+        r.y = y + m; r.out = out + m;
+        if (out2) { r.out2 = out2 + m; r.post_ea = after->ea; r.post_ib = after->ib; }
+        r.b1 = R.conv1.bias; r.b2 = R.conv2.bias;
+        r.w1h = R.conv1.wh; r.w2ph = R.conv2.whp; r.wsc1 = R.conv1.wsc; r.wsc2 = R.conv2.wsc;
+        r.ea1 = R.act1.ea; r.ib1 = R.act1.ib; r.ea2 = R.act2.ea; r.ib2 = R.act2.ib;
+        r.frames = ps.fr; r.ppf = ppf; r.Tmax = Tmax; r.B = ps.nb; r.C = C; r.K = R.conv1.K; r.dil = R.conv1.dil;
+        r.hist = ps.hist_frames * ppf;
+        launch_resunit(r, st_);
+    });
+}
+void CodecRunner::resunit(const Pass& ps, const CodecW::Res& R, int C, int Tmax, int ppf, const uint16_t* y, uint16_t* out, uint16_t* out2,
+                          const SnakeW* after) {
+    launch([&] {
+        const size_t m = size_t(ps.hist_frames) * ppf * C;
+        ResUnitH1Args r{};
+        r.y = y + m; r.out = out + m;
+        if (out2) { r.out2 = out2 + m; r.post_ea = after->ea16; r.post_ib = after->ib16; }
+        r.b1 = R.conv1.bias; r.b2 = R.conv2.bias;
+        r.w1 = R.conv1.w1; r.w2p = R.conv2.w1p;
+        r.ea1 = R.act1.ea16; r.ib1 = R.act1.ib16; r.ea2 = R.act2.ea16; r.ib2 = R.act2.ib16;
+        r.frames = ps.fr; r.ppf = ppf; r.Tmax = Tmax; r.B = ps.nb; r.C = C; r.dil = R.conv1.dil;
+        r.hist = ps.hist_frames * ppf;
+        launch_resunit_h1(r, st_);
+    });
+}
+
+// ---- where the tail's tensors live: get(bytes per frame, does a later causal conv read back into it?) and put() when done ----
+// One-shot and chunked decode: the four scratch buffers, a released one is handed out again. The tail never holds more than
+// four tensors at once (decode's and decode_chunked's scratch arithmetic counts on four); its input sits in slot[0].
+struct CodecRunner::Ring {
+    void* slot[4];
+    size_t slot_bytes, frames;  // bytes per slot; rows x frames of one pass
+    bool taken[4] = {true, false, false, false};
+    Ring(float* const* bufs, size_t bytes, size_t rows_x_frames) : slot{bufs[0], bufs[1], bufs[2], bufs[3]}, slot_bytes(bytes), frames(rows_x_frames) {}
+    void* get(size_t frame_bytes, bool) {
+        Q3_CHECK(frames * frame_bytes <= slot_bytes, 7, "internal error: codec tail tensor wider than its scratch buffer");
+        const int i = int(std::find(taken, taken + 4, false) - taken);
+        Q3_CHECK(i < 4, 7, "internal error: codec tail holds more than four tensors");
+        taken[i] = true;
+        return slot[i];
+    }
+    void put(const void* p) {
+        const int i = int(std::find(slot, slot + 4, p) - slot);
+        Q3_CHECK(i < 4 && taken[i], 7, "internal error: codec tail released a tensor it does not hold");
+        taken[i] = false;
+    }
+};
+
+// Streamed decode: every tensor in its own persistent piece of the arena, Tal = hist + chunk frames per row, whose first `hist`
+// frames are the previous chunk's last ones (rolled in by stream_push), so a conv's causal halo comes from memory instead of
+// being zero (first chunk: the margins are zero, i.e. exactly the reference's left padding). Nothing is handed out twice.
+uint8_t* CodecRunner::Stream::take(size_t bytes) {
+    off = align_up(off, 256);
+    uint8_t* p = dry ? nullptr : arena + off;
+    off += bytes;
+    return p;
+}
+void* CodecRunner::Stream::get(size_t frame_bytes, bool reads_back) {
+    Q3_CHECK(frame_bytes % 4 == 0, 7, "internal error: a streamed tensor's frame is not whole floats");  // roll_history moves floats
+    uint8_t* p = take(size_t(cfg.rows) * Tal * frame_bytes);
+    if (reads_back && !dry) rolls.emplace_back(reinterpret_cast<float*>(p), frame_bytes / 4);
+    return p;
+}
+
+// Steps 5-7 (SpeechTokenizer.swift:767-781): the causal tail. In: [nb][Trows][latent] with fr[b] valid frames per row behind
+// ps.hist_frames frames of history; out: pcm [nb][Trows * upsample] (row stride Trows * upsample). Every tensor is addressed as
+// base + hist_frames * elements per frame; the one-shot decode has no margin.
+template <class Mem>
+void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float* pcm) {
     const CodecW& w = m_.codec;
-    const Stream& S = stream_;
-    const int H = ps.hist_frames;
-    const size_t nblk = w.blocks.size();
-    auto hb = [&](size_t frame_halves, bool keeps) { return reinterpret_cast<uint16_t*>(sbuf(frame_halves / 2, keeps)); };
-    uint16_t* h = nullptr;   // the residual stream
-    uint16_t* ys = nullptr;  // SnakeBeta of the previous stage's output = the next transposed conv's input
-    size_t fh = size_t(ppf) * w.init_conv.N;  // float16 elements per frame of the current tensor
-    Q3_CHECK(fh % 2 == 0, 7, "internal error: odd float16 frame size in a streamed decode");
-    {
-        uint16_t* y = hb(fh, nblk == 0);
-        ys = nblk ? hb(fh, true) : nullptr;  // transposed conv: one row back
-        conv_h1(ps, w.init_conv, h32, true, T, ppf, y, nullptr, nblk ? &w.blocks[0].snake : nullptr, ys);
-        h = y;
+    const int nb = ps.nb, H = ps.hist_frames;
+    const int32_t* fr = ps.fr;
+    int T = Trows, ppf = 1;  // T: rows of a tensor at the current rate
+    auto f32 = [&](size_t per_frame, bool reads_back) { return static_cast<float*>(mem.get(per_frame * sizeof(float), reads_back)); };
+    // 5. upsample stages: transposed conv (k = stride) + ConvNeXt (:767-775)
+    float* h = in;
+    for (size_t i = 0; i < w.ups.size(); ++i) {
+        const auto& U = w.ups[i];
+        const int C = U.tconv.N / U.stride;
+        const size_t ff = size_t(ppf) * U.stride * C;  // floats per frame behind the transposed conv
+        float* y = f32(ff, true);                      // dwconv reads six rows back
+        float* t1 = f32(ff, false);
+        float* t2 = f32(size_t(ppf) * U.stride * U.pw1.N, false);
+        conv(ps, U.tconv, h, T, ppf, y, nullptr, nullptr, 0);  // [T][s*C] == [T*s][C]
+        mem.put(h);
+        T *= U.stride;
+        ppf *= U.stride;
+        launch([&] {
+            launch_dwconv_ln(y + size_t(H) * ff, U.dw_w, U.dw_b, U.ln_w, U.ln_b, 1e-6f, C, fr, ppf, T, nb, t1 + size_t(H) * ff, st_, H * ppf);
+        });
+        conv(ps, U.pw1, t1, T, ppf, t2, nullptr, nullptr, 1);
+        float* yo = f32(ff, i + 1 == w.ups.size());      // the last stage feeds initConv (k7)
+        conv(ps, U.pw2, t2, T, ppf, yo, nullptr, y, 0);  // yo = y + gamma * (pwconv2(...) + b)  (:396-400); y stays dwconv's history
+        mem.put(y);
+        mem.put(t1);
+        mem.put(t2);
+        h = yo;
+        capture(ps, ("upsample" + std::to_string(i)).c_str(), h, T, C);
     }
-    for (size_t i = 0; i < nblk; ++i) {
-        const auto& Bk = w.blocks[i];
-        const SnakeW* after = i + 1 < nblk ? &w.blocks[i + 1].snake : nullptr;
-        const bool lastb = i + 1 == nblk;
-        bool fused = !no_fuse_ && resunit_h1_supported(Bk.Cout, Bk.res[0].conv1.K, 9);
-        for (int j = 0; j < 3; ++j)
-            fused = fused && Bk.res[j].conv1.w1 && Bk.res[j].conv2.w1p && Bk.res[j].conv1.N == Bk.Cout && Bk.res[j].conv2.K == 1 &&
-                    resunit_h1_supported(Bk.Cout, Bk.res[j].conv1.K, Bk.res[j].conv1.dil);
-        fh = size_t(ppf) * Bk.stride * Bk.Cout;
-        Q3_CHECK(fh % 2 == 0, 7, "internal error: odd float16 frame size in a streamed decode");
-        uint16_t* hs_next = after ? hb(fh, true) : nullptr;
-        if (fused) {
-            uint16_t* yb[4];
-            for (int j = 0; j < 3; ++j) yb[j] = hb(fh, true);   // inputs of the three units (k7, dilated)
-            yb[3] = hb(fh, lastb);                               // block output; the last one feeds outConv (k7)
-            conv_h1(ps, Bk.tconv, ys, false, T, ppf, yb[0], nullptr, nullptr, nullptr);
-            T *= Bk.stride;
-            ppf *= Bk.stride;
-            for (int j = 0; j < 3; ++j) {
-                ResUnitH1Args r{};
-                r.y = yb[j] + size_t(H) * fh; r.out = yb[j + 1] + size_t(H) * fh;
-                if (j == 2 && after) { r.out2 = hs_next + size_t(H) * fh; r.post_ea = after->ea16; r.post_ib = after->ib16; }
-                r.b1 = Bk.res[j].conv1.bias; r.b2 = Bk.res[j].conv2.bias;
-                r.w1 = Bk.res[j].conv1.w1; r.w2p = Bk.res[j].conv2.w1p;
-                r.ea1 = Bk.res[j].act1.ea16; r.ib1 = Bk.res[j].act1.ib16; r.ea2 = Bk.res[j].act2.ea16; r.ib2 = Bk.res[j].act2.ib16;
-                r.frames = ps.fr; r.ppf = ppf; r.Tmax = T; r.B = ps.nb; r.C = Bk.Cout; r.dil = Bk.res[j].conv1.dil;
-                r.hist = H * ppf;
-                if (!S.dry) launch_resunit_h1(r, st_);
+    // 6. MainDecoder (:681-690), on E = fp32 tensors or, for a float16 speech tokenizer, float16 ones as the reference computes
+    // it. Every SnakeBeta sits in front of a conv; it is evaluated in the epilogue of the conv that PRODUCES the tensor (one
+    // sinf per element) and the activated copy is what the next conv stages.
+    auto main_decoder = [&](auto elem) {
+        using E = decltype(elem);
+        constexpr bool f16 = std::is_same<E, uint16_t>::value;
+        auto ten = [&](size_t per_frame, bool reads_back) { return static_cast<E*>(mem.get(per_frame * sizeof(E), reads_back)); };
+        auto cv = [&](const ConvW& cw, const void* x, bool x_f32, E* out, const E* res, const SnakeW* post, E* out2) {
+            if constexpr (f16) conv_h1(ps, cw, x, x_f32, T, ppf, out, res, post, out2);
+            else conv(ps, cw, static_cast<const float*>(x), T, ppf, out, nullptr, res, 0, post, out2);
+        };
+        const size_t nblk = w.blocks.size();
+        size_t ef = size_t(ppf) * w.init_conv.N;  // elements per frame of the current tensor
+        E* y = ten(ef, nblk == 0);                // the residual stream; without blocks it feeds outConv (k7)
+        E* ys = nblk ? ten(ef, true) : nullptr;   // SnakeBeta of it = the next transposed conv's input (one row back)
+        cv(w.init_conv, h, true, y, nullptr, nblk ? &w.blocks[0].snake : nullptr, ys);
+        mem.put(h);
+        capture(ps, "init_conv", y, T, w.init_conv.N);
+        for (size_t i = 0; i < nblk; ++i) {
+            const auto& Bk = w.blocks[i];
+            const SnakeW* after = i + 1 < nblk ? &w.blocks[i + 1].snake : nullptr;
+            const bool lastb = i + 1 == nblk;  // the last block feeds outConv (k7)
+            ef = size_t(ppf) * Bk.stride * Bk.Cout;
+            mem.put(y);  // the block reads the activated copy alone
+            E* ys_next = nullptr;
+            if (fused_block(Bk, E{})) {
+                y = ten(ef, true);  // the units' inputs: k7, dilated
+                cv(Bk.tconv, ys, false, y, nullptr, nullptr, nullptr);  // snake (already applied by the producer) -> transposed conv
+                mem.put(ys);
+                T *= Bk.stride;
+                ppf *= Bk.stride;
+                for (int j = 0; j < 3; ++j) {
+                    E* yout = ten(ef, j < 2 || lastb);
+                    if (j == 2 && after) ys_next = ten(ef, true);
+                    resunit(ps, Bk.res[j], Bk.Cout, T, ppf, y, yout, ys_next, after);
+                    mem.put(y);
+                    y = yout;
+                }
+            } else {
+                y = ten(ef, lastb);
+                E* ya = ten(ef, true);  // act1(y): conv1's input (k7, dilated)
+                cv(Bk.tconv, ys, false, y, nullptr, &Bk.res[0].act1, ya);  // snake -> transposed conv (:474-475)
+                mem.put(ys);
+                T *= Bk.stride;
+                ppf *= Bk.stride;
+                E* t1 = ten(ef, false);
+                for (int j = 0; j < 3; ++j) {  // DecoderResidualUnit (:430-437): y += conv2(act2(conv1(act1(y))))
+                    cv(Bk.res[j].conv1, ya, false, nullptr, nullptr, &Bk.res[j].act2, t1);
+                    const SnakeW* next = j < 2 ? &Bk.res[j + 1].act1 : after;
+                    E* yn = next ? ten(ef, true) : nullptr;  // the next unit's input, or the next block's
+                    cv(Bk.res[j].conv2, t1, false, y, y, next, yn);
+                    mem.put(ya);
+                    ya = yn;
+                }
+                mem.put(t1);
+                ys_next = ya;
             }
-            h = yb[3];
-        } else {
-            uint16_t* y = hb(fh, lastb);
-            uint16_t* ya[3];
-            for (int j = 0; j < 3; ++j) ya[j] = hb(fh, true);  // act1_j(y): conv1_j's input (k7, dilated)
-            uint16_t* t1 = hb(fh, false);
-            conv_h1(ps, Bk.tconv, ys, false, T, ppf, y, nullptr, &Bk.res[0].act1, ya[0]);
-            T *= Bk.stride;
-            ppf *= Bk.stride;
-            for (int j = 0; j < 3; ++j) {
-                conv_h1(ps, Bk.res[j].conv1, ya[j], false, T, ppf, nullptr, nullptr, &Bk.res[j].act2, t1);
-                const SnakeW* next = j < 2 ? &Bk.res[j + 1].act1 : after;
-                conv_h1(ps, Bk.res[j].conv2, t1, false, T, ppf, y, y, next, j < 2 ? ya[j + 1] : hs_next);
-            }
-            h = y;
+            ys = ys_next;
+            capture(ps, ("block" + std::to_string(i)).c_str(), y, T, Bk.Cout);
         }
-        ys = hs_next;
-    }
-    if (!S.dry)
-        launch_out_conv_h1(h + size_t(H) * fh, w.out_C, w.out_snake.ea16, w.out_snake.ib16, w.out_w, w.out_b, ps.fr, ppf, T, ps.nb,
-                           pcm + size_t(H) * ppf, st_, nf_dev_, H * ppf);
+        // 7. outSnake -> outConv -> clip (:687-688, :781)
+        launch([&] {
+            const E* x = y + size_t(H) * ppf * w.out_C;
+            float* out = pcm + size_t(H) * ppf;
+            if constexpr (f16)
+                launch_out_conv_h1(x, w.out_C, w.out_snake.ea16, w.out_snake.ib16, w.out_w, w.out_b, fr, ppf, T, nb, out, st_, nf_dev_ + ps.row0, H * ppf);
+            else
+                launch_out_conv(x, w.out_C, w.out_snake.ea, w.out_snake.ib, w.out_w, w.out_b, fr, ppf, T, nb, out, st_, H * ppf, nf_dev_ + ps.row0);
+        });
+        mem.put(y);
+    };
+    if (w.f16_main && !fp32_mfma_ && !no_h1_) main_decoder(uint16_t{});
+    else main_decoder(float{});
     Q3_CHECK(ppf == up_, 7, "internal error: codec upsampling mismatch");
 }
 
@@ -448,8 +403,7 @@ int CodecRunner::decode(const int32_t* codes_dev, int code_stride_frames, const 
     int rows_per_chunk = int(std::max<size_t>(1, kScratchBudget / (4 * per_frame * Fmax * sizeof(float))));
     rows_per_chunk = std::min(rows_per_chunk, B);
     const size_t big = align_up(size_t(rows_per_chunk) * Fmax * per_frame * sizeof(float), 256);
-    ensure(align_up(pcm_floats * sizeof(float), 256) + 4 * big);
-    float* pcm = reinterpret_cast<float*>(buf_);
+    float* pcm = reinterpret_cast<float*>(buf_.grow(align_up(pcm_floats * sizeof(float), 256) + 4 * big));
     float* bufs[4];
     for (int i = 0; i < 4; ++i) bufs[i] = reinterpret_cast<float*>(buf_ + align_up(pcm_floats * sizeof(float), 256) + size_t(i) * big);
     upload_lens(frames.data(), B);
@@ -460,7 +414,8 @@ int CodecRunner::decode(const int32_t* codes_dev, int code_stride_frames, const 
         ps.fr = lens_dev_ + r0;
         ps.stage = &stage; ps.stage_out = stage_out; ps.stage_T = stage_T; ps.stage_C = stage_C;
         run_front(ps, codes_dev + size_t(r0) * code_stride_frames * 16, code_stride_frames, Fmax, bufs);
-        run_tail(ps, Fmax, bufs, pcm + size_t(r0) * Fmax * up_);
+        Ring ring(bufs, big, size_t(ps.nb) * Fmax);
+        run_tail(ps, ring, bufs[0], Fmax, pcm + size_t(r0) * Fmax * up_);
     }
     if (nonfinite_host) Q3_HIP(hipMemcpyAsync(nonfinite_host, nf_dev_, size_t(B) * 4, hipMemcpyDeviceToHost, st_));
     *pcm_dev = pcm;
@@ -488,18 +443,13 @@ int CodecRunner::decode_chunked(const int32_t* codes_dev, int code_stride_frames
     const size_t per_frame = floats_per_frame();
     const size_t front_bytes = align_up(size_t(B) * Fmax * dc.latent_dim * sizeof(float), 256);
     // front: four buffers of [B][Fmax] x (widest front tensor); tail: four of [B][Tc] x per_frame; x_all keeps the front's result
-    size_t front_pf = std::max<size_t>(size_t(2) * m_.codec.inner, size_t(dc.codebook_dim));
-    front_pf = std::max(front_pf, size_t(3) * dc.num_attention_heads * 64);
-    front_pf = std::max(front_pf, size_t(2) * dc.intermediate_size);
-    front_pf = std::max(front_pf, size_t(dc.latent_dim));
     // rows per pass: like decode(), a batch whose activations exceed the scratch budget goes through in groups of rows (the
     // codes of a finished AR loop must never be lost to a scratch limit); x_all always holds every row
-    const size_t per_row = std::max(size_t(Fmax) * front_pf, size_t(Tc) * per_frame) * sizeof(float);
+    const size_t per_row = std::max(size_t(Fmax) * front_floats_per_frame(), size_t(Tc) * per_frame) * sizeof(float);
     const int G = int(std::min<size_t>(size_t(B), std::max<size_t>(1, kScratchBudget / (4 * per_row))));
     const size_t big = align_up(size_t(G) * per_row, 256);
     const size_t pcm_bytes = align_up(size_t(G) * Tc * up_ * sizeof(float), 256);
-    ensure(pcm_bytes + front_bytes + 4 * big);
-    float* pcm = reinterpret_cast<float*>(buf_);
+    float* pcm = reinterpret_cast<float*>(buf_.grow(pcm_bytes + front_bytes + 4 * big));
     float* x_all = reinterpret_cast<float*>(buf_ + pcm_bytes);
     float* bufs[4];
     for (int i = 0; i < 4; ++i) bufs[i] = reinterpret_cast<float*>(buf_ + pcm_bytes + front_bytes + size_t(i) * big);
@@ -531,7 +481,8 @@ int CodecRunner::decode_chunked(const int32_t* codes_dev, int code_stride_frames
             ps.nb = std::min(G, B - r0); ps.row0 = r0; ps.fr = lens_dev_ + size_t(1 + k) * B + r0; ps.stage = &none;
             Q3_HIP(hipMemcpy2DAsync(bufs[0], size_t(T) * row_in, x_all + (size_t(r0) * Fmax + h0) * dc.latent_dim, size_t(Fmax) * row_in,
                                     size_t(T) * row_in, size_t(ps.nb), hipMemcpyDeviceToDevice, st_));
-            run_tail(ps, T, bufs, pcm);
+            Ring ring(bufs, big, size_t(ps.nb) * T);
+            run_tail(ps, ring, bufs[0], T, pcm);
             Q3_HIP(hipMemcpy2DAsync(pcm_host + (size_t(r0) * Fmax + f0) * up_, size_t(Fmax) * up_ * sizeof(float), pcm + size_t(f0 - h0) * up_,
                                     size_t(T) * up_ * sizeof(float), size_t(f1 - f0) * up_ * sizeof(float), size_t(ps.nb),
                                     hipMemcpyDeviceToHost, st_));
@@ -569,19 +520,20 @@ int CodecRunner::hist_frames() const {
     return need;
 }
 
-float* CodecRunner::sbuf(size_t frame_floats, bool keeps_history) {
+void CodecRunner::stream_prefix() {
     Stream& S = stream_;
-    S.off = align_up(S.off, 256);
-    float* p = S.dry ? nullptr : reinterpret_cast<float*>(S.arena + S.off);
-    S.off += size_t(S.cfg.rows) * S.Tal * frame_floats * sizeof(float);
-    if (keeps_history && !S.dry) S.rolls.emplace_back(p, frame_floats);
-    return p;
+    S.off = 0;
+    S.rolls.clear();
+    for (auto& f : S.fbufs) f = reinterpret_cast<float*>(S.take(S.fbuf_floats * sizeof(float)));
+    const size_t all = size_t(S.cfg.rows) * S.cfg.max_frames * m_.cfg.codec.latent_dim * sizeof(float);
+    S.x_all = S.cfg.window < 0 ? reinterpret_cast<float*>(S.take(all)) : nullptr;
+    S.lat = static_cast<float*>(S.get(size_t(m_.cfg.codec.latent_dim) * sizeof(float), false));
+    S.pcm = static_cast<float*>(S.get(size_t(up_) * sizeof(float), false));
 }
 
 void CodecRunner::stream_open(const StreamCfg& cfg) {
     Stream& S = stream_;
     Q3_CHECK(!S.open, 3, "Invalid input: a streamed decode is already open on this model");
-    const CodecDecoderConfig& dc = m_.cfg.codec;
     S.cfg = cfg;
     S.hist = hist_frames();
     Q3_CHECK(cfg.rows >= 1 && cfg.max_frames >= 1 && cfg.lookahead >= 0, 3, "Invalid input: streamed decode geometry");
@@ -593,21 +545,11 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
     const int n_chunks = ceil_div(cfg.max_frames, cfg.chunk_frames);
     // front scratch: the widest front tensor over the longest window
     const int Fwin = cfg.window < 0 ? cfg.max_frames : std::min(cfg.max_frames, cfg.window + cfg.chunk_frames + cfg.lookahead);
-    size_t front_pf = std::max<size_t>(size_t(2) * m_.codec.inner, size_t(dc.codebook_dim));
-    front_pf = std::max(front_pf, size_t(3) * dc.num_attention_heads * 64);
-    front_pf = std::max(front_pf, size_t(2) * dc.intermediate_size);
-    front_pf = std::max(front_pf, size_t(dc.latent_dim));
-    S.fbuf_floats = size_t(cfg.rows) * Fwin * front_pf;
-    // layout pass (no launches: the walk below and run_tail_stream only count), then one allocation
-    auto take = [&](size_t floats) {
-        S.off = align_up(S.off, 256);
-        float* p = S.arena ? reinterpret_cast<float*>(S.arena + S.off) : nullptr;
-        S.off += floats * sizeof(float);
-        return p;
-    };
-    // Whatever leaves this function -- the arena allocation failing, a check inside run_tail_stream -- the counting mode
-    // ends with it: conv() launches nothing while `dry` is set, and a runner left in that state would turn every later
-    // decode of the model into launches of the glue kernels alone (finite garbage, status OK).
+    S.fbuf_floats = size_t(cfg.rows) * Fwin * front_floats_per_frame();
+    // Layout pass (no launches: the walk only counts), then one allocation. Whatever leaves this function -- the arena
+    // allocation failing, a check inside run_tail -- the counting mode ends with it: nothing is launched while `dry` is set,
+    // and a runner left in that state would turn every later decode of the model into launches of the glue kernels alone
+    // (finite garbage, status OK).
     struct DryOff {
         Stream& s;
         ~DryOff() {
@@ -616,46 +558,21 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
         }
     } dry_off{S};
     S.dry = true;
-    S.off = 0;
-    for (int i = 0; i < 4; ++i) (void)take(S.fbuf_floats);
-    if (cfg.window < 0) (void)take(size_t(cfg.rows) * cfg.max_frames * dc.latent_dim);
-    (void)sbuf(size_t(dc.latent_dim), false);
-    (void)sbuf(size_t(up_), false);
-    {
-        Pass ps{};
-        ps.nb = cfg.rows;
-        ps.hist_frames = S.hist;
-        run_tail_stream(ps, nullptr, nullptr);
-    }
+    Pass ps{};
+    ps.nb = cfg.rows;
+    ps.hist_frames = S.hist;
+    stream_prefix();
+    run_tail(ps, S, S.lat, S.Tal, S.pcm);
     const size_t need = align_up(S.off, 256);
-    if (need > S.arena_bytes) {
-        Q3_HIP(hipStreamSynchronize(st_));
-        if (S.arena) Q3_HIP(hipFree(S.arena));
-        S.arena = nullptr;
-        S.arena_bytes = 0;
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&S.arena), need));
-        S.arena_bytes = need;
-    }
+    if (need > S.arena.capacity()) Q3_HIP(hipStreamSynchronize(st_));  // the old arena may still be read
+    S.arena.grow(need);
     S.dry = false;
-    S.off = 0;
-    S.rolls.clear();
-    for (auto& f : S.fbufs) f = take(S.fbuf_floats);
-    S.x_all = cfg.window < 0 ? take(size_t(cfg.rows) * cfg.max_frames * dc.latent_dim) : nullptr;
-    S.lat = sbuf(size_t(dc.latent_dim), false);
-    S.pcm = sbuf(size_t(up_), false);
-    S.dry = false;
+    stream_prefix();
     // history margins start as zeros: the causal left padding of the first chunk
     Q3_HIP(hipMemsetAsync(S.arena, 0, need, st_));
     const size_t slots = size_t(2) * n_chunks + 2;
-    if (slots * cfg.rows > S.lens_slots) {
-        if (S.lens_host) Q3_HIP(hipHostFree(S.lens_host));
-        if (S.lens_dev) Q3_HIP(hipFree(S.lens_dev));
-        S.lens_host = nullptr;
-        S.lens_dev = nullptr;
-        Q3_HIP(hipHostMalloc(reinterpret_cast<void**>(&S.lens_host), slots * cfg.rows * 4, hipHostMallocDefault));
-        Q3_HIP(hipMalloc(reinterpret_cast<void**>(&S.lens_dev), slots * cfg.rows * 4));
-        S.lens_slots = slots * cfg.rows;
-    }
+    S.lens_host.grow(slots * cfg.rows);
+    S.lens_dev.grow(slots * cfg.rows);
     Q3_CHECK(cfg.rows <= kMaxRows, 3, "Invalid input: too many rows in one codec decode");
     Q3_HIP(hipMemsetAsync(nf_dev_, 0, size_t(cfg.rows) * 4, st_));
     S.open = true;
@@ -675,7 +592,7 @@ int CodecRunner::stream_push(const int32_t* codes_dev, int code_stride_frames, c
     const int B = S.cfg.rows, C = S.cfg.chunk_frames, W = S.cfg.window, L = S.cfg.lookahead;
     const size_t lat = size_t(dc.latent_dim);
     auto lens_slot = [&](const std::vector<int32_t>& v) {
-        Q3_CHECK((S.lens_used + 1) * B <= S.lens_slots, 7, "internal error: streamed decode ran out of length slots");
+        Q3_CHECK((S.lens_used + 1) * B <= S.lens_dev.capacity(), 7, "internal error: streamed decode ran out of length slots");
         int32_t* h = S.lens_host + S.lens_used * B;
         int32_t* d = S.lens_dev + S.lens_used * B;
         std::memcpy(h, v.data(), size_t(B) * 4);
@@ -732,20 +649,9 @@ int CodecRunner::stream_push(const int32_t* codes_dev, int code_stride_frames, c
         for (int b = 0; b < B; ++b) v[size_t(b)] = std::max(0, std::min(avail[b], f1) - f0);
         ps.fr = lens_slot(v);
         ps.hist_frames = S.hist;
-        S.off = 0;       // the same walk over the arena as in stream_open
-        S.rolls.clear();
-        {
-            auto skip = [&](size_t floats) {
-                S.off = align_up(S.off, 256);
-                S.off += floats * sizeof(float);
-            };
-            for (int i = 0; i < 4; ++i) skip(S.fbuf_floats);
-            if (W < 0) skip(size_t(B) * S.cfg.max_frames * lat);
-            (void)sbuf(lat, false);
-            (void)sbuf(size_t(up_), false);
-        }
+        stream_prefix();  // the same walk over the arena as in stream_open
         Q3_HIP(hipMemsetAsync(S.pcm, 0, size_t(B) * S.Tal * up_ * 4, st_));
-        run_tail_stream(ps, S.lat, S.pcm);
+        run_tail(ps, S, S.lat, S.Tal, S.pcm);
         for (auto& r : S.rolls)
             launch_roll_history(r.first + size_t(S.hist) * r.second, int64_t(S.Tal) * int64_t(r.second), int64_t(S.hist) * int64_t(r.second),
                                 int64_t(C) * int64_t(r.second), B, st_);
@@ -762,109 +668,6 @@ int CodecRunner::stream_push(const int32_t* codes_dev, int code_stride_frames, c
         ++S.next_chunk;
     }
     return S.next_chunk;
-}
-
-// run_tail (steps 5-7, SpeechTokenizer.swift:767-781) over one chunk of a stream. The launches and their arguments are
-// run_tail's; what differs is where the tensors live: each in its own persistent buffer of Tal = hist + chunk frames per row
-// whose first `hist` frames are the previous chunk's last ones (rolled in by stream_push), so a conv's causal halo comes
-// from memory instead of being zero (first chunk: the margins are zero, i.e. exactly the reference's left padding).
-void CodecRunner::run_tail_stream(const Pass& ps, float* lat, float* pcm) {
-    const CodecDecoderConfig& dc = m_.cfg.codec;
-    const CodecW& w = m_.codec;
-    const Stream& S = stream_;
-    const int nb = ps.nb;
-    const int32_t* fr = ps.fr;
-    const int H = ps.hist_frames;
-    int T = S.Tal, ppf = 1;  // T: rows of an allocation at the current rate
-    float* h = lat;
-    // 5. upsample stages
-    for (size_t i = 0; i < w.ups.size(); ++i) {
-        const auto& U = w.ups[i];
-        const int C = U.tconv.N / U.stride;
-        const size_t ff = size_t(ppf) * U.stride * C;  // floats per frame behind the transposed conv
-        float* y = sbuf(ff, true);                     // dwconv reads six rows back
-        float* t1 = sbuf(ff, false);
-        float* t2 = sbuf(size_t(ppf) * U.stride * U.pw1.N, false);
-        const bool last = i + 1 == w.ups.size();
-        float* yo = sbuf(ff, last);                    // the last stage feeds initConv (k7)
-        conv(ps, U.tconv, h, T, ppf, y, nullptr, nullptr, 0);
-        T *= U.stride;
-        ppf *= U.stride;
-        if (!S.dry)
-            launch_dwconv_ln(y + size_t(H) * ff, U.dw_w, U.dw_b, U.ln_w, U.ln_b, 1e-6f, C, fr, ppf, T, nb, t1 + size_t(H) * ff, st_, H * ppf);
-        conv(ps, U.pw1, t1, T, ppf, t2, nullptr, nullptr, 1);
-        conv(ps, U.pw2, t2, T, ppf, yo, nullptr, y, 0);  // out of place: y keeps the values dwconv needs as history
-        h = yo;
-    }
-    // 6. MainDecoder
-    const size_t nblk = w.blocks.size();
-    if (w.f16_main && !fp32_mfma_ && !no_h1_) {  // a float16 speech tokenizer: float16 from initConv on, as in run_tail
-        run_main_h1_stream(ps, h, T, ppf, pcm);
-        return;
-    }
-    float* ys = nullptr;  // SnakeBeta of the previous stage's output = the next transposed conv's input
-    {
-        const size_t ff = size_t(ppf) * w.init_conv.N;
-        float* y = sbuf(ff, nblk == 0);
-        ys = nblk ? sbuf(ff, true) : nullptr;  // transposed conv: one row back
-        conv(ps, w.init_conv, h, T, ppf, y, nullptr, nullptr, 0, nblk ? &w.blocks[0].snake : nullptr, ys);
-        h = y;
-    }
-    for (size_t i = 0; i < nblk; ++i) {
-        const auto& Bk = w.blocks[i];
-        const SnakeW* after = i + 1 < nblk ? &w.blocks[i + 1].snake : nullptr;
-        const bool lastb = i + 1 == nblk;
-        bool fused = !fp32_mfma_ && !no_fuse_ && resunit_supported(Bk.Cout, Bk.res[0].conv1.K, 9);
-        for (int j = 0; j < 3; ++j)
-            fused = fused && Bk.res[j].conv1.wh && Bk.res[j].conv2.whp &&
-                    Bk.res[j].conv1.N == Bk.Cout && Bk.res[j].conv2.K == 1 &&
-                    resunit_supported(Bk.Cout, Bk.res[j].conv1.K, Bk.res[j].conv1.dil);
-        const size_t ff = size_t(ppf) * Bk.stride * Bk.Cout;
-        float* hs_next = after ? sbuf(ff, true) : nullptr;
-        if (fused) {
-            float* yb[4];
-            for (int j = 0; j < 3; ++j) yb[j] = sbuf(ff, true);   // inputs of the three units (k7, dilated)
-            yb[3] = sbuf(ff, lastb);                               // block output; the last one feeds outConv (k7)
-            conv(ps, Bk.tconv, ys, T, ppf, yb[0], nullptr, nullptr, 0);
-            T *= Bk.stride;
-            ppf *= Bk.stride;
-            for (int j = 0; j < 3; ++j) {
-                ResUnitArgs r{};
-                r.y = yb[j] + size_t(H) * ff; r.out = yb[j + 1] + size_t(H) * ff;
-                if (j == 2 && after) { r.out2 = hs_next + size_t(H) * ff; r.post_ea = after->ea; r.post_ib = after->ib; }
-                r.b1 = Bk.res[j].conv1.bias; r.b2 = Bk.res[j].conv2.bias;
-                r.w1h = Bk.res[j].conv1.wh; r.w2ph = Bk.res[j].conv2.whp; r.wsc1 = Bk.res[j].conv1.wsc; r.wsc2 = Bk.res[j].conv2.wsc;
-                r.ea1 = Bk.res[j].act1.ea; r.ib1 = Bk.res[j].act1.ib; r.ea2 = Bk.res[j].act2.ea; r.ib2 = Bk.res[j].act2.ib;
-                r.frames = fr; r.ppf = ppf; r.Tmax = T; r.B = nb; r.C = Bk.Cout; r.K = Bk.res[j].conv1.K; r.dil = Bk.res[j].conv1.dil;
-                r.hist = H * ppf;
-                if (!S.dry) launch_resunit(r, st_);
-            }
-            h = yb[3];
-        } else {
-            float* y = sbuf(ff, lastb);
-            float* ya[3];
-            for (int j = 0; j < 3; ++j) ya[j] = sbuf(ff, true);  // act1_j(y): conv1_j's input (k7, dilated)
-            float* t1 = sbuf(ff, false);
-            conv(ps, Bk.tconv, ys, T, ppf, y, nullptr, nullptr, 0, &Bk.res[0].act1, ya[0]);
-            T *= Bk.stride;
-            ppf *= Bk.stride;
-            for (int j = 0; j < 3; ++j) {
-                conv(ps, Bk.res[j].conv1, ya[j], T, ppf, nullptr, nullptr, nullptr, 0, &Bk.res[j].act2, t1);
-                const SnakeW* next = j < 2 ? &Bk.res[j + 1].act1 : after;
-                conv(ps, Bk.res[j].conv2, t1, T, ppf, y, nullptr, y, 0, next, j < 2 ? ya[j + 1] : hs_next);
-            }
-            h = y;
-        }
-        ys = hs_next;
-    }
-    // 7. outSnake -> outConv -> clip
-    if (!S.dry) {
-        const size_t ff = size_t(ppf) * w.out_C;
-        launch_out_conv(h + size_t(H) * ff, w.out_C, w.out_snake.ea, w.out_snake.ib, w.out_w, w.out_b, fr, ppf, T, nb,
-                        pcm + size_t(H) * ppf, st_, H * ppf, nf_dev_);
-    }
-    Q3_CHECK(ppf == up_, 7, "internal error: codec upsampling mismatch");
-    (void)dc;
 }
 
 }  // namespace q3

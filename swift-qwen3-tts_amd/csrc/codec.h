@@ -12,7 +12,6 @@ namespace q3 {
 class CodecRunner {
   public:
     CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false);
-    ~CodecRunner();
     // codes_dev: [B][code_stride_frames][16] int32 on the device; rows decode frames[b] frames.
     // pcm_dev receives [B][Fmax*upsample] float32 (Fmax = max(frames)); returns Fmax.
     // If `stage` is non-empty the activation after that stage is copied to stage_out ([B][T][C]).
@@ -73,41 +72,55 @@ class CodecRunner {
         int* stage_T = nullptr;
         int* stage_C = nullptr;
     };
+    // Every launch of the tail goes through here: the counting pass of stream_open (stream_.dry) walks the tail for its
+    // tensors alone, so nothing inside `f` is evaluated then -- neither the launch nor the addresses it is given.
+    template <class F>
+    void launch(F&& f) {
+        if (!stream_.dry) f();
+    }
     void conv(const Pass& ps, const struct ConvW& cw, const float* x, int Tmax, int ppf, float* out, const struct SnakeW* sn,
               const float* res, int act, const struct SnakeW* post = nullptr, float* out2 = nullptr);
-    void capture(const Pass& ps, const char* name, const float* t, int T, int C);
-    void run_front(const Pass& ps, const int32_t* codes, int code_stride_frames, int Fmax, float* const* bufs);
-    void run_tail(const Pass& ps, int Tframes, float* const* bufs, float* pcm);
-    // the MainDecoder (initConv .. outConv) of a float16 speech tokenizer on codec_conv_h1.hip: float16 tensors in the same
-    // four scratch buffers; in: bufs[cur] = the last ConvNeXt stage's fp32 output at T positions
-    void run_main_h1(const Pass& ps, int T, int ppf, int cur, float* const* bufs, float* pcm);
+    // the same on the float16 tensors of a float16 speech tokenizer's MainDecoder (codec_conv_h1.hip); x: float16, or fp32 when x_f32
     void conv_h1(const Pass& ps, const struct ConvW& cw, const void* x, bool x_f32, int Tmax, int ppf, uint16_t* out, const uint16_t* res,
                  const struct SnakeW* post, uint16_t* out2);
-    void capture_h(const Pass& ps, const char* name, const uint16_t* t, int T, int C);
-    // the tail over one chunk of a stream: `lat` = the chunk's pre-transformer frames (stream layout), pcm out (stream layout)
-    void run_tail_stream(const Pass& ps, float* lat, float* pcm);
-    void run_main_h1_stream(const Pass& ps, const float* h32, int T, int ppf, float* pcm);  // its float16 half (run_main_h1's twin)
-    float* sbuf(size_t frame_floats, bool keeps_history);  // next persistent tensor of the stream (same order every chunk)
+    // one DecoderResidualUnit of a narrow block in one launch, when fused_block() says so; out2: the next block's SnakeBeta copy
+    bool fused_block(const CodecW::Block& Bk, float) const;
+    bool fused_block(const CodecW::Block& Bk, uint16_t) const;
+    void resunit(const Pass& ps, const CodecW::Res& R, int C, int Tmax, int ppf, const float* y, float* out, float* out2, const struct SnakeW* after);
+    void resunit(const Pass& ps, const CodecW::Res& R, int C, int Tmax, int ppf, const uint16_t* y, uint16_t* out, uint16_t* out2,
+                 const struct SnakeW* after);
+    void capture(const Pass& ps, const char* name, const float* t, int T, int C);
+    void capture(const Pass& ps, const char* name, const uint16_t* t, int T, int C);
+    void run_front(const Pass& ps, const int32_t* codes, int code_stride_frames, int Fmax, float* const* bufs);
+    // The causal tail. `in`: the pre-transformer's frames, `Trows` rows per batch row in every tensor (streams: history
+    // margin + chunk); the tensors in between come from `mem`: a Ring over the four scratch buffers, or the open Stream.
+    struct Ring;
+    template <class Mem>
+    void run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float* pcm);
     struct Stream {
-        bool open = false, dry = false;
+        bool open = false, dry = false;  // dry: the counting pass of stream_open (no memory behind the tensors, no launches)
         StreamCfg cfg;
         int hist = 0, Tal = 0;       // margin frames, frames per allocation (hist + chunk)
         int next_chunk = 0;
         bool front_done = false;     // window < 0: the pre-transformer ran over all frames
-        uint8_t* arena = nullptr;
-        size_t arena_bytes = 0, off = 0;
+        DevBuf<uint8_t> arena;
+        size_t off = 0;
         std::vector<std::pair<float*, size_t>> rolls;  // (allocation base, frame floats) of the tensors with history
         float *lat = nullptr, *pcm = nullptr, *x_all = nullptr;
         float* fbufs[4] = {nullptr, nullptr, nullptr, nullptr};
         size_t fbuf_floats = 0;
-        int32_t* lens_host = nullptr;  // pinned, one slot per (chunk, kind): never reused inside a stream
-        int32_t* lens_dev = nullptr;
-        size_t lens_slots = 0, lens_used = 0;
+        PinnedBuf<int32_t> lens_host;  // one slot per (chunk, kind): never reused inside a stream
+        DevBuf<int32_t> lens_dev;
+        size_t lens_used = 0;
+        uint8_t* take(size_t bytes);  // bump allocation (same order in stream_open's two passes and in every chunk)
+        // the tail's next persistent tensor of Tal frames per row; one a later causal conv reads back into gets its margin rolled
+        void* get(size_t frame_bytes, bool reads_back);
+        void put(const void*) {}
     } stream_;
+    void stream_prefix();  // rewinds the arena and lays out its fixed part: front buffers, x_all, lat, pcm
+    size_t front_floats_per_frame() const;
     size_t floats_per_frame() const;
     void upload_lens(const int32_t* lens, int n);
-    int32_t* lens_host_ = nullptr;
-    int32_t* nf_dev_ = nullptr;  // [kMaxRows] non-finite flags of the decode in flight (out_conv)
     static constexpr int kMaxRows = 4096;
     const Model& m_;
     hipStream_t st_;
@@ -115,11 +128,10 @@ class CodecRunner {
     bool no_h1_ = false;      // Q3TTS_CODEC_NO_F16=1: a float16 speech tokenizer through the up-cast (fp32-equivalent) path
     bool no_fuse_ = false;    // Q3TTS_CODEC_NO_FUSE=1: residual units of the narrow blocks as two launches each
     bool fp32_mfma_ = false;  // Q3TTS_CODEC_FP32=1: contract on the fp32 matrix-core path instead of the split one
-    uint8_t* buf_ = nullptr;
-    size_t buf_bytes_ = 0;
-    int32_t* lens_dev_ = nullptr;
-    int lens_cap_ = 0;
-    void ensure(size_t bytes);
+    DevBuf<uint8_t> buf_;         // scratch of decode / decode_chunked
+    DevBuf<int32_t> lens_dev_;
+    PinnedBuf<int32_t> lens_host_;
+    DevBuf<int32_t> nf_dev_;      // [kMaxRows] non-finite flags of the decode in flight (out_conv)
 };
 
 }  // namespace q3

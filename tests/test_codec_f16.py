@@ -167,7 +167,7 @@ def _full_width_f16_checkpoint(d):
 @pytest.mark.parametrize("width", ["tiny", "real"])
 def test_float16_streamed_decode_is_the_float16_decode(tiny_h, tmp_path_factory, width):
     """Audio that leaves while tokens are still being generated, from a float16 speech tokenizer: the stream's tail runs the same
-    float16 kernels with the conv state carried in the tensors' history margins (CodecRunner::run_main_h1_stream), so
+    float16 kernels with the conv state carried in the tensors' history margins (CodecRunner::run_tail, tensors from the Stream arena), so
       * with the pre-transformer over all frames (window < 0) the streamed waveform IS the one-shot float16 decode, bit for bit,
         ragged rows included -- the property the fp32-equivalent stream has had since round 3;
       * with a sliding window it is the oracle's windowed restatement with the float16 tail (codec_decode_streamed(f16=True))

@@ -54,10 +54,22 @@ typedef struct {
     int32_t n_streams;  /* lanes the batch is split over (own HIP stream + hipGraph + host thread each);
                            0 = default (1). Results do not depend on it (rows are independent). With more than one
                            lane q3tts_generate_begin runs its job to completion (TOKEN, INFO and AUDIO events fire inside
-                           begin) and q3tts_generate_end only hands the results over: nothing overlaps */
-    int32_t codec_overlap_cus; /* compute units a codec decode is confined to while the NEXT batch's frame loop runs beside it
+                           begin) and q3tts_generate_end only hands the results over: nothing overlaps.
+                           With one lane (the default) the handle holds TWO job contexts, each with the whole per-batch state
+                           at max_batch x (max_prompt + max_frames) -- activation workspace, paged KV pool, per-row state, frame
+                           graphs, codec scratch -- so that two outstanding jobs generate side by side (q3tts_generate_begin).
+                           The second context is allocated at load and costs what the first one does: the KV pool,
+                           max_batch x ceil((max_prompt + max_frames + 1) / 64) pages of 64 tokens x layers x kv heads x 128 x
+                           2 (K, V) x 2 bytes, is the large part, the codec decoder's scratch (grown by the first decode on
+                           each context) the other. For the 1.7B talker, measured:
+                           at max_batch 32, max_frames 208, max_prompt 128 the second context adds 1.5 GiB at load (1.4 GiB of
+                           it KV pool) and 19.1 GiB once it has decoded 32 x 200 frames (the codec scratch); at the defaults
+                           (max_batch 1, max_frames 2048, max_prompt 512) 0.3 GiB at load and 0.9 GiB after a 200-frame call */
+    int32_t codec_overlap_cus; /* compute units a codec decode is confined to while other batches' frame loops run beside it
                            (q3tts_generate_begin with more_follows != 0); multiple of 8; 0 = default (tuned for a 1.7B
-                           talker at batch 32), -1 = never confine. Results do not depend on it */
+                           talker at batch 32: half of the CUs for a job whose AR loop ran inside begin, three quarters for
+                           a background job), n > 0 = that many for every job, -1 = never confine. Results do not depend
+                           on it */
     int32_t codec_fp32;  /* 1: the codec decoder's convolutions on the fp32 matrix cores (the reference's arithmetic range, 2.4x the
                            time) instead of fp16 matrix cores with every fp32 operand split into two fp16 planes (same accuracy,
                            activations limited to |x| < 65504: a decode that leaves that range reports
@@ -228,13 +240,25 @@ void q3tts_result_free(q3tts_result* results, int32_t n);
 
 /* q3tts_generate in two halves, for callers with a queue of batches (the reference has neither batches nor a queue:
  * its generate() decodes one-shot after the loop, Qwen3.swift:943-959, which is what each job still does).
- *   begin: prompt assembly, prefill and the AR loop of this batch (TOKEN events fire here); returns once the codes exist
- *          and their codec decode has been queued on the engine's second HIP stream.
- *   end:   waits for that decode, fills `results` (n_reqs entries of the begin call), fires INFO and AUDIO events, and
- *          releases the job.
- * A second begin may be issued before the first job's end: its AR loop (a latency-bound chain of small launches) then
- * overlaps the first job's decode (matrix-core work). At most 2 jobs may be outstanding per model handle; results do
- * not depend on the interleaving (the decode reads job-owned copies of the codes). q3tts_generate == begin + end.
+ *   begin: input checks, voice front end, prompt assembly and prefill of this batch, on the calling thread: whatever can
+ *          refuse a request refuses it here, and a begin that fails leaves the other job and both job slots as they were.
+ *          With `cb` != NULL (or audio_chunk_frames > 0) the AR loop runs inside begin as well: TOKEN events fire here,
+ *          on the calling thread, and begin returns once the codes exist and their codec decode has been queued on the
+ *          job's codec stream. With `cb` == NULL and audio_chunk_frames == 0 (a throughput job: nobody listens) begin
+ *          returns as soon as the prefill is queued -- BEFORE the codes exist -- and the AR loop runs on a thread owned by
+ *          the job's context. `reqs` is only read during begin either way.
+ *   end:   waits for the AR loop and the decode, fills `results` (n_reqs entries of the begin call), fires INFO and AUDIO
+ *          events, and releases the job. A failure of a background AR loop is reported here, with its status; the job
+ *          slot is released whatever end returns.
+ * A second begin may be issued before the first job's end. The handle has two job contexts (q3tts_load_opts.n_streams) and
+ * a job takes the free one, so the second job's AR loop -- a latency-bound chain of small launches that cannot fill the
+ * chip alone -- runs beside the first job's AR loop when both are background jobs, and beside its decode (matrix-core
+ * work) in any case. At most 2 jobs may be outstanding per model handle; results do not depend on the interleaving (jobs
+ * share nothing but the weights; the decode reads job-owned copies of the codes). q3tts_generate == begin + end, with the
+ * AR loop on the calling thread; successive calls alternate between the two contexts. q3tts_last_timing describes the job
+ * that was ENDED last. q3tts_model_free with jobs begun and never ended lets their AR loops finish first. The entry points
+ * that work on one engine (q3tts_codec_decode / _encode / _encoded_frames, q3tts_speaker_embedding, the q3tts_debug_* calls)
+ * use the first context and wait for a background AR loop still running on it.
  * `more_follows` != 0 says that another begin will be issued before this job's end: the decode is then confined to part
  * of the chip so that the next batch's launch chain keeps room (a decode that fills every CU stalls that chain and
  * nothing is gained); 0 (the last batch of a queue) lets the decode use the whole chip. Results do not depend on it. */

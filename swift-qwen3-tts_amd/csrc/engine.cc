@@ -59,6 +59,7 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
         // (mask bits interleave over the XCDs) the decode takes 1.7x as long but leaves the chain room: 879 -> 826 ms
         // per pipelined step at 1.7B / batch 32 (96 CUs: 841, 160: 841, 192: 856). A decode that nothing overlaps
         // (generate(), codec_decode) uses the unmasked stream. q3tts_load_opts.codec_overlap_cus overrides the CU count.
+        // (Half is the share beside ONE chain; a background job's decode gets a wider stream, prepare_job_pair.)
         int least = 0, greatest = 0;
         Q3_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         Q3_HIP(hipStreamCreateWithPriority(&st_, hipStreamNonBlocking, greatest));
@@ -69,14 +70,7 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
         if (opts.codec_overlap_cus > 0) cus = opts.codec_overlap_cus;   // q3tts_load_opts: the caller's own tuning
         else if (opts.codec_overlap_cus < 0) cus = 0;
         cus = std::min(cus, prop.multiProcessorCount) / 8 * 8;
-        if (cus > 0 && cus < prop.multiProcessorCount) {
-            std::vector<uint32_t> mask(size_t(ceil_div(prop.multiProcessorCount, 32)), 0u);
-            // mask bit i = CU (i / 8) of XCD (i % 8), CUs of an XCD numbered round-robin over its shader engines: the first
-            // half of the bits is half of every shader engine of every XCD. (Every other CU instead -- whole shader
-            // engines -- left the AR chain's workgroups queueing on the busy engines: 1008 against 807 ms per step.)
-            for (int i = 0; i < cus; ++i) mask[size_t(i / 32)] |= 1u << (i % 32);
-            Q3_HIP(hipExtStreamCreateWithCUMask(&st_codec_part_, uint32_t(mask.size()), mask.data()));
-        }
+        if (cus > 0 && cus < prop.multiProcessorCount) st_codec_part_ = masked_stream(cus, prop.multiProcessorCount);
     }
     for (auto& J : jobs_) {
         for (auto& e : J.ev_codec) Q3_HIP(hipEventCreate(&e));
@@ -110,7 +104,43 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
     if (m_->has_codec_encoder || m_->has_speaker_encoder) fe_ = std::make_unique<VoiceFrontEnd>(*m_, st_);
 }
 
+// mask bit i = CU (i / 8) of XCD (i % 8), CUs of an XCD numbered round-robin over its shader engines: the first `cus` bits are
+// the same share of every shader engine of every XCD. (Every other CU instead -- whole shader engines -- left the AR chain's
+// workgroups queueing on the busy engines: 1008 against 807 ms per step.)
+hipStream_t Engine::masked_stream(int cus, int total) {
+    std::vector<uint32_t> mask(size_t(ceil_div(total, 32)), 0u);
+    for (int i = 0; i < cus; ++i) mask[size_t(i / 32)] |= 1u << (i % 32);
+    hipStream_t st = nullptr;
+    Q3_HIP(hipExtStreamCreateWithCUMask(&st, uint32_t(mask.size()), mask.data()));
+    return st;
+}
+
+// This engine is one of an EngineGroup's two job contexts and jobs may run in the background (Engine::begin). Called at load:
+// nothing here is left for a steady-state step.
+void Engine::prepare_job_pair() {
+    job_chains = 2;  // two jobs' chains submit at once: under the AQL ring they count as two
+    // The decode's share of the chip was tuned beside ONE chain (half of the CUs, Engine::Engine), and a job whose frame loop
+    // runs inside begin still gets that. Two background jobs reach their decodes together, so such a decode mostly runs beside
+    // the other decode or one chain's tail, and the wider it is the sooner the next pair starts: 1.7B / batch 32 x 200 frames,
+    // frames/s at 64 / 96 / 128 / 160 / 192 CUs / unconfined: 9101 / 10097 / 10934 / 11042 / 11213 / 11222
+    // (profiles/r06_concurrent_jobs_ab.txt). A background job's decode therefore gets three quarters of the CUs: that keeps the
+    // confinement for a chain that does run beside it at no measurable cost against none. The caller's own
+    // codec_overlap_cus, when set, holds for every job.
+    if (opts_.codec_overlap_cus != 0 || !st_codec_part_ || st_codec_wide_) return;
+    hipDeviceProp_t prop{};
+    Q3_HIP(hipGetDeviceProperties(&prop, m_->device));
+    st_codec_wide_ = masked_stream(prop.multiProcessorCount * 3 / 4 / 8 * 8, prop.multiProcessorCount);
+}
+
 Engine::~Engine() {
+    if (worker_.joinable()) {  // a back half that was begun runs to its end first: it uses everything destroyed below
+        {
+            std::lock_guard<std::mutex> lk(work_mu_);
+            work_stop_ = true;
+        }
+        work_cv_.notify_all();
+        worker_.join();
+    }
     if (stager_.joinable()) {
         {
             std::lock_guard<std::mutex> lk(stage_mu_);
@@ -157,6 +187,7 @@ Engine::~Engine() {
         }
         (void)hipFree(stamps_);
     }
+    if (st_codec_wide_) (void)hipStreamDestroy(st_codec_wide_);
     if (st_codec_part_) (void)hipStreamDestroy(st_codec_part_);
     if (st_codec_) (void)hipStreamDestroy(st_codec_);
     if (st_) (void)hipStreamDestroy(st_);
@@ -1094,8 +1125,8 @@ void Engine::generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp
 }
 
 // The codec runner's scratch is shared by both codec streams: before it moves to the other one, the one it ran on drains.
-hipStream_t Engine::codec_stream(bool overlapped) {
-    hipStream_t want = overlapped && st_codec_part_ ? st_codec_part_ : st_codec_;
+hipStream_t Engine::codec_stream(bool overlapped, bool wide) {
+    hipStream_t want = overlapped && st_codec_part_ ? (wide && st_codec_wide_ ? st_codec_wide_ : st_codec_part_) : st_codec_;
     if (want != codec_->stream()) {
         Q3_HIP(hipStreamSynchronize(codec_->stream()));
         codec_->set_stream(want);
@@ -1154,7 +1185,7 @@ struct Engine::StreamedDecode {
 };
 
 int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const DebugOpts* dbg,
-                  bool overlapped) {
+                  bool overlapped, bool background) {
     Q3_HIP(hipSetDevice(m_->device));  // lanes run on their own host threads
     std::vector<ResolvedRequest> rr;
     double t_start = 0;
@@ -1175,12 +1206,83 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     Job& J = jobs_[slot];
     J.reset(n, codec_->upsample());
     J.chunk_frames = sp.audio_chunk_frames;
-    StreamedDecode sd(*this, J, sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && !any_clone && !dbg, sp, cb, user);
+    J.busy = true;  // nothing below gives the slot back except end() -- or a back half that fails inside this call
+    // The throughput jobs -- nobody listens for TOKEN events, nothing is streamed or dumped -- leave the frame loop to the
+    // worker thread, so that the caller can begin the next batch on the other context while this chain runs.
+    if (background && !cb && !dbg && sp.audio_chunk_frames == 0) {
+        J.background = true;
+        J.rr = std::move(rr);
+        J.np = std::move(np);
+        J.sp = sp;
+        J.overlapped = overlapped;
+        J.t_start = t_start;
+        std::lock_guard<std::mutex> lk(work_mu_);
+        if (!worker_.joinable()) worker_ = std::thread([this] { worker_loop(); });
+        J.back = 1;
+        J.back_status = 0;
+        J.back_err.clear();
+        work_ = &J;
+        work_cv_.notify_all();
+        return slot;
+    }
+    try {
+        back_half(J, rr, np, sp, cb, user, dbg, sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && !any_clone && !dbg, overlapped,
+                  t_start);
+    } catch (...) {
+        J.busy = false;
+        throw;
+    }
+    return slot;
+}
+
+void Engine::back_half(Job& J, const std::vector<ResolvedRequest>& rr, const std::vector<int>& np, const q3tts_sampling& sp,
+                       q3tts_event_cb cb, void* user, const DebugOpts* dbg, bool streamed, bool overlapped, double t_start) {
+    if (J.background && debug_env().fail_back_half) throw Error(7, "back half failed on request (Q3TTS_TEST_FAIL_BACK_HALF)");
+    StreamedDecode sd(*this, J, streamed, sp, cb, user);
     const int launched = frame_loop(J, rr, sp, cb, user, dbg, sd);
     hand_off(J, rr, sd, launched, overlapped);
     job_timing(J, np, launched);
     publish_job(J, cb, user, request_base, t_start, overlapped);  // a pipelined job: its rows are copied out while the next batch runs
-    return slot;
+}
+
+void Engine::worker_loop() {
+    std::unique_lock<std::mutex> lk(work_mu_);
+    for (;;) {
+        work_cv_.wait(lk, [&] { return work_ || work_stop_; });
+        if (!work_) return;  // (stop: only once the job that was begun has run)
+        Job& J = *work_;
+        work_ = nullptr;
+        lk.unlock();
+        int status = 0;
+        std::string err;
+        try {
+            Q3_HIP(hipSetDevice(m_->device));
+            back_half(J, J.rr, J.np, J.sp, nullptr, nullptr, nullptr, false, J.overlapped, J.t_start);
+        } catch (const Error& e) {
+            status = e.status;
+            err = e.what();
+        } catch (const std::exception& e) {
+            status = 7;
+            err = e.what();
+        } catch (...) {
+            status = 7;
+            err = "unknown exception in a job's frame loop";
+        }
+        lk.lock();
+        J.back_status = status;
+        J.back_err = err;
+        J.back = 0;
+        work_cv_.notify_all();
+    }
+}
+
+void Engine::drain() {
+    std::unique_lock<std::mutex> lk(work_mu_);
+    work_cv_.wait(lk, [&] {
+        for (const auto& J : jobs_)
+            if (J.back) return false;
+        return true;
+    });
 }
 
 int Engine::open_job(const q3tts_request* reqs, int n, const q3tts_sampling& sp, const DebugOpts* dbg, std::vector<ResolvedRequest>& rr,
@@ -1275,7 +1377,7 @@ int Engine::frame_loop(Job& J, const std::vector<ResolvedRequest>& rr, const q3t
     // Frames are enqueued in bursts with at most two bursts in flight (event ring), so the AQL queue never fills:
     // a host thread blocked on queue back-pressure starves the other lanes' submissions (measured: lanes gave no
     // speed-up until the depth was bounded). Variable-length runs also poll the finished flags once per burst.
-    const int burst_frames = std::max(1, max_inflight_frames / 2);
+    const int burst_frames = std::max(1, max_inflight_frames / job_chains / 2);
     hipEvent_t ring[2] = {burst_ev_[0], burst_ev_[1]};
     int bursts = 0;
     bool done = false;
@@ -1389,7 +1491,7 @@ void Engine::hand_off(Job& J, const std::vector<ResolvedRequest>& rr, StreamedDe
 }
 
 void Engine::start_decode(Job& J, const std::vector<int>& dframes, bool overlapped, const int32_t* codes_host) {
-    hipStream_t cst = codec_stream(overlapped);
+    hipStream_t cst = codec_stream(overlapped, J.background);
     Q3_HIP(hipEventRecord(J.ev_codec[0], cst));
     if (J.Fdec > 0) {
         const size_t floats = size_t(J.n) * J.Fdec * J.up;
@@ -1452,6 +1554,7 @@ void Engine::release_job(Job& J) {
     }
     J.st_pcm.clear();  // frees every row not handed over to a result
     J.st_codes.clear();
+    J.back_status = 0;
     J.busy = false;
 }
 
@@ -1468,7 +1571,7 @@ void Engine::Job::reset(int rows, int upsample) {
     held_from.assign(size_t(n), -1);
     std::memset(nf_host, 0, nf_host.capacity() * 4);
     n_chunks = chunk_frames = chunks_fired = 0;
-    streamed = decoded = false;
+    streamed = decoded = background = false;
     t_first_audio = t_done = 0;
     timing = q3tts_timing{};
 }
@@ -1699,6 +1802,11 @@ void Engine::end(int job, q3tts_result* results) {
         ~Release() { e->release_job(*j); }
     } release{this, &J};
     Q3_HIP(hipSetDevice(m_->device));
+    {   // a back half on the worker thread: wait for it; what it threw is reported here, with its status
+        std::unique_lock<std::mutex> lk(work_mu_);
+        work_cv_.wait(lk, [&] { return J.back == 0; });
+        if (J.back_status) throw Error(J.back_status, J.back_err);
+    }
     const int n = J.n;
     const std::vector<int64_t>& row_ns = J.row_ns;
     if (J.n_chunks > 0) fire_chunks(J, J.n_chunks, nullptr, true);  // AUDIO_CHUNK events not delivered inside the loop
@@ -2253,8 +2361,9 @@ void Engine::debug_codec_stage(const int32_t* codes, int n_frames, const char* s
 // ------------------------------------------------------------------------------------------------
 EngineGroup::EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts) : model_(std::move(model)), opts_(opts) {
     int lanes = opts.n_streams;
-    // Measured: a lane's frame step takes ~4-5 ms whatever its batch size (latency-bound chain),
-    // and n concurrent chains overlap by only 1.6x (n=2) / 2.2x (n=4), so splitting a batch into lanes never pays.
+    // Measured: a lane's frame step takes ~4-5 ms whatever its batch size (latency-bound chain), and
+    // n concurrent chains overlap by 1.6x (n=2) / 2.2x (n=4). Splitting ONE batch into lanes therefore never pays -- each
+    // lane's chain is as long as the whole batch's. Two WHOLE batches on two chains do: that is the second job context below.
     if (lanes <= 0) lanes = 1;
     lanes = std::max(1, std::min(lanes, opts.max_batch));
     q3tts_load_opts lo = opts;
@@ -2266,15 +2375,40 @@ EngineGroup::EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& op
         lanes_.back()->max_inflight_frames = std::max(2, 12000 / 650 / lanes);
     }
     speakers = lanes_[0]->speakers;
+    if (lanes == 1) {
+        // The second job context: a full engine of its own (stream, workspace, KV pool, frame graphs, codec runner) on the
+        // shared model. Allocated here, at load, so that no steady-state step allocates; include/q3tts.h states the memory.
+        ctx1_ = std::make_unique<Engine>(model_.get(), lo);
+        ctx1_->cb_mutex = &cb_mutex_;
+        background_ = !debug_env().serial_jobs;  // (the serial switch: both contexts exist and alternate, on the parent's schedule)
+        if (background_)
+            for (Engine* e : {lanes_[0].get(), ctx1_.get()}) e->prepare_job_pair();
+    }
+}
+
+EngineGroup::~EngineGroup() {  // jobs begun and never ended: each engine lets its worker finish before its streams go
+    ctx1_.reset();
+    lanes_.clear();
+}
+
+Engine* EngineGroup::free_context() {
+    Engine* c[2] = {lanes_[0].get(), ctx1_.get()};
+    for (int k = 1; k <= 2; ++k) {
+        const int i = (last_ctx_ + k) & 1;
+        if (c[i]->job_outstanding()) continue;
+        last_ctx_ = i;
+        c[i]->row_offset = 0;
+        c[i]->request_base = 0;
+        return c[i];
+    }
+    throw Error(3, "Invalid input: two jobs are already outstanding (q3tts_generate_end must be called first)");
 }
 
 int EngineGroup::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, bool more_follows) {
     Q3_CHECK(n >= 1 && n <= opts_.max_batch, 3, "Invalid input: batch size must be between 1 and max_batch");
     if (lanes_.size() == 1) {
-        Engine& e = *lanes_[0];
-        e.row_offset = 0;
-        e.request_base = 0;
-        return e.begin(reqs, n, sp, cb, user, nullptr, more_follows);
+        Engine* e = free_context();
+        return (e == ctx1_.get() ? Engine::kJobSlots : 0) + e->begin(reqs, n, sp, cb, user, nullptr, more_follows, background_);
     }
     int slot = -1;
     for (int i = 0; i < Engine::kJobSlots; ++i)
@@ -2289,8 +2423,10 @@ int EngineGroup::begin(const q3tts_request* reqs, int n, const q3tts_sampling& s
 
 void EngineGroup::end(int job, q3tts_result* results) {
     if (lanes_.size() == 1) {
-        lanes_[0]->end(job, results);
-        timing = lanes_[0]->timing;
+        Q3_CHECK(job >= 0 && job < 2 * Engine::kJobSlots, 3, "Invalid input: no such outstanding job");
+        Engine& e = job >= Engine::kJobSlots ? *ctx1_ : *lanes_[0];
+        e.end(job % Engine::kJobSlots, results);
+        timing = e.timing;
         return;
     }
     Q3_CHECK(job >= 0 && job < Engine::kJobSlots && parked_[job].busy, 3, "Invalid input: no such outstanding job");
@@ -2334,10 +2470,13 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
     std::vector<int> lo((size_t)(L + 1), 0);
     const int per = n / L, rem = n % L;
     for (int i = 0; i < L; ++i) lo[size_t(i) + 1] = lo[size_t(i)] + per + (i < rem ? 1 : 0);
+    std::vector<Engine*> eng((size_t)(L));
+    for (int i = 0; i < L; ++i) eng[size_t(i)] = lanes_[size_t(i)].get();
+    if (L == 1) eng[0] = free_context();  // one lane: the call runs on the context that has no job outstanding
     run_lanes(L, L == 1 || n == 1, [&](int i) {
         const int a = lo[size_t(i)], b = lo[size_t(i) + 1];
         if (b <= a) return;
-        Engine& e = *lanes_[size_t(i)];
+        Engine& e = *eng[size_t(i)];
         e.row_offset = uint32_t(a);
         e.request_base = a;
         DebugOpts d;
@@ -2358,7 +2497,7 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
     timing = q3tts_timing{};
     for (int i = 0; i < L; ++i) {
         if (lo[size_t(i) + 1] <= lo[size_t(i)]) continue;
-        const q3tts_timing& t = lanes_[size_t(i)]->timing;
+        const q3tts_timing& t = eng[size_t(i)]->timing;
         timing.prefill_ms = std::max(timing.prefill_ms, t.prefill_ms);
         timing.decode_ms = std::max(timing.decode_ms, t.decode_ms);
         timing.codec_ms = std::max(timing.codec_ms, t.codec_ms);
@@ -2380,6 +2519,7 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     bool outstanding = false;
     for (const auto& p : parked_) outstanding = outstanding || p.busy;
     for (const auto& l : lanes_) outstanding = outstanding || l->job_outstanding();
+    outstanding = outstanding || (ctx1_ && ctx1_->job_outstanding());  // (the queued path itself runs on the first context alone)
     Q3_CHECK(!outstanding, 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
     Q3_CHECK(model_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
     // every request is checked before any GPU work: a bad one late in the queue must not fail after the others were delivered

@@ -77,15 +77,23 @@ class Engine {
 
     void generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
                   q3tts_result* results, const DebugOpts* dbg);
-    // generate() in two halves (q3tts_generate_begin / _end): begin returns once the AR loop has finished and the codec
-    // decode of its codes is queued on the codec stream; end waits for the PCM and fills the results. A second begin()
-    // may run between the two: its AR loop (a latency-bound chain that leaves the matrix cores idle) then overlaps the
-    // first job's decode (matrix-core bound). Jobs may end in any order; at most kJobSlots are outstanding.
+    // generate() in two halves (q3tts_generate_begin / _end). The front half of begin -- input checks, voice front end, prompt
+    // assembly, row reservation, prefill enqueued -- always runs on the caller's thread, so whatever can refuse a request
+    // refuses it inside begin. The back half -- frame loop, hand-off to the codec stream, timing -- runs there too when the job
+    // has an event callback, DebugOpts or chunked audio, or when `background` is false: begin then returns once the AR loop
+    // has finished and the decode of its codes is queued. Otherwise the back half runs
+    // on this engine's worker thread and begin returns as soon as the prefill is enqueued; end waits for the back half and
+    // rethrows what it threw. end then waits for the PCM and fills the results. Jobs may end in any order; at most kJobSlots
+    // are outstanding. An EngineGroup with one lane keeps two engines (contexts) and gives each job the free one, so the AR
+    // loops of two outstanding background jobs run side by side, each chain on a stream of its own.
     static constexpr int kJobSlots = 2;
     int begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const DebugOpts* dbg,
-              bool overlapped);  // overlapped: another batch's AR loop is expected to run beside this one's decode
+              bool overlapped,  // overlapped: another batch's AR loop is expected to run beside this one's decode
+              bool background = false);
     void end(int job, q3tts_result* results);
     bool job_outstanding() const;
+    void prepare_job_pair();  // at load, by an EngineGroup that will run background jobs on its two contexts
+    void drain();             // returns once no back half is queued or running on the worker thread
     // Continuous batching (q3tts_generate_queued). check_queued resolves one request and applies every limit the slot loop
     // would hit (prompt, trailing text, max_frames, RoPE range) on the host, before any GPU work. run_queued keeps `slots`
     // rows in flight: at each burst boundary finished rows are retired (codes copied out, decode queued on the codec stream
@@ -117,12 +125,16 @@ class Engine {
     std::mutex* cb_mutex = nullptr;  // serialises event callbacks across lanes
     int request_base = 0;          // added to request_index in events
     int max_inflight_frames = 16;  // frame steps queued but not finished (two bursts of half this)
+    int job_chains = 1;            // contexts whose begin / end jobs may submit at once: each job's frame loop keeps to its share of
+                                   // max_inflight_frames (the queued path runs alone on the first context and keeps all of it)
   private:
     q3tts_load_opts opts_;
     hipStream_t st_ = nullptr;
     hipStream_t st_codec_ = nullptr;       // codec decode that nothing overlaps (lower priority than st_)
     hipStream_t st_codec_part_ = nullptr;  // codec decode beside the next batch's AR loop: confined to half of the CUs
-    hipStream_t codec_stream(bool overlapped);
+    hipStream_t st_codec_wide_ = nullptr;  // the same for a background job, whose decode runs beside the other job's: three quarters
+    hipStream_t masked_stream(int cus, int total);
+    hipStream_t codec_stream(bool overlapped, bool wide = false);
     hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t burst_ev_[2] = {nullptr, nullptr};
     hipEvent_t ev_fe_[2] = {nullptr, nullptr};
@@ -165,8 +177,18 @@ class Engine {
     // One slot per outstanding job: everything the second half (codec decode -> results) needs after the next begin()
     // has started to overwrite the engine's per-call state.
     struct Job {
-        bool busy = false;
+        std::atomic<bool> busy{false};
         uint64_t seq = 0;                 // begin order
+        // a back half on the worker thread: what it needs once begin() has returned (the caller's request memory is only
+        // valid during begin), and how it ended
+        std::vector<ResolvedRequest> rr;
+        std::vector<int> np;
+        q3tts_sampling sp{};
+        bool overlapped = false;
+        bool background = false;  // the back half runs on the worker thread (and the decode on the wider masked stream)
+        int back = 0;         // 1: queued for or running on the worker thread (work_mu_)
+        int back_status = 0;  // q3::Error status the back half ended with (0: it finished)
+        std::string back_err;
         int n = 0, Fdec = 0, up = 0;
         std::vector<int> frames, ref_T, target_tokens, n_prompt;
         std::vector<int> req_index;   // queued decode batch: row b is request req_index[b] (results / events); empty: row b
@@ -292,6 +314,15 @@ class Engine {
     int frame_loop(Job& J, const std::vector<ResolvedRequest>& rr, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
                    const DebugOpts* dbg, StreamedDecode& sd);
     void hand_off(Job& J, const std::vector<ResolvedRequest>& rr, StreamedDecode& sd, int launched, bool overlapped);
+    // frame_loop, hand_off, job_timing, publish_job: on the caller's thread inside begin, or on the worker thread
+    void back_half(Job& J, const std::vector<ResolvedRequest>& rr, const std::vector<int>& np, const q3tts_sampling& sp,
+                   q3tts_event_cb cb, void* user, const DebugOpts* dbg, bool streamed, bool overlapped, double t_start);
+    void worker_loop();  // one long-lived thread per engine, started by the first background job
+    std::thread worker_;
+    std::mutex work_mu_;
+    std::condition_variable work_cv_;
+    Job* work_ = nullptr;  // the job whose back half the worker takes next
+    bool work_stop_ = false;
     void job_timing(Job& J, const std::vector<int>& np, int launched);
     void upload_sampling(const q3tts_sampling& sp, uint32_t row0);  // sp_dev_ on st_
     int64_t kv_bytes(int n_prompt, int frames) const;  // talker KV bytes the frame steps of one row read
@@ -337,20 +368,26 @@ class Engine {
 };
 
 
-// The object behind q3tts_model: the model plus `n_lanes` engines. q3tts_generate splits its rows
-// contiguously over the lanes; each lane is driven by its own host thread on its own HIP stream, so
-// the latency-bound frame steps of independent rows overlap on the GPU (the frame step is a chain
-// of ~800 short dependent kernels; one chain cannot fill 256 CUs, several chains can).
+// The object behind q3tts_model: the model plus its engines. With n_streams > 1 they are lanes: q3tts_generate splits its
+// rows contiguously over them, each lane driven by its own host thread on its own HIP stream. That never pays (a lane's
+// frame step does not shrink with its rows) and stays as documented. With one lane (the default) the
+// group holds TWO full-size engines, the job contexts: chains on different streams do overlap (1.6x for two), so two whole
+// batches, each on a context of its own, are what the two-deep pipeline runs side by side (Engine::begin).
 class EngineGroup {
   public:
     EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts);
     Model& model() { return *model_; }
-    Engine& lane0() { return *lanes_[0]; }
+    ~EngineGroup();
+    Engine& lane0() {  // the engine behind the single-engine entry points; a back half still running on it finishes first
+        lanes_[0]->drain();
+        return *lanes_[0];
+    }
     int n_lanes() const { return int(lanes_.size()); }
     const q3tts_load_opts& opts() const { return opts_; }
     void generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
                   q3tts_result* results, const DebugOpts* dbg);
-    // Two-deep pipeline (Engine::begin / end). With more than one lane a job runs to completion inside begin.
+    // Two-deep pipeline (Engine::begin / end); the job id names the context and its slot. With more than one lane a job runs
+    // to completion inside begin.
     int begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, bool more_follows);
     void end(int job, q3tts_result* results);
     // q3tts_generate_queued: every request checked up front; `slots` rows split over the lanes, one shared queue
@@ -371,8 +408,14 @@ class EngineGroup {
     } parked_[Engine::kJobSlots];
     std::unique_ptr<Model> model_;
     q3tts_load_opts opts_;
-    std::vector<std::unique_ptr<Engine>> lanes_;
     std::mutex cb_mutex_;
+    std::vector<std::unique_ptr<Engine>> lanes_;
+    // one lane: the second job context (lanes_[0] is the first). A job takes a context without an outstanding job, the one
+    // that was not used last first, so that plain q3tts_generate calls alternate and a host's warm-up calls warm both.
+    std::unique_ptr<Engine> ctx1_;
+    int last_ctx_ = 1;
+    bool background_ = false;  // jobs without a callback run their back half on the context's worker (off: Q3TTS_SERIAL_JOBS)
+    Engine* free_context();  // throws when both contexts have a job outstanding
 };
 
 }  // namespace q3

@@ -26,6 +26,10 @@ struct DebugEnv {
     int pf_budget_kb;        // Q3TTS_PF_BUDGET_KB: bytes per XCD that may sit touched-ahead in its L2
     int pf_ahead;            // Q3TTS_PF_AHEAD: how many launches ahead a launch may look for a stream to touch
     int pf_skip;             // Q3TTS_PF_SKIP: pass over this many candidate streams first (experiments: which stream pays)
+    bool serial_jobs;        // Q3TTS_SERIAL_JOBS: every q3tts_generate_begin runs its frame loop on the caller's thread (A/B and
+                             // equality tests of the background back half, engine.h)
+    bool fail_back_half;     // Q3TTS_TEST_FAIL_BACK_HALF: a background job's back half throws on the host before it launches anything
+                             // (tests: the error must come out of q3tts_generate_end and the job slot must be released)
 };
 const DebugEnv& debug_env();
 void debug_env_reload();

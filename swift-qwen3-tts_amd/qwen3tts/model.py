@@ -324,10 +324,15 @@ class Qwen3TTSModel:
                              top_p: float = 1.0, repetition_penalty: float = 1.05, seed: int = 0, force_frames: int = 0,
                              on_event: Optional[Callable[[int, str, object], None]] = None, audio_chunk_frames: int = 0,
                              more_follows: bool = True, row_base: int = 0):
-        """First half of generate_batch (q3tts_generate_begin): returns a job once the AR loop has produced the codes and
-        their codec decode is queued. The next batch may be begun before this one is ended: its AR loop then overlaps
-        this batch's decode. At most two jobs may be outstanding. more_follows=False (the last batch of a queue) lets the
-        decode use the whole chip instead of leaving room for a next batch."""
+        """First half of generate_batch (q3tts_generate_begin). Input checks, prompt assembly and prefill happen here, so
+        a bad request raises here. With on_event the AR loop runs inside this call too (TOKEN events fire here) and the job
+        is returned once the codes exist and their codec decode is queued. Without on_event (and without audio_chunk_frames)
+        the job is returned as soon as the prefill is queued and the AR loop runs on a library thread: the next batch may be
+        begun at once, it takes the model's other job context, and the two AR loops run side by side on the GPU. Either
+        way the next batch's AR loop overlaps this batch's decode. At most two jobs may be outstanding; a failure of a
+        background AR loop is raised by generate_batch_end; last_timing() describes the job ended last.
+        more_follows=False (the last batch of a queue) lets the decode use the whole chip instead of leaving room for a
+        next batch."""
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames, row_base=row_base)
         cb = self._event_cb(on_event)

@@ -26,10 +26,6 @@ const DebugEnv* read_env() {
     d->chunk_qsplit = number("Q3TTS_CHUNK_QSPLIT", 0);
     d->conv_no_pw = flag("Q3TTS_CONV_NO_PW");
     d->nt_off = std::getenv("Q3TTS_NT") && number("Q3TTS_NT", 1) == 0;
-    d->prefetch = number("Q3TTS_PF", 1);
-    d->pf_budget_kb = number("Q3TTS_PF_BUDGET_KB", 2560);
-    d->pf_ahead = number("Q3TTS_PF_AHEAD", 3);
-    d->pf_skip = number("Q3TTS_PF_SKIP", 0);
     d->serial_jobs = number("Q3TTS_SERIAL_JOBS", 0) != 0;
     d->fail_back_half = number("Q3TTS_TEST_FAIL_BACK_HALF", 0) != 0;
     return d;

@@ -77,10 +77,6 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, const int kv
         }
     }
 
-    // behind this launch's own requests: weight lines of a later launch (prefetch.h), retired by the last instruction
-    uint32_t pfv[kPfTouches];
-    if constexpr (Q3_PF_MODE != 0) pf_issue<kPfTouches>(a.pf, uint32_t(kvh) + uint32_t(b) * a.pf.gx, NTH, tid, pfv);
-
     auto norm_rope_r = [&](float x0, float x1, uint16_t w0, uint16_t w1, float& o0, float& o1) {
         const float ss = wave_sum(x0 * x0 + x1 * x1);
         const float rstd = 1.0f / sqrtf(ss / (float)D + a.eps);
@@ -219,6 +215,5 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& a, const int kv
         const int col = (kvh * REP) * D + 8 * p;
         *reinterpret_cast<uint4*>(a.out + act_tiled_offset(b, col, a.outMB)) = *reinterpret_cast<const uint4*>(out_s + 8 * p);
     }
-    if constexpr (Q3_PF_MODE != 0) pf_retire<kPfTouches>(pfv);
 }
 

@@ -201,20 +201,7 @@ __global__ __launch_bounds__(NTH) void attn_chunk_kernel(AttnArgs a) {
 
 }  // namespace
 
-int attn_decode_threads(const AttnArgs& a) {
-    const int rep = a.n_heads / a.n_kv;
-    return (a.max_pages > 1 && rep <= 2) ? 512 : 256;
-}
-
-void launch_attn_decode(const AttnArgs& a0, hipStream_t st) {
-    AttnArgs a = a0;
-    if (!a.pf.base) {  // a caller outside the frame step's plan: an empty range on a valid address
-        a.pf = PfArgs{};
-        a.pf.base = reinterpret_cast<const uint8_t*>(a.qkv);
-        a.pf.span = 128; a.pf.lines = 1; a.pf.inv_lines = 1.0f;
-    }
-    a.pf.gx = uint32_t(a.n_kv);  // this launch's own geometry for its touch descriptor (prefetch.h)
-    a.pf.wg_per_xcd = uint32_t((a.n_kv * a.B + 7) / 8);
+void launch_attn_decode(const AttnArgs& a, hipStream_t st) {
     const int rep = a.n_heads / a.n_kv;
     Q3_CHECK(rep * a.n_kv == a.n_heads && rep >= 1 && rep <= kMaxRep, 3, "attn_decode: unsupported GQA ratio");
     dim3 grid(a.n_kv, a.B);

@@ -103,12 +103,6 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
         __builtin_amdgcn_sched_barrier(0);
     }
 
-    constexpr bool PF = gemm_touches(MB, CH);
-    uint32_t pfv[PF ? kPfTouches : 1];
-    if constexpr (PF && Q3_PF_MODE == 2) {
-        pf_issue<kPfTouches>(a.pf, uint32_t(tile) + blockIdx.y * a.pf.gx, NW * 64, threadIdx.x, pfv);
-        __builtin_amdgcn_sched_barrier(0);
-    }
     // 1. weight loads: they depend on nothing
     constexpr int CHR = CH > 0 ? CH : 1;
     constexpr int WL = QUANT ? 1 : 4;  // dwordx4 loads per (chunk, tile): packed int4 needs one
@@ -180,9 +174,6 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
     }
         }
     }
-    // 1c. decode shapes: touch weight lines of a later launch (prefetch.h) -- behind this launch's own requests, so its own
-    //     operands return first; the values are never looked at and are retired by the kernel's last instruction
-    if constexpr (PF && Q3_PF_MODE != 2) pf_issue<kPfTouches>(a.pf, uint32_t(tile) + blockIdx.y * a.pf.gx, NW * 64, threadIdx.x, pfv);
     __builtin_amdgcn_sched_barrier(0);  // every request above is issued before any arithmetic below
     uint4 hv_pre = make_uint4(0, 0, 0, 0);
     if constexpr (EPI == 3 && NT == 1) {
@@ -399,5 +390,4 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
         }
     }
     }
-    if constexpr (PF) pf_retire<kPfTouches>(pfv);
 }

@@ -60,23 +60,9 @@ __global__ __launch_bounds__(512) void gemm_skinny_side_kernel(GemmSideArgs s) {
     gemm_skinny_body<MB, 0, 8, CH, true, QUANT, 1, false>(s.g, blockIdx.x, blockIdx.y * MB);
 }
 
-// a with the launch's own geometry written into its touch descriptor (prefetch.h: gx, wg_per_xcd)
-inline GemmArgs with_geometry(const GemmArgs& a, const dim3& grid) {
-    GemmArgs b = a;
-    if (!b.pf.base) {  // a caller outside the frame step's plan: an empty range on a valid address (the touch loads are unconditional)
-        b.pf = PfArgs{};
-        b.pf.base = reinterpret_cast<const uint8_t*>(a.W);
-        b.pf.span = 128; b.pf.lines = 1; b.pf.inv_lines = 1.0f;
-    }
-    b.pf.gx = grid.x;
-    b.pf.wg_per_xcd = (grid.x * grid.y + 7) / 8;
-    return b;
-}
-
 template <int MB, int EPI, bool NORM, bool QUANT, bool NTW>
-void launch_mb(const GemmArgs& a0, const SkinnyGeom& g, hipStream_t st) {
+void launch_mb(const GemmArgs& a, const SkinnyGeom& g, hipStream_t st) {
     const dim3 grid(g.gx, g.split);
-    const GemmArgs a = with_geometry(a0, grid);
 #define Q3_GEMM(NWv, CHv) \
     hipLaunchKernelGGL((gemm_skinny_kernel<MB, EPI, NWv, CHv, NORM, QUANT, 1, NTW>), grid, dim3(NWv * 64), 0, st, a)
     if constexpr (MB == 4 && !NORM && !NTW) {
@@ -195,11 +181,11 @@ SkinnyGeom skinny_geometry(const GemmArgs& a) {
         if (g.nw == 4) g.ch = 1;
         else if (g.ch != 1 && g.ch != 2 && g.ch != 3 && g.ch != 6) g.ch = 0;
     }
-    g.touches = gemm_touches(g.mbw, g.ch);
     return g;
 }
 
-bool gemm_norm_rows_rides(const GemmArgs& a, const NormRowsArgs& n) {
+// whether launch_gemm_skinny_with_norm_rows launches for these arguments
+static bool gemm_norm_rows_rides(const GemmArgs& a, const NormRowsArgs& n) {
     if (a.epi != 0 || !a.norm_w || a.nt_weights || n.M <= 0 || n.H > 4096) return false;
     if (a.K % 128 != 0 || a.N % 16 != 0) return false;
     const SkinnyGeom g = skinny_geometry(a);
@@ -213,8 +199,7 @@ bool launch_gemm_skinny_with_norm_rows(const GemmArgs& a, const NormRowsArgs& n,
     Q3_CHECK(a.ss_in && a.ss_count >= 1 && a.ss_ld >= a.Mpad && a.xMB * 16 >= a.Mpad, 3, "gemm_skinny: norm prologue needs sums of squares");
     const int tiles = g.gx;
     const dim3 grid(tiles + n.M, g.split), block(512);
-    GemmSideArgs s{with_geometry(a, dim3(tiles, g.split)), n, tiles};
-    s.g.pf.gx = grid.x;  // the riders sit behind the tiles along x; they touch nothing themselves
+    const GemmSideArgs s{a, n, tiles};
     const bool q = a.Wsb != nullptr;
 #define Q3_SIDE(MBv, CHv)                                                                              \
     do {                                                                                               \

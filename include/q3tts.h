@@ -379,6 +379,43 @@ q3tts_status q3tts_debug_sample(q3tts_model* m, const uint16_t* logits, int32_t 
 q3tts_status q3tts_debug_linear(q3tts_model* m, const uint16_t* x, const uint16_t* W, const uint16_t* bias,
                                 int32_t M, int32_t K, int32_t N, uint16_t* y);
 
+/* One launch of the decode attention (csrc/kernels/attn_decode.hip: per-head QK RMSNorm -> RoPE -> KV append -> GQA
+ * attention over the paged cache) on caller-supplied buffers, through the product's own launch_attn_decode, so that the
+ * (GQA ratio, wide, nt_kv, chunk) dispatch picks the kernel instantiation exactly as a frame step would. The call allocates
+ * its own device buffers and frees them; it touches neither the model's weights nor its caches. Every argument is checked
+ * on the host (INVALID_INPUT): n_heads / n_kv in 1..4, chunk <= 16, every block-table entry a live position can reach
+ * in [0, n_pages), kv_len (or fixed_len) + the live positions <= max_pages * 64 (64 with identity_pages) and <= n_pos,
+ * identity_pages implies B <= n_pages.
+ *   rows = max(chunk, 1) * B; qkv/out row of chunk element p of batch row b is p * B + b.
+ *   kpool / vpool are read (initial contents) and written back WHOLE after the launch, so a caller sees every slot that
+ *   was or was not written. out comes back untiled; a row the kernel did not write (padding of a right-aligned chunk)
+ *   holds 0xFFFF in every element. */
+typedef struct {
+    int32_t n_heads, n_kv, B;
+    float eps, scale;
+    int32_t max_pages;       /* block_table columns */
+    int32_t fixed_len;       /* >= 0: every row's cache holds this many tokens (kv_len ignored); -1: kv_len */
+    int32_t identity_pages;  /* 1: row b owns page b (block_table ignored) */
+    int32_t chunk;           /* 0 / 1: one position per row; 2..16: that many consecutive positions per row */
+    int32_t chunk_r_base;    /* with chunk_n_prompt: element p of row b is prompt position chunk_r_base + chunk_n_prompt[b] + p */
+    int32_t nt_kv;
+    int32_t n_pos;           /* rows of the RoPE tables */
+    int32_t n_pages;         /* pages of each pool */
+    const uint16_t* qkv;             /* [rows][(n_heads + 2 n_kv) * 128] bf16 */
+    const uint16_t* qn_w;            /* [128] */
+    const uint16_t* kn_w;            /* [128] */
+    const uint16_t* rope_cos;        /* [n_pos][128] */
+    const uint16_t* rope_sin;
+    const int32_t* kv_len;           /* [B] */
+    const uint8_t* active;           /* [B] or NULL */
+    const int32_t* block_table;      /* [B][max_pages] */
+    const int32_t* chunk_n_prompt;   /* [B] or NULL (every chunk element is live) */
+    uint16_t* kpool;                 /* in / out [n_pages][n_kv][64][128] */
+    uint16_t* vpool;
+    uint16_t* out;                   /* out [rows][n_heads * 128] row-major */
+} q3tts_attn_debug;
+q3tts_status q3tts_debug_attention(q3tts_model* m, const q3tts_attn_debug* a);
+
 /* Codec decoder with intermediate activations (SpeechTokenizer.swift:754-784) for one utterance:
  * stage names: "quantizer","pre_conv","pre_transformer","upsample0","upsample1","init_conv",
  * "block0".."block3". Output is channels-last [T][C] float32; *T,*C receive the shape. */

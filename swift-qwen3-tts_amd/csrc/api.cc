@@ -421,6 +421,13 @@ q3tts_status q3tts_debug_linear(q3tts_model* m, const uint16_t* x, const uint16_
     });
 }
 
+q3tts_status q3tts_debug_attention(q3tts_model* m, const q3tts_attn_debug* a) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && a, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_attention(*a);
+    });
+}
+
 q3tts_status q3tts_codec_decode_streamed(q3tts_model* m, const int32_t* codes, const int32_t* n_frames, int32_t batch, int32_t max_frames,
                                          int32_t chunk_frames, int32_t window, int32_t lookahead, float* pcm) {
     return guarded(m, [&] {

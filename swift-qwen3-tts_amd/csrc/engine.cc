@@ -2093,6 +2093,88 @@ void Engine::debug_linear(const uint16_t* x, const uint16_t* W, const uint16_t* 
         if (p) (void)hipFree(p);
 }
 
+// One launch_attn_decode on the caller's buffers (q3tts.h). Everything the kernels turn into an address -- cache lengths,
+// block-table entries, the padding of a right-aligned chunk -- is checked here against the sizes the caller states.
+void Engine::debug_attention(const q3tts_attn_debug& d) {
+    Q3_CHECK(d.qkv && d.qn_w && d.kn_w && d.rope_cos && d.rope_sin && d.kpool && d.vpool && d.out, 3, "debug_attention: null argument");
+    Q3_CHECK(d.n_kv >= 1 && d.n_kv <= 64 && d.n_heads >= d.n_kv && d.n_heads % d.n_kv == 0 && d.n_heads / d.n_kv <= 4, 3,
+             "debug_attention: unsupported GQA ratio");
+    Q3_CHECK(d.B >= 1 && d.B <= 256, 3, "debug_attention: batch out of range");
+    Q3_CHECK(d.chunk >= 0 && d.chunk <= 16, 3, "debug_attention: at most 16 positions per launch");
+    Q3_CHECK(d.max_pages >= 1 && d.max_pages <= 64 && d.n_pages >= 1 && d.n_pages <= 4096 && d.n_pos >= 1 && d.n_pos <= 65536, 3,
+             "debug_attention: sizes out of range");
+    Q3_CHECK(d.fixed_len >= -1, 3, "debug_attention: fixed_len out of range");
+    Q3_CHECK(d.fixed_len >= 0 || d.kv_len, 3, "debug_attention: kv_len missing");
+    Q3_CHECK(d.identity_pages || d.block_table, 3, "debug_attention: block_table missing");
+    Q3_CHECK(!d.identity_pages || d.B <= d.n_pages, 3, "debug_attention: identity_pages needs a page per row");
+    const int B = d.B, C = std::max(d.chunk, 1), rows = C * B;
+    const int cap = (d.identity_pages ? 1 : d.max_pages) * kPageTokens;
+    for (int b = 0; b < B; ++b) {
+        const int len0 = d.fixed_len >= 0 ? d.fixed_len : d.kv_len[b];
+        int live = 1;  // the one-position kernel addresses the new token's slot and RoPE row whether or not it appends
+        if (d.chunk > 1 && d.chunk_n_prompt) {
+            const int64_t r0 = int64_t(d.chunk_r_base) + d.chunk_n_prompt[b];
+            live = r0 < 0 ? int(std::max<int64_t>(0, C + r0)) : C;
+        } else if (d.chunk > 1) {
+            live = C;
+        }
+        Q3_CHECK(len0 >= 0 && len0 <= cap && len0 + live <= cap && len0 + live <= d.n_pos, 3,
+                 "debug_attention: cache length beyond the pages or the RoPE tables");
+        if (!d.identity_pages)
+            for (int pg = 0; pg * kPageTokens < len0 + live; ++pg) {
+                const int32_t e = d.block_table[size_t(b) * d.max_pages + pg];
+                Q3_CHECK(e >= 0 && e < d.n_pages, 3, "debug_attention: block-table entry outside the pool");
+            }
+    }
+    const int ld = (d.n_heads + 2 * d.n_kv) * kHeadDim, odim = d.n_heads * kHeadDim;
+    const int Mp = int(align_up(size_t(rows), 16));
+    const size_t pool = size_t(d.n_pages) * d.n_kv * kPageTokens * kHeadDim;
+    const size_t tab = size_t(d.n_pos) * kHeadDim;
+    DevBuf<uint16_t> qkv, w, rope, kp, vp, ot, ol;
+    DevBuf<int32_t> ints;
+    DevBuf<uint8_t> act;
+    qkv.grow(size_t(rows) * ld);
+    w.grow(2 * kHeadDim);
+    rope.grow(2 * tab);
+    kp.grow(pool);
+    vp.grow(pool);
+    ot.grow(size_t(Mp) * odim);
+    ol.grow(size_t(rows) * odim);
+    ints.grow(size_t(B) * (2 + d.max_pages));
+    act.grow(size_t(B));
+    int32_t *kv_len = ints, *n_prompt = kv_len + B, *bt = n_prompt + B;
+    Q3_HIP(hipMemset(ints, 0, size_t(B) * (2 + d.max_pages) * 4));
+    Q3_HIP(hipMemcpy(qkv, d.qkv, size_t(rows) * ld * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(w, d.qn_w, kHeadDim * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(w + kHeadDim, d.kn_w, kHeadDim * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(rope, d.rope_cos, tab * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(rope + tab, d.rope_sin, tab * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(kp, d.kpool, pool * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(vp, d.vpool, pool * 2, hipMemcpyHostToDevice));
+    if (d.kv_len) Q3_HIP(hipMemcpy(kv_len, d.kv_len, size_t(B) * 4, hipMemcpyHostToDevice));
+    if (d.chunk_n_prompt) Q3_HIP(hipMemcpy(n_prompt, d.chunk_n_prompt, size_t(B) * 4, hipMemcpyHostToDevice));
+    if (d.block_table) Q3_HIP(hipMemcpy(bt, d.block_table, size_t(B) * d.max_pages * 4, hipMemcpyHostToDevice));
+    if (d.active) Q3_HIP(hipMemcpy(act, d.active, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemset(ot, 0xff, size_t(Mp) * odim * 2));  // rows the kernel leaves alone come back as 0xFFFF
+    AttnArgs at{};
+    at.qkv = qkv; at.ld = ld; at.qn_w = w; at.kn_w = w + kHeadDim; at.eps = d.eps;
+    at.rope_cos = rope; at.rope_sin = rope + tab;
+    at.kpool = kp; at.vpool = vp;
+    at.block_table = bt; at.max_pages = d.max_pages; at.kv_len = kv_len; at.active = d.active ? (const uint8_t*)act : nullptr;
+    at.out = ot; at.outMB = Mp / 16; at.n_heads = d.n_heads; at.n_kv = d.n_kv; at.B = B;
+    at.scale = d.scale;
+    at.fixed_len = d.fixed_len; at.identity_pages = d.identity_pages ? 1 : 0;
+    at.chunk = d.chunk; at.chunk_n_prompt = d.chunk_n_prompt ? n_prompt : nullptr; at.chunk_r_base = d.chunk_r_base;
+    at.nt_kv = d.nt_kv ? 1 : 0;
+    launch_attn_decode(at, st_);
+    Q3_HIP(hipGetLastError());  // an instantiation the device cannot launch must not pass as "nothing written"
+    launch_untile_rows(ot, Mp / 16, ol, odim, rows, odim, st_);
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy(d.out, ol, size_t(rows) * odim * 2, hipMemcpyDeviceToHost));
+    Q3_HIP(hipMemcpy(d.kpool, kp, pool * 2, hipMemcpyDeviceToHost));
+    Q3_HIP(hipMemcpy(d.vpool, vp, pool * 2, hipMemcpyDeviceToHost));
+}
+
 // Codes a CALLER hands in (q3tts_codec_decode, q3tts_codec_decode_streamed) index the RVQ tables on the GPU: every code of every frame
 // that will be decoded is checked against the tables as loaded. (Codes the engine sampled itself are inside by construction:
 // the samplers draw below the vocabulary, the tables have at least that many rows.)

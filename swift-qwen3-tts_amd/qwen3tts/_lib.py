@@ -75,6 +75,15 @@ class Timing(C.Structure):
                 ("frontend_ms", C.c_double), ("first_audio_ms", C.c_double), ("launches_per_frame_step", C.c_int32)]
 
 
+class AttnDebug(C.Structure):  # q3tts_attn_debug
+    _fields_ = [("n_heads", C.c_int32), ("n_kv", C.c_int32), ("B", C.c_int32), ("eps", C.c_float), ("scale", C.c_float),
+                ("max_pages", C.c_int32), ("fixed_len", C.c_int32), ("identity_pages", C.c_int32), ("chunk", C.c_int32),
+                ("chunk_r_base", C.c_int32), ("nt_kv", C.c_int32), ("n_pos", C.c_int32), ("n_pages", C.c_int32),
+                ("qkv", u16p), ("qn_w", u16p), ("kn_w", u16p), ("rope_cos", u16p), ("rope_sin", u16p),
+                ("kv_len", i32p), ("active", u8p), ("block_table", i32p), ("chunk_n_prompt", i32p),
+                ("kpool", u16p), ("vpool", u16p), ("out", u16p)]
+
+
 _lib = None
 
 
@@ -136,6 +145,7 @@ def lib() -> C.CDLL:
     L.q3tts_debug_sample.argtypes = [vp, u16p, C.c_int32, C.c_int32, C.POINTER(Sampling), u8p, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, i32p]
     L.q3tts_debug_linear.argtypes = [vp, u16p, u16p, u16p, C.c_int32, C.c_int32, C.c_int32, u16p]
+    L.q3tts_debug_attention.argtypes = [vp, C.POINTER(AttnDebug)]
     L.q3tts_debug_codec_stage.argtypes = [vp, i32p, C.c_int32, C.c_char_p, f32p, C.c_int64, i32p, i32p]
     _lib = L
     return L

@@ -546,6 +546,40 @@ class Qwen3TTSModel:
                                                  y.ctypes.data_as(L.u16p)))
         return y
 
+    def debug_attention(self, qkv: np.ndarray, qn_w: np.ndarray, kn_w: np.ndarray, rope_cos: np.ndarray, rope_sin: np.ndarray,
+                        kpool: np.ndarray, vpool: np.ndarray, *, n_heads: int, n_kv: int, B: int, kv_len=None, active=None,
+                        block_table=None, max_pages: int = 1, eps: float = 1e-6, scale: float = 128.0 ** -0.5,
+                        fixed_len: int = -1, identity_pages: int = 0, chunk: int = 0, chunk_n_prompt=None,
+                        chunk_r_base: int = 0, nt_kv: int = 0):
+        """One launch of the decode attention on these buffers (q3tts_debug_attention). qkv [max(chunk, 1) * B][(n_heads +
+        2 n_kv) * 128], pools [n_pages][n_kv][64][128], all bf16 bit patterns. Returns (out [rows][n_heads * 128], kpool,
+        vpool): the pools as the launch left them; the arguments are not modified."""
+        rows = max(chunk, 1) * B
+        u16 = lambda x: np.ascontiguousarray(x, np.uint16)
+        i32 = lambda x: None if x is None else np.ascontiguousarray(x, np.int32)
+        qkv, qn_w, kn_w, rope_cos, rope_sin = u16(qkv), u16(qn_w), u16(kn_w), u16(rope_cos), u16(rope_sin)
+        kpool, vpool = u16(kpool).copy(), u16(vpool).copy()
+        if qkv.shape != (rows, (n_heads + 2 * n_kv) * 128) or qn_w.shape != (128,) or kn_w.shape != (128,):
+            raise ValueError("debug_attention: qkv / norm weight shape")
+        if rope_cos.ndim != 2 or rope_cos.shape[1] != 128 or rope_sin.shape != rope_cos.shape:
+            raise ValueError("debug_attention: RoPE table shape")
+        if kpool.ndim != 4 or kpool.shape[1:] != (n_kv, 64, 128) or vpool.shape != kpool.shape:
+            raise ValueError("debug_attention: pool shape")
+        kv_len, block_table, chunk_n_prompt = i32(kv_len), i32(block_table), i32(chunk_n_prompt)
+        active = None if active is None else np.ascontiguousarray(active, np.uint8)
+        for arr, shape in ((kv_len, (B,)), (active, (B,)), (block_table, (B, max_pages)), (chunk_n_prompt, (B,))):
+            if arr is not None and arr.shape != shape:
+                raise ValueError("debug_attention: per-row argument shape")
+        out = np.zeros((rows, n_heads * 128), np.uint16)
+        ptr = lambda x, t: None if x is None else x.ctypes.data_as(t)
+        a = L.AttnDebug(n_heads, n_kv, B, eps, scale, max_pages, fixed_len, identity_pages, chunk, chunk_r_base, nt_kv,
+                        rope_cos.shape[0], kpool.shape[0], ptr(qkv, L.u16p), ptr(qn_w, L.u16p), ptr(kn_w, L.u16p),
+                        ptr(rope_cos, L.u16p), ptr(rope_sin, L.u16p), ptr(kv_len, L.i32p), ptr(active, L.u8p),
+                        ptr(block_table, L.i32p), ptr(chunk_n_prompt, L.i32p), ptr(kpool, L.u16p), ptr(vpool, L.u16p),
+                        ptr(out, L.u16p))
+        self._check(self._lib.q3tts_debug_attention(self._h, C.byref(a)))
+        return out, kpool, vpool
+
     def debug_codec_stage(self, codes: np.ndarray, stage: str) -> np.ndarray:
         codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
         F = codes.shape[0]

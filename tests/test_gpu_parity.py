@@ -413,6 +413,39 @@ def test_wide_talker_teacher_forced_logits(tmp_path):
         m.close()
 
 
+@pytest.mark.parametrize("paged", [False, True], ids=["one-page", "paged"])
+@pytest.mark.parametrize("n_heads,n_kv", [(2, 2), (3, 1), (4, 1)])
+def test_other_gqa_ratios_teacher_forced_logits(tmp_path, n_heads, n_kv, paged):
+    """Query heads per kv head of 1, 3 and 4 (every preset has 2) in the talker and the code predictor: the attention
+    instantiations for those ratios and the o_proj operand layout for those head counts, through a chunked prefill and 4
+    forced frames, with the talker's cache on one page (max_prompt + max_frames <= 64: 256-thread kernels) and on several
+    (512-thread kernels for one query head per kv head). tests/test_attention_block.py checks the kernels alone."""
+    from oracle import oracle as O
+    from qwen3tts import Qwen3TTSModel, synth
+    d = str(tmp_path / "gqa")
+    ov = {}
+    for pre in ("talker_config.", "talker_config.code_predictor_config."):
+        ov[pre + "num_attention_heads"] = n_heads
+        ov[pre + "num_key_value_heads"] = n_kv
+    synth.write_checkpoint(d, "tiny-b", seed=100 + 10 * n_heads + n_kv, overrides=ov)
+    mp, mf = (96, 32) if paged else (48, 16)
+    m = Qwen3TTSModel.from_pretrained(d, max_batch=3, max_frames=mf, max_prompt=mp)
+    om = O.OracleModel(d)
+    try:
+        rng = np.random.default_rng(n_heads * 7 + n_kv)
+        F = 4
+        forced = np.concatenate([rng.integers(0, 2048, size=(F, 1)), rng.integers(0, 256, size=(F, 15))], -1).astype(np.int32)
+        tr = om.generate_codes(oreq(row=1, n_text=24), O.Sampling(temperature=0.0, force_frames=F), forced_codes=forced,
+                               keep_logits=True)
+        tl, cl, _ = m.debug_generate_forced([greq(row=1, n_text=24)], forced[None], temperature=0.0)
+        for got, exp in ((tl[0], np.stack(tr.talker_logits)), (cl[0], np.stack(tr.cp_logits))):
+            a, b = bf16_to_f32(got), bf16_to_f32(exp)
+            tol = 2 * ULP * np.abs(b).max(axis=-1, keepdims=True)
+            assert (np.abs(a - b) <= tol).all(), float(np.abs(a - b).max())
+    finally:
+        m.close()
+
+
 def test_scheduling_modes_agree(ckpt_dirs):
     """The same request gives the same codes and PCM whichever way its steps are scheduled: batch 3 (prefill 8 positions
     per launch, the predictor's step 0 as one two-position pass) vs batch 40 (one position per launch, step 0 as two

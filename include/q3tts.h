@@ -184,7 +184,8 @@ typedef struct {
                                    reference's end trim to count(code0 > 0) frames (SpeechTokenizer.swift:831-833) cannot apply
                                    to samples that have already left. audio_chunk_frames must be at
                                    least the causal tail's history (3 frames for the shipped decoder geometry; checked before any
-                                   GPU work). Not combined with voice-clone rows (those fall back to 0) */
+                                   GPU work). Not combined with voice-clone rows (those fall back to 0). Also honoured by
+                                   q3tts_generate_queued, per request: every request of the queue is streamed as if alone */
     int32_t audio_lookahead_frames; /* frames to the right of a chunk that must exist before it is decoded (default 4) */
     uint32_t row_base;    /* new: global index of reqs[0] in a job whose rows are sharded over several processes (one
                              replica per GPU). A row's random stream is keyed by (seed, row_base + row index), so a sharded
@@ -276,14 +277,33 @@ q3tts_status q3tts_generate_end(q3tts_model* m, q3tts_job* job, q3tts_result* re
  * i draws from random stream (seed, row_base + i), whatever slot or lane serves it.
  * Events, per request with request_index = i: TOKEN*, INFO, AUDIO. A request's INFO and AUDIO fire as soon as its audio is
  * decoded, which can be before later requests have started; the interleaving across requests is unspecified.
+ * Streamed audio (sampling->audio_chunk_frames > 0 AND audio_window_frames > 0): every request's audio leaves in pieces
+ * while it generates, each request as if it had been streamed alone.
+ *   - results[i] (codes, pcm, n_frames, n_samples, status) is bit-identical to what q3tts_generate returns for reqs[i] alone
+ *     with the same sampling (streaming fields included) and row_base = sampling->row_base + i; slot, lane, admission burst and
+ *     whichever other rows share a decoder pass do not change it. Equivalently pcm is q3tts_codec_decode_streamed(codes_i,
+ *     audio_chunk_frames, audio_window_frames, audio_lookahead_frames). As in a streamed q3tts_generate, AUDIO carries all
+ *     generated frames: n_samples = n_frames * samples_per_frame, no end trim.
+ *   - Chunks are per request: chunk k of a request with n frames covers frames [kC, min(n, (k+1)C)), its pre-transformer
+ *     window is [max(0, kC - W), min(n, (k+1)C + L)), and it is decodable once the request has (k+1)C + L frames or is final.
+ *   - Events per request: TOKEN* and AUDIO_CHUNK* interleaved, then INFO, then AUDIO. AUDIO_CHUNK carries request_index = i and
+ *     sample_offset = k * C * samples_per_frame, in order; the pieces concatenate to AUDIO. INFO and AUDIO fire once the
+ *     request's last chunk has landed on the host.
+ *   - A request whose chunk leaves the fp16 range follows the rule of a streamed q3tts_generate: it delivers nothing more from
+ *     its first flagged chunk on, is decoded again on the fp32 matrix cores once the queue has drained (its remaining
+ *     AUDIO_CHUNK events, INFO and AUDIO leave then), and only if that fails too ends in AUDIO_DECODING_FAILED -- alone.
+ *   - n_streams > 1: each lane streams its own slots; results do not depend on the lane count.
  * Every request is checked before any GPU work (prompt length, max_tokens <= max_frames, speaker, route, RoPE range). Refused
- * with Q3TTS_ERR_INVALID_INPUT, the engine staying usable: slots outside 1..max_batch, a voice-clone request (ref_audio !=
- * NULL), audio_chunk_frames > 0, a q3tts_generate_begin job outstanding on the handle. force_frames keeps its meaning.
+ * with Q3TTS_ERR_INVALID_INPUT before any GPU work, the engine staying usable: slots outside 1..max_batch, a voice-clone request
+ * (ref_audio != NULL), audio_chunk_frames > 0 with audio_window_frames == 0 (chunks cut after a request's end give a queue
+ * nothing: its AUDIO already leaves as soon as it is decoded), audio_chunk_frames > 0 below the causal tail's history (as a
+ * streamed q3tts_generate), a q3tts_generate_begin job outstanding on the handle. force_frames keeps its meaning.
  * A request whose first token is EOS fails alone (GENERATION_FAILED), as does a row whose decode leaves the fp16 range even
  * on the fp32 re-decode (AUDIO_DECODING_FAILED); the others are delivered.
  * q3tts_last_timing afterwards: frame_steps = frame-step replays, prefill_ms = sum of all admission prefills, codec_ms = sum
- * of the decode batches, rows = n_reqs. A request's q3tts_gen_info times run from its admission to its retirement (the burst
- * boundary at which its finished row was seen), not over the whole call. */
+ * of the decode batches (streamed: of the stream's passes), rows = n_reqs; streamed: first_audio_ms = time from the call to
+ * the first AUDIO_CHUNK samples of any request on the host. A request's q3tts_gen_info times run from its admission to its
+ * retirement (the burst boundary at which its finished row was seen), not over the whole call. */
 q3tts_status q3tts_generate_queued(q3tts_model* m, const q3tts_request* reqs, int32_t n_reqs, int32_t slots,
                                    const q3tts_sampling* sampling, q3tts_event_cb cb, void* user, q3tts_result* results);
 
@@ -421,6 +441,17 @@ q3tts_status q3tts_debug_attention(q3tts_model* m, const q3tts_attn_debug* a);
  * "block0".."block3". Output is channels-last [T][C] float32; *T,*C receive the shape. */
 q3tts_status q3tts_debug_codec_stage(q3tts_model* m, const int32_t* codes, int32_t n_frames,
                                      const char* stage, float* out, int64_t cap_floats, int32_t* T, int32_t* C);
+
+/* The slotted codec stream of a streamed q3tts_generate_queued, driven by the queue's schedule without the talker (a test hook:
+ * the real layer widths in seconds). codes [n_reqs][max_frames][16], n_frames[n_reqs] <= max_frames. Requests take the free ones
+ * of `slots` rows (1..max_batch) in index order; every running request gains `burst` frames per step; one that reaches its count
+ * is final, is retired behind that step's chunks, and its slot is reset and refilled. pcm [n_reqs][max_frames * 1920] receives
+ * every request's samples: bit-identical to q3tts_codec_decode_streamed(codes_i, chunk_frames, window, lookahead) of it alone.
+ * Codes are checked against the RVQ tables on the host as in q3tts_codec_decode; chunk_frames below the causal tail's history,
+ * window < 0 or slots outside 1..max_batch are Q3TTS_ERR_INVALID_INPUT. */
+q3tts_status q3tts_debug_codec_stream_slots(q3tts_model* m, const int32_t* codes, const int32_t* n_frames, int32_t n_reqs,
+                                            int32_t max_frames, int32_t slots, int32_t burst, int32_t chunk_frames, int32_t window,
+                                            int32_t lookahead, float* pcm);
 
 /* Activation scratch the codec decoder may use per pass (default 24 GB; 0 restores it): a small value forces the paths that
  * take a large batch through in groups of rows. Process-wide. */

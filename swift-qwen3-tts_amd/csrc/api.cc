@@ -436,6 +436,14 @@ q3tts_status q3tts_codec_decode_streamed(q3tts_model* m, const int32_t* codes, c
     });
 }
 
+q3tts_status q3tts_debug_codec_stream_slots(q3tts_model* m, const int32_t* codes, const int32_t* n_frames, int32_t n_reqs, int32_t max_frames,
+                                            int32_t slots, int32_t burst, int32_t chunk_frames, int32_t window, int32_t lookahead, float* pcm) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && codes && n_frames && pcm, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_codec_stream_slots(codes, n_frames, n_reqs, max_frames, slots, burst, chunk_frames, window, lookahead, pcm);
+    });
+}
+
 void q3tts_debug_set_codec_scratch(uint64_t bytes) { q3::CodecRunner::set_scratch_budget(size_t(bytes)); }
 
 void q3tts_debug_reload_env(void) { q3::debug_env_reload(); }

@@ -118,7 +118,8 @@ void CodecRunner::capture(const Pass& ps, const char* name, const float* t, int 
 
 // Steps 1-4 (SpeechTokenizer.swift:757-765): split-RVQ dequantisation, pre_conv, pre_transformer over ALL frames of a row
 // (its attention has neither mask nor positions, :512-528). Result: bufs[0] = [nb][Fmax][latent].
-void CodecRunner::run_front(const Pass& ps, const int32_t* codes, int code_stride_frames, int Fmax, float* const* bufs) {
+void CodecRunner::run_front(const Pass& ps, const int32_t* codes, int code_stride_frames, int Fmax, float* const* bufs,
+                            const int32_t* first_frame) {
     const CodecDecoderConfig& dc = m_.cfg.codec;
     const CodecW& w = m_.codec;
     const int nb = ps.nb;
@@ -126,7 +127,7 @@ void CodecRunner::run_front(const Pass& ps, const int32_t* codes, int code_strid
     int T = Fmax, ppf = 1;
     // 1-2. Split-RVQ dequantisation (SpeechTokenizer.swift:214-226)
     launch_rvq_gather(codes, code_stride_frames, w.cb_first, w.cb_rest_dev, int(w.cb_rest.size()), w.inner, fr, Fmax, nb,
-                      bufs[0], w.cb_first_rows, w.cb_rest_rows, st_);
+                      bufs[0], w.cb_first_rows, w.cb_rest_rows, st_, first_frame);
     conv(ps, w.rvq_out, bufs[0], T, ppf, bufs[1], nullptr, nullptr, 0);
     capture(ps, "quantizer", bufs[1], T, w.rvq_out.N);
     // 3. pre_conv (:759)
@@ -267,8 +268,10 @@ uint8_t* CodecRunner::Stream::take(size_t bytes) {
 }
 void* CodecRunner::Stream::get(size_t frame_bytes, bool reads_back) {
     Q3_CHECK(frame_bytes % 4 == 0, 7, "internal error: a streamed tensor's frame is not whole floats");  // roll_history moves floats
-    uint8_t* p = take(size_t(cfg.rows) * Tal * frame_bytes);
+    const size_t bytes = size_t(cfg.rows) * Tal * frame_bytes;
+    uint8_t* p = take(bytes);
     if (reads_back && !dry) rolls.emplace_back(reinterpret_cast<float*>(p), frame_bytes / 4);
+    if (reads_back && dry) roll_offs.emplace_back(off - bytes, frame_bytes / 4);  // the table of a slotted stream
     return p;
 }
 
@@ -524,6 +527,7 @@ void CodecRunner::stream_prefix() {
     Stream& S = stream_;
     S.off = 0;
     S.rolls.clear();
+    if (S.dry) S.roll_offs.clear();
     for (auto& f : S.fbufs) f = reinterpret_cast<float*>(S.take(S.fbuf_floats * sizeof(float)));
     const size_t all = size_t(S.cfg.rows) * S.cfg.max_frames * m_.cfg.codec.latent_dim * sizeof(float);
     S.x_all = S.cfg.window < 0 ? reinterpret_cast<float*>(S.take(all)) : nullptr;
@@ -575,7 +579,125 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
     S.lens_dev.grow(slots * cfg.rows);
     Q3_CHECK(cfg.rows <= kMaxRows, 3, "Invalid input: too many rows in one codec decode");
     Q3_HIP(hipMemsetAsync(nf_dev_, 0, size_t(cfg.rows) * 4, st_));
+    if (cfg.per_row) {
+        Q3_CHECK(cfg.window >= 0, 3, "Invalid input: a slotted stream needs a sliding window (audio_window_frames >= 0)");
+        Q3_CHECK(m_.cfg.codec.latent_dim % 4 == 0, 3, "Invalid input: a slotted stream needs a latent width of whole float4s");
+        SlotPlanCfg pc;
+        pc.rows = cfg.rows; pc.chunk = cfg.chunk_frames; pc.window = cfg.window; pc.lookahead = cfg.lookahead; pc.max_frames = cfg.max_frames;
+        S.plan.open(pc);
+        // the tensors with history, as one table for roll_history_rows (the counting pass recorded their places in the arena)
+        std::vector<RollDesc> table;
+        S.roll_max_ff = 0;
+        for (auto& r : S.roll_offs) {
+            Q3_CHECK(r.first + size_t(cfg.rows) * S.Tal * r.second * 4 <= need, 7, "internal error: a streamed tensor outside its arena");
+            table.push_back(RollDesc{reinterpret_cast<float*>(S.arena + r.first), int64_t(r.second)});
+            S.roll_max_ff = std::max<int64_t>(S.roll_max_ff, int64_t(r.second));
+        }
+        S.n_roll = int(table.size());
+        if (table.size() * sizeof(RollDesc) > S.roll_desc.capacity()) Q3_HIP(hipStreamSynchronize(st_));
+        S.roll_desc.grow(std::max<size_t>(table.size() * sizeof(RollDesc), 16));
+        Q3_HIP(hipStreamSynchronize(st_));  // `table` is pageable stack memory: the copy below must not outlive it
+        Q3_HIP(hipMemcpy(S.roll_desc, table.data(), table.size() * sizeof(RollDesc), hipMemcpyHostToDevice));
+        const size_t R = size_t(cfg.rows);
+        S.ring_pcm.grow(size_t(kRingSlots) * R * cfg.chunk_frames * up_);
+        S.ring_nf.grow(size_t(kRingSlots) * R);
+        S.ring_args_host.grow(size_t(kRingSlots) * 5 * R);
+        S.ring_args_dev.grow(size_t(kRingSlots) * 5 * R);
+        while (S.ring_ev.size() < size_t(2) * kRingSlots) {
+            hipEvent_t e = nullptr;
+            Q3_HIP(hipEventCreate(&e));
+            S.ring_ev.push_back(e);
+        }
+        S.ring_busy.assign(size_t(kRingSlots), 0);
+        S.ring_next = 0;
+    }
     S.open = true;
+}
+
+void CodecRunner::stream_reset_row(int b) {
+    Stream& S = stream_;
+    Q3_CHECK(S.open && S.cfg.per_row, 3, "Invalid input: no slotted stream is open");
+    Q3_CHECK(b >= 0 && b < S.cfg.rows, 3, "Invalid input: row outside the slotted stream");
+    S.plan.reset_row(b);
+    launch_roll_history_rows(reinterpret_cast<const RollDesc*>(static_cast<uint8_t*>(S.roll_desc)), S.n_roll, S.roll_max_ff, S.Tal, S.hist,
+                             S.cfg.chunk_frames, nullptr, b, S.cfg.rows, nf_dev_, st_);
+}
+
+void CodecRunner::stream_release(int ring) {
+    Q3_CHECK(ring >= 0 && ring < kRingSlots && stream_.ring_busy.size() == size_t(kRingSlots), 3, "Invalid input: no such ring slot");
+    stream_.ring_busy[size_t(ring)] = 0;
+}
+
+bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_frames, const int* avail, const uint8_t* final_rows,
+                                   std::vector<SlotPass>& out) {
+    Stream& S = stream_;
+    Q3_CHECK(S.open && S.cfg.per_row, 3, "Invalid input: no slotted stream is open");
+    const CodecDecoderConfig& dc = m_.cfg.codec;
+    const int B = S.cfg.rows, C = S.cfg.chunk_frames;
+    const size_t lat = size_t(dc.latent_dim);
+    const int Fwin = std::min(S.cfg.max_frames, S.cfg.window + C + S.cfg.lookahead);  // the front scratch's frames per row (stream_open)
+    Q3_CHECK(code_stride_frames >= S.cfg.max_frames, 3, "Invalid input: code rows shorter than the stream's max_frames");
+    const std::string none;
+    std::vector<RowPlan> rows;
+    for (;;) {
+        bool any = false;
+        for (int b = 0; b < B && !any; ++b) any = S.plan.decodable(b, std::min(avail[b], S.cfg.max_frames), final_rows && final_rows[b]);
+        if (!any) return false;
+        if (S.ring_busy[size_t(S.ring_next)]) return true;  // the oldest pass has not been taken yet
+        const int slot = S.ring_next;
+        S.plan.plan_pass(avail, final_rows, rows);
+        // ---- per-row arguments of this pass; everything that becomes an address is checked here ----
+        int32_t* h = S.ring_args_host + size_t(slot) * 5 * B;
+        int32_t* d = S.ring_args_dev + size_t(slot) * 5 * B;
+        int Fw = 0, max_take = 0;
+        for (int b = 0; b < B; ++b) {
+            const RowPlan& r = rows[size_t(b)];
+            if (r.part) {
+                Q3_CHECK(r.w0 >= 0 && r.wlen >= 1 && r.wlen <= Fwin && r.w0 + r.wlen <= code_stride_frames && r.take >= 1 && r.take <= C &&
+                             r.f0 >= r.w0 && r.f0 - r.w0 + r.take <= r.wlen,
+                         7, "internal error: a slotted pass outside its buffers");
+            }
+            h[0 * B + b] = r.part ? r.wlen : 0;
+            h[1 * B + b] = r.part ? r.take : 0;
+            h[2 * B + b] = r.part ? r.w0 : 0;
+            h[3 * B + b] = r.part ? r.f0 - r.w0 : 0;
+            h[4 * B + b] = r.part ? 1 : 0;  // roll the participants, leave the others
+            Fw = std::max(Fw, h[0 * B + b]);
+            max_take = std::max(max_take, h[1 * B + b]);
+        }
+        S.ring_busy[size_t(slot)] = 1;
+        S.ring_next = (slot + 1) % kRingSlots;
+        hipEvent_t begun = S.ring_ev[size_t(2) * slot], done = S.ring_ev[size_t(2) * slot + 1];
+        Q3_HIP(hipEventRecord(begun, st_));
+        // (the pinned arguments of a ring slot are rewritten only after the caller has waited for the slot's `done`)
+        Q3_HIP(hipMemcpyAsync(d, h, size_t(5) * B * 4, hipMemcpyHostToDevice, st_));
+        Pass ps{};
+        ps.nb = B;
+        ps.stage = &none;
+        // ---- pre-transformer over every participant's own window [w0_b, w0_b + wlen_b) ----
+        ps.fr = d + 0 * B;
+        run_front(ps, codes_dev, code_stride_frames, Fw, S.fbufs, d + 2 * B);
+        launch_stream_take_chunk(S.fbufs[0], int64_t(Fw) * int64_t(lat), S.lat + size_t(S.hist) * lat, int64_t(S.Tal) * int64_t(lat), int(lat),
+                                 max_take, d + 3 * B, d + 1 * B, B, st_);
+        // ---- the causal tail over the chunks, state carried in the participants' margins ----
+        ps.fr = d + 1 * B;
+        ps.hist_frames = S.hist;
+        stream_prefix();  // the same walk over the arena as in stream_open
+        Q3_HIP(hipMemsetAsync(S.pcm, 0, size_t(B) * S.Tal * up_ * 4, st_));
+        run_tail(ps, S, S.lat, S.Tal, S.pcm);
+        Q3_CHECK(int(S.rolls.size()) == S.n_roll, 7, "internal error: the slotted stream's history table is stale");
+        launch_roll_history_rows(reinterpret_cast<const RollDesc*>(static_cast<uint8_t*>(S.roll_desc)), S.n_roll, S.roll_max_ff, S.Tal, S.hist, C,
+                                 d + 4 * B, -1, B, nullptr, st_);
+        float* pcm_slot = S.ring_pcm + size_t(slot) * B * C * up_;
+        int32_t* nf_slot = S.ring_nf + size_t(slot) * B;
+        Q3_HIP(hipMemcpy2DAsync(pcm_slot, size_t(C) * up_ * sizeof(float), S.pcm + size_t(S.hist) * up_, size_t(S.Tal) * up_ * sizeof(float),
+                                size_t(C) * up_ * sizeof(float), size_t(B), hipMemcpyDeviceToHost, st_));
+        Q3_HIP(hipMemcpyAsync(nf_slot, nf_dev_, size_t(B) * 4, hipMemcpyDeviceToHost, st_));
+        Q3_HIP(hipEventRecord(done, st_));
+        SlotPass sp;
+        sp.ring = slot; sp.begun = begun; sp.done = done; sp.pcm = pcm_slot; sp.nf = nf_slot; sp.rows = rows;
+        out.push_back(std::move(sp));
+    }
 }
 
 void CodecRunner::stream_close(int32_t* nonfinite_host) {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "model.h"
+#include "stream_plan.h"
 
 namespace q3 {
 
@@ -44,6 +45,7 @@ class CodecRunner {
     // window < 0: the pre-transformer runs ONCE over all frames (needs every code up front; exact, for tests and offline use).
     struct StreamCfg {
         int rows = 0, chunk_frames = 0, window = 0, lookahead = 0, max_frames = 0;
+        bool per_row = false;  // a slotted stream (below): rows are slots of a queue, each at a chunk phase of its own
     };
     void stream_open(const StreamCfg& cfg);
     // Rows have avail[b] frames so far (final[b]: the row will get no more). Decodes every chunk that has become decodable;
@@ -55,6 +57,31 @@ class CodecRunner {
     int stream_push(const int32_t* codes_dev, int code_stride_frames, const int* avail, const uint8_t* final_rows, float* pcm_host,
                     size_t pcm_row_stride, std::vector<hipEvent_t>& chunk_done, int32_t* nf_chunks_host = nullptr);
     void stream_close(int32_t* nonfinite_host = nullptr);
+    // ---- slotted stream (StreamCfg::per_row; window >= 0): the rows are the slots of a continuous-batching queue ------------
+    // Requests enter and leave rows at different moments, so every row has its own next chunk (stream_plan.h decides who
+    // decodes what); a pass decodes one chunk for each row that has one and leaves the others alone: length 0 in every
+    // kernel, margins not rolled, nothing of theirs written. A row's result is what a lock-step stream over that row alone
+    // produces, bit for bit. The samples of a pass go to a pinned ring slot [rows][chunk_frames * upsample] with the rows'
+    // non-finite flags as they stand behind the pass and an event behind both; the caller scatters them and gives the slot back.
+    struct SlotPass {
+        int ring = -1;                // ring slot, to be handed to stream_release once the samples have been taken
+        hipEvent_t begun = nullptr, done = nullptr;  // in front of the pass / behind its copies to the host (timing enabled)
+        const float* pcm = nullptr;   // [rows][chunk_frames * upsample], valid behind `done`
+        const int32_t* nf = nullptr;  // [rows]
+        std::vector<RowPlan> rows;    // who took part, with which chunk
+    };
+    // A new request takes row b: its chunks count from 0, its history margins in every tensor with history and its non-finite
+    // flag are cleared ON THE CODEC STREAM -- behind the previous occupant's last chunk (issued by an earlier push), in front of
+    // the new occupant's first. A row takes part in no pass before its first reset.
+    void stream_reset_row(int b);
+    // Rows have avail[b] frames of their current request in codes_dev [rows][code_stride_frames][16] (final_rows[b]: no more
+    // will come). Issues passes until no row has a decodable chunk (returns false) or the ring is full (returns true: take a
+    // pass, release it, push again). Issued passes are appended to `out`, oldest first. No host synchronisation.
+    bool stream_push_rows(const int32_t* codes_dev, int code_stride_frames, const int* avail, const uint8_t* final_rows,
+                          std::vector<SlotPass>& out);
+    void stream_release(int ring);
+    int stream_chunks_of(int frames) const { return stream_.plan.chunks_of(frames); }
+    static constexpr int kRingSlots = 8;
     bool streaming() const { return stream_.open; }
     int hist_frames() const;
     int upsample() const { return up_; }
@@ -91,7 +118,9 @@ class CodecRunner {
                  const struct SnakeW* after);
     void capture(const Pass& ps, const char* name, const float* t, int T, int C);
     void capture(const Pass& ps, const char* name, const uint16_t* t, int T, int C);
-    void run_front(const Pass& ps, const int32_t* codes, int code_stride_frames, int Fmax, float* const* bufs);
+    // first_frame (device [nb], slotted stream): row b's window starts at that frame of its code row; nullptr: at frame 0
+    void run_front(const Pass& ps, const int32_t* codes, int code_stride_frames, int Fmax, float* const* bufs,
+                   const int32_t* first_frame = nullptr);
     // The causal tail. `in`: the pre-transformer's frames, `Trows` rows per batch row in every tensor (streams: history
     // margin + chunk); the tensors in between come from `mem`: a Ring over the four scratch buffers, or the open Stream.
     struct Ring;
@@ -112,6 +141,22 @@ class CodecRunner {
         PinnedBuf<int32_t> lens_host;  // one slot per (chunk, kind): never reused inside a stream
         DevBuf<int32_t> lens_dev;
         size_t lens_used = 0;
+        // slotted stream
+        SlotPlanner plan;
+        std::vector<std::pair<size_t, size_t>> roll_offs;  // (arena offset, frame floats) of `rolls`, from the counting pass
+        DevBuf<uint8_t> roll_desc;     // RollDesc table of `rolls` (codec_kernels.h)
+        int n_roll = 0;
+        int64_t roll_max_ff = 0;
+        PinnedBuf<float> ring_pcm;     // [kRingSlots][rows][chunk * upsample]
+        PinnedBuf<int32_t> ring_nf;    // [kRingSlots][rows]
+        PinnedBuf<int32_t> ring_args_host;  // [kRingSlots][5][rows]: window lengths, takes, first frames, chunk offsets, roll modes
+        DevBuf<int32_t> ring_args_dev;
+        std::vector<hipEvent_t> ring_ev;    // two per slot: begun, done
+        std::vector<uint8_t> ring_busy;
+        int ring_next = 0;
+        ~Stream() {
+            for (auto e : ring_ev) (void)hipEventDestroy(e);
+        }
         uint8_t* take(size_t bytes);  // bump allocation (same order in stream_open's two passes and in every chunk)
         // the tail's next persistent tensor of Tal frames per row; one a later causal conv reads back into gets its margin rolled
         void* get(size_t frame_bytes, bool reads_back);

@@ -124,7 +124,8 @@ void launch_resunit(const ResUnitArgs& a, hipStream_t st);
 // Split-RVQ gather (SpeechTokenizer.swift:214-226, 81-96): out[b][f] = [cb_first[c0] | sum_j cb_rest[j][c_{j+1}]]
 void launch_rvq_gather(const int32_t* codes, int code_stride_frames, const float* cb_first,
                        const float* const* cb_rest, int n_rest, int inner, const int32_t* frames, int Fmax, int B,
-                       float* out, int rows_first, int rows_rest, hipStream_t st);  // rows: a code is clamped into its table
+                       float* out, int rows_first, int rows_rest, hipStream_t st,  // rows: a code is clamped into its table
+                       const int32_t* first_frame = nullptr);  // device [B] or nullptr (0): row b starts at this frame of its code row
 // fp32 RMSNorm over the last dim (SpeechTokenizer.swift:581-582,626): out = (x*rstd)*w
 void launch_rmsnorm_f32(const float* x, const float* w, float eps, int C, const int32_t* frames, int ppf, int Tmax,
                         int B, float* out, hipStream_t st);
@@ -144,6 +145,20 @@ void launch_out_conv(const float* x, int C, const float* ea, const float* ib, co
                      int32_t* nonfinite = nullptr);  // nonfinite[b] |= 1 when row b's pre-clip waveform holds an inf / NaN
 // streamed decode: rows [chunk_rows - keep_rows, chunk_rows) of every batch row move to [-keep_rows, 0) (history of the next chunk)
 void launch_roll_history(float* cur, int64_t bstride, int64_t keep_floats, int64_t chunk_floats, int B, hipStream_t st);
+// ---- slotted stream (rows of a queue at chunk phases of their own, codec.h) ----
+// lat[b][t][:] = front[b][off[b] + t][:] for t < take[b]; rows with take[b] == 0 are left alone. Strides in floats, `lat` behind
+// the history margin, latent a multiple of 4 (16-byte loads and stores). The caller has checked off[b] + take[b] against the
+// front's frames and take[b] <= max_take against the chunk.
+void launch_stream_take_chunk(const float* front, int64_t front_bstride, float* lat, int64_t lat_bstride, int latent, int max_take,
+                              const int32_t* off, const int32_t* take, int B, hipStream_t st);
+struct RollDesc {  // one tensor with history: allocation base ([B][Tal] frames) and floats per frame (float16 tensors: whole floats)
+    float* base;
+    int64_t frame_floats;
+};
+// launch_roll_history over the n_desc tensors of a device table at once and row by row. mode (device [B]): 0 skip, 1 roll, 2 zero
+// the margin. mode == nullptr: only_row's margins are zeroed and nonfinite[only_row] cleared (a new request takes the row).
+void launch_roll_history_rows(const RollDesc* desc, int n_desc, int64_t max_frame_floats, int Tal, int hist, int chunk, const int32_t* mode,
+                              int only_row, int B, int32_t* nonfinite, hipStream_t st);
 
 // ---- voice-clone front end (kernels/voice_frontend.hip) ------------------------------------------
 // first SEANet conv: 1 -> C channels, causal k taps (SpeechTokenizerEncoder.swift:404-414). w [C][K], out [S][C]

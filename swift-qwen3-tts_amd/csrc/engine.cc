@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <deque>
+#include <functional>
 #include <thread>
 
 #include "codec.h"
@@ -1782,6 +1783,126 @@ ResolvedRequest Engine::check_queued(const q3tts_request& r, const q3tts_samplin
     return o;
 }
 
+// The audio side of a streamed queue: one slotted codec stream (codec.h) over the queue's slots on the confined codec stream,
+// the passes in flight, and every request's PCM as its chunks land. A request is complete once it has been retired and its
+// last chunk has been taken from the ring.
+struct Engine::SlotStream {
+    Engine& e;
+    hipStream_t cst = nullptr;
+    const int C, up;
+    bool hold = true;  // a request stops taking chunks at its first one flagged non-finite (the engine re-decodes it in fp32)
+    struct Out {       // one request
+        MallocPtr<float> pcm;  // [cap frames * up]
+        int frames = -1;       // its length, once retired
+        int landed = 0;        // chunks taken from the ring
+        int held_from = -1;    // first chunk held back
+        bool complete = false;
+    };
+    std::vector<Out> out;         // by request index
+    std::vector<int> req_of_row;  // the request in row b, -1: none
+    struct Flight {
+        CodecRunner::SlotPass pass;
+        std::vector<int> req;     // req_of_row when the pass was issued
+    };
+    std::deque<Flight> flights;
+    std::vector<CodecRunner::SlotPass> issued;
+    hipEvent_t ev_codes = nullptr, ev_pushed = nullptr;  // st_ -> cst: the codes are copied; cst -> st_: the last push has been read
+    bool have_first = false;
+    double codec_ms = 0, first_audio_ms = 0;
+    double t_call = 0;  // host clock at the call's start (first_audio_ms counts from it); 0: not timed
+    std::function<void(int, int, const float*, int64_t, int64_t)> on_chunk;  // request, chunk, samples, count, offset
+    std::function<void(int)> on_complete;
+
+    SlotStream(Engine& eng, int rows, int n_reqs, int chunk, int window, int lookahead, int max_frames, bool overlapped)
+        : e(eng), C(chunk), up(eng.codec_->upsample()), out(size_t(n_reqs)), req_of_row(size_t(rows), -1) {
+        for (hipEvent_t* ev : {&ev_codes, &ev_pushed}) Q3_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        cst = e.codec_stream(overlapped);
+        CodecRunner::StreamCfg cfg;
+        cfg.rows = rows; cfg.chunk_frames = chunk; cfg.window = window; cfg.lookahead = lookahead; cfg.max_frames = max_frames;
+        cfg.per_row = true;
+        e.codec_->stream_open(cfg);
+    }
+    ~SlotStream() {  // whatever ends the call: the runner's stream is closed and nothing of it is still running
+        if (e.codec_->streaming()) e.codec_->stream_close();
+        (void)hipStreamSynchronize(cst);
+        for (hipEvent_t ev : {ev_codes, ev_pushed})
+            if (ev) (void)hipEventDestroy(ev);
+    }
+    void admit(int row, int req, int cap_frames) {
+        e.codec_->stream_reset_row(row);  // on cst: behind the previous occupant's last chunk, in front of this one's first
+        req_of_row[size_t(row)] = req;
+        Out& o = out[size_t(req)];
+        o.pcm.reset(static_cast<float*>(std::malloc(std::max<size_t>(size_t(cap_frames) * up * 4, 4))));
+        Q3_CHECK(o.pcm != nullptr, 5, "out of host memory for the results");
+    }
+    void check_complete(int req) {
+        Out& o = out[size_t(req)];
+        if (o.complete || o.frames < 0 || o.landed < e.codec_->stream_chunks_of(o.frames)) return;
+        o.complete = true;
+        if (on_complete) on_complete(req);
+    }
+    // the oldest pass in flight, if it has landed (wait: whatever it takes): samples to the requests, ring slot given back
+    bool take(bool wait) {
+        if (flights.empty()) return false;
+        Flight& f = flights.front();
+        if (wait) {
+            Q3_HIP(hipEventSynchronize(f.pass.done));
+        } else {
+            const hipError_t q = hipEventQuery(f.pass.done);
+            if (q == hipErrorNotReady) return false;
+            Q3_HIP(q);
+        }
+        float ms = 0;
+        Q3_HIP(hipEventElapsedTime(&ms, f.pass.begun, f.pass.done));
+        codec_ms += ms;
+        if (!have_first && t_call > 0) {  // the first samples of any request are on the host
+            first_audio_ms = (now_s() - t_call) * 1e3;
+            have_first = true;
+        }
+        std::vector<int> touched;
+        for (size_t b = 0; b < f.pass.rows.size(); ++b) {
+            const RowPlan& r = f.pass.rows[b];
+            if (!r.part) continue;
+            const int req = f.req[b];
+            Out& o = out[size_t(req)];
+            if (hold && o.held_from < 0 && f.pass.nf[b]) o.held_from = r.k;
+            if (o.held_from < 0) {
+                const int64_t off = int64_t(r.k) * C * up, n = int64_t(r.take) * up;
+                std::memcpy(o.pcm.get() + off, f.pass.pcm + b * size_t(C) * up, size_t(n) * 4);
+                if (on_chunk) on_chunk(req, r.k, o.pcm.get() + off, n, off);
+            }
+            ++o.landed;
+            touched.push_back(req);
+        }
+        e.codec_->stream_release(f.pass.ring);
+        flights.pop_front();
+        for (int req : touched) check_complete(req);
+        return true;
+    }
+    // every chunk that avail / fin now allow, on cst; a full ring is emptied from its oldest pass on
+    void push(const int32_t* codes_dev, int code_stride_frames, const int* avail, const uint8_t* fin) {
+        for (;;) {
+            issued.clear();
+            const bool more = e.codec_->stream_push_rows(codes_dev, code_stride_frames, avail, fin, issued);
+            for (auto& p : issued) flights.push_back(Flight{std::move(p), req_of_row});
+            if (!more) break;
+            take(true);
+        }
+        Q3_HIP(hipEventRecord(ev_pushed, cst));
+    }
+    void retire(int row, int frames) {
+        const int req = req_of_row[size_t(row)];
+        req_of_row[size_t(row)] = -1;
+        out[size_t(req)].frames = frames;
+        check_complete(req);
+    }
+    void finish() {  // every pass taken, the runner's stream closed
+        while (take(true)) {}
+        e.codec_->stream_close();
+        Q3_HIP(hipStreamSynchronize(cst));
+    }
+};
+
 void Engine::ensure_queue_ws() {
     if (qws_) return;
     const TalkerConfig& t = m_->cfg.talker;
@@ -1951,6 +2072,76 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         publish_job(J, cb, user, 0, t_call, true);  // copied out by the staging thread while the frame loop goes on
     };
 
+    // ---- streamed audio (audio_chunk_frames > 0 with audio_window_frames > 0): every request's chunks leave while it generates ----
+    // A slotted codec stream over the S slots decodes them; retired rows do not go through the decode batches above: a
+    // request's AUDIO is the concatenation of its chunks, INFO and AUDIO fire once the last one has landed. Only requests held
+    // back at a chunk that left the fp16 range are decoded again (fp32), behind the loop.
+    const bool streamed = sp.audio_chunk_frames > 0;
+    const int up = codec_->upsample();
+    DevBuf<int32_t> scodes;          // [S][Fcap][16]: the codes the stream reads, copied from codes_ burst by burst
+    std::unique_ptr<SlotStream> ss;  // (its destructor closes the runner's stream whatever ends this call; it goes before scodes)
+    std::vector<int> copied((size_t)(S), 0);   // frames [0, copied) of the slot's current request are in scodes
+    std::vector<uint8_t> reused((size_t)(S), 0);  // the slot has had an earlier occupant whose codes the stream may still read
+    std::vector<Retired> gone;       // streamed: retired requests by index (codes, span) until they are complete
+    std::vector<int> held;           // streamed: complete but held back, for the fp32 re-decode
+    auto fill_result = [&](int req, q3tts_status status, float* pcm) {  // as end() fills a row; pcm: ownership passes
+        const Retired& w = gone[size_t(req)];
+        q3tts_result& r = q.results[req];
+        std::memset(&r, 0, sizeof(r));
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        r.info.prompt_token_count = (*q.reqs)[size_t(req)].target_token_count;
+        r.info.generation_token_count = w.frames;
+        r.info.generate_time = w.span;
+        r.info.tokens_per_second = w.span > 0 ? double(w.frames) / w.span : 0;
+        r.info.peak_memory_usage = double(total_b - free_b) / 1e9;
+        r.status = status;
+        if (status != Q3TTS_OK) {
+            std::free(pcm);
+            return;
+        }
+        r.codes = static_cast<int32_t*>(std::malloc(size_t(w.frames) * 16 * 4));
+        if (!r.codes) {
+            std::free(pcm);
+            throw Error(5, "out of host memory for the results");
+        }
+        std::memcpy(r.codes, w.codes.data(), size_t(w.frames) * 16 * 4);
+        r.n_frames = w.frames;
+        r.n_samples = int64_t(w.frames) * up;  // all generated frames: what has left cannot be trimmed (include/q3tts.h)
+        r.pcm = pcm;
+        if (cb) {
+            std::unique_lock<std::mutex> lk = cb_lock();
+            q3tts_event ev{};
+            ev.kind = Q3TTS_EVENT_INFO;
+            ev.request_index = req;
+            ev.info = &r.info;
+            cb(user, &ev);
+            ev.kind = Q3TTS_EVENT_AUDIO;
+            ev.info = nullptr;
+            ev.pcm = r.pcm;
+            ev.n_samples = r.n_samples;
+            cb(user, &ev);
+        }
+    };
+    if (streamed) {
+        gone.resize(size_t(q.n));
+        scodes.grow(size_t(S) * Fcap_ * 16);
+        ss = std::make_unique<SlotStream>(*this, S, q.n, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
+                                          Fcap_, true);
+        ss->t_call = t_call;
+        if (cb)
+            ss->on_chunk = [&](int req, int, const float* pcm, int64_t n, int64_t off) {
+                std::unique_lock<std::mutex> lk = cb_lock();
+                audio_chunk(cb, user, req, pcm, n, off);
+            };
+        ss->on_complete = [&](int req) {
+            SlotStream::Out& o = ss->out[size_t(req)];
+            if (gone[size_t(req)].frames == 0) fill_result(req, Q3TTS_ERR_GENERATION_FAILED, o.pcm.release());  // Qwen3.swift:939-941
+            else if (o.held_from >= 0) held.push_back(req);
+            else fill_result(req, Q3TTS_OK, o.pcm.release());
+        };
+    }
+
     const int burst_frames = std::max(1, max_inflight_frames / 2);
     std::vector<int32_t> h_nframes((size_t)(S), 0);
     std::vector<uint8_t> h_fin((size_t)(S), 0);
@@ -1961,8 +2152,17 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     Q3_HIP(hipEventRecord(ev_[2], st_));
     for (;;) {
         // ---- admission: free slots in slot order take the next requests in request order ----
+        std::vector<int> before;
+        if (streamed)
+            for (const QSlot& x : sl) before.push_back(x.req);
         const int admitted = admit(q, sl, drained);
         served += admitted;
+        if (streamed)  // a new occupant: the row's chunks, history margins and non-finite flag start over, in codec-stream order
+            for (int s = 0; s < S; ++s)
+                if (sl[size_t(s)].req >= 0 && before[size_t(s)] < 0) {
+                    ss->admit(s, sl[size_t(s)].req, (*q.reqs)[size_t(sl[size_t(s)].req)].max_frames);
+                    copied[size_t(s)] = 0;
+                }
         // ---- burst: no longer than the first running row's remaining frames (its cap ends it on time) ----
         int running = 0, burst = burst_frames;
         for (const QSlot& x : sl)
@@ -1983,7 +2183,48 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         // ---- while the burst runs: deliver the decode batch that has landed, start the next one ----
         if (dec >= 0) deliver(false);
         if (dec < 0 && !waiting.empty()) decode(true);
+        if (streamed) {  // chunks that have landed leave while the burst runs, without waiting for them
+            for (;;) {
+                const hipError_t bq = hipEventQuery(burst_ev_[0]);
+                if (bq != hipErrorNotReady) {
+                    Q3_HIP(bq);
+                    break;
+                }
+                if (!ss->take(false)) std::this_thread::yield();
+            }
+        }
         Q3_HIP(hipEventSynchronize(burst_ev_[0]));
+        if (streamed) {
+            // ---- the new frames of every running slot into the stream's own code buffer, then every chunk they allow ----
+            // A continuing request's new frames lie behind everything an issued pass reads (windows end at the frames that
+            // had been copied). A NEW occupant's first frames overwrite what the previous occupant's last chunks read: that
+            // copy waits for ev_pushed, recorded on the codec stream behind the latest push -- the one that issued them.
+            bool first_copy = false;
+            for (int s = 0; s < S; ++s)
+                first_copy = first_copy || (sl[size_t(s)].req >= 0 && copied[size_t(s)] == 0 && reused[size_t(s)] && h_nframes[size_t(s)] > 0);
+            if (first_copy) Q3_HIP(hipStreamWaitEvent(st_, ss->ev_pushed, 0));
+            std::vector<int> avail((size_t)(S), 0);
+            bool any_copy = false;
+            for (int s = 0; s < S; ++s) {
+                if (sl[size_t(s)].req < 0) continue;
+                const int nf = std::min(h_nframes[size_t(s)], Fcap_);
+                avail[size_t(s)] = nf;
+                if (nf > copied[size_t(s)]) {
+                    const size_t at = (size_t(s) * Fcap_ + copied[size_t(s)]) * 16;
+                    Q3_HIP(hipMemcpyAsync(scodes + at, codes_ + at, size_t(nf - copied[size_t(s)]) * 64, hipMemcpyDeviceToDevice, st_));
+                    copied[size_t(s)] = nf;
+                    reused[size_t(s)] = 1;
+                    any_copy = true;
+                }
+            }
+            if (any_copy) {
+                Q3_HIP(hipEventRecord(ss->ev_codes, st_));
+                Q3_HIP(hipStreamWaitEvent(ss->cst, ss->ev_codes, 0));
+            }
+            std::vector<uint8_t> fin((size_t)(S), 0);
+            for (int s = 0; s < S; ++s) fin[size_t(s)] = sl[size_t(s)].req >= 0 && h_fin[size_t(s)] ? 1 : 0;
+            ss->push(scodes, Fcap_, avail.data(), fin.data());  // a retiring row's remaining chunks are all issued here
+        }
         if (admitted) {
             float ms = 0;
             Q3_HIP(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
@@ -1991,6 +2232,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         }
         // ---- TOKEN events (generation order), retirement ----
         bool any_retired = false;
+        std::vector<int> retiring;  // streamed: rows retired at this boundary
         const double now = now_s();
         for (int s = 0; s < S; ++s) {
             QSlot& x = sl[size_t(s)];
@@ -2000,14 +2242,17 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             if (cb) emit_tokens(cb, user, s, x.req, nf, x.reported);
             if (!h_fin[size_t(s)]) continue;
             // copied out before the slot's next admission resets its row (stream order on st_)
-            waiting.push_back(Retired{x.req, nf, now - x.t0, std::vector<int32_t>((size_t)(nf) * 16)});
+            Retired& w = streamed ? gone[size_t(x.req)] : (waiting.push_back(Retired{}), waiting.back());
+            w = Retired{x.req, nf, now - x.t0, std::vector<int32_t>((size_t)(nf) * 16)};
             if (nf > 0)
-                Q3_HIP(hipMemcpyAsync(waiting.back().codes.data(), codes_ + size_t(s) * Fcap_ * 16, size_t(nf) * 64, hipMemcpyDeviceToHost, st_));
+                Q3_HIP(hipMemcpyAsync(w.codes.data(), codes_ + size_t(s) * Fcap_ * 16, size_t(nf) * 64, hipMemcpyDeviceToHost, st_));
             kvb += kv_bytes(x.np, nf);
+            if (streamed) retiring.push_back(s);
             x = QSlot{};
             any_retired = true;
         }
         if (any_retired) Q3_HIP(hipStreamSynchronize(st_));
+        for (int s : retiring) ss->retire(s, std::min(h_nframes[size_t(s)], Fcap_));  // (complete at once when its chunks have landed)
     }
     Q3_HIP(hipEventRecord(ev_[3], st_));
     Q3_HIP(hipStreamSynchronize(st_));
@@ -2016,12 +2261,61 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         if (dec >= 0) deliver(true);
         else decode(false);
     }
+    double first_audio_ms = 0;
+    if (streamed) {
+        ss->finish();  // the passes still in flight; every request is complete behind this
+        codec_ms = ss->codec_ms;
+        first_audio_ms = ss->first_audio_ms;
+        // ---- requests held back at a chunk that left the fp16 range: once more on the fp32 matrix cores, as redo_rows_fp32 does
+        // for a streamed job: chunks below the held one stay as delivered, the rest (events included) come from the exact decode
+        for (size_t h0 = 0; h0 < held.size(); h0 += size_t(Bm_)) {
+            const int R = int(std::min(held.size() - h0, size_t(Bm_)));
+            std::vector<int> dframes((size_t)(R));
+            int Fd = 0;
+            for (int i = 0; i < R; ++i) Fd = std::max(Fd, dframes[size_t(i)] = gone[size_t(held[h0 + i])].frames);
+            PinnedBuf<int32_t> nf;
+            PinnedBuf<float> hpcm;
+            std::memset(nf.grow(size_t(R)), 0, size_t(R) * 4);
+            const bool widest = codec_->fp32_convs();  // already the fp32 kernels: nothing wider to fall back to
+            if (!widest) {
+                hipStream_t cst = codec_stream(false);
+                DevBuf<int32_t> dcodes;
+                dcodes.grow(size_t(R) * Fd * 16);
+                hpcm.grow(size_t(R) * Fd * up);
+                for (int i = 0; i < R; ++i)
+                    Q3_HIP(hipMemcpy(dcodes + size_t(i) * Fd * 16, gone[size_t(held[h0 + i])].codes.data(), size_t(dframes[size_t(i)]) * 64,
+                                     hipMemcpyHostToDevice));
+                float* pcm_dev = nullptr;
+                codec_->decode(dcodes, Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
+                Q3_HIP(hipMemcpyAsync(hpcm, pcm_dev, size_t(R) * Fd * up * 4, hipMemcpyDeviceToHost, cst));
+                Q3_HIP(hipStreamSynchronize(cst));
+            }
+            for (int i = 0; i < R; ++i) {
+                const int req = held[h0 + i];
+                SlotStream::Out& o = ss->out[size_t(req)];
+                if (widest || nf[i]) {  // never hand out a waveform with holes in it
+                    fill_result(req, Q3TTS_ERR_AUDIO_DECODING_FAILED, o.pcm.release());
+                    last_error = kCodecRangeMsg;
+                    continue;
+                }
+                const int64_t step = int64_t(sp.audio_chunk_frames) * up, ns = int64_t(dframes[size_t(i)]) * up;
+                const int64_t from = std::min(ns, int64_t(o.held_from) * step);
+                std::memcpy(o.pcm.get() + from, hpcm + size_t(i) * Fd * up + from, size_t(ns - from) * 4);
+                if (cb) {
+                    std::unique_lock<std::mutex> lk = cb_lock();
+                    for (int64_t lo = from; lo < ns; lo += step) audio_chunk(cb, user, req, o.pcm.get() + lo, std::min(step, ns - lo), lo);
+                }
+                fill_result(req, Q3TTS_OK, o.pcm.release());
+            }
+        }
+    }
     q3tts_timing tm{};
     float loop_ms = 0;
     Q3_HIP(hipEventElapsedTime(&loop_ms, ev_[2], ev_[3]));
     tm.prefill_ms = prefill_ms;
     tm.decode_ms = std::max(0.0, double(loop_ms) - prefill_ms);
     tm.codec_ms = codec_ms;
+    tm.first_audio_ms = first_audio_ms;
     tm.frame_steps = launched;
     tm.rows = served;
     tm.kv_bytes_read = kvb;
@@ -2294,6 +2588,56 @@ void Engine::codec_decode_streamed(const int32_t* codes, const int32_t* n_frames
         std::memcpy(pcm + size_t(b) * max_frames * up, hpcm + size_t(b) * max_frames * up, size_t(n_frames[b]) * up * 4);
 }
 
+void Engine::check_stream_chunk(int chunk_frames) const {
+    Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");
+    const int hist = codec_->hist_frames();
+    Q3_CHECK(chunk_frames >= hist, 3, "Invalid input: audio_chunk_frames of a streamed decode must be at least " + std::to_string(hist));
+}
+
+// The slotted stream as a streamed queue drives it, without the talker: the schedule of stream_plan.h decides when a request
+// takes a slot, how many frames it has at each push and when it is retired; the codes come from the caller.
+void Engine::debug_codec_stream_slots(const int32_t* codes, const int32_t* n_frames, int n_reqs, int max_frames, int slots, int burst,
+                                      int chunk_frames, int window, int lookahead, float* pcm) {
+    Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");
+    Q3_CHECK(n_reqs >= 1 && max_frames >= 1 && burst >= 1 && chunk_frames >= 1 && window >= 0 && lookahead >= 0, 3,
+             "Invalid input: empty codec batch");
+    Q3_CHECK(slots >= 1 && slots <= Bm_, 3, "Invalid input: slots must be between 1 and max_batch");
+    for (int i = 0; i < n_reqs; ++i) Q3_CHECK(n_frames[i] >= 0 && n_frames[i] <= max_frames, 3, "Invalid input: n_frames out of range");
+    check_caller_codes(m_->codec, codes, n_frames, n_reqs, max_frames);
+    check_stream_chunk(chunk_frames);
+    const int up = codec_->upsample();
+    DevBuf<int32_t> all, scodes;  // every request's codes; the stream's own buffer [slots][max_frames][16]
+    all.grow(size_t(n_reqs) * max_frames * 16);
+    scodes.grow(size_t(slots) * max_frames * 16);
+    Q3_HIP(hipMemcpy(all, codes, size_t(n_reqs) * max_frames * 16 * 4, hipMemcpyHostToDevice));
+    SlotStream ss(*this, slots, n_reqs, chunk_frames, window, lookahead, max_frames, false);
+    ss.hold = false;  // (as q3tts_codec_decode_streamed: the samples as the default kernels produce them)
+    std::vector<int> copied((size_t)(slots), 0);
+    replay_queue_schedule(
+        n_frames, n_reqs, slots, burst,
+        [&](int s, int r) {
+            ss.admit(s, r, max_frames);
+            copied[size_t(s)] = 0;
+        },
+        [&](const int* avail, const uint8_t* fin, const int* req) {
+            for (int s = 0; s < slots; ++s) {  // on the codec stream itself: behind every pass that read the slot's earlier codes
+                if (req[s] < 0 || avail[s] <= copied[size_t(s)]) continue;
+                Q3_HIP(hipMemcpyAsync(scodes + (size_t(s) * max_frames + copied[size_t(s)]) * 16,
+                                      all + (size_t(req[s]) * max_frames + copied[size_t(s)]) * 16, size_t(avail[s] - copied[size_t(s)]) * 64,
+                                      hipMemcpyDeviceToDevice, ss.cst));
+                copied[size_t(s)] = avail[s];
+            }
+            ss.push(scodes, max_frames, avail, fin);
+            for (int s = 0; s < slots; ++s)
+                if (req[s] >= 0 && fin[s]) ss.retire(s, avail[s]);
+        });
+    ss.finish();
+    for (int i = 0; i < n_reqs; ++i) {
+        Q3_CHECK(ss.out[size_t(i)].complete, 7, "internal error: a request of the slotted stream was left incomplete");
+        std::memcpy(pcm + size_t(i) * max_frames * up, ss.out[size_t(i)].pcm.get(), size_t(n_frames[i]) * up * 4);
+    }
+}
+
 void Engine::debug_codec_stage(const int32_t* codes, int n_frames, const char* stage, float* out, int64_t cap, int* T, int* C) {
     Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");
     DevBuf<int32_t> dcodes;
@@ -2466,7 +2810,8 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
                                   q3tts_result* results) {
     Q3_CHECK(n >= 1, 3, "Invalid input: n_reqs must be at least 1");
     Q3_CHECK(slots >= 1 && slots <= opts_.max_batch, 3, "Invalid input: slots must be between 1 and max_batch");
-    Q3_CHECK(sp.audio_chunk_frames == 0, 3,
+    // chunks cut after a request's end (audio_window_frames == 0) give a queue nothing: its AUDIO already leaves as soon as it is decoded
+    Q3_CHECK(sp.audio_chunk_frames == 0 || sp.audio_window_frames > 0, 3,
              "Invalid input: audio_chunk_frames is not supported by q3tts_generate_queued (each request's audio is delivered whole)");
     bool outstanding = false;
     for (const auto& p : parked_) outstanding = outstanding || p.busy;
@@ -2484,6 +2829,8 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
             throw Error(e.status, std::string(e.what()) + " (request " + std::to_string(i) + ")");
         }
     }
+    if (sp.audio_chunk_frames > 0)  // a streamed queue: the causal tail's history must fit into a chunk (as a streamed q3tts_generate)
+        lanes_[0]->check_stream_chunk(sp.audio_chunk_frames);
     QueueShared q;
     q.reqs = &rr;
     q.n = n;
@@ -2504,6 +2851,7 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
         timing.prefill_ms += t.prefill_ms;
         timing.decode_ms = std::max(timing.decode_ms, t.decode_ms);
         timing.codec_ms += t.codec_ms;
+        if (t.first_audio_ms > 0) timing.first_audio_ms = timing.first_audio_ms > 0 ? std::min(timing.first_audio_ms, t.first_audio_ms) : t.first_audio_ms;
         timing.frame_steps += t.frame_steps;
         timing.launches_per_frame_step = std::max(timing.launches_per_frame_step, t.launches_per_frame_step);
         timing.kv_bytes_read += t.kv_bytes_read;

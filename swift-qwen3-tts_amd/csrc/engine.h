@@ -99,6 +99,7 @@ class Engine {
     // rows in flight: at each burst boundary finished rows are retired (codes copied out, decode queued on the codec stream
     // beside the frame loop) and their slots take the next requests of `q`, prefilled as a sub-batch of their own.
     ResolvedRequest check_queued(const q3tts_request& r, const q3tts_sampling& sp) const;
+    void check_stream_chunk(int chunk_frames) const;  // a streamed decode's chunk must hold the causal tail's history
     void run_queued(QueueShared& q, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
     void debug_prepare_inputs(const q3tts_request& req, uint16_t* input_embeds, int cap_prompt, int* n_prompt,
                               uint16_t* trailing, int cap_trailing, int* n_trailing, uint16_t* tts_pad);
@@ -110,6 +111,9 @@ class Engine {
                       int64_t* audio_lengths);
     void codec_decode_streamed(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, int chunk_frames, int window,
                                int lookahead, float* pcm);
+    // q3tts_debug_codec_stream_slots: the slotted stream of a streamed queue driven by the queue's schedule without the talker
+    void debug_codec_stream_slots(const int32_t* codes, const int32_t* n_frames, int n_reqs, int max_frames, int slots, int burst,
+                                  int chunk_frames, int window, int lookahead, float* pcm);
     void debug_codec_stage(const int32_t* codes, int n_frames, const char* stage, float* out, int64_t cap, int* T, int* C);
     // voice-clone front end (SpeechTokenizer.swift:841-846; Qwen3.swift:222-249); host buffers in and out
     int codec_encode(const float* audio, int64_t n_samples, int32_t* codes, int cap_frames);
@@ -291,6 +295,7 @@ class Engine {
                      const q3tts_sampling& sp);
     void debug_buffers(int n, const DebugOpts& dbg);
     struct StreamedDecode;
+    struct SlotStream;  // the audio side of a streamed queue (run_queued) and of q3tts_debug_codec_stream_slots
     // the bursts of frame steps with their TOKEN events and streamed chunks; fills J.frames, returns the frame steps
     int frame_loop(Job& J, const std::vector<ResolvedRequest>& rr, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
                    const DebugOpts* dbg, StreamedDecode& sd);

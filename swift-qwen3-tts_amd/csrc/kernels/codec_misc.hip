@@ -23,10 +23,12 @@ __device__ __forceinline__ float block_sum_256(float v, float* sh) {
 __global__ __launch_bounds__(256) void rvq_gather_kernel(const int32_t* codes, int code_stride_frames,
                                                          const float* cb_first, const float* const* cb_rest, int n_rest,
                                                          int inner, const int32_t* frames, int Fmax, float* out,
-                                                         int rows_first, int rows_rest) {
+                                                         int rows_first, int rows_rest, const int32_t* first_frame) {
     const int f = blockIdx.x, b = blockIdx.y;
     if (f >= frames[b]) return;
-    const int32_t* c = codes + ((size_t)b * code_stride_frames + f) * 16;
+    // first_frame (slotted stream): row b's frame 0 is frame first_frame[b] of its code row; nullptr: 0 for every row
+    const int f_src = f + (first_frame ? first_frame[b] : 0);
+    const int32_t* c = codes + ((size_t)b * code_stride_frames + f_src) * 16;
     float* o = out + ((size_t)b * Fmax + f) * 2 * inner;
     // a code is a row index: kept inside the table whatever produced it (caller codes are rejected on the host before they get
     // here, Engine::check_caller_codes; sampled codes are inside by construction -- the clamp is the seat belt, not the rule)
@@ -238,7 +240,60 @@ __global__ __launch_bounds__(256) void roll_history_kernel(float* cur, int64_t b
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < keep / 4; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
 }
 
+// slotted stream: lat[b][t][:] = front[b][off[b] + t][:] for t < take[b] (rows with take 0 are left alone). `lat` points behind
+// the history margin; strides in floats; a frame is lat4 float4s.
+__global__ __launch_bounds__(256) void stream_take_chunk_kernel(const float* front, int64_t front_bstride, float* lat, int64_t lat_bstride,
+                                                                int lat4, const int32_t* off, const int32_t* take) {
+    const int b = blockIdx.y;
+    const int n = take[b];
+    if (n <= 0) return;
+    const float4* src = reinterpret_cast<const float4*>(front + (int64_t)b * front_bstride) + (int64_t)off[b] * lat4;
+    float4* dst = reinterpret_cast<float4*>(lat + (int64_t)b * lat_bstride);
+    const int64_t total = (int64_t)n * lat4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
+}
+
+// slotted stream: roll_history over every tensor of the table in one launch, row by row: mode[b] 0 leaves row b alone, 1 moves
+// its last `hist` frames of the chunk into the margin, 2 zeroes the margin (a new request takes the row). mode == nullptr:
+// the launch is a reset of `only_row` alone (grid.y == 1), which also clears that row's non-finite flag.
+__global__ __launch_bounds__(256) void roll_history_rows_kernel(const RollDesc* desc, int Tal, int hist, int chunk, const int32_t* mode,
+                                                                int only_row, int32_t* nonfinite) {
+    const int b = mode ? (int)blockIdx.y : only_row;
+    const int m = mode ? mode[b] : 2;
+    if (m == 0) return;
+    if (!mode && nonfinite && blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) nonfinite[b] = 0;
+    const RollDesc d = desc[blockIdx.z];
+    float* row = d.base + (int64_t)b * Tal * d.frame_floats;
+    const int64_t keep = (int64_t)hist * d.frame_floats, from = (int64_t)chunk * d.frame_floats;
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if ((d.frame_floats & 3) == 0) {  // allocations are 256-byte aligned: whole float4s throughout
+        float4* dst = reinterpret_cast<float4*>(row);
+        const float4* src = reinterpret_cast<const float4*>(row + from);
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int64_t i = i0; i < keep / 4; i += step) dst[i] = m == 1 ? src[i] : zero;
+    } else {
+        for (int64_t i = i0; i < keep; i += step) row[i] = m == 1 ? row[from + i] : 0.f;
+    }
+}
+
 }  // namespace
+
+void launch_stream_take_chunk(const float* front, int64_t front_bstride, float* lat, int64_t lat_bstride, int latent, int max_take,
+                              const int32_t* off, const int32_t* take, int B, hipStream_t st) {
+    Q3_CHECK(latent >= 4 && latent % 4 == 0 && front_bstride % 4 == 0 && lat_bstride % 4 == 0, 3, "stream_take_chunk: latent width must be whole float4s");
+    if (B <= 0 || max_take <= 0) return;
+    const int gx = int(std::min<int64_t>(64, (int64_t(max_take) * (latent / 4) + 255) / 256));
+    hipLaunchKernelGGL(stream_take_chunk_kernel, dim3(gx, B), dim3(256), 0, st, front, front_bstride, lat, lat_bstride, latent / 4, off, take);
+}
+
+void launch_roll_history_rows(const RollDesc* desc, int n_desc, int64_t max_frame_floats, int Tal, int hist, int chunk, const int32_t* mode,
+                              int only_row, int B, int32_t* nonfinite, hipStream_t st) {
+    Q3_CHECK(chunk >= hist && Tal == hist + chunk, 3, "roll_history: chunk shorter than the history");
+    Q3_CHECK(mode != nullptr || (only_row >= 0 && only_row < B), 3, "roll_history: row outside the stream");
+    if (n_desc <= 0 || B <= 0 || hist <= 0) return;
+    const int gx = int(std::max<int64_t>(1, std::min<int64_t>(64, (int64_t(hist) * max_frame_floats / 4 + 255) / 256)));
+    hipLaunchKernelGGL(roll_history_rows_kernel, dim3(gx, mode ? B : 1, n_desc), dim3(256), 0, st, desc, Tal, hist, chunk, mode, only_row, nonfinite);
+}
 
 void launch_roll_history(float* cur, int64_t bstride, int64_t keep_floats, int64_t chunk_floats, int B, hipStream_t st) {
     Q3_CHECK(keep_floats % 4 == 0 && chunk_floats >= keep_floats, 3, "roll_history: chunk shorter than the history");
@@ -249,10 +304,10 @@ void launch_roll_history(float* cur, int64_t bstride, int64_t keep_floats, int64
 
 void launch_rvq_gather(const int32_t* codes, int code_stride_frames, const float* cb_first, const float* const* cb_rest,
                        int n_rest, int inner, const int32_t* frames, int Fmax, int B, float* out, int rows_first, int rows_rest,
-                       hipStream_t st) {
+                       hipStream_t st, const int32_t* first_frame) {
     Q3_CHECK(rows_first >= 1 && rows_rest >= 1 && n_rest >= 1 && n_rest <= 15, 3, "rvq_gather: empty codebook");
     hipLaunchKernelGGL(rvq_gather_kernel, dim3(Fmax, B), dim3(256), 0, st, codes, code_stride_frames, cb_first, cb_rest,
-                       n_rest, inner, frames, Fmax, out, rows_first, rows_rest);
+                       n_rest, inner, frames, Fmax, out, rows_first, rows_rest, first_frame);
 }
 void launch_rmsnorm_f32(const float* x, const float* w, float eps, int C, const int32_t* frames, int ppf, int Tmax, int B,
                         float* out, hipStream_t st) {

@@ -125,6 +125,9 @@ def lib() -> C.CDLL:
     L.q3tts_result_free.restype = None
     L.q3tts_codec_decode.argtypes = [vp, i32p, i32p, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_int64)]
     L.q3tts_codec_decode_streamed.argtypes = [vp, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p]
+    if hasattr(L, "q3tts_debug_codec_stream_slots"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_debug_codec_stream_slots.argtypes = [vp, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                     C.c_int32, f32p]
     L.q3tts_debug_set_codec_scratch.argtypes = [C.c_uint64]
     L.q3tts_debug_set_codec_scratch.restype = None
     L.q3tts_debug_reload_env.argtypes = []

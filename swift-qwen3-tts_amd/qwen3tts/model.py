@@ -266,8 +266,11 @@ class Qwen3TTSModel:
                         row_base: int = 0) -> List[GenerationResult]:
         """Continuous batching (q3tts_generate_queued): any number of requests with at most `slots` rows in flight (default
         max_batch); a finished row's slot takes the next request. Result i is bit-identical to generate_batch([reqs[i]],
-        row_base=row_base + i). Events as generate_batch's, except that a request's ("info", ...) / ("audio", ...) arrive as
-        soon as its audio is decoded. Voice-clone requests and audio_chunk_frames > 0 are refused."""
+        row_base=row_base + i) with the same keywords. Events as generate_batch's, except that a request's ("info", ...) /
+        ("audio", ...) arrive as soon as its audio is decoded. With audio_chunk_frames > 0 and audio_window_frames > 0 every
+        request's audio is streamed as if it ran alone: ("audio_chunk", (offset, samples)) events carry its request index and
+        leave while it generates, "info" / "audio" once its last chunk has landed. Refused: voice-clone requests,
+        audio_chunk_frames > 0 without a window (audio_window_frames == 0) or below the decoder's history."""
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
                            audio_window_frames, audio_lookahead_frames, row_base)
@@ -489,6 +492,21 @@ class Qwen3TTSModel:
         pcm = np.zeros((B, F * self.info.samples_per_frame), np.float32)
         self._check(self._lib.q3tts_codec_decode_streamed(self._h, codes.ctypes.data_as(L.i32p), nf.ctypes.data_as(L.i32p), B, F,
                                                           chunk_frames, window, lookahead, pcm.ctypes.data_as(L.f32p)))
+        return pcm
+
+    def debug_codec_stream_slots(self, codes: np.ndarray, n_frames: Sequence[int], slots: int, burst: int, chunk_frames: int,
+                                 window: int, lookahead: int) -> np.ndarray:
+        """The slotted codec stream of a streamed queue without the talker (q3tts_debug_codec_stream_slots): codes
+        [n_reqs][max_frames][16]; requests take `slots` rows in order and gain `burst` frames per step. Returns pcm
+        [n_reqs][max_frames * 1920], request i equal to codec_decode_streamed of it alone."""
+        codes = np.ascontiguousarray(codes, np.int32)
+        N, F, G = codes.shape
+        nf = np.asarray(n_frames, np.int32)
+        assert nf.shape == (N,) and G == 16
+        pcm = np.zeros((N, F * self.info.samples_per_frame), np.float32)
+        self._check(self._lib.q3tts_debug_codec_stream_slots(self._h, codes.ctypes.data_as(L.i32p), nf.ctypes.data_as(L.i32p), N, F,
+                                                             int(slots), int(burst), int(chunk_frames), int(window), int(lookahead),
+                                                             pcm.ctypes.data_as(L.f32p)))
         return pcm
 
     def debug_prepare_inputs(self, req: GenerationRequest):

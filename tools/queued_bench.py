@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Continuous batching against static batches.
 
-  python tools/queued_bench.py [--preset 1.7b] [--slots 32] [--requests 256]
+  python tools/queued_bench.py [--preset 1.7b] [--slots 32] [--requests 256] [--stream CHUNK,WINDOW,LOOKAHEAD]
 
 Two workloads on bench.py's synthetic checkpoint and request builder:
   ragged   max_tokens uniform in 50..400 (seeded), temperature 0.9, seed 1234: rows end at their caps (or EOS) at different frames
@@ -11,6 +11,10 @@ and two paths for each:
   queued   one q3tts_generate_queued call with `slots` rows in flight
 Prints, per run, frames/s (generated frames over the wall time of the whole workload, codec decode included), frame steps,
 prefill and codec milliseconds, and whether every request's codes and PCM are bit-identical between the two paths.
+--stream CHUNK,WINDOW,LOOKAHEAD adds, on the ragged workload, the queue with streamed audio (audio_chunk_frames / audio_window_frames /
+audio_lookahead_frames) next to the same run without it, both with an event callback: frames/s of each, and per request the time
+from its admission to its first AUDIO_CHUNK (streamed) or to its AUDIO (not streamed), median and worst. A request's admission is
+its last TOKEN's arrival (the burst boundary that retired it) minus its generate_time (admission -> retirement).
 """
 from __future__ import annotations
 
@@ -57,12 +61,35 @@ def run_queued(model, reqs, slots, kw):
     return out, dt, tm.frame_steps, tm.prefill_ms, tm.codec_ms
 
 
+def run_queued_timed(model, reqs, slots, kw):
+    """The queued path with a callback that stamps every request's last TOKEN, first AUDIO_CHUNK and AUDIO."""
+    last_token, first_chunk, audio = {}, {}, {}
+
+    def on_event(i, kind, payload):
+        t = time.perf_counter()
+        if kind == "token":
+            last_token[i] = t
+        elif kind == "audio_chunk":
+            first_chunk.setdefault(i, t)
+        elif kind == "audio":
+            audio[i] = t
+
+    t0 = time.perf_counter()
+    out = model.generate_queued(reqs, slots=slots, on_event=on_event, **kw)
+    dt = time.perf_counter() - t0
+    tm = model.last_timing()
+    first = first_chunk if first_chunk else audio
+    lat = [first[i] - (last_token[i] - out[i].info.generate_time) for i in range(len(reqs)) if i in first and i in last_token]
+    return out, dt, tm, np.asarray(lat)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--preset", default="1.7b")
     ap.add_argument("--slots", type=int, default=32)
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--n-text", type=int, default=32)
+    ap.add_argument("--stream", default=None, metavar="CHUNK,WINDOW,LOOKAHEAD", help="also run the ragged queue with streamed audio")
     args = ap.parse_args()
     from qwen3tts import Qwen3TTSModel
 
@@ -97,6 +124,22 @@ def main():
         same = all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio) for x, y in zip(a, b))
         print(f"{name:8s} bit-identical codes + pcm, all {len(a)} requests: {same}   queued / static: frame_steps {sb / sa:.3f}  "
               f"frames/s {(fb / db) / (fa / da):.3f}", flush=True)
+    if args.stream:
+        c, w, l = (int(x) for x in args.stream.split(","))
+        skw = dict(audio_chunk_frames=c, audio_window_frames=w, audio_lookahead_frames=l)
+        run_queued_timed(model, warm, args.slots, dict(sampling, **skw))  # stream arena, pinned ring
+        rows = {}
+        for name, kw in (("queued", dict(sampling)), ("streamed", dict(sampling, **skw))):
+            out, dt, tm, lat = run_queued_timed(model, ragged, args.slots, kw)
+            frames = sum(int(r.codes.shape[0]) for r in out)
+            rows[name] = (out, frames / dt)
+            what = "admission -> first AUDIO_CHUNK" if name == "streamed" else "admission -> AUDIO"
+            print(f"ragged   {name:8s} (callback) frames {frames:7d}  wall {dt:8.3f} s  frames/s {frames / dt:9.1f}  frame_steps {tm.frame_steps:6d}  "
+                  f"codec {tm.codec_ms:8.1f} ms  first_audio {tm.first_audio_ms:7.1f} ms  {what}: median {np.median(lat) * 1e3:7.1f} ms  "
+                  f"worst {lat.max() * 1e3:7.1f} ms  failed {sum(1 for r in out if r.status != 0)}", flush=True)
+        same = all(np.array_equal(x.codes, y.codes) for x, y in zip(rows["queued"][0], rows["streamed"][0]))
+        print(f"ragged   streamed --stream {args.stream}: same codes as the queue without it: {same}   frames/s streamed / queued: "
+              f"{rows['streamed'][1] / rows['queued'][1]:.3f}", flush=True)
     model.close()
 
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define Q3TTS_ABI_VERSION 3
+#define Q3TTS_ABI_VERSION 4
 
 typedef struct q3tts_model q3tts_model;
 
@@ -144,7 +144,8 @@ typedef struct {
      *   ref_audio     = reference waveform, 24 kHz mono float32 (host memory, read during the call; a NaN or infinite
      *                   sample is Q3TTS_ERR_INVALID_INPUT)
      *   ref_text_ids  = tokens of "<|im_start|>assistant\n{referenceText}<|im_end|>\n" (:448-449)
-     * The reference's default repetition penalty on this path is 1.5 (:1017): set it in q3tts_sampling.
+     * The reference's default repetition penalty on this path is 1.5 (:1017), against 1.05 for generate(): a batch that mixes
+     * both gives each request its own through q3tts_sampling.per_request (Q3TTS_ROW_REPETITION_PENALTY).
      * Result: pcm = audio of the target text only (reference part cut proportionally, :1195-1199),
      * codes = generated frames only. */
     const float* ref_audio;
@@ -157,6 +158,27 @@ typedef struct {
                       required and validated against talker_config.spk_id (:803-811), instruct optional. Ignored for
                       voice-clone requests (ref_audio != NULL) */
 } q3tts_request;
+
+/* Sampling parameters of ONE request of a call (new: the reference samples one utterance per call, so its arguments are
+ * per request by construction). `set` names the fields that override the call's q3tts_sampling for this request; the others
+ * are ignored and the request inherits the call's values. A set seed replaces the seed of the request's random stream
+ * (seed, row_base + i); the stream's key, row_base + i, stays.
+ * Checked before any GPU work, the engine staying usable (Q3TTS_ERR_INVALID_INPUT): bits of `set` other than the five below;
+ * of the set fields, a temperature, top_p or repetition_penalty that is NaN or infinite, top_k < 0, repetition_penalty <= 0,
+ * top_p outside [0, 1] (top_p <= 0 keeps its meaning of "no top-p"). */
+#define Q3TTS_ROW_TEMPERATURE        1u
+#define Q3TTS_ROW_TOP_K              2u
+#define Q3TTS_ROW_TOP_P              4u
+#define Q3TTS_ROW_REPETITION_PENALTY 8u
+#define Q3TTS_ROW_SEED               16u
+typedef struct {
+    uint32_t set;   /* which fields below override the call's q3tts_sampling for this request */
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    float repetition_penalty;
+    uint64_t seed;
+} q3tts_row_sampling;
 
 /* Defaults as generate(): 0.9 / 50 / 1.0 / 1.05 (Qwen3.swift:1296-1299). */
 typedef struct {
@@ -190,6 +212,16 @@ typedef struct {
     uint32_t row_base;    /* new: global index of reqs[0] in a job whose rows are sharded over several processes (one
                              replica per GPU). A row's random stream is keyed by (seed, row_base + row index), so a sharded
                              job draws what the same rows would draw in one call. Default 0 */
+    const q3tts_row_sampling* per_request; /* new: [n_reqs] (q3tts_debug_sample: [rows]) or NULL (default): request i samples
+                             with the call's values above with per_request[i]'s set fields folded in. force_frames, the
+                             audio_* fields and row_base stay call-wide. Read only during the call (q3tts_generate_begin:
+                             during begin, like reqs). Row independence holds for every entry point that takes a
+                             q3tts_sampling -- q3tts_generate, _begin / _end (foreground and background),
+                             q3tts_generate_queued (streamed or not, any n_streams), q3tts_debug_generate_forced and
+                             q3tts_debug_sample: results[i] is bit-identical in codes, pcm, n_frames, n_samples and status to
+                             q3tts_generate of reqs[i] alone, with per_request == NULL, the call's sampling with row i's set
+                             fields folded in, and row_base = sampling->row_base + i. The frame graphs do not depend on
+                             the values: no call re-captures one because parameters changed */
 } q3tts_sampling;
 void q3tts_default_sampling(q3tts_sampling* s);
 

@@ -101,6 +101,7 @@ void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
     s->audio_window_frames = 0;
     s->audio_lookahead_frames = 4;
     s->row_base = 0;
+    s->per_request = nullptr;
 }
 
 q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts, q3tts_model** out) {
@@ -409,6 +410,7 @@ q3tts_status q3tts_debug_sample(q3tts_model* m, const uint16_t* logits, int32_t 
                                 int32_t suppress_hi, int32_t eos_id, uint32_t row0, uint32_t draw, int32_t* tokens) {
     return guarded(m, [&] {
         Q3_CHECK(m && logits && sampling && tokens, 3, "Invalid input: null argument");
+        q3::check_row_sampling(*sampling, rows);
         m->eng->lane0().debug_sample(logits, rows, V, *sampling, seen, suppress_lo, suppress_hi, eos_id, row0, draw, tokens);
     });
 }

@@ -282,7 +282,7 @@ void Engine::alloc_workspace() {
         prompt_ = b.take<uint16_t>(size_t(Bm_) * Pcap_ * H);
         trailing_ = b.take<uint16_t>(size_t(Bm_) * Tcap_ * H);
         tts_pad_ = b.take<uint16_t>(size_t(H));
-        sp_dev_ = b.take<SamplingParams>(1);
+        sp_dev_ = b.take<SamplingParams>(size_t(Bm_));
         ids_dev_ = b.take<int32_t>(size_t(proj_cap_));
         proj_in_ = b.take<uint16_t>(size_t(64) * TH);
         proj_mid_ = b.take<uint16_t>(size_t(64) * TH);
@@ -1085,6 +1085,7 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
         J.rr = std::move(rr);
         J.np = std::move(np);
         J.sp = sp;
+        J.sp.per_request = nullptr;  // (the caller's array was read by reserve_rows above; it is theirs again once begin returns)
         J.overlapped = overlapped;
         J.t_start = t_start;
         std::lock_guard<std::mutex> lk(work_mu_);
@@ -1205,7 +1206,7 @@ int Engine::reserve_rows(const std::vector<ResolvedRequest>& rr, const std::vect
     Q3_HIP(hipMemsetAsync(finished_, 0, size_t(n), st_));
     Q3_HIP(hipMemsetAsync(seen_, 0, size_t(n) * m_->cfg.talker.vocab_size, st_));
     Q3_HIP(hipMemsetAsync(codes_, 0, size_t(n) * Fcap_ * 16 * 4, st_));
-    upload_sampling(sp, row_offset + sp.row_base);
+    upload_sampling(sp, row_offset + sp.row_base, n);
     return Pmax;
 }
 
@@ -1453,9 +1454,39 @@ void Engine::Job::clear_chunk_flags(int frames) {
     std::memset(nf_chunk_host.grow(slots), 0, slots * 4);
 }
 
-void Engine::upload_sampling(const q3tts_sampling& sp, uint32_t row0) {
-    SamplingParams sph{sp.temperature, sp.top_k, sp.top_p, sp.repetition_penalty, sp.seed, row0, sp.force_frames > 0 ? 1 : 0};
-    Q3_HIP(hipMemcpyAsync(sp_dev_, &sph, sizeof(sph), hipMemcpyHostToDevice, st_));
+void check_row_sampling(const q3tts_sampling& sp, int n) {
+    if (!sp.per_request) return;
+    constexpr uint32_t kKnown = Q3TTS_ROW_TEMPERATURE | Q3TTS_ROW_TOP_K | Q3TTS_ROW_TOP_P | Q3TTS_ROW_REPETITION_PENALTY | Q3TTS_ROW_SEED;
+    for (int i = 0; i < n; ++i) {
+        const q3tts_row_sampling& r = sp.per_request[i];
+        const std::string at = " (per_request[" + std::to_string(i) + "])";
+        Q3_CHECK((r.set & ~kKnown) == 0, 3, "Invalid input: unknown bits in q3tts_row_sampling.set" + at);
+        if (r.set & Q3TTS_ROW_TEMPERATURE) Q3_CHECK(std::isfinite(r.temperature), 3, "Invalid input: temperature must be finite" + at);
+        if (r.set & Q3TTS_ROW_TOP_K) Q3_CHECK(r.top_k >= 0, 3, "Invalid input: top_k must not be negative" + at);
+        if (r.set & Q3TTS_ROW_TOP_P)
+            Q3_CHECK(std::isfinite(r.top_p) && r.top_p >= 0.f && r.top_p <= 1.f, 3, "Invalid input: top_p must be in [0, 1]" + at);
+        if (r.set & Q3TTS_ROW_REPETITION_PENALTY)
+            Q3_CHECK(std::isfinite(r.repetition_penalty) && r.repetition_penalty > 0.f, 3,
+                     "Invalid input: repetition_penalty must be finite and positive" + at);
+    }
+}
+
+SamplingParams fold_sampling(const q3tts_sampling& sp, int i, uint32_t row0) {
+    SamplingParams o{sp.temperature, sp.top_k, sp.top_p, sp.repetition_penalty, sp.seed, row0, sp.force_frames > 0 ? 1 : 0};
+    if (!sp.per_request) return o;
+    const q3tts_row_sampling& r = sp.per_request[i];
+    if (r.set & Q3TTS_ROW_TEMPERATURE) o.temperature = r.temperature;
+    if (r.set & Q3TTS_ROW_TOP_K) o.top_k = r.top_k;
+    if (r.set & Q3TTS_ROW_TOP_P) o.top_p = r.top_p;
+    if (r.set & Q3TTS_ROW_REPETITION_PENALTY) o.rep_penalty = r.repetition_penalty;
+    if (r.set & Q3TTS_ROW_SEED) o.seed = r.seed;
+    return o;
+}
+
+void Engine::upload_sampling(const q3tts_sampling& sp, uint32_t row0, int n) {
+    std::vector<SamplingParams> h;
+    for (int b = 0; b < n; ++b) h.push_back(fold_sampling(sp, b, row0));
+    Q3_HIP(hipMemcpyAsync(sp_dev_, h.data(), h.size() * sizeof(SamplingParams), hipMemcpyHostToDevice, st_));
 }
 
 int64_t Engine::kv_bytes(int n_prompt, int frames) const {
@@ -1961,15 +1992,16 @@ int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained) {
     for (int p : np) Pmax = std::max(Pmax, p);
     // the sub-batch's arrays: block table (its slots' pages), cache lengths 0, prompt lengths, admission descriptors
     const size_t nbt = size_t(k) * max_pages_;
-    q_host_.assign(nbt + 2 * size_t(k) + 4 * size_t(k), 0);
+    q_host_.assign(nbt + 2 * size_t(k), 0);
     int32_t* hbt = q_host_.data();
     int32_t* hnp = hbt + nbt + k;
-    AdmitDesc* hd = reinterpret_cast<AdmitDesc*>(hbt + nbt + 2 * size_t(k));
+    q_desc_host_.assign(size_t(k), AdmitDesc{});
+    AdmitDesc* hd = q_desc_host_.data();
     for (int j = 0; j < k; ++j) {
         const int s = slots[size_t(j)];
         for (int i = 0; i < max_pages_; ++i) hbt[size_t(j) * max_pages_ + i] = s * max_pages_ + i;
         hnp[j] = np[size_t(j)];
-        hd[j] = AdmitDesc{s, nt[size_t(j)], rr[size_t(j)].max_frames, keys[size_t(j)]};
+        hd[j] = AdmitDesc{s, nt[size_t(j)], rr[size_t(j)].max_frames, keys[size_t(j)], q.params[size_t(idx[size_t(j)])]};
     }
     Q3_HIP(hipMemcpyAsync(q_bt_, hbt, nbt * 4, hipMemcpyHostToDevice, st_));
     Q3_HIP(hipMemcpyAsync(q_kv_len_, hbt + nbt, size_t(k) * 4, hipMemcpyHostToDevice, st_));
@@ -1983,6 +2015,7 @@ int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained) {
     a.H = m_->cfg.talker.hidden_size; a.V = m_->cfg.talker.vocab_size; a.Fmax = Fcap_; a.slots = Bm_;
     a.kv_len = kv_len_; a.n_prompt = n_prompt_; a.n_trailing = n_trailing_; a.max_frames = max_frames_; a.n_frames = n_frames_;
     a.cp_len = cp_len_; a.trailing_idx = trailing_idx_; a.cur_codes = cur_codes_; a.codes = codes_; a.row_key = row_key_;
+    a.sp = sp_dev_;
     a.finished = finished_; a.active = active_; a.seen = seen_;
     launch_admit_rows(a, k, st_);
     Q3_HIP(hipEventRecord(ev_[1], st_));
@@ -2012,7 +2045,12 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     Q3_HIP(hipMemsetAsync(row_key_, 0, size_t(S) * 4, st_));
     Q3_HIP(hipMemsetAsync(active_, 0, size_t(S), st_));
     Q3_HIP(hipMemsetAsync(finished_, 1, size_t(S), st_));
-    upload_sampling(sp, 0u);
+    {  // every slot's entry holds the call's own values until an admission writes its request's (an empty slot's sampler returns early,
+       // but reads its entry with the other operands first)
+        q3tts_sampling call_wide = sp;
+        call_wide.per_request = nullptr;
+        upload_sampling(call_wide, 0u, S);
+    }
     build_cp_proj_tables();
     struct KeyScope {
         Engine* e;
@@ -2338,8 +2376,9 @@ void Engine::debug_sample(const uint16_t* logits, int rows, int V, const q3tts_s
     Q3_HIP(hipMemcpy(max_frames_, big.data(), size_t(rows) * 4, hipMemcpyHostToDevice));
     Q3_HIP(hipMemset(finished_, 0, size_t(rows)));
     Q3_HIP(hipMemset(active_, 1, size_t(rows)));
-    SamplingParams sph{sp.temperature, sp.top_k, sp.top_p, sp.repetition_penalty, sp.seed, row0, sp.force_frames > 0 ? 1 : 0};
-    Q3_HIP(hipMemcpy(sp_dev_, &sph, sizeof(sph), hipMemcpyHostToDevice));
+    std::vector<SamplingParams> sph;
+    for (int r = 0; r < rows; ++r) sph.push_back(fold_sampling(sp, r, row0));
+    Q3_HIP(hipMemcpy(sp_dev_, sph.data(), sph.size() * sizeof(SamplingParams), hipMemcpyHostToDevice));
     SamplerArgs sa{};
     sa.logits = tk_.logits; sa.ldl = Vt; sa.V = V; sa.sp = sp_dev_;
     sa.is_talker = (eos_id >= 0 || suppress_hi > suppress_lo || seen) ? 1 : 0;
@@ -2702,6 +2741,7 @@ Engine* EngineGroup::free_context() {
 
 int EngineGroup::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, bool more_follows) {
     Q3_CHECK(n >= 1 && n <= opts_.max_batch, 3, "Invalid input: batch size must be between 1 and max_batch");
+    check_row_sampling(sp, n);
     if (lanes_.size() == 1) {
         Engine* e = free_context();
         return (e == ctx1_.get() ? Engine::kJobSlots : 0) + e->begin(reqs, n, sp, cb, user, nullptr, more_follows, background_);
@@ -2761,6 +2801,7 @@ void EngineGroup::run_lanes(int L, bool serial, F&& fn) {
 void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
                            q3tts_result* results, const DebugOpts* dbg) {
     Q3_CHECK(n >= 1 && n <= opts_.max_batch, 3, "Invalid input: batch size must be between 1 and max_batch");
+    check_row_sampling(sp, n);
     const int L = int(lanes_.size());
     // contiguous split: lane i takes rows [lo_i, hi_i)
     std::vector<int> lo((size_t)(L + 1), 0);
@@ -2787,7 +2828,9 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
             if (d.cp_logits) d.cp_logits += size_t(a) * fr * (t.num_code_groups - 1) * t.cp.vocab_size;
             dp = &d;
         }
-        e.generate(reqs + a, b - a, sp, cb, user, results + a, dp);
+        q3tts_sampling ls = sp;  // the lane's rows are requests [a, b): their entries of the per-request array
+        if (ls.per_request) ls.per_request += a;
+        e.generate(reqs + a, b - a, ls, cb, user, results + a, dp);
     });
     // aggregate timing: lanes run concurrently, so spans are maxima and volumes are sums
     timing = q3tts_timing{};
@@ -2819,6 +2862,7 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     outstanding = outstanding || (ctx1_ && ctx1_->job_outstanding());  // (the queued path itself runs on the first context alone)
     Q3_CHECK(!outstanding, 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
     Q3_CHECK(model_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
+    check_row_sampling(sp, n);
     // every request is checked before any GPU work: a bad one late in the queue must not fail after the others were delivered
     std::vector<ResolvedRequest> rr;
     rr.reserve(size_t(n));
@@ -2835,6 +2879,7 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     q.reqs = &rr;
     q.n = n;
     q.row_base = sp.row_base;
+    for (int i = 0; i < n; ++i) q.params.push_back(fold_sampling(sp, i, 0u));  // (a queued slot keys on row_key_, not on row0)
     q.results = results;
     // each lane runs a slot pool of its own; all of them take requests from the one queue
     const int L = int(lanes_.size());

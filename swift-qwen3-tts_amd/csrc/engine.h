@@ -45,6 +45,11 @@ struct ResolvedRequest {
     int ref_off = 0;      // offset of this request's [16][ref_T] codes in ref_codes_dev_
 };
 
+// q3tts_sampling.per_request: the set fields of its n entries are checked on the host, before any GPU work (status 3)
+void check_row_sampling(const q3tts_sampling& sp, int n);
+// request i's parameters as the sampler reads them: the call's values with per_request[i]'s set fields folded in
+SamplingParams fold_sampling(const q3tts_sampling& sp, int i, uint32_t row0);
+
 class CodecRunner;
 class VoiceFrontEnd;
 
@@ -61,6 +66,7 @@ struct QueueShared {
     int n = 0;
     std::atomic<int> next{0};
     uint32_t row_base = 0;
+    std::vector<SamplingParams> params;  // [n] every request's folded sampling parameters (an admission writes them to its slot)
     q3tts_result* results = nullptr;
 };
 
@@ -169,7 +175,7 @@ class Engine {
     int32_t *trailing_idx_ = nullptr, *n_trailing_ = nullptr, *n_prompt_ = nullptr, *cur_codes_ = nullptr, *codes_ = nullptr;
     uint8_t *active_ = nullptr, *finished_ = nullptr, *seen_ = nullptr;
     uint16_t *prompt_ = nullptr, *trailing_ = nullptr, *tts_pad_ = nullptr;
-    SamplingParams* sp_dev_ = nullptr;
+    SamplingParams* sp_dev_ = nullptr;  // [max_batch] row b's sampling parameters (a queued call: slot b's)
     // prompt-assembly scratch
     int32_t* ids_dev_ = nullptr;
     uint16_t *proj_in_ = nullptr, *proj_mid_ = nullptr, *proj_out_ = nullptr;
@@ -310,7 +316,7 @@ class Engine {
     Job* work_ = nullptr;  // the job whose back half the worker takes next
     bool work_stop_ = false;
     void job_timing(Job& J, const std::vector<int>& np, int launched);
-    void upload_sampling(const q3tts_sampling& sp, uint32_t row0);  // sp_dev_ on st_
+    void upload_sampling(const q3tts_sampling& sp, uint32_t row0, int n);  // sp_dev_[0, n) on st_: entry b = fold_sampling(sp, b, row0)
     int64_t kv_bytes(int n_prompt, int frames) const;  // talker KV bytes the frame steps of one row read
     int launches_per_step(int B) const;
     // builds prompt_/trailing_/tts_pad_ for rows [0,n); fills host-side lengths. trailing_rows: row of trailing_ that
@@ -337,6 +343,7 @@ class Engine {
     int32_t *q_bt_ = nullptr, *q_kv_len_ = nullptr, *q_n_prompt_ = nullptr;  // the admitted sub-batch
     uint8_t* q_active_ = nullptr;
     AdmitDesc* q_desc_ = nullptr;
+    std::vector<AdmitDesc> q_desc_host_;
     uint32_t* row_key_ = nullptr;  // [max_batch] random key of every slot
     std::vector<int32_t> q_host_;  // staging of the sub-batch's arrays (alive until the next boundary's sync)
     void ensure_queue_ws();

@@ -148,7 +148,7 @@ struct FrameEndArgs {  // Qwen3.swift:919-935 + loop bookkeeping
 void launch_frame_end(const FrameEndArgs& a, hipStream_t st);
 
 // ---- sampler (sampler.hip) ---------------------------------------------------------------------
-struct SamplingParams {  // lives in device memory so the captured graph does not depend on it
+struct SamplingParams {  // lives in device memory so the captured graph does not depend on it; one entry per row
     float temperature;
     int top_k;
     float top_p;
@@ -161,7 +161,7 @@ struct SamplingParams {  // lives in device memory so the captured graph does no
 struct SamplerArgs {
     const uint16_t* logits;  // [B][ldl]
     int ldl, V;
-    const SamplingParams* sp;
+    const SamplingParams* sp;  // [B] row b's parameters (mask_eos and row0 are the same in every entry of a call)
     int is_talker;           // 1: suppress range + repetition penalty + EOS handling; 0: plain (code predictor)
     int suppress_lo, suppress_hi, eos_id;
     uint8_t* seen;           // [B][V] (talker only)
@@ -191,7 +191,7 @@ struct SamplerArgs {
     int B;
     uint16_t* logits_dump;   // [B][forced_frames][dump_ld] (tests) or nullptr
     int dump_ld, dump_off;
-    const uint32_t* row_key; // [B] random stream of row b (queued slots: the request's global index), or nullptr: sp->row0 + b
+    const uint32_t* row_key; // [B] random stream of row b (queued slots: the request's global index), or nullptr: sp[b].row0 + b
 };
 void launch_sampler(const SamplerArgs& a, hipStream_t st);
 // The frame's last draw with its row's end-of-frame job riding along (kernels/row_jobs.h frame_end_job): the sampler is that
@@ -229,12 +229,14 @@ void launch_prefill_chunk_load(const PrefillLoadArgs& a, int C, hipStream_t st);
 void launch_advance_len_chunk(int32_t* kv_len, const int32_t* n_prompt, int r_base, int C, int B, hipStream_t st);
 
 // Continuous batching (Engine::run_queued): row j of a prefilled sub-batch moves into frame-step row (slot) desc[j].slot --
-// its last prompt position's input row and that row's sum of squares, its cache length and lengths, its random key -- and
+// its last prompt position's input row and that row's sum of squares, its cache length and lengths, its random key, its
+// sampling parameters (the whole entry, so nothing of the slot's previous occupant is left) -- and
 // the slot's per-row loop state is reset (frame count, predictor cache length, trailing-text index, codes in flight,
 // repetition flags, code history; finished = 0, active = 1). One workgroup per admitted row.
 struct AdmitDesc {
     int32_t slot, n_trailing, max_frames;
     uint32_t row_key;
+    SamplingParams sp;  // the request's parameters: the call's with its own overrides folded in
 };
 struct AdmitArgs {
     const AdmitDesc* desc;     // [k]
@@ -249,6 +251,7 @@ struct AdmitArgs {
     int H, V, Fmax, slots;
     int32_t *kv_len, *n_prompt, *n_trailing, *max_frames, *n_frames, *cp_len, *trailing_idx, *cur_codes, *codes;
     uint32_t* row_key;
+    SamplingParams* sp;        // [slots] the frame step's per-row sampling parameters
     uint8_t *finished, *active, *seen;
 };
 void launch_admit_rows(const AdmitArgs& a, int k, hipStream_t st);

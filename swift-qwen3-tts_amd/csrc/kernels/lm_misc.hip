@@ -182,6 +182,7 @@ __global__ __launch_bounds__(256) void admit_rows_kernel(AdmitArgs a) {
         a.n_trailing[s] = d.n_trailing;
         a.max_frames[s] = d.max_frames;
         a.row_key[s] = d.row_key;
+        a.sp[s] = d.sp;
         a.n_frames[s] = 0;
         a.cp_len[s] = 0;
         a.trailing_idx[s] = 0;

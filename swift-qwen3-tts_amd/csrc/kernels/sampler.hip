@@ -188,7 +188,7 @@ __device__ __forceinline__ void sampler_body(const SamplerArgs& a, const FrameEn
         raw[k] = lrow[ic];
         was_seen[k] = want_seen ? a.seen[(size_t)b * V + ic] : (uint8_t)0;
     }
-    const SamplingParams sp = *a.sp;
+    const SamplingParams sp = a.sp[b];  // the row's own parameters: block-uniform, a scalar load issued with the operands above
     const bool row_done = a.finished[b] != 0;
     const int frame = a.n_frames[b];
     // (read from an address that is always valid, with the other operands: under a branch on the pointer this byte was a
@@ -333,17 +333,38 @@ __device__ __forceinline__ void sampler_body(const SamplerArgs& a, const FrameEn
                 __syncthreads();
             }
         }
-        // ---- 6: top-p (rare path): ascending sort, sequential cumulative sum like the oracle ----
+        // ---- 6: top-p: ascending sort, sequential cumulative sum like the oracle, over the finite elements only ----
+        // One row of a batch may ask for top-p while the others do not, and the launch lasts as long as its slowest workgroup,
+        // so the work here follows the number of elements that are still finite (top_k of them; all V with top-k off)
+        // instead of kMaxV. Exact, because of what the full-width form did with the others: an element at -inf has the
+        // smallest key of all finite-or-infinite values, adds rbf(exp(-inf)) = +0 to the running sum ahead of every finite
+        // element, and is "cut" to -inf again (thr > 0 whenever use_top_p holds); the keys (key16 << 16 | index) are unique, so
+        // the finite elements come out of a sort of their own in the order they had among all kMaxV.
+        // NaN logits (a damaged checkpoint) take this path too and agree with the full-width form: a NaN is != -inf and is
+        // compacted; one with the sign bit set sorts ahead of -inf there and first here, and from it on the running sum is NaN
+        // in both forms (NaN + 0 = NaN), which cuts every element behind it; one with the sign bit clear sorts behind +inf
+        // in both forms. Between them the -inf elements only ever add +0.
         if (use_top_p) {
+            const int lane = tid & 63;
 #pragma unroll
-            for (int k = 0; k < kElems; ++k) {
+            for (int k = 0; k < kElems; ++k) {  // compaction, one LDS atomic per wave and slice
                 const int i = k * kThreads + tid;
-                sortbuf[i] = (i < V) ? ((key16(l[k]) << 16) | (uint32_t)i) : 0xffffffffu;
+                const bool keep = i < V && l[k] != -INFINITY;
+                const unsigned long long bal = __ballot(keep);
+                int base = 0;
+                if (lane == 0 && bal) base = atomicAdd(&n_surv, __popcll(bal));
+                base = __shfl(base, 0, 64);
+                if (keep) sortbuf[base + __popcll(bal & ((1ull << lane) - 1ull))] = (key16(l[k]) << 16) | (uint32_t)i;
             }
             __syncthreads();
-            for (int size = 2; size <= kMaxV; size <<= 1) {
+            const int nf = n_surv;
+            int P = 2;  // the sort's width: the next power of two at or above nf (<= kMaxV, since nf <= V <= kMaxV)
+            while (P < nf) P <<= 1;
+            for (int q = nf + tid; q < P; q += kThreads) sortbuf[q] = 0xffffffffu;
+            __syncthreads();
+            for (int size = 2; size <= P; size <<= 1) {
                 for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                    for (int t = tid; t < kMaxV / 2; t += kThreads) {
+                    for (int t = tid; t < P / 2; t += kThreads) {
                         const int lo = 2 * t - (t & (stride - 1));
                         const int hi = lo + stride;
                         const bool up = ((lo & size) == 0);
@@ -356,14 +377,17 @@ __device__ __forceinline__ void sampler_body(const SamplerArgs& a, const FrameEn
                     __syncthreads();
                 }
             }
+            // the terms of the sum, by all threads (sval is free until the categorical stage); the sum itself stays sequential
+            for (int r = tid; r < nf; r += kThreads) sval[r] = rbf(q3_expf(vals[sortbuf[r] & 0xffffu]));
+            __syncthreads();
             if (tid == 0) {
                 const float thr = rbf(1.0f - sp.top_p);
                 float run = 0.f;
-                for (int r = 0; r < V; ++r) {
-                    const int i = (int)(sortbuf[r] & 0xffffu);
-                    run += rbf(q3_expf(vals[i]));
-                    if (!(rbf(run) > thr)) vals[i] = -INFINITY;
+                for (int r = 0; r < nf; ++r) {
+                    run += sval[r];
+                    if (!(rbf(run) > thr)) vals[sortbuf[r] & 0xffffu] = -INFINITY;
                 }
+                n_surv = 0;  // the categorical stage below compacts what is left
             }
             __syncthreads();
 #pragma unroll

@@ -44,10 +44,19 @@ class Request(C.Structure):
                 ("n_ref_text_ids", C.c_int32), ("route", C.c_int32)]
 
 
+ROW_TEMPERATURE, ROW_TOP_K, ROW_TOP_P, ROW_REPETITION_PENALTY, ROW_SEED = 1, 2, 4, 8, 16  # q3tts_row_sampling.set
+
+
+class RowSampling(C.Structure):  # q3tts_row_sampling
+    _fields_ = [("set", C.c_uint32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("repetition_penalty", C.c_float), ("seed", C.c_uint64)]
+
+
 class Sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
                 ("repetition_penalty", C.c_float), ("seed", C.c_uint64), ("force_frames", C.c_int32), ("audio_chunk_frames", C.c_int32),
-                ("audio_window_frames", C.c_int32), ("audio_lookahead_frames", C.c_int32), ("row_base", C.c_uint32)]
+                ("audio_window_frames", C.c_int32), ("audio_lookahead_frames", C.c_int32), ("row_base", C.c_uint32),
+                ("per_request", C.POINTER(RowSampling))]
 
 
 class GenInfo(C.Structure):

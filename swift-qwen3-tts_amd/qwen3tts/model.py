@@ -46,6 +46,17 @@ class AudioGenerationInfo:  # GenerationTypes.swift:15-21
 
 
 @dataclass
+class RequestSampling:
+    """Sampling parameters of one request of a call (q3tts_row_sampling): a field that is None inherits the call's value.
+    A seed replaces the seed of the request's random stream; the stream's key (row_base + request index) stays."""
+    temperature: Optional[float] = None
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    repetition_penalty: Optional[float] = None
+    seed: Optional[int] = None
+
+
+@dataclass
 class GenerationRequest:
     """One utterance after tokenisation (see q3tts_request in include/q3tts.h)."""
     text_ids: Sequence[int]
@@ -60,6 +71,8 @@ class GenerationRequest:
     ref_text_ids: Optional[Sequence[int]] = None
     # 0: generate() (routed by tts_model_type); 1 / 2: generateVoiceDesign / generateCustomVoice called directly (q3tts.h)
     route: int = 0
+    # this request's own sampling parameters (None: the call's); a static batch or a queue may mix them freely
+    sampling: Optional[RequestSampling] = None
 
 
 @dataclass
@@ -229,9 +242,32 @@ class Qwen3TTSModel:
         return arr, keep
 
     @staticmethod
-    def _sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames=0,
-                  audio_window_frames=0, audio_lookahead_frames=4, row_base=0) -> L.Sampling:
+    def _row_sampling(rows: Sequence[Optional[RequestSampling]]):
+        """The q3tts_row_sampling array of a call, or None when no request carries parameters of its own."""
+        if not any(r is not None for r in rows):
+            return None
+        arr = (L.RowSampling * len(rows))()
+        for i, r in enumerate(rows):
+            if r is None:
+                continue
+            for bit, name in ((L.ROW_TEMPERATURE, "temperature"), (L.ROW_TOP_K, "top_k"), (L.ROW_TOP_P, "top_p"),
+                              (L.ROW_REPETITION_PENALTY, "repetition_penalty"), (L.ROW_SEED, "seed")):
+                v = getattr(r, name)
+                if v is not None:
+                    arr[i].set |= bit
+                    setattr(arr[i], name, v)
+        return arr
+
+    @classmethod
+    def _sampling(cls, temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames=0,
+                  audio_window_frames=0, audio_lookahead_frames=4, row_base=0, reqs=None) -> L.Sampling:
+        """`reqs`: the call's requests; their `sampling` fields become per_request (the array rides on the returned struct,
+        which therefore has to stay alive for as long as the library reads it: the call, or begin)."""
         s = L.Sampling()
+        rows = cls._row_sampling([getattr(r, "sampling", None) for r in reqs]) if reqs is not None else None
+        if rows is not None:
+            s._rows = rows
+            s.per_request = C.cast(rows, C.POINTER(L.RowSampling))
         s.temperature, s.top_k, s.top_p = temperature, top_k, top_p
         s.repetition_penalty, s.seed, s.force_frames = repetition_penalty, seed, force_frames
         s.audio_chunk_frames = audio_chunk_frames
@@ -252,7 +288,7 @@ class Qwen3TTSModel:
         pre-transformer then sees a sliding window; the waveform is within a stated tolerance of the one-shot decode)."""
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
-                           audio_window_frames, audio_lookahead_frames, row_base)
+                           audio_window_frames, audio_lookahead_frames, row_base, reqs=reqs)
         cb = self._event_cb(on_event)
         res = (L.Result * len(reqs))()
         st = self._lib.q3tts_generate(self._h, arr, len(reqs), C.byref(s), cb, None, res)
@@ -273,7 +309,7 @@ class Qwen3TTSModel:
         audio_chunk_frames > 0 without a window (audio_window_frames == 0) or below the decoder's history."""
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
-                           audio_window_frames, audio_lookahead_frames, row_base)
+                           audio_window_frames, audio_lookahead_frames, row_base, reqs=reqs)
         cb = self._event_cb(on_event)
         res = (L.Result * len(reqs))()
         n_slots = int(self.info.max_batch) if slots is None else int(slots)
@@ -337,12 +373,13 @@ class Qwen3TTSModel:
         more_follows=False (the last batch of a queue) lets the decode use the whole chip instead of leaving room for a
         next batch."""
         arr, keep = self._marshal(reqs)
-        s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames, row_base=row_base)
+        s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames, row_base=row_base,
+                           reqs=reqs)
         cb = self._event_cb(on_event)
         job = C.c_void_p()
         self._check(self._lib.q3tts_generate_begin(self._h, arr, len(reqs), C.byref(s), cb, None, 1 if more_follows else 0,
                                                    C.byref(job)))
-        del keep  # request memory is only read during begin
+        del keep, s  # request memory and the per-request sampling array are only read during begin
         return (job, len(reqs), cb)  # the callback object must outlive the job (INFO / AUDIO fire in end)
 
     def generate_batch_end(self, job) -> List[GenerationResult]:
@@ -524,7 +561,7 @@ class Qwen3TTSModel:
         return ie[: n1.value].copy(), tr[: n2.value].copy(), pad
 
     def debug_generate_forced(self, reqs: Sequence[GenerationRequest], forced_codes: np.ndarray, temperature=0.0,
-                              top_k=50, top_p=1.0, repetition_penalty=1.05, seed=0):
+                              top_k=50, top_p=1.0, repetition_penalty=1.05, seed=0, row_base=0):
         arr, keep = self._marshal(reqs)
         n = len(reqs)
         forced = np.ascontiguousarray(forced_codes, np.int32).reshape(n, -1, 16)
@@ -533,7 +570,7 @@ class Qwen3TTSModel:
         tl = np.zeros((n, F, V), np.uint16)
         cl = np.zeros((n, F, G - 1, Vc), np.uint16)
         sampled = np.zeros((n, F, 16), np.int32)
-        s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, 0)
+        s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, 0, row_base=row_base, reqs=reqs)
         self._check(self._lib.q3tts_debug_generate_forced(
             self._h, arr, n, C.byref(s), forced.ctypes.data_as(L.i32p), F, tl.ctypes.data_as(L.u16p),
             cl.ctypes.data_as(L.u16p), sampled.ctypes.data_as(L.i32p)))
@@ -542,10 +579,16 @@ class Qwen3TTSModel:
 
     def debug_sample(self, logits: np.ndarray, temperature=0.9, top_k=50, top_p=1.0, repetition_penalty=1.0,
                      seed=0, seen: Optional[np.ndarray] = None, suppress=(0, 0), eos_id=-1, row0=0, draw=0,
-                     mask_eos=False):
+                     mask_eos=False, per_row: Optional[Sequence[Optional[RequestSampling]]] = None):
+        """`per_row`: one RequestSampling (or None) per row of `logits`, folded into the keywords like a request's."""
         logits = np.ascontiguousarray(logits, np.uint16)
         rows, V = logits.shape
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, 1 if mask_eos else 0)
+        if per_row is not None:
+            assert len(per_row) == rows
+            s._rows = self._row_sampling(per_row)
+            if s._rows is not None:
+                s.per_request = C.cast(s._rows, C.POINTER(L.RowSampling))
         toks = np.zeros(rows, np.int32)
         sp = np.ascontiguousarray(seen, np.uint8).ctypes.data_as(L.u8p) if seen is not None else None
         self._check(self._lib.q3tts_debug_sample(self._h, logits.ctypes.data_as(L.u16p), rows, V, C.byref(s), sp,

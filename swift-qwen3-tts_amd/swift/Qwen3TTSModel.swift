@@ -64,10 +64,29 @@ public enum AudioGeneration: Sendable {   // GenerationTypes.swift:51-58
 public typealias Qwen3TTSGeneration = AudioGeneration
 
 /// One row of `generateBatch`: the arguments of `generate` that differ per utterance.
+/// Sampling parameters of one request of a batch (q3tts_row_sampling): nil inherits the call's value.
+public struct Qwen3TTSRequestSampling: Sendable {
+    public var temperature: Float?, topK: Int?, topP: Float?, repetitionPenalty: Float?, seed: UInt64?
+    public init(temperature: Float? = nil, topK: Int? = nil, topP: Float? = nil, repetitionPenalty: Float? = nil, seed: UInt64? = nil) {
+        self.temperature = temperature; self.topK = topK; self.topP = topP; self.repetitionPenalty = repetitionPenalty; self.seed = seed
+    }
+    var row: q3tts_row_sampling {
+        var r = q3tts_row_sampling()
+        if let v = temperature { r.set |= UInt32(Q3TTS_ROW_TEMPERATURE); r.temperature = v }
+        if let v = topK { r.set |= UInt32(Q3TTS_ROW_TOP_K); r.top_k = Int32(v) }
+        if let v = topP { r.set |= UInt32(Q3TTS_ROW_TOP_P); r.top_p = v }
+        if let v = repetitionPenalty { r.set |= UInt32(Q3TTS_ROW_REPETITION_PENALTY); r.repetition_penalty = v }
+        if let v = seed { r.set |= UInt32(Q3TTS_ROW_SEED); r.seed = v }
+        return r
+    }
+}
+
 public struct Qwen3TTSBatchRequest: Sendable {
     public var text: String, speaker: String?, instruct: String?, language: String
-    public init(text: String, speaker: String? = nil, instruct: String? = nil, language: String = "auto") {
-        self.text = text; self.speaker = speaker; self.instruct = instruct; self.language = language
+    public var sampling: Qwen3TTSRequestSampling?  // this request's own parameters (nil: the call's)
+    public init(text: String, speaker: String? = nil, instruct: String? = nil, language: String = "auto",
+                sampling: Qwen3TTSRequestSampling? = nil) {
+        self.text = text; self.speaker = speaker; self.instruct = instruct; self.language = language; self.sampling = sampling
     }
 }
 
@@ -223,7 +242,12 @@ public final class Qwen3TTSModel {
         sampling.repetition_penalty = repetitionPenalty; sampling.seed = seed
         var results = [q3tts_result](repeating: q3tts_result(), count: n)
         defer { q3tts_result_free(&results, Int32(n)) }
-        let st = q3tts_generate(handle, &reqs, Int32(n), &sampling, nil, nil, &results)
+        // per-request parameters: an entry with set == 0 inherits everything; the array is only read during the call
+        let rows = requests.map { $0.sampling?.row ?? q3tts_row_sampling() }
+        let st = rows.withUnsafeBufferPointer { rp -> q3tts_status in
+            if requests.contains(where: { $0.sampling != nil }) { sampling.per_request = rp.baseAddress }
+            return q3tts_generate(handle, &reqs, Int32(n), &sampling, nil, nil, &results)
+        }
         guard st == Q3TTS_OK else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
         return results.map { $0.status == Q3TTS_OK ? Array(UnsafeBufferPointer(start: $0.pcm, count: Int($0.n_samples))) : nil }
     }

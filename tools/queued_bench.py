@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Continuous batching against static batches.
 
-  python tools/queued_bench.py [--preset 1.7b] [--slots 32] [--requests 256] [--stream CHUNK,WINDOW,LOOKAHEAD]
+  python tools/queued_bench.py [--preset 1.7b] [--slots 32] [--requests 256] [--stream CHUNK,WINDOW,LOOKAHEAD] [--mixed-sampling]
 
 Two workloads on bench.py's synthetic checkpoint and request builder:
   ragged   max_tokens uniform in 50..400 (seeded), temperature 0.9, seed 1234: rows end at their caps (or EOS) at different frames
@@ -15,6 +15,9 @@ prefill and codec milliseconds, and whether every request's codes and PCM are bi
 audio_lookahead_frames) next to the same run without it, both with an event callback: frames/s of each, and per request the time
 from its admission to its first AUDIO_CHUNK (streamed) or to its AUDIO (not streamed), median and worst. A request's admission is
 its last TOKEN's arrival (the burst boundary that retired it) minus its generate_time (admission -> retirement).
+--mixed-sampling gives the ragged workload's requests parameters of their own (q3tts_sampling.per_request), four sets in turn:
+the call's, greedy, top-k 20 / top-p 0.9 / T 0.7 with a seed, and repetition penalty 1.5; static and queued must still agree bit
+for bit, and the queue's rows now include top-p rows beside the others in every frame step.
 """
 from __future__ import annotations
 
@@ -89,9 +92,10 @@ def main():
     ap.add_argument("--slots", type=int, default=32)
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--n-text", type=int, default=32)
+    ap.add_argument("--mixed-sampling", action="store_true", help="ragged workload: four per-request parameter sets in turn")
     ap.add_argument("--stream", default=None, metavar="CHUNK,WINDOW,LOOKAHEAD", help="also run the ragged queue with streamed audio")
     args = ap.parse_args()
-    from qwen3tts import Qwen3TTSModel
+    from qwen3tts import Qwen3TTSModel, RequestSampling
 
     ckpt = bench.ensure_checkpoint(args.preset, 0, None)
     model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=128)
@@ -103,6 +107,11 @@ def main():
     for r, c in zip(base, caps):
         # max_tokens is the cap; target_token_count only lifts the max(75, 6 x target) floor above it (Qwen3.swift:822-823)
         ragged.append(type(r)(r.text_ids, 100, r.instruct_ids, r.speaker, r.language, int(c)))
+    if args.mixed_sampling:
+        sets = [None, RequestSampling(temperature=0.0), RequestSampling(temperature=0.7, top_k=20, top_p=0.9, seed=99),
+                RequestSampling(repetition_penalty=1.5)]
+        for i, r in enumerate(ragged):
+            r.sampling = sets[i % 4]
     sampling = dict(temperature=0.9, top_k=50, top_p=1.0, repetition_penalty=1.05, seed=1234)
     workloads = [("ragged", ragged, dict(sampling)), ("uniform", base, dict(sampling, force_frames=200))]
 

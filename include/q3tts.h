@@ -339,6 +339,50 @@ q3tts_status q3tts_generate_end(q3tts_model* m, q3tts_job* job, q3tts_result* re
 q3tts_status q3tts_generate_queued(q3tts_model* m, const q3tts_request* reqs, int32_t n_reqs, int32_t slots,
                                    const q3tts_sampling* sampling, q3tts_event_cb cb, void* user, q3tts_result* results);
 
+/* Reusable voice prompts (new: the reference encodes the clip inside every generateVoiceClone call, Qwen3.swift:436-444,
+ * 521-525). A voice is one reference clip and its transcript, encoded ONCE and held on the device: what a voice-clone request
+ * needs from its reference -- the 16 code rows of the clip, the prompt rows made of them (the speaker x-vector and one embedding
+ * sum per reference frame) -- plus host copies of the codes and of the reference text. Requests then name it, and a request that
+ * does costs no more to admit than an ordinary one: no upload, no codec encoder, no speaker encoder, no copy back to the host.
+ * That is what lets q3tts_generate_queued_voices serve voice-clone requests, which q3tts_generate_queued refuses.
+ *   q3tts_voice_create: ref_audio / ref_text_ids as in q3tts_request, with every check a voice-clone request gets (status 1
+ *     without the speech tokenizer encoder; 3 for an empty clip, a non-finite sample, fewer than 5 or out-of-range reference-text
+ *     ids, an encoder codebook beyond the embedding tables). It synchronises before it returns; from then on the voice is read-only
+ *     and may be named by any number of requests, in any call on this handle, whichever job context, lane or slot serves them.
+ *     Like the other entry points that work on one engine it uses the first context and waits for a background AR loop on it.
+ *     q3tts_last_timing afterwards: frontend_ms of this clip.
+ *   q3tts_voice_free: releases the voice's buffers. Freeing a voice while a call that names it is running (a q3tts_generate_begin
+ *     job included, until its end) is a caller error. q3tts_model_free releases the voices still alive; their pointers are dead
+ *     after it.
+ *   q3tts_voice_get_info: device_bytes = 64 * ref_frames (codes) + 2 * hidden_size * (1 + ref_frames) (prompt rows).
+ * voices[i] == NULL: request i is what it is without this argument (q3tts_generate_voices with every entry NULL behaves as
+ * q3tts_generate). voices[i] != NULL: request i is a voice-clone request whose reference is that voice; speaker, instruct_ids
+ * and route are ignored, as for ref_audio.
+ * For both entry points results[i] is bit-identical -- status, codes, pcm, n_frames, n_samples -- to what q3tts_generate returns
+ * for reqs[i] alone with ref_audio / ref_text_ids set to the voice's clip and text, the call's sampling with per_request[i]
+ * folded in and row_base = sampling->row_base + i, whatever slot, lane, admission burst or decode batch serves it.
+ * q3tts_last_timing.frontend_ms is 0 for a call whose clone rows are all voices. Events and everything else as
+ * q3tts_generate / q3tts_generate_queued.
+ * Refused with Q3TTS_ERR_INVALID_INPUT before any GPU work, the engine staying usable: a voice created on another model handle
+ * (or already freed); a voice together with ref_audio or ref_text_ids on the same request; an ICL prompt longer than max_prompt
+ * (the queue computes the length in its pre-flight check); and for q3tts_generate_queued_voices also audio_chunk_frames > 0 with
+ * any non-NULL voice (streamed audio for voice rows is not built) and a request that carries ref_audio (as q3tts_generate_queued).
+ * q3tts_generate_voices with the streaming fields set treats voice rows as it treats ref_audio rows. */
+typedef struct q3tts_voice q3tts_voice;
+q3tts_status q3tts_voice_create(q3tts_model* m, const float* ref_audio, int64_t n_ref_samples, const int32_t* ref_text_ids,
+                                int32_t n_ref_text_ids, q3tts_voice** out);
+void q3tts_voice_free(q3tts_model* m, q3tts_voice* v);
+typedef struct {
+    int32_t ref_frames, ref_text_tokens;
+    int64_t n_ref_samples, device_bytes;
+} q3tts_voice_info;
+q3tts_status q3tts_voice_get_info(const q3tts_voice* v, q3tts_voice_info* out);
+q3tts_status q3tts_generate_voices(q3tts_model* m, const q3tts_request* reqs, const q3tts_voice* const* voices, int32_t n_reqs,
+                                   const q3tts_sampling* sampling, q3tts_event_cb cb, void* user, q3tts_result* results);
+q3tts_status q3tts_generate_queued_voices(q3tts_model* m, const q3tts_request* reqs, const q3tts_voice* const* voices,
+                                          int32_t n_reqs, int32_t slots, const q3tts_sampling* sampling, q3tts_event_cb cb,
+                                          void* user, q3tts_result* results);
+
 /* Qwen3TTSSpeechTokenizer.decode (Models/SpeechTokenizer.swift:823-836): codes
  * [batch][max_frames][num_code_groups] -> pcm [batch][max_frames*1920] (caller-allocated),
  * audio_lengths[batch] = count(code0 > 0) * 1920. n_frames[b] <= max_frames are the valid rows. Every code of a valid row is
@@ -484,6 +528,17 @@ q3tts_status q3tts_debug_codec_stage(q3tts_model* m, const int32_t* codes, int32
 q3tts_status q3tts_debug_codec_stream_slots(q3tts_model* m, const int32_t* codes, const int32_t* n_frames, int32_t n_reqs,
                                             int32_t max_frames, int32_t slots, int32_t burst, int32_t chunk_frames, int32_t window,
                                             int32_t lookahead, float* pcm);
+
+/* build_decode_codes_rows (the one launch that writes the decoder's input [reference ++ generated] for every row of a decode
+ * batch) on caller-supplied rows, through the product's launcher. refs: the rows' reference codes one after the other, row r's
+ * as [16][ref_T[r]] (ref_T[r] == 0: a row without a reference); gen [R][gen_stride][16] with n_frames[r] <= gen_stride valid
+ * frames; out [R][Fdec][16] is uploaded as the caller filled it and comes back whole, so a caller sees what was and was not
+ * written (a row with n_frames[r] == 0 writes nothing). misalign != 0 places gen and out 4 bytes off a 16-byte boundary on the
+ * device, which takes the launch through its 4-byte loads and stores. ref_T[r] + n_frames[r] > Fdec is Q3TTS_ERR_DEVICE
+ * (the launcher's own bounds check). */
+q3tts_status q3tts_debug_build_decode_codes(q3tts_model* m, const int32_t* refs, const int32_t* ref_T, const int32_t* gen,
+                                            const int32_t* n_frames, int32_t R, int32_t gen_stride, int32_t Fdec, int32_t misalign,
+                                            int32_t* out);
 
 /* Activation scratch the codec decoder may use per pass (default 24 GB; 0 restores it): a small value forces the paths that
  * take a large batch through in groups of rows. Process-wide. */

@@ -49,6 +49,10 @@ struct HandleUse {  // the handle's one-caller-at-a-time contract (struct q3tts_
     }
 };
 
+// q3tts_voice is q3::Voice behind the boundary
+q3::Voice* voice_of(q3tts_voice* v) { return reinterpret_cast<q3::Voice*>(v); }
+const q3::Voice* voice_of(const q3tts_voice* v) { return reinterpret_cast<const q3::Voice*>(v); }
+
 template <class F>
 q3tts_status guarded(q3tts_model* m, F&& f) {
     HandleUse use(m);
@@ -204,34 +208,70 @@ const char* q3tts_model_speaker_name(const q3tts_model* m, int32_t i) {
     return m->eng->speakers[size_t(i)].c_str();
 }
 
-q3tts_status q3tts_generate(q3tts_model* m, const q3tts_request* reqs, int32_t n_reqs, const q3tts_sampling* sampling,
-                            q3tts_event_cb cb, void* user, q3tts_result* results) {
+// q3tts_generate / _queued (slots < 0: the static path) with or without a voice per request
+static q3tts_status generate_any(q3tts_model* m, const q3tts_request* reqs, const q3tts_voice* const* voices, bool with_voices,
+                                 int32_t n_reqs, int32_t slots, const q3tts_sampling* sampling, q3tts_event_cb cb, void* user,
+                                 q3tts_result* results) {
     return guarded(m, [&] {
-        Q3_CHECK(m && reqs && results, 3, "Invalid input: null argument");
+        Q3_CHECK(m && reqs && results && (voices || !with_voices), 3, "Invalid input: null argument");
         q3tts_sampling sp;
         if (sampling) sp = *sampling;
         else q3tts_default_sampling(&sp);
         std::memset(results, 0, sizeof(q3tts_result) * size_t(n_reqs > 0 ? n_reqs : 0));
-        m->eng->generate(reqs, n_reqs, sp, cb, user, results, nullptr);
+        std::vector<const q3::Voice*> vs;
+        for (int i = 0; with_voices && i < n_reqs; ++i) vs.push_back(voice_of(voices[i]));
+        const q3::Voice* const* vp = with_voices ? vs.data() : nullptr;
+        if (slots < 0) m->eng->generate(reqs, n_reqs, sp, cb, user, results, nullptr, vp);
+        else m->eng->generate_queued(reqs, n_reqs, slots, sp, cb, user, results, vp);
         for (int i = 0; i < n_reqs; ++i)
             if (results[i].status == Q3TTS_ERR_GENERATION_FAILED)
                 m->eng->last_error = "Generation failed: No tokens generated";  // Qwen3.swift:940
     });
 }
 
+q3tts_status q3tts_generate(q3tts_model* m, const q3tts_request* reqs, int32_t n_reqs, const q3tts_sampling* sampling,
+                            q3tts_event_cb cb, void* user, q3tts_result* results) {
+    return generate_any(m, reqs, nullptr, false, n_reqs, -1, sampling, cb, user, results);
+}
+
 q3tts_status q3tts_generate_queued(q3tts_model* m, const q3tts_request* reqs, int32_t n_reqs, int32_t slots,
                                    const q3tts_sampling* sampling, q3tts_event_cb cb, void* user, q3tts_result* results) {
+    return generate_any(m, reqs, nullptr, false, n_reqs, slots < 0 ? 0 : slots, sampling, cb, user, results);
+}
+
+q3tts_status q3tts_voice_create(q3tts_model* m, const float* ref_audio, int64_t n_ref_samples, const int32_t* ref_text_ids,
+                                int32_t n_ref_text_ids, q3tts_voice** out) {
+    if (out) *out = nullptr;
     return guarded(m, [&] {
-        Q3_CHECK(m && reqs && results, 3, "Invalid input: null argument");
-        q3tts_sampling sp;
-        if (sampling) sp = *sampling;
-        else q3tts_default_sampling(&sp);
-        std::memset(results, 0, sizeof(q3tts_result) * size_t(n_reqs > 0 ? n_reqs : 0));
-        m->eng->generate_queued(reqs, n_reqs, slots, sp, cb, user, results);
-        for (int i = 0; i < n_reqs; ++i)
-            if (results[i].status == Q3TTS_ERR_GENERATION_FAILED)
-                m->eng->last_error = "Generation failed: No tokens generated";  // Qwen3.swift:940
+        Q3_CHECK(m && out, 3, "Invalid input: null argument");
+        *out = reinterpret_cast<q3tts_voice*>(m->eng->create_voice(ref_audio, n_ref_samples, ref_text_ids, n_ref_text_ids));
     });
+}
+
+void q3tts_voice_free(q3tts_model* m, q3tts_voice* v) {
+    if (!m || !v) return;
+    (void)guarded(m, [&] { m->eng->free_voice(voice_of(v)); });
+}
+
+q3tts_status q3tts_voice_get_info(const q3tts_voice* v, q3tts_voice_info* out) {
+    if (!v || !out) return Q3TTS_ERR_INVALID_INPUT;
+    const q3::Voice& x = *voice_of(v);
+    out->ref_frames = x.ref_T;
+    out->ref_text_tokens = int32_t(x.ref_text_ids.size());
+    out->n_ref_samples = x.n_ref_samples;
+    out->device_bytes = x.device_bytes;
+    return Q3TTS_OK;
+}
+
+q3tts_status q3tts_generate_voices(q3tts_model* m, const q3tts_request* reqs, const q3tts_voice* const* voices, int32_t n_reqs,
+                                   const q3tts_sampling* sampling, q3tts_event_cb cb, void* user, q3tts_result* results) {
+    return generate_any(m, reqs, voices, true, n_reqs, -1, sampling, cb, user, results);
+}
+
+q3tts_status q3tts_generate_queued_voices(q3tts_model* m, const q3tts_request* reqs, const q3tts_voice* const* voices, int32_t n_reqs,
+                                          int32_t slots, const q3tts_sampling* sampling, q3tts_event_cb cb, void* user,
+                                          q3tts_result* results) {
+    return generate_any(m, reqs, voices, true, n_reqs, slots < 0 ? 0 : slots, sampling, cb, user, results);
 }
 
 struct q3tts_job {
@@ -443,6 +483,15 @@ q3tts_status q3tts_debug_codec_stream_slots(q3tts_model* m, const int32_t* codes
     return guarded(m, [&] {
         Q3_CHECK(m && codes && n_frames && pcm, 3, "Invalid input: null argument");
         m->eng->lane0().debug_codec_stream_slots(codes, n_frames, n_reqs, max_frames, slots, burst, chunk_frames, window, lookahead, pcm);
+    });
+}
+
+q3tts_status q3tts_debug_build_decode_codes(q3tts_model* m, const int32_t* refs, const int32_t* ref_T, const int32_t* gen,
+                                            const int32_t* n_frames, int32_t R, int32_t gen_stride, int32_t Fdec, int32_t misalign,
+                                            int32_t* out) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && ref_T && gen && n_frames && out && R >= 1 && gen_stride >= 1 && Fdec >= 1, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_build_decode_codes(refs, ref_T, gen, n_frames, R, gen_stride, Fdec, misalign != 0, out);
     });
 }
 

@@ -571,7 +571,21 @@ hipGraphExec_t Engine::frame_graph(int B) {
 // ------------------------------------------------------------------------------------------------
 // request resolution: routing and validation of generate() (Qwen3.swift:1291-1373, 803-811, 303-319)
 // ------------------------------------------------------------------------------------------------
-ResolvedRequest Engine::resolve(const q3tts_request& r, const q3tts_sampling& sp) const {
+void Engine::check_reference(const float* ref_audio, int64_t n_ref_samples, const int32_t* ref_text_ids, int n_ref_text_ids) const {
+    Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");  // Qwen3.swift:1029-1031
+    Q3_CHECK(m_->has_codec_encoder, 1,
+             "Model not initialized: Voice cloning (ICL mode) requires the speech tokenizer encoder. Make sure to load a model "
+             "with encoder weights.");  // :1033-1038
+    Q3_CHECK(ref_audio && n_ref_samples > 0, 3, "Invalid input: reference audio is empty");
+    {   // a NaN sample would spread through the encoders into every logit of the row
+        bool finite = true;
+        for (int64_t i = 0; i < n_ref_samples; ++i) finite = finite && (std::fabs(ref_audio[i]) <= 3.0e38f);
+        Q3_CHECK(finite, 3, "Invalid input: reference audio holds non-finite samples");
+    }
+    Q3_CHECK(ref_text_ids && n_ref_text_ids >= 5, 3, "Invalid input: ref_text_ids must hold the chat-template tokens");
+}
+
+ResolvedRequest Engine::resolve(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice) const {
     const ModelConfig& cfg = m_->cfg;
     const TalkerConfig& t = cfg.talker;
     ResolvedRequest o;
@@ -586,25 +600,22 @@ ResolvedRequest Engine::resolve(const q3tts_request& r, const q3tts_sampling& sp
         return s;
     };
     bool use_speaker = false, use_instruct = false;
-    if (r.ref_audio != nullptr) {  // generateVoiceClone (Qwen3.swift:1009-1046): no routing by model type, no speaker/instruct
-        Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");  // :1029-1031
-        Q3_CHECK(m_->has_codec_encoder, 1,
-                 "Model not initialized: Voice cloning (ICL mode) requires the speech tokenizer encoder. Make sure to load a model "
-                 "with encoder weights.");  // :1033-1038
-        Q3_CHECK(r.n_ref_samples > 0, 3, "Invalid input: reference audio is empty");
-        {   // a NaN sample would spread through the encoders into every logit of the row
-            bool finite = true;
-            for (int64_t i = 0; i < int64_t(r.n_ref_samples); ++i) finite = finite && (std::fabs(r.ref_audio[i]) <= 3.0e38f);
-            Q3_CHECK(finite, 3, "Invalid input: reference audio holds non-finite samples");
-        }
-        Q3_CHECK(r.ref_text_ids && r.n_ref_text_ids >= 5, 3, "Invalid input: ref_text_ids must hold the chat-template tokens");
+    if (r.ref_audio != nullptr || voice) {  // generateVoiceClone (Qwen3.swift:1009-1046): no routing by model type, no speaker/instruct
+        if (!voice) check_reference(r.ref_audio, r.n_ref_samples, r.ref_text_ids, r.n_ref_text_ids);  // (a voice passed them when it was made)
         Q3_CHECK(r.n_text_ids >= 8, 3, "Invalid input: text_ids must hold the chat-template tokens");
         Q3_CHECK(m_->codec_enc.bins <= t.vocab_size && m_->codec_enc.bins <= t.cp.vocab_size, 3,
                  "Invalid input: encoder codebook larger than the codec embedding tables");
         o.clone = true;
-        o.ref_audio = r.ref_audio;
-        o.n_ref_samples = r.n_ref_samples;
-        o.ref_text_ids.assign(r.ref_text_ids, r.ref_text_ids + r.n_ref_text_ids);
+        if (voice) {
+            o.voice = voice;
+            o.ref_T = voice->ref_T;
+            o.n_ref_samples = voice->n_ref_samples;
+            o.ref_text_ids = voice->ref_text_ids;
+        } else {
+            o.ref_audio = r.ref_audio;
+            o.n_ref_samples = r.n_ref_samples;
+            o.ref_text_ids.assign(r.ref_text_ids, r.ref_text_ids + r.n_ref_text_ids);
+        }
         const std::string lang = lower(r.language ? r.language : "auto");
         if (lang != "auto") {  // :515-519 (no dialect override on this path)
             auto it = t.codec_language_id.find(lang);
@@ -789,13 +800,16 @@ const float* Engine::upload_audio(const float* audio, int64_t n) {
 
 // Steps 1, 5 and 8 of prepareICLGenerationInputs (Qwen3.swift:436-444, 479-491, 521-525) for every voice-clone row:
 // reference codes, the per-frame sums of their 16 embeddings and the speaker x-vector, all left on the device.
-void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
+// A row whose reference is a voice skips all of it: its prompt rows and code rows are copied from the voice, device to device.
+bool Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
     const int H = m_->cfg.talker.hidden_size;
-    Q3_CHECK(fe_ != nullptr, 1, "Model not initialized: Speech tokenizer encoder not available");
+    int n_clone = 0;  // rows that carry a waveform
+    for (auto& r : reqs) n_clone += (r.clone && !r.voice) ? 1 : 0;
+    Q3_CHECK(n_clone == 0 || fe_ != nullptr, 1, "Model not initialized: Speech tokenizer encoder not available");
     size_t total_codes = 0, total_rows = 0;
     for (auto& r : reqs) {
         if (!r.clone) continue;
-        r.ref_T = fe_->encoded_frames(r.n_ref_samples);
+        r.ref_T = r.voice ? r.voice->ref_T : fe_->encoded_frames(r.n_ref_samples);
         r.ref_off = int(total_codes);
         r.extra_base = int(total_rows);
         total_codes += size_t(16) * r.ref_T;
@@ -803,8 +817,12 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
     }
     ref_codes_dev_.grow(total_codes);
     extra_.grow(total_rows * H);
-    int n_clone = 0;
-    for (auto& r : reqs) n_clone += r.clone ? 1 : 0;
+    for (auto& r : reqs) {
+        if (!r.voice) continue;
+        Q3_HIP(hipMemcpyAsync(extra_ + size_t(r.extra_base) * H, r.voice->rows_dev, size_t(1 + r.ref_T) * H * 2, hipMemcpyDeviceToDevice, st_));
+        Q3_HIP(hipMemcpyAsync(ref_codes_dev_ + r.ref_off, r.voice->codes_dev, size_t(16) * r.ref_T * 4, hipMemcpyDeviceToDevice, st_));
+    }
+    if (n_clone == 0) return false;  // nothing to encode: the front-end lanes are neither created nor touched
     const int K = std::min(4, n_clone);
     while (int(fe_lanes_.size()) < K) {
         FeLane L;
@@ -817,7 +835,7 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
     // every clip zero-padded to the longest one: the (causal) codec encoder then runs ONCE over all of them
     int64_t S_max = 0;
     for (auto& r : reqs)
-        if (r.clone) S_max = std::max<int64_t>(S_max, r.n_ref_samples);
+        if (r.clone && !r.voice) S_max = std::max<int64_t>(S_max, r.n_ref_samples);
     if (size_t(S_max) * n_clone > ref_audio_dev_.capacity()) {
         Q3_HIP(hipStreamSynchronize(st_));
         ref_audio_dev_.grow(size_t(S_max) * n_clone);
@@ -826,7 +844,7 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
     std::vector<int64_t> valid, offs;  // samples per clip, offset of its codes
     int i = 0;
     for (auto& r : reqs) {
-        if (!r.clone) continue;
+        if (!r.clone || r.voice) continue;
         Q3_HIP(hipMemcpyAsync(ref_audio_dev_ + size_t(i) * S_max, r.ref_audio, size_t(r.n_ref_samples) * 4, hipMemcpyHostToDevice, st_));
         valid.push_back(r.n_ref_samples);
         offs.push_back(r.ref_off);
@@ -837,7 +855,7 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
     if (m_->has_speaker_encoder) {
         i = 0;
         for (auto& r : reqs) {
-            if (!r.clone) continue;
+            if (!r.clone || r.voice) continue;
             FeLane& L = fe_lanes_[size_t(i % K)];
             if (i < K) Q3_HIP(hipStreamWaitEvent(L.st, fe_uploaded_, 0));
             // The x-vector is fp32; it enters the prompt in the talker's storage dtype like every other row
@@ -854,7 +872,7 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
         fe_->encode_batch(ref_audio_dev_ + size_t(lo) * S_max, nb, S_max, valid.data() + lo, offs.data() + lo, ref_codes_dev_);
     }
     for (auto& r : reqs) {
-        if (!r.clone) continue;
+        if (!r.clone || r.voice) continue;
         launch_ref_embed_rows(ref_codes_dev_ + r.ref_off, r.ref_T, 16, m_->codec_emb, m_->cp_emb_dev, H,
                               extra_ + size_t(r.extra_base + 1) * H, H, st_);
     }
@@ -863,6 +881,7 @@ void Engine::prepare_clone_rows(std::vector<ResolvedRequest>& reqs) {
             Q3_HIP(hipEventRecord(fe_lanes_[size_t(k)].done, fe_lanes_[size_t(k)].st));
             Q3_HIP(hipStreamWaitEvent(st_, fe_lanes_[size_t(k)].done, 0));
         }
+    return true;
 }
 
 int Engine::encoded_frames(int64_t n_samples) const {
@@ -904,6 +923,49 @@ void Engine::speaker_embedding(const float* audio, int64_t n_samples, float* out
     Q3_HIP(hipEventElapsedTime(&ms, ev_fe_[0], ev_fe_[1]));
     timing = q3tts_timing{};
     timing.frontend_ms = ms;
+}
+
+std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids) {
+    const TalkerConfig& t = m_->cfg.talker;
+    const int H = t.hidden_size;
+    check_reference(audio, n_samples, ref_text_ids, n_ref_text_ids);
+    Q3_CHECK(fe_ != nullptr, 1, "Model not initialized: Speech tokenizer encoder not available");
+    Q3_CHECK(m_->codec_enc.bins <= t.vocab_size && m_->codec_enc.bins <= t.cp.vocab_size, 3,
+             "Invalid input: encoder codebook larger than the codec embedding tables");
+    for (int i = 0; i < n_ref_text_ids; ++i)
+        Q3_CHECK(ref_text_ids[i] >= 0 && ref_text_ids[i] < t.text_vocab_size, 3, "Invalid input: reference text token id out of range");
+    auto v = std::make_unique<Voice>();
+    const int T = fe_->encoded_frames(n_samples);
+    v->ref_T = T;
+    v->n_ref_samples = n_samples;
+    v->ref_text_ids.assign(ref_text_ids, ref_text_ids + n_ref_text_ids);
+    v->codes_dev.grow(size_t(16) * T);
+    v->rows_dev.grow(size_t(1 + T) * H);
+    v->device_bytes = int64_t(size_t(16) * T * 4 + size_t(1 + T) * H * 2);
+    const float* a = upload_audio(audio, n_samples);
+    Q3_HIP(hipEventRecord(ev_fe_[0], st_));
+    fe_->encode(a, n_samples, v->codes_dev);
+    if (m_->has_speaker_encoder) {  // fp32 x-vector, then the talker's storage dtype like every other prompt row (prepare_clone_rows)
+        spk_f32_.grow(size_t(H));
+        fe_->speaker_embedding(a, n_samples, spk_f32_);
+        launch_f32_to_bf16(spk_f32_, v->rows_dev, H, st_);
+    } else {
+        Q3_HIP(hipMemsetAsync(v->rows_dev, 0, size_t(H) * 2, st_));  // (no prompt row names it)
+    }
+    launch_ref_embed_rows(v->codes_dev, T, 16, m_->codec_emb, m_->cp_emb_dev, H, v->rows_dev + size_t(H), H, st_);
+    Q3_HIP(hipEventRecord(ev_fe_[1], st_));
+    std::vector<int32_t> rows(size_t(16) * T);
+    Q3_HIP(hipMemcpyAsync(rows.data(), v->codes_dev, rows.size() * 4, hipMemcpyDeviceToHost, st_));
+    Q3_HIP(hipStreamSynchronize(st_));  // from here on the voice is read-only: any context, any lane
+    v->code0.assign(rows.begin(), rows.begin() + T);
+    v->codes_host.resize(size_t(T) * 16);
+    for (int f = 0; f < T; ++f)
+        for (int g = 0; g < 16; ++g) v->codes_host[size_t(f) * 16 + g] = rows[size_t(g) * T + f];
+    float ms = 0;
+    Q3_HIP(hipEventElapsedTime(&ms, ev_fe_[0], ev_fe_[1]));
+    timing = q3tts_timing{};
+    timing.frontend_ms = ms;
+    return v;
 }
 
 void Engine::debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C) {
@@ -991,8 +1053,8 @@ void Engine::enqueue_prefill(Stream& w, int n, int Pmax, const int32_t* block_ta
 // generate
 // ------------------------------------------------------------------------------------------------
 void Engine::generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                      q3tts_result* results, const DebugOpts* dbg) {
-    end(begin(reqs, n, sp, cb, user, dbg, false), results);
+                      q3tts_result* results, const DebugOpts* dbg, const Voice* const* voices) {
+    end(begin(reqs, n, sp, cb, user, dbg, false, false, voices), results);
 }
 
 // The codec runner's scratch is shared by both codec streams: before it moves to the other one, the one it ran on drains.
@@ -1056,15 +1118,16 @@ struct Engine::StreamedDecode {
 };
 
 int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const DebugOpts* dbg,
-                  bool overlapped, bool background) {
+                  bool overlapped, bool background, const Voice* const* voices) {
     Q3_HIP(hipSetDevice(m_->device));  // lanes run on their own host threads
     std::vector<ResolvedRequest> rr;
     double t_start = 0;
-    const int slot = open_job(reqs, n, sp, dbg, rr, t_start);
+    const int slot = open_job(reqs, n, sp, dbg, rr, t_start, voices);
     bool any_clone = false;
     for (auto& r : rr) any_clone = any_clone || r.clone;
     Q3_HIP(hipEventRecord(ev_fe_[0], st_));
-    if (any_clone) prepare_clone_rows(rr);  // codec encoder + speaker encoder, once per request (Qwen3.swift:443, :524)
+    // codec encoder + speaker encoder, once per request that carries a waveform (Qwen3.swift:443, :524)
+    const bool frontend = any_clone && prepare_clone_rows(rr);
     Q3_HIP(hipEventRecord(ev_fe_[1], st_));
     std::vector<int> np, nt;
     assemble_prompts(rr, np, nt);
@@ -1077,6 +1140,7 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     Job& J = jobs_[slot];
     J.reset(n, codec_->upsample());
     J.chunk_frames = sp.audio_chunk_frames;
+    J.frontend = frontend;
     J.busy = true;  // nothing below gives the slot back except end() -- or a back half that fails inside this call
     // The throughput jobs -- nobody listens for TOKEN events, nothing is streamed or dumped -- leave the frame loop to the
     // worker thread, so that the caller can begin the next batch on the other context while this chain runs.
@@ -1158,7 +1222,7 @@ void Engine::drain() {
 }
 
 int Engine::open_job(const q3tts_request* reqs, int n, const q3tts_sampling& sp, const DebugOpts* dbg, std::vector<ResolvedRequest>& rr,
-                     double& t_start) {
+                     double& t_start, const Voice* const* voices) {
     Q3_CHECK(n >= 1 && n <= Bm_, 3, "Invalid input: batch size must be between 1 and max_batch");
     Q3_CHECK(m_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
     Q3_CHECK(sp.audio_chunk_frames >= 0, 3, "Invalid input: audio_chunk_frames must not be negative");
@@ -1171,7 +1235,7 @@ int Engine::open_job(const q3tts_request* reqs, int n, const q3tts_sampling& sp,
     Q3_CHECK(slot >= 0, 3, "Invalid input: two jobs are already outstanding (q3tts_generate_end must be called first)");
     t_start = now_s();
     Q3_HIP(hipEventRecord(jobs_[slot].ev_begin, st_));
-    for (int i = 0; i < n; ++i) rr.push_back(resolve(reqs[i], sp));
+    for (int i = 0; i < n; ++i) rr.push_back(resolve(reqs[i], sp, voices ? voices[i] : nullptr));
     if (dbg)
         for (auto& r : rr) r.max_frames = dbg->frames;
     for (auto& r : rr) Q3_CHECK(r.max_frames <= Fcap_, 3, "Invalid input: max_tokens exceeds the configured max_frames");
@@ -1341,18 +1405,24 @@ void Engine::hand_off(Job& J, const std::vector<ResolvedRequest>& rr, StreamedDe
     if (Fdec > 0) {
         // The decoder reads a copy owned by the job: the next begin() overwrites codes_ while this decode may still run.
         J.dec_codes.grow(size_t(n) * Fdec * 16);
-        if (any_clone) {
+        if (any_clone) {  // every row in one launch: [reference ++] generated. Frames behind a row's own are not written (nor were
+                          // they by the per-row launches before): the decoder is given dframes and reads nothing beyond them
+            J.row_desc.assign(size_t(n), DecodeRowDesc{});
             for (int b = 0; b < n; ++b) {
                 const auto& r = rr[size_t(b)];
-                if (J.frames[size_t(b)] == 0) continue;
-                launch_build_decode_codes(r.clone ? ref_codes_dev_ + r.ref_off : nullptr, r.clone ? r.ref_T : 0,
-                                          codes_ + size_t(b) * Fcap_ * 16, J.frames[size_t(b)], J.dec_codes + size_t(b) * Fdec * 16, st_);
-                if (r.clone) {
+                if (J.frames[size_t(b)] == 0) continue;  // (F == 0: the row's descriptor writes nothing)
+                J.row_desc[size_t(b)] = DecodeRowDesc{r.clone ? ref_codes_dev_ + r.ref_off : nullptr, codes_ + size_t(b) * Fcap_ * 16,
+                                                      r.clone ? r.ref_T : 0, J.frames[size_t(b)], b, 0};
+                if (r.voice) {
+                    J.ref_code0[size_t(b)] = r.voice->code0;
+                } else if (r.clone) {
                     J.ref_code0[size_t(b)].resize(size_t(r.ref_T));
                     Q3_HIP(hipMemcpyAsync(J.ref_code0[size_t(b)].data(), ref_codes_dev_ + r.ref_off, size_t(r.ref_T) * 4,
                                           hipMemcpyDeviceToHost, st_));
                 }
             }
+            Q3_HIP(hipMemcpyAsync(J.row_desc_dev.grow(size_t(n)), J.row_desc.data(), size_t(n) * sizeof(DecodeRowDesc), hipMemcpyHostToDevice, st_));
+            launch_build_decode_codes_rows(J.row_desc.data(), J.row_desc_dev, n, J.dec_codes, n, Fdec, st_);
         } else {
             Q3_HIP(hipMemcpy2DAsync(J.dec_codes, size_t(Fdec) * 64, codes_, size_t(Fcap_) * 64, size_t(Fdec) * 64, size_t(n),
                                     hipMemcpyDeviceToDevice, st_));
@@ -1368,10 +1438,32 @@ void Engine::start_decode(Job& J, const std::vector<int>& dframes, bool overlapp
     if (J.Fdec > 0) {
         const size_t floats = size_t(J.n) * J.Fdec * J.up;
         J.pcm_host.grow(floats);
-        if (codes_host) {
+        if (codes_host && J.voices.empty()) {
             J.dec_codes.grow(size_t(J.n) * J.Fdec * 16);
             Q3_HIP(hipMemcpy2DAsync(J.dec_codes, size_t(J.Fdec) * 64, codes_host, size_t(Fcap_) * 64, size_t(J.Fdec) * 64, size_t(J.n),
                                     hipMemcpyHostToDevice, cst));
+        } else if (codes_host) {
+            // Rows with a reference in front: J.Fdec may exceed Fcap_, the stride of codes_host. The generated codes are staged
+            // as they lie on the host; one launch then writes every row behind its voice's reference frames, read from the voice.
+            J.dec_codes.grow(size_t(J.n) * J.Fdec * 16);
+            // (the builder writes a row's own frames only; what lies behind them is zero, as after the 2-D upload of the zeroed
+            // codes_host above, although CodecRunner::decode is given dframes and reads no frame of a row beyond them)
+            Q3_HIP(hipMemsetAsync(J.dec_codes, 0, size_t(J.n) * J.Fdec * 64, cst));
+            J.gen_codes.grow(size_t(J.n) * Fcap_ * 16);
+            int Fgen = 0;
+            for (int b = 0; b < J.n; ++b) Fgen = std::max(Fgen, J.frames[size_t(b)]);
+            Q3_CHECK(Fgen <= Fcap_, 7, "internal error: more generated frames than max_frames");
+            Q3_HIP(hipMemcpy2DAsync(J.gen_codes, size_t(Fcap_) * 64, codes_host, size_t(Fcap_) * 64, size_t(Fgen) * 64, size_t(J.n),
+                                    hipMemcpyHostToDevice, cst));
+            J.row_desc.assign(size_t(J.n), DecodeRowDesc{});
+            for (int b = 0; b < J.n; ++b) {
+                const Voice* v = J.voices[size_t(b)];
+                J.row_desc[size_t(b)] = DecodeRowDesc{v ? static_cast<const int32_t*>(v->codes_dev) : nullptr,
+                                                      J.gen_codes + size_t(b) * Fcap_ * 16, v ? v->ref_T : 0, J.frames[size_t(b)], b, 0};
+            }
+            Q3_HIP(hipMemcpyAsync(J.row_desc_dev.grow(size_t(J.n)), J.row_desc.data(), size_t(J.n) * sizeof(DecodeRowDesc),
+                                  hipMemcpyHostToDevice, cst));
+            launch_build_decode_codes_rows(J.row_desc.data(), J.row_desc_dev, J.n, J.dec_codes, J.n, J.Fdec, cst);
         }
         if (J.chunk_frames > 0) {
             // pre-transformer once over all frames, then the causal tail chunk by chunk (codec.h decode_chunked)
@@ -1395,7 +1487,7 @@ void Engine::job_timing(Job& J, const std::vector<int>& np, int launched) {
     Q3_HIP(hipEventElapsedTime(&ms, ev_[1], ev_[2]));
     J.timing.decode_ms = ms;
     Q3_HIP(hipEventElapsedTime(&ms, ev_fe_[0], ev_fe_[1]));
-    J.timing.frontend_ms = ms;
+    J.timing.frontend_ms = J.frontend ? ms : 0;  // (a call whose references are all voices has no front end to time)
     J.timing.frame_steps = launched;
     J.timing.launches_per_frame_step = launches_per_step(J.n);
     J.timing.rows = J.n;
@@ -1443,7 +1535,8 @@ void Engine::Job::reset(int rows, int upsample) {
     held_from.assign(size_t(n), -1);
     std::memset(nf_host, 0, nf_host.capacity() * 4);
     n_chunks = chunk_frames = chunks_fired = 0;
-    streamed = decoded = background = false;
+    streamed = decoded = background = frontend = false;
+    voices.clear();
     t_first_audio = t_done = 0;
     timing = q3tts_timing{};
 }
@@ -1796,19 +1889,26 @@ bool Engine::job_outstanding() const {
 }
 
 // resolve() plus every limit a request would otherwise hit inside the slot loop, on the host: the lengths are the ones
-// assemble_prompts produces for a request that is not a voice clone (those are refused here)
-ResolvedRequest Engine::check_queued(const q3tts_request& r, const q3tts_sampling& sp) const {
+// assemble_prompts produces -- for an ordinary request, or with `voice` for the ICL prompt of a voice-clone request (a
+// request that carries its clip as ref_audio is refused here: its front end has no place at a burst boundary)
+ResolvedRequest Engine::check_queued(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice) const {
     const TalkerConfig& t = m_->cfg.talker;
     Q3_CHECK(r.ref_audio == nullptr, 3, "Invalid input: voice-clone requests (ref_audio) are not supported by q3tts_generate_queued");
-    ResolvedRequest o = resolve(r, sp);
+    ResolvedRequest o = resolve(r, sp, voice);
     Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");  // Qwen3.swift:799-801
     Q3_CHECK(o.max_frames <= Fcap_, 3, "Invalid input: max_tokens exceeds the configured max_frames");
     Q3_CHECK(o.language_id < t.vocab_size && o.speaker_token < t.vocab_size, 3, "Invalid input: codec prefix id out of range");
-    const int nc = (o.language_id < 0 ? 3 : 4) + (o.speaker_token >= 0 ? 1 : 0) + 2;  // codec prefix (Qwen3.swift:322-359)
-    const int np = int(o.instruct_ids.size()) + 3 + nc;                                // instruct, role, prefix, first text token
-    Q3_CHECK(np <= Pcap_, 3, "Invalid input: prompt longer than max_prompt");
     const int tl = int(o.text_ids.size());
-    const int nt = (tl - 5 > 4 ? tl - 9 : 0) + 1;                                      // trailing text + tts_eos (:394-406)
+    int nc = (o.language_id < 0 ? 3 : 4) + (o.speaker_token >= 0 ? 1 : 0) + 2;  // codec prefix (Qwen3.swift:322-359)
+    int np = int(o.instruct_ids.size()) + 3 + nc;                                // instruct, role, prefix, first text token
+    int nt = (tl - 5 > 4 ? tl - 9 : 0) + 1;                                      // trailing text + tts_eos (:394-406)
+    if (o.clone) {  // the ICL prompt (assemble_prompts): role, prefix with the x-vector, reference text, target text, tts_eos,
+                    // codec_bos, one row per reference frame; the trailing text is tts_pad alone
+        nc += m_->has_speaker_encoder ? 1 : 0;
+        np = 3 + (nc - 1) + (int(o.ref_text_ids.size()) - 5) + (tl - 8) + 2 + o.ref_T;
+        nt = 1;
+    }
+    Q3_CHECK(np <= Pcap_, 3, "Invalid input: prompt longer than max_prompt");
     Q3_CHECK(nt <= Tcap_, 3, "Invalid input: text longer than max_prompt");
     Q3_CHECK(np + o.max_frames + 1 <= m_->talker.max_pos, 3, "Invalid input: sequence longer than the RoPE table");
     return o;
@@ -1986,6 +2086,20 @@ int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained) {
     }
     const int k = int(rr.size());
     if (k == 0) return 0;
+    {   // voice rows: their prompt rows (x-vector, reference frames) into extra_ for this sub-batch, device to device; no front end
+        const int H = m_->cfg.talker.hidden_size;
+        size_t rows = 0;
+        for (auto& r : rr)
+            if (r.voice) {
+                r.extra_base = int(rows);
+                rows += size_t(1) + r.ref_T;
+            }
+        Q3_CHECK(rows * H <= extra_.capacity(), 7, "internal error: voice rows beyond the queue's reservation");  // (run_queued)
+        for (auto& r : rr)
+            if (r.voice)
+                Q3_HIP(hipMemcpyAsync(extra_ + size_t(r.extra_base) * H, r.voice->rows_dev, size_t(1 + r.ref_T) * H * 2,
+                                      hipMemcpyDeviceToDevice, st_));
+    }
     std::vector<int> np, nt;
     assemble_prompts(rr, np, nt, &slots);  // prompt_ rows 0..k-1; trailing text into the slots' rows (synchronises st_)
     int Pmax = 0;
@@ -2035,6 +2149,12 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     Q3_CHECK(S >= 1 && S <= Bm_, 3, "Invalid input: slots must be between 1 and max_batch");
     Q3_CHECK(!job_outstanding(), 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
     ensure_queue_ws();
+    {   // an admission's voice rows go through extra_: room for S rows with the longest reference, so that no boundary allocates
+        int ref_max = -1;
+        for (const auto& r : *q.reqs)
+            if (r.voice) ref_max = std::max(ref_max, r.ref_T);
+        if (ref_max >= 0) extra_.grow(size_t(S) * (1 + ref_max) * m_->cfg.talker.hidden_size);
+    }
     const double t_call = now_s();
     // every slot starts empty: finished, inactive, an empty cache in its own pages
     std::vector<int32_t> bt(size_t(S) * max_pages_);
@@ -2095,17 +2215,29 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         J.req_index.assign(size_t(R), 0);
         J.row_span.assign(size_t(R), 0);
         J.codes_host.assign(size_t(R) * Fcap_ * 16, 0);
+        std::vector<int> dframes((size_t)(R), 0);  // frames the decoder sees per row: [reference ++] generated, as hand_off
+        std::vector<const Voice*> voices((size_t)(R), nullptr);
+        bool any_voice = false;
         for (int b = 0; b < R; ++b) {
             const Retired& w = waiting[size_t(b)];
+            const ResolvedRequest& rq = (*q.reqs)[size_t(w.req)];
             J.frames[size_t(b)] = w.frames;
-            J.target_tokens[size_t(b)] = (*q.reqs)[size_t(w.req)].target_token_count;
+            J.target_tokens[size_t(b)] = rq.target_token_count;
             J.req_index[size_t(b)] = w.req;
             J.row_span[size_t(b)] = w.span;
             std::copy(w.codes.begin(), w.codes.end(), J.codes_host.begin() + ptrdiff_t(size_t(b) * Fcap_ * 16));
-            J.Fdec = std::max(J.Fdec, w.frames);
+            if (rq.voice) {  // compute_cuts then trims and cuts exactly as the static path does
+                any_voice = true;
+                voices[size_t(b)] = rq.voice;
+                J.ref_T[size_t(b)] = rq.voice->ref_T;
+                J.ref_code0[size_t(b)] = rq.voice->code0;
+            }
+            dframes[size_t(b)] = w.frames > 0 ? w.frames + J.ref_T[size_t(b)] : 0;
+            J.Fdec = std::max(J.Fdec, dframes[size_t(b)]);
         }
+        if (any_voice) J.voices = std::move(voices);
         waiting.erase(waiting.begin(), waiting.begin() + R);
-        start_decode(J, J.frames, overlapped, J.codes_host.data());
+        start_decode(J, dframes, overlapped, J.codes_host.data());
         dec = 0;
         publish_job(J, cb, user, 0, t_call, true);  // copied out by the staging thread while the frame loop goes on
     };
@@ -2428,6 +2560,36 @@ void Engine::debug_linear(const uint16_t* x, const uint16_t* W, const uint16_t* 
 
 // One launch_attn_decode on the caller's buffers (q3tts.h). Everything the kernels turn into an address -- cache lengths,
 // block-table entries, the padding of a right-aligned chunk -- is checked here against the sizes the caller states.
+void Engine::debug_build_decode_codes(const int32_t* refs, const int32_t* ref_T, const int32_t* gen, const int32_t* n_frames, int R,
+                                      int gen_stride, int Fdec, bool misalign, int32_t* out) {
+    size_t ref_total = 0;
+    for (int r = 0; r < R; ++r) {
+        Q3_CHECK(ref_T[r] >= 0 && n_frames[r] >= 0 && n_frames[r] <= gen_stride, 3, "Invalid input: frame counts out of range");
+        ref_total += size_t(16) * ref_T[r];
+    }
+    Q3_CHECK(ref_total == 0 || refs, 3, "Invalid input: null argument");
+    const size_t off = misalign ? 1 : 0, n_gen = size_t(R) * gen_stride * 16, n_out = size_t(R) * Fdec * 16;
+    DevBuf<int32_t> d_ref, d_gen, d_out;
+    DevBuf<DecodeRowDesc> d_desc;
+    d_ref.grow(std::max<size_t>(ref_total, 1));
+    d_gen.grow(n_gen + off);
+    d_out.grow(n_out + off);
+    d_desc.grow(size_t(R));
+    if (ref_total) Q3_HIP(hipMemcpyAsync(d_ref, refs, ref_total * 4, hipMemcpyHostToDevice, st_));
+    Q3_HIP(hipMemcpyAsync(d_gen + off, gen, n_gen * 4, hipMemcpyHostToDevice, st_));
+    Q3_HIP(hipMemcpyAsync(d_out + off, out, n_out * 4, hipMemcpyHostToDevice, st_));
+    std::vector<DecodeRowDesc> desc((size_t)(R));
+    size_t at = 0;
+    for (int r = 0; r < R; ++r) {
+        desc[size_t(r)] = DecodeRowDesc{ref_T[r] > 0 ? d_ref + at : nullptr, d_gen + off + size_t(r) * gen_stride * 16, ref_T[r], n_frames[r], r, 0};
+        at += size_t(16) * ref_T[r];
+    }
+    Q3_HIP(hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(DecodeRowDesc), hipMemcpyHostToDevice, st_));
+    launch_build_decode_codes_rows(desc.data(), d_desc, R, d_out + off, R, Fdec, st_);
+    Q3_HIP(hipMemcpyAsync(out, d_out + off, n_out * 4, hipMemcpyDeviceToHost, st_));
+    Q3_HIP(hipStreamSynchronize(st_));
+}
+
 void Engine::debug_attention(const q3tts_attn_debug& d) {
     Q3_CHECK(d.qkv && d.qn_w && d.kn_w && d.rope_cos && d.rope_sin && d.kpool && d.vpool && d.out, 3, "debug_attention: null argument");
     Q3_CHECK(d.n_kv >= 1 && d.n_kv <= 64 && d.n_heads >= d.n_kv && d.n_heads % d.n_kv == 0 && d.n_heads / d.n_kv <= 4, 3,
@@ -2798,10 +2960,44 @@ void EngineGroup::run_lanes(int L, bool serial, F&& fn) {
         if (codes[size_t(i)]) throw Error(codes[size_t(i)], errs[size_t(i)]);
 }
 
+Voice* EngineGroup::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids) {
+    std::unique_ptr<Voice> v = lane0().create_voice(audio, n_samples, ref_text_ids, n_ref_text_ids);
+    timing = lanes_[0]->timing;
+    v->owner = this;
+    voices_.push_back(std::move(v));
+    return voices_.back().get();
+}
+
+bool EngineGroup::mine(const Voice* v) const {
+    for (const auto& p : voices_)
+        if (p.get() == v) return true;
+    return false;
+}
+
+void EngineGroup::free_voice(Voice* v) {
+    for (size_t i = 0; i < voices_.size(); ++i)
+        if (voices_[i].get() == v) {
+            voices_.erase(voices_.begin() + ptrdiff_t(i));
+            return;
+        }
+}
+
+void EngineGroup::check_voices(const q3tts_request* reqs, int n, const Voice* const* voices) const {
+    if (!voices) return;
+    for (int i = 0; i < n; ++i) {
+        if (!voices[i]) continue;
+        Q3_CHECK(mine(voices[i]), 3,
+                 "Invalid input: the voice of request " + std::to_string(i) + " was not created on this model handle (or has been freed)");
+        Q3_CHECK(reqs[i].ref_audio == nullptr && reqs[i].ref_text_ids == nullptr, 3,
+                 "Invalid input: request " + std::to_string(i) + " names a voice and carries ref_audio / ref_text_ids as well");
+    }
+}
+
 void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                           q3tts_result* results, const DebugOpts* dbg) {
+                           q3tts_result* results, const DebugOpts* dbg, const Voice* const* voices) {
     Q3_CHECK(n >= 1 && n <= opts_.max_batch, 3, "Invalid input: batch size must be between 1 and max_batch");
     check_row_sampling(sp, n);
+    check_voices(reqs, n, voices);
     const int L = int(lanes_.size());
     // contiguous split: lane i takes rows [lo_i, hi_i)
     std::vector<int> lo((size_t)(L + 1), 0);
@@ -2830,7 +3026,7 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
         }
         q3tts_sampling ls = sp;  // the lane's rows are requests [a, b): their entries of the per-request array
         if (ls.per_request) ls.per_request += a;
-        e.generate(reqs + a, b - a, ls, cb, user, results + a, dp);
+        e.generate(reqs + a, b - a, ls, cb, user, results + a, dp, voices ? voices + a : nullptr);
     });
     // aggregate timing: lanes run concurrently, so spans are maxima and volumes are sums
     timing = q3tts_timing{};
@@ -2850,7 +3046,7 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
 }
 
 void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                                  q3tts_result* results) {
+                                  q3tts_result* results, const Voice* const* voices) {
     Q3_CHECK(n >= 1, 3, "Invalid input: n_reqs must be at least 1");
     Q3_CHECK(slots >= 1 && slots <= opts_.max_batch, 3, "Invalid input: slots must be between 1 and max_batch");
     // chunks cut after a request's end (audio_window_frames == 0) give a queue nothing: its AUDIO already leaves as soon as it is decoded
@@ -2863,12 +3059,17 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     Q3_CHECK(!outstanding, 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
     Q3_CHECK(model_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
     check_row_sampling(sp, n);
+    check_voices(reqs, n, voices);
+    if (voices && sp.audio_chunk_frames > 0)  // (the slotted stream would need a reference prefix per row: DESIGN.md section 9)
+        for (int i = 0; i < n; ++i)
+            Q3_CHECK(!voices[i], 3, "Invalid input: streamed audio (audio_chunk_frames > 0) is not supported for voice requests by "
+                                    "q3tts_generate_queued_voices");
     // every request is checked before any GPU work: a bad one late in the queue must not fail after the others were delivered
     std::vector<ResolvedRequest> rr;
     rr.reserve(size_t(n));
     for (int i = 0; i < n; ++i) {
         try {
-            rr.push_back(lanes_[0]->check_queued(reqs[i], sp));
+            rr.push_back(lanes_[0]->check_queued(reqs[i], sp, voices ? voices[i] : nullptr));
         } catch (const Error& e) {
             throw Error(e.status, std::string(e.what()) + " (request " + std::to_string(i) + ")");
         }

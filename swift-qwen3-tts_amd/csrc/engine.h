@@ -29,6 +29,21 @@ struct DebugOpts {
     int32_t* sampled = nullptr;         // host [n][frames][16]
 };
 
+// A reusable voice prompt (q3tts_voice): one reference clip and its transcript, encoded once (Engine::create_voice) and then
+// read-only, so that every job context and every lane may read it. The device buffers hold what prepare_clone_rows produces
+// for a waveform row; the host copies spare the requests that name the voice any device-to-host copy.
+struct Voice {
+    const void* owner = nullptr;        // the EngineGroup it was created on
+    int ref_T = 0;                      // reference frames
+    int64_t n_ref_samples = 0;
+    std::vector<int32_t> ref_text_ids;
+    DevBuf<int32_t> codes_dev;          // [16][ref_T]
+    DevBuf<uint16_t> rows_dev;          // [1 + ref_T][H] bf16: x-vector row (zeros without a speaker encoder), then the frames' embedding sums
+    std::vector<int32_t> codes_host;    // [ref_T][16] frame-major, as the decoder reads them
+    std::vector<int32_t> code0;         // [ref_T] first code row (valid-length count of the end trim)
+    int64_t device_bytes = 0;
+};
+
 struct ResolvedRequest {
     std::vector<int32_t> text_ids, instruct_ids;
     int speaker_token = -1;  // row of the codec embedding table, -1: none
@@ -43,6 +58,7 @@ struct ResolvedRequest {
     int ref_T = 0;        // reference frames (filled by prepare_clone_rows)
     int extra_base = 0;   // first row of this request in extra_: speaker x-vector, then ref_T embedding sums
     int ref_off = 0;      // offset of this request's [16][ref_T] codes in ref_codes_dev_
+    const Voice* voice = nullptr;  // clone row whose reference is a voice: no waveform, no front end (ref_T known at once)
 };
 
 // q3tts_sampling.per_request: the set fields of its n entries are checked on the host, before any GPU work (status 3)
@@ -81,8 +97,9 @@ class Engine {
     std::string last_error;
     q3tts_timing timing{};
 
+    // voices: [n] or nullptr; a non-null entry makes request i a voice-clone request whose reference is that voice
     void generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                  q3tts_result* results, const DebugOpts* dbg);
+                  q3tts_result* results, const DebugOpts* dbg, const Voice* const* voices = nullptr);
     // generate() in two halves (q3tts_generate_begin / _end). The front half of begin -- input checks, voice front end, prompt
     // assembly, row reservation, prefill enqueued -- always runs on the caller's thread, so whatever can refuse a request
     // refuses it inside begin. The back half -- frame loop, hand-off to the codec stream, timing -- runs there too when the job
@@ -95,16 +112,17 @@ class Engine {
     static constexpr int kJobSlots = 2;
     int begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const DebugOpts* dbg,
               bool overlapped,  // overlapped: another batch's AR loop is expected to run beside this one's decode
-              bool background = false);
+              bool background = false, const Voice* const* voices = nullptr);
     void end(int job, q3tts_result* results);
     bool job_outstanding() const;
     void prepare_job_pair();  // at load, by an EngineGroup that will run background jobs on its two contexts
     void drain();             // returns once no back half is queued or running on the worker thread
-    // Continuous batching (q3tts_generate_queued). check_queued resolves one request and applies every limit the slot loop
-    // would hit (prompt, trailing text, max_frames, RoPE range) on the host, before any GPU work. run_queued keeps `slots`
+    // Continuous batching (q3tts_generate_queued). check_queued resolves one request (with `voice`: a voice-clone request, whose
+    // ICL prompt length it computes) and applies every limit the slot loop would hit (prompt, trailing text, max_frames, RoPE
+    // range) on the host, before any GPU work. run_queued keeps `slots`
     // rows in flight: at each burst boundary finished rows are retired (codes copied out, decode queued on the codec stream
     // beside the frame loop) and their slots take the next requests of `q`, prefilled as a sub-batch of their own.
-    ResolvedRequest check_queued(const q3tts_request& r, const q3tts_sampling& sp) const;
+    ResolvedRequest check_queued(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice = nullptr) const;
     void check_stream_chunk(int chunk_frames) const;  // a streamed decode's chunk must hold the causal tail's history
     void run_queued(QueueShared& q, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
     void debug_prepare_inputs(const q3tts_request& req, uint16_t* input_embeds, int cap_prompt, int* n_prompt,
@@ -113,6 +131,8 @@ class Engine {
                       int suppress_lo, int suppress_hi, int eos_id, uint32_t row0, uint32_t draw, int32_t* tokens);
     void debug_linear(const uint16_t* x, const uint16_t* W, const uint16_t* bias, int M, int K, int N, uint16_t* y);
     void debug_attention(const q3tts_attn_debug& a);
+    void debug_build_decode_codes(const int32_t* refs, const int32_t* ref_T, const int32_t* gen, const int32_t* n_frames, int R,
+                                  int gen_stride, int Fdec, bool misalign, int32_t* out);
     void codec_decode(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, float* pcm,
                       int64_t* audio_lengths);
     void codec_decode_streamed(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, int chunk_frames, int window,
@@ -125,6 +145,8 @@ class Engine {
     int codec_encode(const float* audio, int64_t n_samples, int32_t* codes, int cap_frames);
     int encoded_frames(int64_t n_samples) const;
     void speaker_embedding(const float* audio, int64_t n_samples, float* out, int cap);
+    // q3tts_voice_create: what prepare_clone_rows runs for one clip, into buffers the voice owns; synchronises before it returns
+    std::unique_ptr<Voice> create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids);
     void debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C);
 
     std::vector<std::string> speakers;  // sorted (Qwen3.swift:965-971)
@@ -196,6 +218,7 @@ class Engine {
         std::vector<int> np;
         q3tts_sampling sp{};
         bool overlapped = false;
+        bool frontend = false;    // some row's reference was a waveform: timing.frontend_ms is the front end's time (else 0)
         bool background = false;  // the back half runs on the worker thread (and the decode on the wider masked stream)
         int back = 0;         // 1: queued for or running on the worker thread (work_mu_)
         int back_status = 0;  // q3::Error status the back half ended with (0: it finished)
@@ -207,6 +230,10 @@ class Engine {
         std::vector<std::vector<int32_t>> ref_code0;  // first code row of each reference (valid-length count)
         std::vector<int32_t> codes_host;  // [n][Fcap][16]
         DevBuf<int32_t> dec_codes;        // [n][Fdec][16]: what the decoder reads (reference ++ generated for clone rows)
+        std::vector<const Voice*> voices; // queued decode batch: row b's voice (nullptr: none); empty: no row has one
+        DevBuf<int32_t> gen_codes;        // queued decode batch with voice rows: codes_host on the device, [n][Fcap][16]
+        std::vector<DecodeRowDesc> row_desc;  // launch_build_decode_codes_rows: the rows' descriptors (alive until the slot is reused)
+        DevBuf<DecodeRowDesc> row_desc_dev;
         PinnedBuf<float> pcm_host;        // [n][Fdec * up]
         hipEvent_t ev_codec[2] = {nullptr, nullptr};
         PinnedBuf<int32_t> nf_host;        // [max_batch]: rows whose waveform came out non-finite (CodecRunner::decode)
@@ -236,7 +263,8 @@ class Engine {
         void clear_chunk_flags(int frames);  // nf_chunk_host for a decode of `frames` frames in chunks of chunk_frames
     } jobs_[kJobSlots];
     // a job's codec decode on the codec stream (ev_codec[0], decode -- in chunks when J.chunk_frames > 0 --, PCM to pcm_host,
-    // ev_codec[1]); codes_host: [n][Fcap][16] copied in on that stream first; nullptr: J.dec_codes holds the codes already
+    // ev_codec[1]); codes_host: [n][Fcap][16] copied in on that stream first (behind their voices' reference frames for the
+    // rows of J.voices); nullptr: J.dec_codes holds the codes already
     void start_decode(Job& J, const std::vector<int>& dframes, bool overlapped, const int32_t* codes_host);
     // the job is outstanding: cuts, then handed to the staging thread when `stage` and there is PCM to copy
     void publish_job(Job& J, q3tts_event_cb cb, void* user, int request_base, double t_start, bool stage);
@@ -288,14 +316,16 @@ class Engine {
     };
     std::vector<FeLane> fe_lanes_;
     const float* upload_audio(const float* audio, int64_t n);
-    void prepare_clone_rows(std::vector<ResolvedRequest>& reqs);
+    bool prepare_clone_rows(std::vector<ResolvedRequest>& reqs);  // true: the front end ran (some row carried a waveform)
 
     void alloc_workspace();
-    ResolvedRequest resolve(const q3tts_request& r, const q3tts_sampling& sp) const;
+    ResolvedRequest resolve(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice = nullptr) const;
+    // the checks of a voice-clone reference that do not depend on the request's text (resolve, create_voice)
+    void check_reference(const float* ref_audio, int64_t n_ref_samples, const int32_t* ref_text_ids, int n_ref_text_ids) const;
     // ---- the steps of begin() ----
     // input checks, a free job slot (returned; ev_begin recorded), the resolved requests
     int open_job(const q3tts_request* reqs, int n, const q3tts_sampling& sp, const DebugOpts* dbg, std::vector<ResolvedRequest>& rr,
-                 double& t_start);
+                 double& t_start, const Voice* const* voices);
     // block table, per-row limits and lengths, cleared per-row state, sampling parameters; returns the longest prompt
     int reserve_rows(const std::vector<ResolvedRequest>& rr, const std::vector<int>& np, const std::vector<int>& nt,
                      const q3tts_sampling& sp);
@@ -378,14 +408,19 @@ class EngineGroup {
     int n_lanes() const { return int(lanes_.size()); }
     const q3tts_load_opts& opts() const { return opts_; }
     void generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                  q3tts_result* results, const DebugOpts* dbg);
+                  q3tts_result* results, const DebugOpts* dbg, const Voice* const* voices = nullptr);
+    // q3tts_voice_create / _free: the group owns its voices (whatever is still alive goes with it). A voice of another group,
+    // or one already freed, is not `mine`
+    Voice* create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids);
+    void free_voice(Voice* v);
+    bool mine(const Voice* v) const;
     // Two-deep pipeline (Engine::begin / end); the job id names the context and its slot. With more than one lane a job runs
     // to completion inside begin.
     int begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, bool more_follows);
     void end(int job, q3tts_result* results);
     // q3tts_generate_queued: every request checked up front; `slots` rows split over the lanes, one shared queue
     void generate_queued(const q3tts_request* reqs, int n, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                         q3tts_result* results);
+                         q3tts_result* results, const Voice* const* voices = nullptr);
     std::string last_error;
     q3tts_timing timing{};
     std::vector<std::string> speakers;
@@ -403,6 +438,8 @@ class EngineGroup {
     q3tts_load_opts opts_;
     std::mutex cb_mutex_;
     std::vector<std::unique_ptr<Engine>> lanes_;
+    std::vector<std::unique_ptr<Voice>> voices_;
+    void check_voices(const q3tts_request* reqs, int n, const Voice* const* voices) const;  // status 3 before any GPU work
     // one lane: the second job context (lanes_[0] is the first). A job takes a context without an outstanding job, the one
     // that was not used last first, so that plain q3tts_generate calls alternate and a host's warm-up calls warm both.
     std::unique_ptr<Engine> ctx1_;

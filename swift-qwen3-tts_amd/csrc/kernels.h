@@ -266,8 +266,18 @@ void launch_compose_rows(const uint16_t* proj, int ldp, const uint16_t* table, i
 void launch_ref_embed_rows(const int32_t* codes, int T, int groups, const uint16_t* codec_emb, const uint16_t* const* cp_emb,
                            int H, uint16_t* out, int ldo, hipStream_t st);
 void launch_f32_to_bf16(const float* x, uint16_t* out, int n, hipStream_t st);
-// out [Tref + F][16] = transpose(ref [16][Tref]) ++ gen [F][16]   (Qwen3.swift:1176-1180)
-void launch_build_decode_codes(const int32_t* ref, int Tref, const int32_t* gen, int F, int32_t* out, hipStream_t st);
+// The decoder's input for R rows in one launch: out[dst_row][0 .. Tref + F)[16] = transpose(ref [16][Tref]) ++ gen [F][16]
+// (Qwen3.swift:1176-1180) for row r of `rows` (a device table; `host` is the caller's copy of it, checked here against
+// out [out_rows][Fdec][16]); the frames behind a row's own stay as they are, and a row with F == 0 writes nothing.
+// ref == nullptr (Tref == 0): a row without a reference. 16-byte loads of gen and 16-byte stores where every gen / out
+// pointer allows it, 4-byte ones otherwise.
+struct DecodeRowDesc {
+    const int32_t* ref;  // [16][Tref] or nullptr
+    const int32_t* gen;  // [F][16]
+    int32_t Tref, F, dst_row, pad_;
+};
+void launch_build_decode_codes_rows(const DecodeRowDesc* host, const DecodeRowDesc* rows, int R, int32_t* out, int out_rows,
+                                    int Fdec, hipStream_t st);
 
 // copies rows (bf16) between strided buffers: dst[r][0..dim) = src[r][0..dim)
 void launch_copy_rows(const uint16_t* src, int lds, uint16_t* dst, int ldd, int rows, int dim, hipStream_t st);

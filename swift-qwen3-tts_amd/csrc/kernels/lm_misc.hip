@@ -2,6 +2,8 @@
 // next-input embedding sum and the per-row loop bookkeeping. All are HBM/L2 trivial (<= 64 rows of
 // <= 2048 bf16); they exist to keep the frame step free of host round trips (the reference pays
 // >= 17 eval()/.item() syncs per frame: SURVEY.md section 3.2).
+#include <algorithm>
+
 #include "../common.h"
 #include "../kernels.h"
 #include "row_jobs.h"
@@ -86,12 +88,37 @@ __global__ void ref_embed_rows_kernel(const int32_t* codes, int T, int groups, c
     }
 }
 
-// decoder input of a voice-clone row (Qwen3.swift:1176-1180): reference frames ([16][Tref]) then generated ([F][16])
-__global__ void build_decode_codes_kernel(const int32_t* ref, int Tref, const int32_t* gen, int F, int32_t* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (Tref + F) * 16) return;
-    const int f = i >> 4, g = i & 15;
-    out[i] = f < Tref ? ref[(size_t)g * Tref + f] : gen[(size_t)(f - Tref) * 16 + g];
+// Decoder input of the rows of a decode batch (Qwen3.swift:1176-1180; kernels.h DecodeRowDesc): per row the reference frames
+// ([16][Tref], none for a row without a reference) then the generated ones ([F][16]). blockIdx.y = row, one thread per quarter
+// frame (4 codes, 16 bytes). A pure copy: the reference part transposes [16][Tref] into frames, the generated part moves as is.
+template <bool VEC>
+__global__ __launch_bounds__(256) void build_decode_codes_rows_kernel(const DecodeRowDesc* rows, int32_t* out, int Fdec) {
+    const DecodeRowDesc d = rows[blockIdx.y];
+    if (d.F <= 0) return;
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (d.Tref + d.F) * 4) return;
+    const int f = q >> 2, g = (q & 3) * 4;
+    int32_t v[4];
+    if (f < d.Tref) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = d.ref[(size_t)(g + j) * d.Tref + f];
+    } else {
+        const int32_t* src = d.gen + (size_t)(f - d.Tref) * 16 + g;
+        if constexpr (VEC) {
+            const int4 w = *reinterpret_cast<const int4*>(src);
+            v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = src[j];
+        }
+    }
+    int32_t* dst = out + ((size_t)d.dst_row * Fdec + f) * 16 + g;
+    if constexpr (VEC) {
+        *reinterpret_cast<int4*>(dst) = make_int4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dst[j] = v[j];
+    }
 }
 
 __global__ void f32_to_bf16_kernel(const float* x, uint16_t* out, int n) {
@@ -252,10 +279,22 @@ void launch_ref_embed_rows(const int32_t* codes, int T, int groups, const uint16
     if (T <= 0) return;
     hipLaunchKernelGGL(ref_embed_rows_kernel, dim3(T), dim3(256), 0, st, codes, T, groups, codec_emb, cp_emb, H, out, ldo);
 }
-void launch_build_decode_codes(const int32_t* ref, int Tref, const int32_t* gen, int F, int32_t* out, hipStream_t st) {
-    const int n = (Tref + F) * 16;
-    if (n <= 0) return;
-    hipLaunchKernelGGL(build_decode_codes_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ref, Tref, gen, F, out);
+void launch_build_decode_codes_rows(const DecodeRowDesc* host, const DecodeRowDesc* rows, int R, int32_t* out, int out_rows,
+                                    int Fdec, hipStream_t st) {
+    int frames = 0;
+    bool vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    for (int r = 0; r < R; ++r) {
+        const DecodeRowDesc& d = host[r];
+        if (d.F <= 0) continue;
+        Q3_CHECK(d.Tref >= 0 && (d.Tref == 0 || d.ref) && d.gen && d.dst_row >= 0 && d.dst_row < out_rows && d.Tref + d.F <= Fdec, 7,
+                 "internal error: decode row outside the decoder's code buffer");
+        frames = std::max(frames, d.Tref + d.F);
+        vec = vec && (reinterpret_cast<uintptr_t>(d.gen) & 15) == 0;
+    }
+    if (frames == 0) return;
+    const dim3 grid((frames * 4 + 255) / 256, R);
+    if (vec) hipLaunchKernelGGL(build_decode_codes_rows_kernel<true>, grid, dim3(256), 0, st, rows, out, Fdec);
+    else hipLaunchKernelGGL(build_decode_codes_rows_kernel<false>, grid, dim3(256), 0, st, rows, out, Fdec);
 }
 void launch_f32_to_bf16(const float* x, uint16_t* out, int n, hipStream_t st) {
     if (n <= 0) return;

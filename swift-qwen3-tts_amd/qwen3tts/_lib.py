@@ -84,6 +84,11 @@ class Timing(C.Structure):
                 ("frontend_ms", C.c_double), ("first_audio_ms", C.c_double), ("launches_per_frame_step", C.c_int32)]
 
 
+class VoiceInfo(C.Structure):  # q3tts_voice_info
+    _fields_ = [("ref_frames", C.c_int32), ("ref_text_tokens", C.c_int32), ("n_ref_samples", C.c_int64),
+                ("device_bytes", C.c_int64)]
+
+
 class AttnDebug(C.Structure):  # q3tts_attn_debug
     _fields_ = [("n_heads", C.c_int32), ("n_kv", C.c_int32), ("B", C.c_int32), ("eps", C.c_float), ("scale", C.c_float),
                 ("max_pages", C.c_int32), ("fixed_len", C.c_int32), ("identity_pages", C.c_int32), ("chunk", C.c_int32),
@@ -125,6 +130,14 @@ def lib() -> C.CDLL:
                                  C.POINTER(Result)]
     L.q3tts_generate_queued.argtypes = [vp, C.POINTER(Request), C.c_int32, C.c_int32, C.POINTER(Sampling), EVENT_CB, vp,
                                         C.POINTER(Result)]
+    L.q3tts_voice_create.argtypes = [vp, f32p, C.c_int64, i32p, C.c_int32, C.POINTER(vp)]
+    L.q3tts_voice_free.argtypes = [vp, vp]
+    L.q3tts_voice_free.restype = None
+    L.q3tts_voice_get_info.argtypes = [vp, C.POINTER(VoiceInfo)]
+    L.q3tts_generate_voices.argtypes = [vp, C.POINTER(Request), C.POINTER(vp), C.c_int32, C.POINTER(Sampling), EVENT_CB, vp,
+                                        C.POINTER(Result)]
+    L.q3tts_generate_queued_voices.argtypes = [vp, C.POINTER(Request), C.POINTER(vp), C.c_int32, C.c_int32, C.POINTER(Sampling),
+                                               EVENT_CB, vp, C.POINTER(Result)]
     L.q3tts_generate_begin.argtypes = [vp, C.POINTER(Request), C.c_int32, C.POINTER(Sampling), EVENT_CB, vp, C.c_int32, C.POINTER(vp)]
     L.q3tts_generate_end.argtypes = [vp, vp, C.POINTER(Result)]
     L.q3tts_pcm_to_int16.argtypes = [f32p, C.c_int64, C.POINTER(C.c_int16)]
@@ -158,6 +171,8 @@ def lib() -> C.CDLL:
                                      C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, i32p]
     L.q3tts_debug_linear.argtypes = [vp, u16p, u16p, u16p, C.c_int32, C.c_int32, C.c_int32, u16p]
     L.q3tts_debug_attention.argtypes = [vp, C.POINTER(AttnDebug)]
+    if hasattr(L, "q3tts_debug_build_decode_codes"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_debug_build_decode_codes.argtypes = [vp, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
     L.q3tts_debug_codec_stage.argtypes = [vp, i32p, C.c_int32, C.c_char_p, f32p, C.c_int64, i32p, i32p]
     _lib = L
     return L

@@ -73,6 +73,9 @@ class GenerationRequest:
     route: int = 0
     # this request's own sampling parameters (None: the call's); a static batch or a queue may mix them freely
     sampling: Optional[RequestSampling] = None
+    # a reusable voice prompt (Qwen3TTSModel.create_voice): the request is then a voice-clone request whose reference is that
+    # voice -- no ref_audio / ref_text_ids beside it; speaker, instruct_ids and route are ignored
+    voice: Optional["Voice"] = None
 
 
 @dataclass
@@ -81,6 +84,35 @@ class GenerationResult:
     codes: np.ndarray  # int32 [n_frames][16]
     info: AudioGenerationInfo
     status: int = 0
+
+
+class Voice:
+    """A reference clip and its transcript, encoded once and held on the device (q3tts_voice). Requests name it through
+    GenerationRequest.voice; it stays usable until close() (or the end of a `with` block), or until its model is closed.
+    Closing a voice while a call that names it is running is an error of the caller."""
+
+    def __init__(self, model: "Qwen3TTSModel", handle: C.c_void_p):
+        self._model, self._h = model, handle
+        vi = L.VoiceInfo()
+        model._check(model._lib.q3tts_voice_get_info(handle, C.byref(vi)))
+        self.info = vi  # ref_frames, ref_text_tokens, n_ref_samples, device_bytes
+
+    def close(self):
+        if self._h and self._model._h:  # (a closed model has released its voices already)
+            self._model._lib.q3tts_voice_free(self._model._h, self._h)
+        self._h = None
+
+    def __enter__(self) -> "Voice":
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def chat_template_ids(tokenizer: Callable[[str], List[int]], text: str, instruct: Optional[str] = None) -> dict:
@@ -207,6 +239,31 @@ class Qwen3TTSModel:
         self._check(self._lib.q3tts_model_arena_checksum(self._h, C.byref(v)))
         return int(v.value)
 
+    def create_voice(self, ref_audio: np.ndarray, ref_text_ids: Sequence[int]) -> Voice:
+        """q3tts_voice_create: encodes the reference clip (24 kHz mono float32) once -- codec encoder, speaker encoder, the
+        prompt rows made of them -- and keeps the result on the device. ref_text_ids as GenerationRequest.ref_text_ids."""
+        ra = np.ascontiguousarray(np.asarray(ref_audio, np.float32).reshape(-1))
+        rt = np.ascontiguousarray(ref_text_ids, np.int32)
+        h = C.c_void_p()
+        self._check(self._lib.q3tts_voice_create(self._h, ra.ctypes.data_as(L.f32p), ra.size, rt.ctypes.data_as(L.i32p), rt.size,
+                                                 C.byref(h)))
+        return Voice(self, h)
+
+    @staticmethod
+    def _voices(reqs: Sequence[GenerationRequest]):
+        """The q3tts_voice* array of a call, or None when no request names a voice."""
+        vs = [getattr(r, "voice", None) for r in reqs]
+        if not any(v is not None for v in vs):
+            return None
+        arr = (C.c_void_p * len(reqs))()
+        for i, v in enumerate(vs):
+            if v is None:
+                continue
+            if not v._h:
+                raise Qwen3TTSError(3, "Invalid input: the voice of request %d has been closed" % i)
+            arr[i] = v._h
+        return arr
+
     def last_timing(self) -> L.Timing:
         t = L.Timing()
         self._lib.q3tts_last_timing(self._h, C.byref(t))
@@ -237,6 +294,11 @@ class Qwen3TTSModel:
                 keep += [ra, rt]
                 arr[i].ref_audio = ra.ctypes.data_as(L.f32p)
                 arr[i].n_ref_samples = ra.size
+                arr[i].ref_text_ids = rt.ctypes.data_as(L.i32p)
+                arr[i].n_ref_text_ids = rt.size
+            elif r.ref_text_ids is not None and getattr(r, "voice", None) is not None:
+                rt = np.ascontiguousarray(r.ref_text_ids, np.int32)  # (passed on as given: the library refuses it beside a voice)
+                keep.append(rt)
                 arr[i].ref_text_ids = rt.ctypes.data_as(L.i32p)
                 arr[i].n_ref_text_ids = rt.size
         return arr, keep
@@ -291,7 +353,11 @@ class Qwen3TTSModel:
                            audio_window_frames, audio_lookahead_frames, row_base, reqs=reqs)
         cb = self._event_cb(on_event)
         res = (L.Result * len(reqs))()
-        st = self._lib.q3tts_generate(self._h, arr, len(reqs), C.byref(s), cb, None, res)
+        voices = self._voices(reqs)
+        if voices is not None:
+            st = self._lib.q3tts_generate_voices(self._h, arr, voices, len(reqs), C.byref(s), cb, None, res)
+        else:
+            st = self._lib.q3tts_generate(self._h, arr, len(reqs), C.byref(s), cb, None, res)
         del keep
         return self._collect(st, res, len(reqs))
 
@@ -305,7 +371,8 @@ class Qwen3TTSModel:
         row_base=row_base + i) with the same keywords. Events as generate_batch's, except that a request's ("info", ...) /
         ("audio", ...) arrive as soon as its audio is decoded. With audio_chunk_frames > 0 and audio_window_frames > 0 every
         request's audio is streamed as if it ran alone: ("audio_chunk", (offset, samples)) events carry its request index and
-        leave while it generates, "info" / "audio" once its last chunk has landed. Refused: voice-clone requests,
+        leave while it generates, "info" / "audio" once its last chunk has landed. Refused: voice-clone requests that carry
+        ref_audio (requests that name a `voice` are served, q3tts_generate_queued_voices; not with streamed audio),
         audio_chunk_frames > 0 without a window (audio_window_frames == 0) or below the decoder's history."""
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
@@ -313,7 +380,11 @@ class Qwen3TTSModel:
         cb = self._event_cb(on_event)
         res = (L.Result * len(reqs))()
         n_slots = int(self.info.max_batch) if slots is None else int(slots)
-        st = self._lib.q3tts_generate_queued(self._h, arr, len(reqs), n_slots, C.byref(s), cb, None, res)
+        voices = self._voices(reqs)
+        if voices is not None:
+            st = self._lib.q3tts_generate_queued_voices(self._h, arr, voices, len(reqs), n_slots, C.byref(s), cb, None, res)
+        else:
+            st = self._lib.q3tts_generate_queued(self._h, arr, len(reqs), n_slots, C.byref(s), cb, None, res)
         del keep
         return self._collect(st, res, len(reqs))
 
@@ -372,6 +443,8 @@ class Qwen3TTSModel:
         background AR loop is raised by generate_batch_end; last_timing() describes the job ended last.
         more_follows=False (the last batch of a queue) lets the decode use the whole chip instead of leaving room for a
         next batch."""
+        if self._voices(reqs) is not None:  # (q3tts.h: voices arrive through generate_batch and generate_queued only)
+            raise Qwen3TTSError(3, "Invalid input: requests that name a voice are not supported by generate_batch_begin")
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames, row_base=row_base,
                            reqs=reqs)

@@ -99,8 +99,25 @@ public enum Qwen3TTSChunkedGeneration: Sendable {
     case audio([Float])
 }
 
+/// A reusable voice prompt (q3tts_voice): a reference clip and its transcript, encoded once and held on the device. Made by
+/// `Qwen3TTSModel.createVoice`; requests name it through `generateVoiceClone(text:voice:...)`. It keeps its model alive and
+/// releases its buffers when the last reference goes; it must not go while a call that names it is running.
+public final class Qwen3TTSVoice {
+    fileprivate let model: Qwen3TTSModel
+    fileprivate let handle: OpaquePointer
+    public let info: q3tts_voice_info   // ref_frames, ref_text_tokens, n_ref_samples, device_bytes
+
+    fileprivate init(model: Qwen3TTSModel, handle: OpaquePointer) {
+        self.model = model; self.handle = handle
+        var vi = q3tts_voice_info()
+        q3tts_voice_get_info(handle, &vi)
+        self.info = vi
+    }
+    deinit { q3tts_voice_free(model.handle, handle) }
+}
+
 public final class Qwen3TTSModel {
-    private var handle: OpaquePointer?
+    fileprivate var handle: OpaquePointer?
     public var tokenizer: Tokenizer?
     private let info: q3tts_model_info
     /// Qwen3.swift:31 -- the decoded config.json (Config.swift's type, unchanged)
@@ -265,6 +282,30 @@ public final class Qwen3TTSModel {
                        onEvent: onToken.map { cb in { ev in if case .token(let t) = ev { cb(t) } } })
     }
 
+    /// The reference of a voice-clone request, encoded once (q3tts_voice_create): codec encoder, speaker encoder and the prompt
+    /// rows made of them run here and never again for the requests that name the voice.
+    public func createVoice(referenceAudio: [Float], referenceText: String) throws -> Qwen3TTSVoice {
+        guard let tokenizer else { throw AudioGenerationError.modelNotInitialized("Model not initialized: Tokenizer not loaded") }
+        let refIds = tokenizer.encode(text: "<|im_start|>assistant\n\(referenceText)<|im_end|>\n").map(Int32.init)   // Qwen3.swift:448-449
+        var v: OpaquePointer?
+        let st = referenceAudio.withUnsafeBufferPointer { ra in
+            refIds.withUnsafeBufferPointer { rt in
+                q3tts_voice_create(handle, ra.baseAddress, Int64(ra.count), rt.baseAddress, Int32(rt.count), &v)
+            }
+        }
+        guard st == Q3TTS_OK, let v else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
+        return Qwen3TTSVoice(model: self, handle: v)
+    }
+
+    /// generateVoiceClone with a voice made by `createVoice` instead of the clip: the same audio, bit for bit, without the front end
+    public func generateVoiceClone(text: String, voice: Qwen3TTSVoice, language: String = "auto", temperature: Float = 0.9,
+                                   topK: Int = 50, topP: Float = 1.0, repetitionPenalty: Float = 1.5, maxTokens: Int = 2048,
+                                   seed: UInt64 = 0, onToken: ((Int) -> Void)? = nil) throws -> [Float] {
+        try run(text: text, speaker: nil, instruct: nil, language: language, temperature: temperature, topK: topK,
+                topP: topP, repetitionPenalty: repetitionPenalty, maxTokens: maxTokens, seed: seed, voice: voice,
+                onEvent: onToken.map { cb in { ev in if case .token(let t) = ev { cb(t) } } })
+    }
+
     /// extractSpeakerEmbedding(_:sampleRate:) -- Qwen3.swift:222-249
     public func extractSpeakerEmbedding(_ audio: [Float], sampleRate: Int = 24000) throws -> [Float] {
         var out = [Float](repeating: 0, count: Int(info.speaker_embedding_dim))
@@ -277,7 +318,8 @@ public final class Qwen3TTSModel {
 
     private func run(text: String, speaker: String?, instruct: String?, language: String, temperature: Float, topK: Int,
                      topP: Float, repetitionPenalty: Float, maxTokens: Int, seed: UInt64, route: Int32 = 0,
-                     referenceAudio: [Float] = [], refTextIds: [Int32] = [], chunkFrames: Int = 0, windowFrames: Int = 0,
+                     referenceAudio: [Float] = [], refTextIds: [Int32] = [], voice: Qwen3TTSVoice? = nil, chunkFrames: Int = 0,
+                     windowFrames: Int = 0,
                      onChunk: ((Int, [Float]) -> Void)? = nil,
                      onEvent: ((Qwen3TTSGeneration) -> Void)?) throws -> [Float] {
         guard let tokenizer else { throw AudioGenerationError.modelNotInitialized("Model not initialized: Tokenizer not loaded") }
@@ -316,7 +358,10 @@ public final class Qwen3TTSModel {
                                 req.ref_audio = ra.count > 0 ? ra.baseAddress : nil; req.n_ref_samples = Int64(ra.count)   // generateVoiceClone
                                 req.ref_text_ids = rt.count > 0 ? rt.baseAddress : nil; req.n_ref_text_ids = Int32(rt.count)
                                 req.route = route   // 1 / 2: generateVoiceDesign / generateCustomVoice called directly
-                                return q3tts_generate(handle, &req, 1, &sampling, (onEvent == nil && onChunk == nil) ? nil : eventTrampoline, box.toOpaque(), &result)
+                                let cb: q3tts_event_cb? = (onEvent == nil && onChunk == nil) ? nil : eventTrampoline
+                                guard let voice else { return q3tts_generate(handle, &req, 1, &sampling, cb, box.toOpaque(), &result) }
+                                var vs: [OpaquePointer?] = [voice.handle]   // the request's reference is the voice
+                                return q3tts_generate_voices(handle, &req, &vs, 1, &sampling, cb, box.toOpaque(), &result)
                             }
                         }
                     }

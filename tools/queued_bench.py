@@ -2,6 +2,7 @@
 """Continuous batching against static batches.
 
   python tools/queued_bench.py [--preset 1.7b] [--slots 32] [--requests 256] [--stream CHUNK,WINDOW,LOOKAHEAD] [--mixed-sampling]
+  python tools/queued_bench.py --preset 1.7b-base --voices 4 [--slots 32] [--requests 256]
 
 Two workloads on bench.py's synthetic checkpoint and request builder:
   ragged   max_tokens uniform in 50..400 (seeded), temperature 0.9, seed 1234: rows end at their caps (or EOS) at different frames
@@ -18,6 +19,10 @@ its last TOKEN's arrival (the burst boundary that retired it) minus its generate
 --mixed-sampling gives the ragged workload's requests parameters of their own (q3tts_sampling.per_request), four sets in turn:
 the call's, greedy, top-k 20 / top-p 0.9 / T 0.7 with a seed, and repetition penalty 1.5; static and queued must still agree bit
 for bit, and the queue's rows now include top-p rows beside the others in every frame step.
+--voices N (a Base checkpoint) runs the ragged workload as voice-clone requests with N reference clips (3 s each) shared round-robin:
+  static   pipelined batches whose requests carry their clip as ref_audio (every batch encodes its clips again)
+  queued   one q3tts_generate_queued call whose requests name one of N voices made once by create_voice
+alternating --repeat times, with frames/s, frontend / prefill / codec milliseconds of each and the bit-identity of the two.
 """
 from __future__ import annotations
 
@@ -38,7 +43,7 @@ import bench  # noqa: E402  (checkpoint synthesis and request builder of the hea
 def run_static(model, reqs, slots, kw):
     """Pipelined begin / end batches in request order (bench.py's pipeline): the next batch's frame loop overlaps the decode
     of the one before."""
-    out, steps, pre, codec = [], 0, 0.0, 0.0
+    out, steps, pre, codec, fe = [], 0, 0.0, 0.0, 0.0
     batches = [(lo, reqs[lo:lo + slots]) for lo in range(0, len(reqs), slots)]
     t0 = time.perf_counter()
     job = model.generate_batch_begin(batches[0][1], row_base=batches[0][0], more_follows=len(batches) > 1, **kw)
@@ -52,8 +57,9 @@ def run_static(model, reqs, slots, kw):
         steps += tm.frame_steps
         pre += tm.prefill_ms
         codec += tm.codec_ms
+        fe += tm.frontend_ms
         job = nxt
-    return out, time.perf_counter() - t0, steps, pre, codec
+    return out, time.perf_counter() - t0, steps, pre, codec, fe
 
 
 def run_queued(model, reqs, slots, kw):
@@ -61,7 +67,7 @@ def run_queued(model, reqs, slots, kw):
     out = model.generate_queued(reqs, slots=slots, **kw)
     dt = time.perf_counter() - t0
     tm = model.last_timing()
-    return out, dt, tm.frame_steps, tm.prefill_ms, tm.codec_ms
+    return out, dt, tm.frame_steps, tm.prefill_ms, tm.codec_ms, tm.frontend_ms
 
 
 def run_queued_timed(model, reqs, slots, kw):
@@ -86,6 +92,47 @@ def run_queued_timed(model, reqs, slots, kw):
     return out, dt, tm, np.asarray(lat)
 
 
+def run_voices(model, args):
+    """The ragged workload as voice-clone requests: static ref_audio batches against the queue with voices."""
+    from qwen3tts import GenerationRequest, synth
+    clips = [synth.synthetic_reference_audio(k, 3.0) for k in range(args.voices)]
+    base = bench.build_requests(args.preset, 0, args.requests, args.n_text, 0)
+    texts = [base[k].ref_text_ids for k in range(args.voices)]
+    t0 = time.perf_counter()
+    voices = [model.create_voice(clips[k], texts[k]) for k in range(args.voices)]
+    print(f"# {args.voices} voices created in {(time.perf_counter() - t0) * 1e3:.1f} ms, "
+          f"{sum(v.info.device_bytes for v in voices)} device bytes, {[v.info.ref_frames for v in voices]} reference frames", flush=True)
+    caps = np.random.default_rng(1234).integers(50, 401, size=args.requests)
+    as_audio, as_voice = [], []
+    for i, (r, c) in enumerate(zip(base, caps)):
+        k = i % args.voices
+        as_audio.append(GenerationRequest(r.text_ids, 100, None, None, r.language, int(c), ref_audio=clips[k], ref_text_ids=texts[k]))
+        as_voice.append(GenerationRequest(r.text_ids, 100, None, None, r.language, int(c), voice=voices[k]))
+    kw = dict(temperature=0.9, top_k=50, top_p=1.0, repetition_penalty=1.5, seed=1234)
+    short = lambda rs: [type(r)(r.text_ids, r.target_token_count, None, None, r.language, 8, ref_audio=r.ref_audio,
+                                ref_text_ids=r.ref_text_ids, voice=r.voice) for r in rs[:2 * args.slots]]
+    run_static(model, short(as_audio), args.slots, kw)  # warm-up: frame graphs, projected tables, codec and front-end scratch
+    run_queued(model, short(as_voice), args.slots, kw)
+    print(f"# {args.preset} bf16, {args.requests} voice-clone requests, {args.voices} clips of 3 s, slots {args.slots}; "
+          "frames/s = generated frames / wall time (front end and codec included)")
+    last = {}
+    for rep in range(args.repeat):
+        for path in ("static", "queued"):
+            if path == "static":
+                out, dt, steps, pre, codec, fe = run_static(model, as_audio, args.slots, kw)
+            else:
+                out, dt, steps, pre, codec, fe = run_queued(model, as_voice, args.slots, kw)
+            frames = sum(int(r.codes.shape[0]) for r in out)
+            last[path] = out
+            print(f"run {rep} {path:6s} frames {frames:7d}  wall {dt:8.3f} s  frames/s {frames / dt:9.1f}  frame_steps {steps:6d}  "
+                  f"frontend {fe:8.1f} ms  prefill {pre:8.1f} ms  codec {codec:8.1f} ms  failed {sum(1 for r in out if r.status != 0)}", flush=True)
+    same = all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio)
+               for x, y in zip(last["static"], last["queued"]))
+    print(f"bit-identical codes + pcm, all {args.requests} requests, ref_audio batches against the queue with voices: {same}", flush=True)
+    for v in voices:
+        v.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--preset", default="1.7b")
@@ -94,10 +141,17 @@ def main():
     ap.add_argument("--n-text", type=int, default=32)
     ap.add_argument("--mixed-sampling", action="store_true", help="ragged workload: four per-request parameter sets in turn")
     ap.add_argument("--stream", default=None, metavar="CHUNK,WINDOW,LOOKAHEAD", help="also run the ragged queue with streamed audio")
+    ap.add_argument("--voices", type=int, default=0, metavar="N", help="Base checkpoint: voice-clone requests, N voices shared round-robin")
+    ap.add_argument("--repeat", type=int, default=3, help="--voices: how often the two paths alternate")
     args = ap.parse_args()
     from qwen3tts import Qwen3TTSModel, RequestSampling
 
     ckpt = bench.ensure_checkpoint(args.preset, 0, None)
+    if args.voices > 0:  # (an ICL prompt carries the reference text and one row per reference frame: 3 s are 38 frames)
+        model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=192)
+        run_voices(model, args)
+        model.close()
+        return
     model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=128)
     n_instruct = 16 if args.preset == "1.7b" else 0
     base = bench.build_requests(args.preset, 0, args.requests, args.n_text, n_instruct)
@@ -124,7 +178,7 @@ def main():
     for name, reqs, kw in workloads:
         res = {}
         for path, fn in (("static", run_static), ("queued", run_queued)):
-            out, dt, steps, pre, codec = fn(model, reqs, args.slots, kw)
+            out, dt, steps, pre, codec, _ = fn(model, reqs, args.slots, kw)
             frames = sum(int(r.codes.shape[0]) for r in out)
             res[path] = (out, dt, steps, frames)
             print(f"{name:8s} {path:6s} frames {frames:7d}  wall {dt:8.3f} s  frames/s {frames / dt:9.1f}  frame_steps {steps:6d}  "

@@ -206,7 +206,19 @@ typedef struct {
                                    reference's end trim to count(code0 > 0) frames (SpeechTokenizer.swift:831-833) cannot apply
                                    to samples that have already left. audio_chunk_frames must be at
                                    least the causal tail's history (3 frames for the shipped decoder geometry; checked before any
-                                   GPU work). Not combined with voice-clone rows (those fall back to 0). Also honoured by
+                                   GPU work). A call with a voice-clone row (ref_audio or a voice) falls back to 0 for the whole
+                                   batch unless audio_stream_reference is set. With it a clone row, whose decoder runs over
+                                   [reference ++ generated] frames (Qwen3.swift:1178-1186), is streamed with its R reference
+                                   frames as a prefix of its stream (the definition is at q3tts_codec_decode_streamed_prefixed):
+                                   the prefix is decoded in chunks of its own whose lookahead stops at frame R and whose
+                                   samples are never delivered; generated chunk k covers frames [R + kC, R + (k+1)C) of
+                                   ref ++ gen, its window reaches back into the reference while kC < window, and it is
+                                   decodable once the row has (k+1)C + lookahead generated frames or is final. The row's
+                                   audio is the causal tail's output from sample R * 1920 on: AUDIO_CHUNK.sample_offset =
+                                   k * C * 1920, AUDIO is the concatenation, n * 1920 samples for n generated frames, no end
+                                   trim (as for every streamed row), and the cut is exactly R * 1920 where the one-shot clone
+                                   path's Float proportion (Qwen3.swift:1195-1199) needs the final length and can differ by a
+                                   sample. Plain rows of such a batch are streamed exactly as without the flag. Also honoured by
                                    q3tts_generate_queued, per request: every request of the queue is streamed as if alone */
     int32_t audio_lookahead_frames; /* frames to the right of a chunk that must exist before it is decoded (default 4) */
     uint32_t row_base;    /* new: global index of reqs[0] in a job whose rows are sharded over several processes (one
@@ -222,6 +234,10 @@ typedef struct {
                              q3tts_generate of reqs[i] alone, with per_request == NULL, the call's sampling with row i's set
                              fields folded in, and row_base = sampling->row_base + i. The frame graphs do not depend on
                              the values: no call re-captures one because parameters changed */
+    int32_t audio_stream_reference; /* new, 0 (default): voice-clone rows are never streamed while they generate (see
+                             audio_window_frames and the voices comment). 1, with audio_chunk_frames > 0 and audio_window_frames > 0:
+                             clone rows -- ref_audio rows and voices alike -- are streamed with their reference in front of their
+                             stream, as q3tts_codec_decode_streamed_prefixed defines it. Call-wide, like the other audio_* fields */
 } q3tts_sampling;
 void q3tts_default_sampling(q3tts_sampling* s);
 
@@ -366,8 +382,25 @@ q3tts_status q3tts_generate_queued(q3tts_model* m, const q3tts_request* reqs, in
  * Refused with Q3TTS_ERR_INVALID_INPUT before any GPU work, the engine staying usable: a voice created on another model handle
  * (or already freed); a voice together with ref_audio or ref_text_ids on the same request; an ICL prompt longer than max_prompt
  * (the queue computes the length in its pre-flight check); and for q3tts_generate_queued_voices also audio_chunk_frames > 0 with
- * any non-NULL voice (streamed audio for voice rows is not built) and a request that carries ref_audio (as q3tts_generate_queued).
- * q3tts_generate_voices with the streaming fields set treats voice rows as it treats ref_audio rows. */
+ * any non-NULL voice unless sampling->audio_stream_reference is set (a streamed voice row differs from the one-shot clone result
+ * in trim and cut, so it is streamed only on request), audio_stream_reference without audio_chunk_frames > 0 and
+ * audio_window_frames > 0, and a request that carries ref_audio (as q3tts_generate_queued).
+ * q3tts_generate_voices with the streaming fields set treats voice rows as it treats ref_audio rows.
+ * Streamed voice requests (audio_stream_reference = 1 with audio_chunk_frames > 0 and audio_window_frames > 0; the arithmetic
+ * is defined at q3tts_sampling.audio_window_frames and q3tts_codec_decode_streamed_prefixed): in a static call and in the queue
+ * alike a voice row's reference frames go in front of its stream as a prefix that delivers nothing. results[i] is then
+ * bit-identical to q3tts_generate of reqs[i] alone in its ref_audio form with the same sampling (the flag included) and
+ * row_base = sampling->row_base + i; per request the events are TOKEN and AUDIO_CHUNK interleaved, then INFO, then AUDIO. A
+ * voice is read-only, so what its reference leaves in the decoder's causal tail depends on the voice, on (audio_chunk_frames,
+ * audio_window_frames, audio_lookahead_frames) and on the codec kernels in use alone: the queue decodes the prefix at the first
+ * admission that streams the voice with that geometry, keeps the state on the device beside the voice, and every later
+ * admission -- any slot, lane or call -- puts it back with one launch instead of decoding the reference again. A state is the
+ * tail's history margin of every tensor a causal conv reads back into -- 3 frames of each for the shipped decoder geometry, so
+ * 3 x the summed frame bytes of those tensors per (voice, geometry), the float16 tensors of a float16 speech tokenizer at half
+ * the fp32 size (q3tts_debug_prefix_states reports the bytes held); it is not part of q3tts_voice_info.device_bytes, whose
+ * formula stands, and goes with the voice in q3tts_voice_free. A prefix whose activations left the fp16 range of the default kernels is not kept: its request
+ * is held from its first chunk and decoded again on the fp32 matrix cores like any held streamed request -- one shot over
+ * reference ++ generated, cut at R * 1920, untrimmed. Q3TTS_NO_PREFIX_CACHE=1 decodes every prefix anew (same samples). */
 typedef struct q3tts_voice q3tts_voice;
 q3tts_status q3tts_voice_create(q3tts_model* m, const float* ref_audio, int64_t n_ref_samples, const int32_t* ref_text_ids,
                                 int32_t n_ref_text_ids, q3tts_voice** out);
@@ -396,6 +429,23 @@ q3tts_status q3tts_codec_decode(q3tts_model* m, const int32_t* codes, const int3
  * hold a code sequence and want the bounded-latency arithmetic. */
 q3tts_status q3tts_codec_decode_streamed(q3tts_model* m, const int32_t* codes, const int32_t* n_frames, int32_t batch,
                                          int32_t max_frames, int32_t chunk_frames, int32_t window, int32_t lookahead, float* pcm);
+
+/* The streamed decode of rows that carry a reference prefix: the arithmetic of a streamed voice-clone row. The reference has no
+ * streaming decode; its one-shot clone decode runs over [reference ++ generated] frames and cuts the reference's samples
+ * (Qwen3.swift:1178-1199). Row b of `codes` ([batch][max_frames][16]) holds S = ref ++ gen: R = n_prefix[b] reference frames, then
+ * n = n_frames[b] generated ones, R + n <= max_frames. With C / W / L = chunk_frames / window / lookahead (window >= 0):
+ *   - prefix chunk j covers S[jC, min(R, (j+1)C)); its pre-transformer window is [max(0, jC - W), min(R, (j+1)C + L)) -- the
+ *     lookahead stops at R, so the prefix depends on nothing but the reference and (C, W, L); its samples are never delivered;
+ *   - generated chunk k covers S[R + kC, min(R + n, R + (k+1)C)); its window is [max(0, R + kC - W), min(R + n, R + (k+1)C + L)),
+ *     which reaches back into the reference while kC < W;
+ *   - the causal tail runs over the prefix latents, then the generated ones, with carried state; the row's audio is what it
+ *     gives from sample R * 1920 on: n * 1920 samples, no end trim, the cut exactly R * 1920.
+ * pcm is [batch][Fmax * 1920] with Fmax = max over b of n_frames[b]; row b's first n_frames[b] * 1920 samples are written. It
+ * runs through the slotted stream that serves the queue (batch <= max_batch), every row reset at the start, so a row's samples
+ * do not depend on the rows beside it; a row with R == 0 is q3tts_codec_decode_streamed of its codes, bit for bit. */
+q3tts_status q3tts_codec_decode_streamed_prefixed(q3tts_model* m, const int32_t* codes, const int32_t* n_prefix, const int32_t* n_frames,
+                                                  int32_t batch, int32_t max_frames, int32_t chunk_frames, int32_t window,
+                                                  int32_t lookahead, float* pcm);
 
 /* Qwen3TTSSpeechTokenizer.encode (Models/SpeechTokenizer.swift:841-846 -> SpeechTokenizerEncoder.swift:1031-1056):
  * 24 kHz mono float32 waveform -> codes [16][*n_frames] int32 (code row major, as the reference returns
@@ -517,6 +567,10 @@ q3tts_status q3tts_debug_attention(q3tts_model* m, const q3tts_attn_debug* a);
  * "block0".."block3". Output is channels-last [T][C] float32; *T,*C receive the shape. */
 q3tts_status q3tts_debug_codec_stage(q3tts_model* m, const int32_t* codes, int32_t n_frames,
                                      const char* stage, float* out, int64_t cap_floats, int32_t* T, int32_t* C);
+
+/* The voices' saved tail states (the voices comment above, "streamed voice requests"): how many are held on this handle, their
+ * device bytes, and how many admissions have been served from one since the model was loaded (a test hook). */
+q3tts_status q3tts_debug_prefix_states(q3tts_model* m, int32_t* n_states, int64_t* device_bytes, int64_t* n_restored);
 
 /* The slotted codec stream of a streamed q3tts_generate_queued, driven by the queue's schedule without the talker (a test hook:
  * the real layer widths in seconds). codes [n_reqs][max_frames][16], n_frames[n_reqs] <= max_frames. Requests take the free ones

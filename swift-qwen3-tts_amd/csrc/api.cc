@@ -106,6 +106,7 @@ void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
     s->audio_lookahead_frames = 4;
     s->row_base = 0;
     s->per_request = nullptr;
+    s->audio_stream_reference = 0;
 }
 
 q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts, q3tts_model** out) {
@@ -475,6 +476,22 @@ q3tts_status q3tts_codec_decode_streamed(q3tts_model* m, const int32_t* codes, c
     return guarded(m, [&] {
         Q3_CHECK(m && codes && n_frames && pcm, 3, "Invalid input: null argument");
         m->eng->lane0().codec_decode_streamed(codes, n_frames, batch, max_frames, chunk_frames, window, lookahead, pcm);
+    });
+}
+
+q3tts_status q3tts_codec_decode_streamed_prefixed(q3tts_model* m, const int32_t* codes, const int32_t* n_prefix, const int32_t* n_frames,
+                                                  int32_t batch, int32_t max_frames, int32_t chunk_frames, int32_t window, int32_t lookahead,
+                                                  float* pcm) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && codes && n_prefix && n_frames && pcm, 3, "Invalid input: null argument");
+        m->eng->lane0().codec_decode_streamed_prefixed(codes, n_prefix, n_frames, batch, max_frames, chunk_frames, window, lookahead, pcm);
+    });
+}
+
+q3tts_status q3tts_debug_prefix_states(q3tts_model* m, int32_t* n_states, int64_t* device_bytes, int64_t* n_restored) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && n_states && device_bytes && n_restored, 3, "Invalid input: null argument");
+        m->eng->prefix_cache().stats(n_states, device_bytes, n_restored);
     });
 }
 

@@ -548,7 +548,9 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
     S.lens_used = 0;
     const int n_chunks = ceil_div(cfg.max_frames, cfg.chunk_frames);
     // front scratch: the widest front tensor over the longest window
-    const int Fwin = cfg.window < 0 ? cfg.max_frames : std::min(cfg.max_frames, cfg.window + cfg.chunk_frames + cfg.lookahead);
+    Q3_CHECK(cfg.max_prefix >= 0 && (cfg.max_prefix == 0 || cfg.per_row), 3, "Invalid input: a reference prefix needs a slotted stream");
+    const int Fwin =
+        cfg.window < 0 ? cfg.max_frames : std::min(cfg.max_frames + cfg.max_prefix, cfg.window + cfg.chunk_frames + cfg.lookahead);
     S.fbuf_floats = size_t(cfg.rows) * Fwin * front_floats_per_frame();
     // Layout pass (no launches: the walk only counts), then one allocation. Whatever leaves this function -- the arena
     // allocation failing, a check inside run_tail -- the counting mode ends with it: nothing is launched while `dry` is set,
@@ -588,9 +590,11 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
         // the tensors with history, as one table for roll_history_rows (the counting pass recorded their places in the arena)
         std::vector<RollDesc> table;
         S.roll_max_ff = 0;
+        S.state_bytes = 0;
         for (auto& r : S.roll_offs) {
             Q3_CHECK(r.first + size_t(cfg.rows) * S.Tal * r.second * 4 <= need, 7, "internal error: a streamed tensor outside its arena");
-            table.push_back(RollDesc{reinterpret_cast<float*>(S.arena + r.first), int64_t(r.second)});
+            table.push_back(RollDesc{reinterpret_cast<float*>(S.arena + r.first), int64_t(r.second), int64_t(S.state_bytes)});
+            S.state_bytes += align_up(size_t(S.hist) * r.second * 4, 16);
             S.roll_max_ff = std::max<int64_t>(S.roll_max_ff, int64_t(r.second));
         }
         S.n_roll = int(table.size());
@@ -610,17 +614,51 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
         }
         S.ring_busy.assign(size_t(kRingSlots), 0);
         S.ring_next = 0;
+        S.quiet_args_host.grow(size_t(kQuietSlots) * 5 * R);
+        S.quiet_args_dev.grow(size_t(kQuietSlots) * 5 * R);
+        while (S.quiet_ev.size() < size_t(kQuietSlots)) {
+            hipEvent_t e = nullptr;
+            Q3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            S.quiet_ev.push_back(e);
+        }
+        S.quiet_used.assign(size_t(kQuietSlots), 0);
+        S.quiet_next = 0;
     }
     S.open = true;
 }
 
-void CodecRunner::stream_reset_row(int b) {
+void CodecRunner::stream_reset_row(int b, int prefix) {
     Stream& S = stream_;
     Q3_CHECK(S.open && S.cfg.per_row, 3, "Invalid input: no slotted stream is open");
     Q3_CHECK(b >= 0 && b < S.cfg.rows, 3, "Invalid input: row outside the slotted stream");
-    S.plan.reset_row(b);
+    Q3_CHECK(prefix >= 0 && prefix <= S.cfg.max_prefix, 3, "Invalid input: reference prefix longer than the stream was opened for");
+    S.plan.reset_row(b, prefix);
     launch_roll_history_rows(reinterpret_cast<const RollDesc*>(static_cast<uint8_t*>(S.roll_desc)), S.n_roll, S.roll_max_ff, S.Tal, S.hist,
                              S.cfg.chunk_frames, nullptr, b, S.cfg.rows, nf_dev_, st_);
+}
+
+void CodecRunner::stream_save_row(int b, uint8_t* blob_dev) {
+    Stream& S = stream_;
+    Q3_CHECK(S.open && S.cfg.per_row, 3, "Invalid input: no slotted stream is open");
+    Q3_CHECK(b >= 0 && b < S.cfg.rows, 3, "Invalid input: row outside the slotted stream");
+    launch_history_state_rows(reinterpret_cast<const RollDesc*>(static_cast<uint8_t*>(S.roll_desc)), S.n_roll, S.roll_max_ff, S.Tal, S.hist, b,
+                              S.cfg.rows, blob_dev, false, nullptr, st_);
+}
+
+void CodecRunner::stream_row_flag(int b, int32_t* flag_host) {
+    Q3_CHECK(stream_.open && b >= 0 && b < stream_.cfg.rows, 3, "Invalid input: row outside the slotted stream");
+    Q3_HIP(hipMemcpyAsync(flag_host, nf_dev_ + b, 4, hipMemcpyDeviceToHost, st_));
+}
+
+void CodecRunner::stream_load_row(int b, int prefix, const uint8_t* blob_dev) {
+    Stream& S = stream_;
+    Q3_CHECK(S.open && S.cfg.per_row, 3, "Invalid input: no slotted stream is open");
+    Q3_CHECK(b >= 0 && b < S.cfg.rows, 3, "Invalid input: row outside the slotted stream");
+    Q3_CHECK(prefix >= 1 && prefix <= S.cfg.max_prefix, 3, "Invalid input: reference prefix longer than the stream was opened for");
+    S.plan.reset_row(b, prefix);
+    S.plan.skip_prefix(b);
+    launch_history_state_rows(reinterpret_cast<const RollDesc*>(static_cast<uint8_t*>(S.roll_desc)), S.n_roll, S.roll_max_ff, S.Tal, S.hist, b,
+                              S.cfg.rows, const_cast<uint8_t*>(blob_dev), true, nf_dev_, st_);
 }
 
 void CodecRunner::stream_release(int ring) {
@@ -635,7 +673,7 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
     const CodecDecoderConfig& dc = m_.cfg.codec;
     const int B = S.cfg.rows, C = S.cfg.chunk_frames;
     const size_t lat = size_t(dc.latent_dim);
-    const int Fwin = std::min(S.cfg.max_frames, S.cfg.window + C + S.cfg.lookahead);  // the front scratch's frames per row (stream_open)
+    const int Fwin = std::min(S.cfg.max_frames + S.cfg.max_prefix, S.cfg.window + C + S.cfg.lookahead);  // the front scratch's frames per row (stream_open)
     Q3_CHECK(code_stride_frames >= S.cfg.max_frames, 3, "Invalid input: code rows shorter than the stream's max_frames");
     const std::string none;
     std::vector<RowPlan> rows;
@@ -643,12 +681,17 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
         bool any = false;
         for (int b = 0; b < B && !any; ++b) any = S.plan.decodable(b, std::min(avail[b], S.cfg.max_frames), final_rows && final_rows[b]);
         if (!any) return false;
-        if (S.ring_busy[size_t(S.ring_next)]) return true;  // the oldest pass has not been taken yet
-        const int slot = S.ring_next;
+        // a pass in which no row emits (reference prefixes alone) leaves the ring alone
+        bool emits = false;
+        for (int b = 0; b < B; ++b)
+            emits = emits || (!S.plan.in_prefix(b) && S.plan.decodable(b, std::min(avail[b], S.cfg.max_frames), final_rows && final_rows[b]));
+        if (emits && S.ring_busy[size_t(S.ring_next)]) return true;  // the oldest pass has not been taken yet
+        const int slot = emits ? S.ring_next : S.quiet_next;
         S.plan.plan_pass(avail, final_rows, rows);
         // ---- per-row arguments of this pass; everything that becomes an address is checked here ----
-        int32_t* h = S.ring_args_host + size_t(slot) * 5 * B;
-        int32_t* d = S.ring_args_dev + size_t(slot) * 5 * B;
+        int32_t* h = emits ? S.ring_args_host + size_t(slot) * 5 * B : S.quiet_args_host + size_t(slot) * 5 * B;
+        int32_t* d = emits ? S.ring_args_dev + size_t(slot) * 5 * B : S.quiet_args_dev + size_t(slot) * 5 * B;
+        if (!emits && S.quiet_used[size_t(slot)]) Q3_HIP(hipEventSynchronize(S.quiet_ev[size_t(slot)]));  // its last pass has read them
         int Fw = 0, max_take = 0;
         for (int b = 0; b < B; ++b) {
             const RowPlan& r = rows[size_t(b)];
@@ -665,10 +708,17 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
             Fw = std::max(Fw, h[0 * B + b]);
             max_take = std::max(max_take, h[1 * B + b]);
         }
-        S.ring_busy[size_t(slot)] = 1;
-        S.ring_next = (slot + 1) % kRingSlots;
-        hipEvent_t begun = S.ring_ev[size_t(2) * slot], done = S.ring_ev[size_t(2) * slot + 1];
-        Q3_HIP(hipEventRecord(begun, st_));
+        hipEvent_t begun = nullptr, done = nullptr;
+        if (emits) {
+            S.ring_busy[size_t(slot)] = 1;
+            S.ring_next = (slot + 1) % kRingSlots;
+            begun = S.ring_ev[size_t(2) * slot];
+            done = S.ring_ev[size_t(2) * slot + 1];
+            Q3_HIP(hipEventRecord(begun, st_));
+        } else {
+            S.quiet_used[size_t(slot)] = 1;
+            S.quiet_next = (slot + 1) % kQuietSlots;
+        }
         // (the pinned arguments of a ring slot are rewritten only after the caller has waited for the slot's `done`)
         Q3_HIP(hipMemcpyAsync(d, h, size_t(5) * B * 4, hipMemcpyHostToDevice, st_));
         Pass ps{};
@@ -686,8 +736,13 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
         Q3_HIP(hipMemsetAsync(S.pcm, 0, size_t(B) * S.Tal * up_ * 4, st_));
         run_tail(ps, S, S.lat, S.Tal, S.pcm);
         Q3_CHECK(int(S.rolls.size()) == S.n_roll, 7, "internal error: the slotted stream's history table is stale");
+        // (a row's take is below C at its last chunk and at the end of a reference prefix, after which more chunks follow)
         launch_roll_history_rows(reinterpret_cast<const RollDesc*>(static_cast<uint8_t*>(S.roll_desc)), S.n_roll, S.roll_max_ff, S.Tal, S.hist, C,
-                                 d + 4 * B, -1, B, nullptr, st_);
+                                 d + 4 * B, -1, B, nullptr, st_, d + 1 * B);
+        if (!emits) {
+            Q3_HIP(hipEventRecord(S.quiet_ev[size_t(slot)], st_));
+            continue;
+        }
         float* pcm_slot = S.ring_pcm + size_t(slot) * B * C * up_;
         int32_t* nf_slot = S.ring_nf + size_t(slot) * B;
         Q3_HIP(hipMemcpy2DAsync(pcm_slot, size_t(C) * up_ * sizeof(float), S.pcm + size_t(S.hist) * up_, size_t(S.Tal) * up_ * sizeof(float),

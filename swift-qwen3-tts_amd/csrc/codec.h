@@ -46,6 +46,7 @@ class CodecRunner {
     struct StreamCfg {
         int rows = 0, chunk_frames = 0, window = 0, lookahead = 0, max_frames = 0;
         bool per_row = false;  // a slotted stream (below): rows are slots of a queue, each at a chunk phase of its own
+        int max_prefix = 0;    // slotted stream: the longest reference prefix a row may be reset with (code rows hold prefix ++ frames)
     };
     void stream_open(const StreamCfg& cfg);
     // Rows have avail[b] frames so far (final[b]: the row will get no more). Decodes every chunk that has become decodable;
@@ -73,7 +74,24 @@ class CodecRunner {
     // A new request takes row b: its chunks count from 0, its history margins in every tensor with history and its non-finite
     // flag are cleared ON THE CODEC STREAM -- behind the previous occupant's last chunk (issued by an earlier push), in front of
     // the new occupant's first. A row takes part in no pass before its first reset.
-    void stream_reset_row(int b);
+    // prefix > 0 (a streamed voice-clone row, include/q3tts.h): the row's code row starts with that many reference frames. They
+    // are decoded first, chunk by chunk like any others and with the lookahead stopping at the reference's end, and carry the
+    // tail's state into the first generated chunk; their samples are delivered nowhere (RowPlan::emit == 0) and a pass in
+    // which no row emits takes no ring slot and is not appended to stream_push_rows' `out`.
+    void stream_reset_row(int b, int prefix = 0);
+    // The state a row's occupant has left in the tail -- its margins in every tensor with history -- as one blob of
+    // stream_state_bytes() bytes of device memory (16-byte aligned), saved or restored with one launch on the codec stream.
+    // A row whose prefix has been decoded (stream_in_prefix(b) false after the pushes that decoded it) saved into a blob, and a
+    // later row -- of any index, in any slotted stream of the same chunk / window / lookahead and codec path -- reset by
+    // stream_load_row with the same prefix continue identically, bit for bit: the prefix passes are skipped.
+    size_t stream_state_bytes() const { return stream_.state_bytes; }
+    bool stream_in_prefix(int b) const { return stream_.plan.in_prefix(b); }
+    void stream_save_row(int b, uint8_t* blob_dev);
+    // row b's non-finite flag as it stands on the codec stream, to pinned host memory (a prefix that raised it is not worth keeping)
+    void stream_row_flag(int b, int32_t* flag_host);
+    // which kernels the tail of a stream runs on: 0 two-plane fp16, 1 the float16 MainDecoder, 2 the fp32 matrix cores
+    int stream_path() const { return fp32_mfma_ ? 2 : (m_.codec.f16_main && !no_h1_ ? 1 : 0); }
+    void stream_load_row(int b, int prefix, const uint8_t* blob_dev);
     // Rows have avail[b] frames of their current request in codes_dev [rows][code_stride_frames][16] (final_rows[b]: no more
     // will come). Issues passes until no row has a decodable chunk (returns false) or the ring is full (returns true: take a
     // pass, release it, push again). Issued passes are appended to `out`, oldest first. No host synchronisation.
@@ -82,6 +100,7 @@ class CodecRunner {
     void stream_release(int ring);
     int stream_chunks_of(int frames) const { return stream_.plan.chunks_of(frames); }
     static constexpr int kRingSlots = 8;
+    static constexpr int kQuietSlots = 8;
     bool streaming() const { return stream_.open; }
     int hist_frames() const;
     int upsample() const { return up_; }
@@ -154,8 +173,16 @@ class CodecRunner {
         std::vector<hipEvent_t> ring_ev;    // two per slot: begun, done
         std::vector<uint8_t> ring_busy;
         int ring_next = 0;
+        // passes in which no row emits (reference prefixes alone) take their arguments from a pool of their own
+        size_t state_bytes = 0;
+        PinnedBuf<int32_t> quiet_args_host;  // [kQuietSlots][5][rows]
+        DevBuf<int32_t> quiet_args_dev;
+        std::vector<hipEvent_t> quiet_ev;    // behind the pass that read the slot's arguments
+        std::vector<uint8_t> quiet_used;
+        int quiet_next = 0;
         ~Stream() {
             for (auto e : ring_ev) (void)hipEventDestroy(e);
+            for (auto e : quiet_ev) (void)hipEventDestroy(e);
         }
         uint8_t* take(size_t bytes);  // bump allocation (same order in stream_open's two passes and in every chunk)
         // the tail's next persistent tensor of Tal frames per row; one a later causal conv reads back into gets its margin rolled

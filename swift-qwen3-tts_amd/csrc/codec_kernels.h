@@ -154,11 +154,18 @@ void launch_stream_take_chunk(const float* front, int64_t front_bstride, float* 
 struct RollDesc {  // one tensor with history: allocation base ([B][Tal] frames) and floats per frame (float16 tensors: whole floats)
     float* base;
     int64_t frame_floats;
+    int64_t state_off;  // bytes from the start of a row's state blob to this tensor's margin (launch_history_state_rows), 16-aligned
 };
 // launch_roll_history over the n_desc tensors of a device table at once and row by row. mode (device [B]): 0 skip, 1 roll, 2 zero
 // the margin. mode == nullptr: only_row's margins are zeroed and nonfinite[only_row] cleared (a new request takes the row).
+// take (device [B], optional): the frames row b wrote in this pass; a row with fewer than `chunk` keeps the last `hist` frames
+// of [its old margin ++ those frames]. nullptr: every rolled row wrote a full chunk.
 void launch_roll_history_rows(const RollDesc* desc, int n_desc, int64_t max_frame_floats, int Tal, int hist, int chunk, const int32_t* mode,
-                              int only_row, int B, int32_t* nonfinite, hipStream_t st);
+                              int only_row, int B, int32_t* nonfinite, hipStream_t st, const int32_t* take = nullptr);
+// Row `row`'s margins in every tensor of the table -> blob (load == false), or blob -> margins with nonfinite[row] cleared
+// (load == true). One launch; the blob holds sum over the table of align16(hist * frame bytes) bytes and is 16-byte aligned.
+void launch_history_state_rows(const RollDesc* desc, int n_desc, int64_t max_frame_floats, int Tal, int hist, int row, int B, uint8_t* blob,
+                               bool load, int32_t* nonfinite, hipStream_t st);
 
 // ---- voice-clone front end (kernels/voice_frontend.hip) ------------------------------------------
 // first SEANet conv: 1 -> C channels, causal k taps (SpeechTokenizerEncoder.swift:404-414). w [C][K], out [S][C]

@@ -28,6 +28,7 @@ const DebugEnv* read_env() {
     d->nt_off = std::getenv("Q3TTS_NT") && number("Q3TTS_NT", 1) == 0;
     d->serial_jobs = number("Q3TTS_SERIAL_JOBS", 0) != 0;
     d->fail_back_half = number("Q3TTS_TEST_FAIL_BACK_HALF", 0) != 0;
+    d->no_prefix_cache = number("Q3TTS_NO_PREFIX_CACHE", 0) != 0;
     return d;
 }
 }  // namespace

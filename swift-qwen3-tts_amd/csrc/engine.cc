@@ -1067,6 +1067,130 @@ hipStream_t Engine::codec_stream(bool overlapped, bool wide) {
     return want;
 }
 
+// The audio side of a streamed queue: one slotted codec stream (codec.h) over the queue's slots on the confined codec stream,
+// the passes in flight, and every request's PCM as its chunks land. A request is complete once it has been retired and its
+// last chunk has been taken from the ring.
+struct Engine::SlotStream {
+    Engine& e;
+    hipStream_t cst = nullptr;
+    const int C, up;
+    bool hold = true;  // a request stops taking chunks at its first one flagged non-finite (the engine re-decodes it in fp32)
+    struct Out {       // one request
+        MallocPtr<float> pcm;  // [cap frames * up]
+        int frames = -1;       // its length, once retired
+        int landed = 0;        // chunks taken from the ring
+        int held_from = -1;    // first chunk held back
+        bool complete = false;
+    };
+    std::vector<Out> out;         // by request index
+    std::vector<int> req_of_row;  // the request in row b, -1: none
+    struct Flight {
+        CodecRunner::SlotPass pass;
+        std::vector<int> req;     // req_of_row when the pass was issued
+    };
+    std::deque<Flight> flights;
+    std::vector<CodecRunner::SlotPass> issued;
+    hipEvent_t ev_codes = nullptr, ev_pushed = nullptr;  // st_ -> cst: the codes are copied; cst -> st_: the last push has been read
+    bool have_first = false;
+    double codec_ms = 0, first_audio_ms = 0;
+    double t_call = 0;  // host clock at the call's start (first_audio_ms counts from it); 0: not timed
+    std::function<void(int, int, const float*, int64_t, int64_t)> on_chunk;  // request, chunk, samples, count, offset
+    std::function<void(int)> on_complete;
+
+    SlotStream(Engine& eng, int rows, int n_reqs, int chunk, int window, int lookahead, int max_frames, bool overlapped, int max_prefix = 0)
+        : e(eng), C(chunk), up(eng.codec_->upsample()), out(size_t(n_reqs)), req_of_row(size_t(rows), -1) {
+        for (hipEvent_t* ev : {&ev_codes, &ev_pushed}) Q3_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        cst = e.codec_stream(overlapped);
+        CodecRunner::StreamCfg cfg;
+        cfg.rows = rows; cfg.chunk_frames = chunk; cfg.window = window; cfg.lookahead = lookahead; cfg.max_frames = max_frames;
+        cfg.per_row = true;
+        cfg.max_prefix = max_prefix;
+        e.codec_->stream_open(cfg);
+    }
+    ~SlotStream() {  // whatever ends the call: the runner's stream is closed and nothing of it is still running
+        if (e.codec_->streaming()) e.codec_->stream_close();
+        (void)hipStreamSynchronize(cst);
+        for (hipEvent_t ev : {ev_codes, ev_pushed})
+            if (ev) (void)hipEventDestroy(ev);
+    }
+    // prefix: the reference frames in front of the row's codes (a streamed clone row); state: that prefix's saved tail state
+    void admit(int row, int req, int cap_frames, int prefix = 0, const uint8_t* state = nullptr) {
+        // on cst: behind the previous occupant's last chunk, in front of this one's first
+        if (state) e.codec_->stream_load_row(row, prefix, state);
+        else e.codec_->stream_reset_row(row, prefix);
+        req_of_row[size_t(row)] = req;
+        Out& o = out[size_t(req)];
+        o.pcm.reset(static_cast<float*>(std::malloc(std::max<size_t>(size_t(cap_frames) * up * 4, 4))));
+        Q3_CHECK(o.pcm != nullptr, 5, "out of host memory for the results");
+    }
+    void check_complete(int req) {
+        Out& o = out[size_t(req)];
+        if (o.complete || o.frames < 0 || o.landed < e.codec_->stream_chunks_of(o.frames)) return;
+        o.complete = true;
+        if (on_complete) on_complete(req);
+    }
+    // the oldest pass in flight, if it has landed (wait: whatever it takes): samples to the requests, ring slot given back
+    bool take(bool wait) {
+        if (flights.empty()) return false;
+        Flight& f = flights.front();
+        if (wait) {
+            Q3_HIP(hipEventSynchronize(f.pass.done));
+        } else {
+            const hipError_t q = hipEventQuery(f.pass.done);
+            if (q == hipErrorNotReady) return false;
+            Q3_HIP(q);
+        }
+        float ms = 0;
+        Q3_HIP(hipEventElapsedTime(&ms, f.pass.begun, f.pass.done));
+        codec_ms += ms;
+        if (!have_first && t_call > 0) {  // the first samples of any request are on the host
+            first_audio_ms = (now_s() - t_call) * 1e3;
+            have_first = true;
+        }
+        std::vector<int> touched;
+        for (size_t b = 0; b < f.pass.rows.size(); ++b) {
+            const RowPlan& r = f.pass.rows[b];
+            if (!r.part || !r.emit) continue;  // (a chunk of a reference prefix delivers nothing)
+            const int req = f.req[b];
+            Out& o = out[size_t(req)];
+            if (hold && o.held_from < 0 && f.pass.nf[b]) o.held_from = r.k;
+            if (o.held_from < 0) {
+                const int64_t off = int64_t(r.k) * C * up, n = int64_t(r.take) * up;
+                std::memcpy(o.pcm.get() + off, f.pass.pcm + b * size_t(C) * up, size_t(n) * 4);
+                if (on_chunk) on_chunk(req, r.k, o.pcm.get() + off, n, off);
+            }
+            ++o.landed;
+            touched.push_back(req);
+        }
+        e.codec_->stream_release(f.pass.ring);
+        flights.pop_front();
+        for (int req : touched) check_complete(req);
+        return true;
+    }
+    // every chunk that avail / fin now allow, on cst; a full ring is emptied from its oldest pass on
+    void push(const int32_t* codes_dev, int code_stride_frames, const int* avail, const uint8_t* fin) {
+        for (;;) {
+            issued.clear();
+            const bool more = e.codec_->stream_push_rows(codes_dev, code_stride_frames, avail, fin, issued);
+            for (auto& p : issued) flights.push_back(Flight{std::move(p), req_of_row});
+            if (!more) break;
+            take(true);
+        }
+        Q3_HIP(hipEventRecord(ev_pushed, cst));
+    }
+    void retire(int row, int frames) {
+        const int req = req_of_row[size_t(row)];
+        req_of_row[size_t(row)] = -1;
+        out[size_t(req)].frames = frames;
+        check_complete(req);
+    }
+    void finish() {  // every pass taken, the runner's stream closed
+        while (take(true)) {}
+        e.codec_->stream_close();
+        Q3_HIP(hipStreamSynchronize(cst));
+    }
+};
+
 // A streamed decode (row f1): chunks of the waveform leave while the frame loop is still producing tokens.
 struct Engine::StreamedDecode {
     Engine& e;
@@ -1076,14 +1200,30 @@ struct Engine::StreamedDecode {
     std::vector<int> avail;    // frames of row b the decoder may read
     std::vector<uint8_t> fin;  // row b has all of its frames
     int copied = 0;            // frames [0, copied) of every row are in J.dec_codes
+    // Clone rows streamed with their reference in front (q3tts_sampling.audio_stream_reference): the job's rows are the rows of
+    // a slotted stream, each with its reference frames as prefix (none for a plain row); J.dec_codes holds ref ++ gen per row.
+    std::unique_ptr<SlotStream> ss;
+    std::vector<int> prefix;
+    int stride = 0;  // frames per row of J.dec_codes and J.pcm_host
 
-    StreamedDecode(Engine& eng, Job& job, bool streamed, const q3tts_sampling& sp, q3tts_event_cb cb, void* user)
+    StreamedDecode(Engine& eng, Job& job, bool streamed, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
+                   const std::vector<ResolvedRequest>& rr, double t_start)
         : e(eng), J(job), on(streamed), avail(size_t(job.n), 0), fin(size_t(job.n), 0) {
         if (!on) return;
-        J.Fdec = e.Fcap_;  // row stride of the job's code and PCM buffers: the final lengths are not known yet
         J.cb = cb;         // fire_chunks delivers from inside the frame loop
         J.user = user;
         J.request_base = e.request_base;
+        int ref_max = 0;
+        bool any_clone = false;
+        for (const auto& r : rr) {
+            any_clone = any_clone || r.clone;
+            if (r.clone) ref_max = std::max(ref_max, r.ref_T);
+        }
+        if (any_clone) {
+            open_prefixed(sp, cb, user, rr, ref_max, t_start);
+            return;
+        }
+        J.Fdec = e.Fcap_;  // row stride of the job's code and PCM buffers: the final lengths are not known yet
         J.dec_codes.grow(size_t(J.n) * e.Fcap_ * 16);
         J.pcm_host.grow(size_t(J.n) * e.Fcap_ * J.up);
         J.clear_chunk_flags(e.Fcap_);
@@ -1096,13 +1236,72 @@ struct Engine::StreamedDecode {
         e.codec_->stream_open(cfg);
         J.streamed = true;
     }
+    void open_prefixed(const q3tts_sampling& sp, q3tts_event_cb cb, void* user, const std::vector<ResolvedRequest>& rr, int ref_max,
+                       double t_start) {
+        stride = e.Fcap_ + ref_max;
+        J.Fdec = stride;
+        J.dec_codes.grow(size_t(J.n) * stride * 16);
+        J.pcm_host.grow(size_t(J.n) * stride * J.up);
+        ss = std::make_unique<SlotStream>(e, J.n, J.n, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
+                                          e.Fcap_, true, ref_max);
+        sst = ss->cst;
+        Q3_HIP(hipEventRecord(J.ev_codec[0], sst));
+        ss->t_call = t_start;
+        if (cb) {
+            const int base = e.request_base;
+            Engine* eng = &e;
+            ss->on_chunk = [eng, cb, user, base](int req, int, const float* pcm, int64_t n, int64_t off) {
+                std::unique_lock<std::mutex> lk = eng->cb_lock();
+                audio_chunk(cb, user, base + req, pcm, n, off);
+            };
+        }
+        // every clone row's reference frames to the front of its code row (the builder also moves one generated frame, which
+        // does not exist yet: frame ref_T of the row, read by nothing before feed() has written it)
+        prefix.assign(size_t(J.n), 0);
+        J.row_desc.assign(size_t(J.n), DecodeRowDesc{});
+        for (int b = 0; b < J.n; ++b) {
+            const auto& r = rr[size_t(b)];
+            if (!r.clone || r.ref_T <= 0) continue;
+            prefix[size_t(b)] = r.ref_T;
+            J.row_desc[size_t(b)] = DecodeRowDesc{e.ref_codes_dev_ + r.ref_off, e.codes_ + size_t(b) * e.Fcap_ * 16, r.ref_T, 1, b, 0};
+        }
+        Q3_HIP(hipMemcpyAsync(J.row_desc_dev.grow(size_t(J.n)), J.row_desc.data(), size_t(J.n) * sizeof(DecodeRowDesc), hipMemcpyHostToDevice,
+                              e.st_));
+        launch_build_decode_codes_rows(J.row_desc.data(), J.row_desc_dev, J.n, J.dec_codes, J.n, stride, e.st_);
+        Q3_HIP(hipEventRecord(e.ev_[3], e.st_));
+        Q3_HIP(hipStreamWaitEvent(sst, e.ev_[3], 0));
+        for (int b = 0; b < J.n; ++b) ss->admit(b, b, e.Fcap_, prefix[size_t(b)]);
+        ss->push(J.dec_codes, stride, avail.data(), fin.data());  // the prefixes need no generated frame: they start at once
+        J.streamed = J.prefixed = true;
+    }
     ~StreamedDecode() {  // an exception must not leave the runner's stream open
+        ss.reset();
         if (on && e.codec_->streaming()) e.codec_->stream_close();
+    }
+    // the frame count at which the next chunk of a row that started with the job becomes decodable, given `launched` frame steps
+    int next_need(int launched, int chunk, int lookahead) const {
+        if (!ss) return (J.n_chunks + 1) * chunk + lookahead;
+        const int k = launched < chunk + lookahead ? 0 : (launched - lookahead) / chunk;
+        return (k + 1) * chunk + lookahead;
     }
     // frames [0, upto) of every row exist on the device once the copy below has run: hand them to the decoder, which issues
     // every chunk that avail / fin now allow
     void feed(int upto) {
         if (!on) return;
+        if (ss) {
+            if (upto > copied) {
+                for (int b = 0; b < J.n; ++b)
+                    Q3_HIP(hipMemcpyAsync(J.dec_codes + (size_t(b) * stride + prefix[size_t(b)] + copied) * 16,
+                                          e.codes_ + (size_t(b) * e.Fcap_ + copied) * 16, size_t(upto - copied) * 64, hipMemcpyDeviceToDevice,
+                                          e.st_));
+                copied = upto;
+                Q3_HIP(hipEventRecord(e.ev_[3], e.st_));
+                Q3_HIP(hipStreamWaitEvent(sst, e.ev_[3], 0));
+            }
+            ss->push(J.dec_codes, stride, avail.data(), fin.data());
+            while (ss->take(false)) {}  // what has already landed on the host leaves now
+            return;
+        }
         if (upto > copied) {
             Q3_HIP(hipMemcpy2DAsync(J.dec_codes + size_t(copied) * 16, size_t(e.Fcap_) * 64, e.codes_ + size_t(copied) * 16,
                                     size_t(e.Fcap_) * 64, size_t(upto - copied) * 64, size_t(J.n), hipMemcpyDeviceToDevice, e.st_));
@@ -1114,6 +1313,19 @@ struct Engine::StreamedDecode {
         J.n_chunks = e.codec_->stream_push(J.dec_codes, e.Fcap_, avail.data(), fin.data(), J.pcm_host, size_t(e.Fcap_) * J.up,
                                            J.chunk_done, J.nf_chunk_host);
         if (before == 0 && J.n_chunks > 0) Q3_HIP(hipEventRecord(J.ev_first_audio, sst));  // behind chunk 0's copy to the host
+    }
+    // every row is final: the remaining chunks, then the rows' samples to where a decode of [reference ++ generated] has them
+    void finish_prefixed() {
+        for (int b = 0; b < J.n; ++b) ss->retire(b, J.frames[size_t(b)]);
+        ss->finish();
+        for (int b = 0; b < J.n; ++b) {
+            const SlotStream::Out& o = ss->out[size_t(b)];
+            Q3_CHECK(o.complete, 7, "internal error: a row of the streamed job was left incomplete");
+            std::memcpy(J.pcm_host + (size_t(b) * stride + prefix[size_t(b)]) * J.up, o.pcm.get(), size_t(J.frames[size_t(b)]) * J.up * 4);
+            J.held_from[size_t(b)] = o.held_from;
+            J.nf_host[b] = o.held_from >= 0 ? 1 : 0;
+        }
+        if (ss->have_first) J.timing.first_audio_ms = ss->first_audio_ms;
     }
 };
 
@@ -1162,7 +1374,10 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
         return slot;
     }
     try {
-        back_half(J, rr, np, sp, cb, user, dbg, sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && !any_clone && !dbg, overlapped,
+        // clone rows are streamed only on request (audio_stream_reference: their reference goes in front of their stream);
+        // without it a batch with a clone row is decoded one-shot
+        back_half(J, rr, np, sp, cb, user, dbg,
+                  sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && (!any_clone || sp.audio_stream_reference != 0) && !dbg, overlapped,
                   t_start);
     } catch (...) {
         J.busy = false;
@@ -1174,7 +1389,7 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
 void Engine::back_half(Job& J, const std::vector<ResolvedRequest>& rr, const std::vector<int>& np, const q3tts_sampling& sp,
                        q3tts_event_cb cb, void* user, const DebugOpts* dbg, bool streamed, bool overlapped, double t_start) {
     if (J.background && debug_env().fail_back_half) throw Error(7, "back half failed on request (Q3TTS_TEST_FAIL_BACK_HALF)");
-    StreamedDecode sd(*this, J, streamed, sp, cb, user);
+    StreamedDecode sd(*this, J, streamed, sp, cb, user, rr, t_start);
     const int launched = frame_loop(J, rr, sp, cb, user, dbg, sd);
     hand_off(J, rr, sd, launched, overlapped);
     job_timing(J, np, launched);
@@ -1323,7 +1538,7 @@ int Engine::frame_loop(Job& J, const std::vector<ResolvedRequest>& rr, const q3t
         if (sd.on) {
             // a burst ends where the next chunk becomes decodable (its frames + the lookahead), so the chunk is issued behind
             // exactly the frames it needs instead of behind the rest of a full burst (first audio 139 -> 115 ms at 1.7B / batch 32)
-            const int need = std::min(frames_cap, (J.n_chunks + 1) * sp.audio_chunk_frames + std::max(0, sp.audio_lookahead_frames));
+            const int need = std::min(frames_cap, sd.next_need(launched, sp.audio_chunk_frames, std::max(0, sp.audio_lookahead_frames)));
             if (need > launched) burst = std::min(burst, need - launched);
         }
         for (int i = 0; i < burst; ++i) {
@@ -1387,7 +1602,7 @@ void Engine::hand_off(Job& J, const std::vector<ResolvedRequest>& rr, StreamedDe
         dframes[size_t(b)] = F > 0 ? F + J.ref_T[size_t(b)] : 0;
         Fdec = std::max(Fdec, dframes[size_t(b)]);
     }
-    J.Fdec = sd.on ? Fcap_ : Fdec;
+    J.Fdec = sd.on ? (sd.ss ? sd.stride : Fcap_) : Fdec;  // (a streamed job's row stride was fixed before its lengths were known)
     J.codes_host.resize(size_t(n) * Fcap_ * 16);
     Q3_HIP(hipMemcpyAsync(J.codes_host.data(), codes_, J.codes_host.size() * 4, hipMemcpyDeviceToHost, st_));
     if (sd.on) {  // the remaining chunks: every row is final now
@@ -1396,7 +1611,8 @@ void Engine::hand_off(Job& J, const std::vector<ResolvedRequest>& rr, StreamedDe
             sd.fin[size_t(b)] = 1;
         }
         sd.feed(launched);
-        codec_->stream_close(J.nf_host);
+        if (sd.ss) sd.finish_prefixed();
+        else codec_->stream_close(J.nf_host);
         Q3_HIP(hipStreamSynchronize(st_));
         Q3_HIP(hipEventRecord(J.ev_codec[1], sd.sst));
         J.decoded = Fdec > 0;
@@ -1535,7 +1751,7 @@ void Engine::Job::reset(int rows, int upsample) {
     held_from.assign(size_t(n), -1);
     std::memset(nf_host, 0, nf_host.capacity() * 4);
     n_chunks = chunk_frames = chunks_fired = 0;
-    streamed = decoded = background = frontend = false;
+    streamed = prefixed = decoded = background = frontend = false;
     voices.clear();
     t_first_audio = t_done = 0;
     timing = q3tts_timing{};
@@ -1635,7 +1851,11 @@ void Engine::compute_cuts(Job& J) {
         // concatenation, untrimmed -- include/q3tts.h)
         if (!J.streamed && valid > 0 && valid < ns) ns = valid;
         int64_t cut = 0;
-        if (ref_T > 0) {
+        if (J.prefixed) {
+            // a clone row streamed behind its reference: the samples of its own frames, cut exactly (the Float proportion
+            // below needs the final length, which is not known when the first chunk leaves)
+            cut = int64_t(ref_T) * up;
+        } else if (ref_T > 0) {
             cut = int64_t(float(ref_T) / float(std::max(total_f, 1)) * float(ns));
             if (!(cut > 0 && cut < ns)) cut = 0;
         }
@@ -1770,6 +1990,16 @@ std::vector<int> Engine::redo_rows_fp32(Job& J) {
         // decoded-stream coordinates: sample p of the decode is sample p - cut of the row's audio; chunk k covers
         // [k * step, (k + 1) * step). Chunks below `held` have been delivered from the first decode and stay as they are.
         const int64_t cut = J.row_cut[size_t(b)], ns = J.row_ns[size_t(b)], step = int64_t(std::max(J.chunk_frames, 1)) * up;
+        if (J.prefixed) {  // chunks count from the row's own first frame: chunk k is samples [k * step, (k + 1) * step) of its audio
+            float* own = J.st_pcm[size_t(b)].get();
+            const int64_t at = std::min(ns, int64_t(std::max(0, J.held_from[size_t(b)])) * step);
+            std::memcpy(own + at, hpcm + size_t(i) * Fd * up + cut + at, size_t(ns - at) * 4);
+            if (J.cb) {
+                std::unique_lock<std::mutex> lk = cb_lock();
+                for (int64_t lo = at; lo < ns; lo += step) audio_chunk(J.cb, J.user, J.request_base + b, own + lo, std::min(step, ns - lo), lo);
+            }
+            continue;
+        }
         const int held = J.n_chunks > 0 ? std::max(0, J.held_from[size_t(b)]) : 0;
         const int64_t from = J.n_chunks > 0 ? std::min(ns, std::max<int64_t>(0, int64_t(held) * step - cut)) : 0;
         float* pcm = J.st_pcm[size_t(b)].get();
@@ -1913,126 +2143,6 @@ ResolvedRequest Engine::check_queued(const q3tts_request& r, const q3tts_samplin
     Q3_CHECK(np + o.max_frames + 1 <= m_->talker.max_pos, 3, "Invalid input: sequence longer than the RoPE table");
     return o;
 }
-
-// The audio side of a streamed queue: one slotted codec stream (codec.h) over the queue's slots on the confined codec stream,
-// the passes in flight, and every request's PCM as its chunks land. A request is complete once it has been retired and its
-// last chunk has been taken from the ring.
-struct Engine::SlotStream {
-    Engine& e;
-    hipStream_t cst = nullptr;
-    const int C, up;
-    bool hold = true;  // a request stops taking chunks at its first one flagged non-finite (the engine re-decodes it in fp32)
-    struct Out {       // one request
-        MallocPtr<float> pcm;  // [cap frames * up]
-        int frames = -1;       // its length, once retired
-        int landed = 0;        // chunks taken from the ring
-        int held_from = -1;    // first chunk held back
-        bool complete = false;
-    };
-    std::vector<Out> out;         // by request index
-    std::vector<int> req_of_row;  // the request in row b, -1: none
-    struct Flight {
-        CodecRunner::SlotPass pass;
-        std::vector<int> req;     // req_of_row when the pass was issued
-    };
-    std::deque<Flight> flights;
-    std::vector<CodecRunner::SlotPass> issued;
-    hipEvent_t ev_codes = nullptr, ev_pushed = nullptr;  // st_ -> cst: the codes are copied; cst -> st_: the last push has been read
-    bool have_first = false;
-    double codec_ms = 0, first_audio_ms = 0;
-    double t_call = 0;  // host clock at the call's start (first_audio_ms counts from it); 0: not timed
-    std::function<void(int, int, const float*, int64_t, int64_t)> on_chunk;  // request, chunk, samples, count, offset
-    std::function<void(int)> on_complete;
-
-    SlotStream(Engine& eng, int rows, int n_reqs, int chunk, int window, int lookahead, int max_frames, bool overlapped)
-        : e(eng), C(chunk), up(eng.codec_->upsample()), out(size_t(n_reqs)), req_of_row(size_t(rows), -1) {
-        for (hipEvent_t* ev : {&ev_codes, &ev_pushed}) Q3_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-        cst = e.codec_stream(overlapped);
-        CodecRunner::StreamCfg cfg;
-        cfg.rows = rows; cfg.chunk_frames = chunk; cfg.window = window; cfg.lookahead = lookahead; cfg.max_frames = max_frames;
-        cfg.per_row = true;
-        e.codec_->stream_open(cfg);
-    }
-    ~SlotStream() {  // whatever ends the call: the runner's stream is closed and nothing of it is still running
-        if (e.codec_->streaming()) e.codec_->stream_close();
-        (void)hipStreamSynchronize(cst);
-        for (hipEvent_t ev : {ev_codes, ev_pushed})
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    void admit(int row, int req, int cap_frames) {
-        e.codec_->stream_reset_row(row);  // on cst: behind the previous occupant's last chunk, in front of this one's first
-        req_of_row[size_t(row)] = req;
-        Out& o = out[size_t(req)];
-        o.pcm.reset(static_cast<float*>(std::malloc(std::max<size_t>(size_t(cap_frames) * up * 4, 4))));
-        Q3_CHECK(o.pcm != nullptr, 5, "out of host memory for the results");
-    }
-    void check_complete(int req) {
-        Out& o = out[size_t(req)];
-        if (o.complete || o.frames < 0 || o.landed < e.codec_->stream_chunks_of(o.frames)) return;
-        o.complete = true;
-        if (on_complete) on_complete(req);
-    }
-    // the oldest pass in flight, if it has landed (wait: whatever it takes): samples to the requests, ring slot given back
-    bool take(bool wait) {
-        if (flights.empty()) return false;
-        Flight& f = flights.front();
-        if (wait) {
-            Q3_HIP(hipEventSynchronize(f.pass.done));
-        } else {
-            const hipError_t q = hipEventQuery(f.pass.done);
-            if (q == hipErrorNotReady) return false;
-            Q3_HIP(q);
-        }
-        float ms = 0;
-        Q3_HIP(hipEventElapsedTime(&ms, f.pass.begun, f.pass.done));
-        codec_ms += ms;
-        if (!have_first && t_call > 0) {  // the first samples of any request are on the host
-            first_audio_ms = (now_s() - t_call) * 1e3;
-            have_first = true;
-        }
-        std::vector<int> touched;
-        for (size_t b = 0; b < f.pass.rows.size(); ++b) {
-            const RowPlan& r = f.pass.rows[b];
-            if (!r.part) continue;
-            const int req = f.req[b];
-            Out& o = out[size_t(req)];
-            if (hold && o.held_from < 0 && f.pass.nf[b]) o.held_from = r.k;
-            if (o.held_from < 0) {
-                const int64_t off = int64_t(r.k) * C * up, n = int64_t(r.take) * up;
-                std::memcpy(o.pcm.get() + off, f.pass.pcm + b * size_t(C) * up, size_t(n) * 4);
-                if (on_chunk) on_chunk(req, r.k, o.pcm.get() + off, n, off);
-            }
-            ++o.landed;
-            touched.push_back(req);
-        }
-        e.codec_->stream_release(f.pass.ring);
-        flights.pop_front();
-        for (int req : touched) check_complete(req);
-        return true;
-    }
-    // every chunk that avail / fin now allow, on cst; a full ring is emptied from its oldest pass on
-    void push(const int32_t* codes_dev, int code_stride_frames, const int* avail, const uint8_t* fin) {
-        for (;;) {
-            issued.clear();
-            const bool more = e.codec_->stream_push_rows(codes_dev, code_stride_frames, avail, fin, issued);
-            for (auto& p : issued) flights.push_back(Flight{std::move(p), req_of_row});
-            if (!more) break;
-            take(true);
-        }
-        Q3_HIP(hipEventRecord(ev_pushed, cst));
-    }
-    void retire(int row, int frames) {
-        const int req = req_of_row[size_t(row)];
-        req_of_row[size_t(row)] = -1;
-        out[size_t(req)].frames = frames;
-        check_complete(req);
-    }
-    void finish() {  // every pass taken, the runner's stream closed
-        while (take(true)) {}
-        e.codec_->stream_close();
-        Q3_HIP(hipStreamSynchronize(cst));
-    }
-};
 
 void Engine::ensure_queue_ws() {
     if (qws_) return;
@@ -2293,11 +2403,42 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             cb(user, &ev);
         }
     };
+    // Voice requests of a streamed queue (audio_stream_reference): a slot's code row holds the voice's reference frames, then the
+    // generated ones. The reference is decoded as the row's prefix at the admission (nothing of it is delivered) unless the state
+    // it leaves in the causal tail has been saved before: then one launch puts it back (PrefixCache).
+    const int stride = Fcap_ + (streamed ? q.ref_max : 0);  // frames per row of scodes
+    std::vector<int> prefix_of((size_t)(S), 0);           // reference frames in front of the slot's current request
+    std::vector<DecodeRowDesc> ref_desc;                    // (read by the copy of an admission until that boundary's synchronisation)
+    DevBuf<DecodeRowDesc> ref_desc_dev;
+    struct PendingState {  // a state saved at this call's admissions: published once its prefix is known to have stayed finite
+        std::shared_ptr<PrefixCache::Entry> entry;
+        int flag = 0;  // index into state_flags
+    };
+    std::vector<PendingState> pending;
+    std::vector<std::shared_ptr<PrefixCache::Entry>> in_use;  // states restored in this call stay alive until its stream has drained
+    PinnedBuf<int32_t> state_flags;
+    auto settle = [&](bool wait) {  // saved states whose save has run: into the cache, unless the prefix left the fp16 range
+        for (size_t i = 0; i < pending.size();) {
+            if (wait) {
+                Q3_HIP(hipEventSynchronize(pending[i].entry->ready));
+            } else {
+                const hipError_t pq = hipEventQuery(pending[i].entry->ready);
+                if (pq == hipErrorNotReady) {
+                    ++i;
+                    continue;
+                }
+                Q3_HIP(pq);
+            }
+            if (state_flags[pending[i].flag] == 0) q.prefix_cache->publish(pending[i].entry);
+            pending.erase(pending.begin() + ptrdiff_t(i));
+        }
+    };
     if (streamed) {
         gone.resize(size_t(q.n));
-        scodes.grow(size_t(S) * Fcap_ * 16);
+        scodes.grow(size_t(S) * stride * 16);
+        if (q.prefix_cache) std::memset(state_flags.grow(size_t(q.n)), 0, size_t(q.n) * 4);
         ss = std::make_unique<SlotStream>(*this, S, q.n, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
-                                          Fcap_, true);
+                                          Fcap_, true, q.ref_max);
         ss->t_call = t_call;
         if (cb)
             ss->on_chunk = [&](int req, int, const float* pcm, int64_t n, int64_t off) {
@@ -2327,12 +2468,81 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             for (const QSlot& x : sl) before.push_back(x.req);
         const int admitted = admit(q, sl, drained);
         served += admitted;
-        if (streamed)  // a new occupant: the row's chunks, history margins and non-finite flag start over, in codec-stream order
+        if (streamed) {  // a new occupant: the row's chunks, history margins and non-finite flag start over, in codec-stream order
+            settle(false);
+            std::vector<int> fresh, primed;
+            bool any_ref = false, wait_pushed = false;
             for (int s = 0; s < S; ++s)
                 if (sl[size_t(s)].req >= 0 && before[size_t(s)] < 0) {
-                    ss->admit(s, sl[size_t(s)].req, (*q.reqs)[size_t(sl[size_t(s)].req)].max_frames);
+                    const ResolvedRequest& rq = (*q.reqs)[size_t(sl[size_t(s)].req)];
+                    fresh.push_back(s);
                     copied[size_t(s)] = 0;
+                    prefix_of[size_t(s)] = rq.voice && q.stream_reference ? rq.ref_T : 0;
+                    if (prefix_of[size_t(s)] > 0) {
+                        any_ref = true;
+                        wait_pushed = wait_pushed || reused[size_t(s)];
+                    }
                 }
+            if (any_ref) {
+                // the voices' reference frames to the front of their slots' code rows (the builder also moves one generated frame,
+                // which does not exist yet: frame ref_T of the row, read by nothing before the copy below has written it). They
+                // overwrite what the previous occupant's last chunks read: behind ev_pushed, like a new occupant's first frames.
+                if (wait_pushed) Q3_HIP(hipStreamWaitEvent(st_, ss->ev_pushed, 0));
+                ref_desc.assign(size_t(S), DecodeRowDesc{});
+                for (int s : fresh) {
+                    if (prefix_of[size_t(s)] == 0) continue;
+                    const Voice* v = (*q.reqs)[size_t(sl[size_t(s)].req)].voice;
+                    ref_desc[size_t(s)] = DecodeRowDesc{static_cast<const int32_t*>(v->codes_dev), codes_ + size_t(s) * Fcap_ * 16, v->ref_T, 1, s, 0};
+                    reused[size_t(s)] = 1;
+                }
+                Q3_HIP(hipMemcpyAsync(ref_desc_dev.grow(size_t(S)), ref_desc.data(), size_t(S) * sizeof(DecodeRowDesc), hipMemcpyHostToDevice, st_));
+                launch_build_decode_codes_rows(ref_desc.data(), ref_desc_dev, S, scodes, S, stride, st_);
+                Q3_HIP(hipEventRecord(ss->ev_codes, st_));
+                Q3_HIP(hipStreamWaitEvent(ss->cst, ss->ev_codes, 0));
+            }
+            const size_t state_bytes = codec_->stream_state_bytes();
+            for (int s : fresh) {
+                const int req = sl[size_t(s)].req, R = prefix_of[size_t(s)];
+                const ResolvedRequest& rq = (*q.reqs)[size_t(req)];
+                std::shared_ptr<PrefixCache::Entry> hit;
+                if (R > 0 && q.prefix_cache)
+                    hit = q.prefix_cache->find(rq.voice, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
+                                               codec_->stream_path(), state_bytes);
+                if (hit) {
+                    Q3_HIP(hipStreamWaitEvent(ss->cst, hit->ready, 0));
+                    ss->admit(s, req, rq.max_frames, R, hit->blob);
+                    ++q.prefix_cache->restored;
+                    in_use.push_back(std::move(hit));
+                } else {
+                    ss->admit(s, req, rq.max_frames, R);
+                    if (R > 0) primed.push_back(s);
+                }
+            }
+            if (!primed.empty()) {
+                // the prefixes need no generated frame: they are decoded now, before the row's first generated chunk can follow
+                // them, and the state they leave is taken at once. The other rows have what the last push gave them.
+                std::vector<int> have((size_t)(S), 0);
+                std::vector<uint8_t> none((size_t)(S), 0);
+                for (int s = 0; s < S; ++s) have[size_t(s)] = sl[size_t(s)].req >= 0 ? copied[size_t(s)] : 0;
+                ss->push(scodes, stride, have.data(), none.data());
+                for (int s : primed) {
+                    Q3_CHECK(!codec_->stream_in_prefix(s), 7, "internal error: a reference prefix was left undecoded at its admission");
+                    if (!q.prefix_cache || state_bytes == 0) continue;
+                    const int req = sl[size_t(s)].req;
+                    auto e = std::make_shared<PrefixCache::Entry>();
+                    e->voice = (*q.reqs)[size_t(req)].voice;
+                    e->chunk = sp.audio_chunk_frames; e->window = sp.audio_window_frames; e->lookahead = std::max(0, sp.audio_lookahead_frames);
+                    e->path = codec_->stream_path();
+                    e->bytes = state_bytes;
+                    e->blob.grow(state_bytes);
+                    Q3_HIP(hipEventCreateWithFlags(&e->ready, hipEventDisableTiming));
+                    codec_->stream_save_row(s, e->blob);
+                    codec_->stream_row_flag(s, state_flags + req);
+                    Q3_HIP(hipEventRecord(e->ready, ss->cst));
+                    pending.push_back(PendingState{std::move(e), req});
+                }
+            }
+        }
         // ---- burst: no longer than the first running row's remaining frames (its cap ends it on time) ----
         int running = 0, burst = burst_frames;
         for (const QSlot& x : sl)
@@ -2381,7 +2591,8 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                 avail[size_t(s)] = nf;
                 if (nf > copied[size_t(s)]) {
                     const size_t at = (size_t(s) * Fcap_ + copied[size_t(s)]) * 16;
-                    Q3_HIP(hipMemcpyAsync(scodes + at, codes_ + at, size_t(nf - copied[size_t(s)]) * 64, hipMemcpyDeviceToDevice, st_));
+                    const size_t to = (size_t(s) * stride + prefix_of[size_t(s)] + copied[size_t(s)]) * 16;  // behind the reference
+                    Q3_HIP(hipMemcpyAsync(scodes + to, codes_ + at, size_t(nf - copied[size_t(s)]) * 64, hipMemcpyDeviceToDevice, st_));
                     copied[size_t(s)] = nf;
                     reused[size_t(s)] = 1;
                     any_copy = true;
@@ -2393,7 +2604,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             }
             std::vector<uint8_t> fin((size_t)(S), 0);
             for (int s = 0; s < S; ++s) fin[size_t(s)] = sl[size_t(s)].req >= 0 && h_fin[size_t(s)] ? 1 : 0;
-            ss->push(scodes, Fcap_, avail.data(), fin.data());  // a retiring row's remaining chunks are all issued here
+            ss->push(scodes, stride, avail.data(), fin.data());  // a retiring row's remaining chunks are all issued here
         }
         if (admitted) {
             float ms = 0;
@@ -2434,15 +2645,23 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     double first_audio_ms = 0;
     if (streamed) {
         ss->finish();  // the passes still in flight; every request is complete behind this
+        settle(true);
+        in_use.clear();
         codec_ms = ss->codec_ms;
         first_audio_ms = ss->first_audio_ms;
         // ---- requests held back at a chunk that left the fp16 range: once more on the fp32 matrix cores, as redo_rows_fp32 does
         // for a streamed job: chunks below the held one stay as delivered, the rest (events included) come from the exact decode
         for (size_t h0 = 0; h0 < held.size(); h0 += size_t(Bm_)) {
             const int R = int(std::min(held.size() - h0, size_t(Bm_)));
-            std::vector<int> dframes((size_t)(R));
+            // (a voice request streamed behind its reference: the decoder sees reference ++ generated, as in every clone decode,
+            // and the request's samples start exactly ref_T frames in)
+            std::vector<int> dframes((size_t)(R)), refs((size_t)(R), 0);
             int Fd = 0;
-            for (int i = 0; i < R; ++i) Fd = std::max(Fd, dframes[size_t(i)] = gone[size_t(held[h0 + i])].frames);
+            for (int i = 0; i < R; ++i) {
+                const ResolvedRequest& rq = (*q.reqs)[size_t(held[h0 + i])];
+                if (rq.voice && q.stream_reference) refs[size_t(i)] = rq.voice->ref_T;
+                Fd = std::max(Fd, dframes[size_t(i)] = refs[size_t(i)] + gone[size_t(held[h0 + i])].frames);
+            }
             PinnedBuf<int32_t> nf;
             PinnedBuf<float> hpcm;
             std::memset(nf.grow(size_t(R)), 0, size_t(R) * 4);
@@ -2452,9 +2671,14 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                 DevBuf<int32_t> dcodes;
                 dcodes.grow(size_t(R) * Fd * 16);
                 hpcm.grow(size_t(R) * Fd * up);
-                for (int i = 0; i < R; ++i)
-                    Q3_HIP(hipMemcpy(dcodes + size_t(i) * Fd * 16, gone[size_t(held[h0 + i])].codes.data(), size_t(dframes[size_t(i)]) * 64,
-                                     hipMemcpyHostToDevice));
+                for (int i = 0; i < R; ++i) {
+                    const int ref = refs[size_t(i)];
+                    if (ref > 0)
+                        Q3_HIP(hipMemcpy(dcodes + size_t(i) * Fd * 16, (*q.reqs)[size_t(held[h0 + i])].voice->codes_host.data(), size_t(ref) * 64,
+                                         hipMemcpyHostToDevice));
+                    Q3_HIP(hipMemcpy(dcodes + (size_t(i) * Fd + ref) * 16, gone[size_t(held[h0 + i])].codes.data(),
+                                     size_t(dframes[size_t(i)] - ref) * 64, hipMemcpyHostToDevice));
+                }
                 float* pcm_dev = nullptr;
                 codec_->decode(dcodes, Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
                 Q3_HIP(hipMemcpyAsync(hpcm, pcm_dev, size_t(R) * Fd * up * 4, hipMemcpyDeviceToHost, cst));
@@ -2468,9 +2692,9 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                     last_error = kCodecRangeMsg;
                     continue;
                 }
-                const int64_t step = int64_t(sp.audio_chunk_frames) * up, ns = int64_t(dframes[size_t(i)]) * up;
+                const int64_t step = int64_t(sp.audio_chunk_frames) * up, ns = int64_t(dframes[size_t(i)] - refs[size_t(i)]) * up;
                 const int64_t from = std::min(ns, int64_t(o.held_from) * step);
-                std::memcpy(o.pcm.get() + from, hpcm + size_t(i) * Fd * up + from, size_t(ns - from) * 4);
+                std::memcpy(o.pcm.get() + from, hpcm + (size_t(i) * Fd + refs[size_t(i)]) * up + from, size_t(ns - from) * 4);
                 if (cb) {
                     std::unique_lock<std::mutex> lk = cb_lock();
                     for (int64_t lo = from; lo < ns; lo += step) audio_chunk(cb, user, req, o.pcm.get() + lo, std::min(step, ns - lo), lo);
@@ -2789,6 +3013,51 @@ void Engine::codec_decode_streamed(const int32_t* codes, const int32_t* n_frames
         std::memcpy(pcm + size_t(b) * max_frames * up, hpcm + size_t(b) * max_frames * up, size_t(n_frames[b]) * up * 4);
 }
 
+// The streamed decode of rows that carry a reference prefix (include/q3tts.h, "streamed clone rows"), through the slotted stream
+// with every row reset at the start; the frames arrive a chunk per push, as a stream would deliver them.
+void Engine::codec_decode_streamed_prefixed(const int32_t* codes, const int32_t* n_prefix, const int32_t* n_frames, int batch, int max_frames,
+                                            int chunk_frames, int window, int lookahead, float* pcm) {
+    Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");
+    Q3_CHECK(batch >= 1 && max_frames >= 1 && chunk_frames >= 1 && window >= 0 && lookahead >= 0, 3, "Invalid input: empty codec batch");
+    Q3_CHECK(batch <= Bm_, 3, "Invalid input: batch must be between 1 and max_batch");
+    int Fmax = 0, Rmax = 0;
+    std::vector<int32_t> total((size_t)(batch));
+    for (int b = 0; b < batch; ++b) {
+        Q3_CHECK(n_prefix[b] >= 0 && n_frames[b] >= 0 && int64_t(n_prefix[b]) + n_frames[b] <= max_frames, 3,
+                 "Invalid input: n_prefix + n_frames out of range");
+        total[size_t(b)] = n_prefix[b] + n_frames[b];
+        Fmax = std::max(Fmax, n_frames[b]);
+        Rmax = std::max(Rmax, n_prefix[b]);
+    }
+    check_caller_codes(m_->codec, codes, total.data(), batch, max_frames);
+    check_stream_chunk(chunk_frames);
+    const int up = codec_->upsample();
+    DevBuf<int32_t> dcodes;
+    dcodes.grow(size_t(batch) * max_frames * 16);
+    Q3_HIP(hipMemcpy(dcodes, codes, size_t(batch) * max_frames * 16 * 4, hipMemcpyHostToDevice));
+    SlotStream ss(*this, batch, batch, chunk_frames, window, lookahead, std::max(Fmax, 1), false, Rmax);
+    ss.hold = false;  // (as q3tts_codec_decode_streamed: the samples as the default kernels produce them)
+    for (int b = 0; b < batch; ++b) ss.admit(b, b, std::max(Fmax, 1), n_prefix[b]);
+    std::vector<int> avail((size_t)(batch));
+    std::vector<uint8_t> fin((size_t)(batch));
+    for (int have = chunk_frames;; have += chunk_frames) {
+        bool all = true;
+        for (int b = 0; b < batch; ++b) {
+            avail[size_t(b)] = std::min(n_frames[b], have);
+            fin[size_t(b)] = avail[size_t(b)] == n_frames[b] ? 1 : 0;
+            all = all && fin[size_t(b)];
+        }
+        ss.push(dcodes, max_frames, avail.data(), fin.data());
+        if (all) break;
+    }
+    for (int b = 0; b < batch; ++b) ss.retire(b, n_frames[b]);
+    ss.finish();
+    for (int b = 0; b < batch; ++b) {
+        Q3_CHECK(ss.out[size_t(b)].complete, 7, "internal error: a row of the prefixed stream was left incomplete");
+        std::memcpy(pcm + size_t(b) * Fmax * up, ss.out[size_t(b)].pcm.get(), size_t(n_frames[b]) * up * 4);
+    }
+}
+
 void Engine::check_stream_chunk(int chunk_frames) const {
     Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");
     const int hist = codec_->hist_frames();
@@ -2977,6 +3246,7 @@ bool EngineGroup::mine(const Voice* v) const {
 void EngineGroup::free_voice(Voice* v) {
     for (size_t i = 0; i < voices_.size(); ++i)
         if (voices_[i].get() == v) {
+            prefix_cache_.drop(v);  // (no call is running: a saved state is read only inside a queued call)
             voices_.erase(voices_.begin() + ptrdiff_t(i));
             return;
         }
@@ -3060,7 +3330,10 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     Q3_CHECK(model_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
     check_row_sampling(sp, n);
     check_voices(reqs, n, voices);
-    if (voices && sp.audio_chunk_frames > 0)  // (the slotted stream would need a reference prefix per row: DESIGN.md section 9)
+    Q3_CHECK(sp.audio_stream_reference == 0 || (sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0), 3,
+             "Invalid input: audio_stream_reference needs audio_chunk_frames > 0 and audio_window_frames > 0 in q3tts_generate_queued");
+    if (voices && sp.audio_chunk_frames > 0 && sp.audio_stream_reference == 0)  // (only on request: the result differs from the one-shot
+                                                                                 // clone decode in trim and cut, include/q3tts.h)
         for (int i = 0; i < n; ++i)
             Q3_CHECK(!voices[i], 3, "Invalid input: streamed audio (audio_chunk_frames > 0) is not supported for voice requests by "
                                     "q3tts_generate_queued_voices");
@@ -3082,6 +3355,12 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     q.row_base = sp.row_base;
     for (int i = 0; i < n; ++i) q.params.push_back(fold_sampling(sp, i, 0u));  // (a queued slot keys on row_key_, not on row0)
     q.results = results;
+    if (sp.audio_stream_reference != 0 && sp.audio_chunk_frames > 0) {
+        q.stream_reference = true;
+        for (const auto& r : rr)
+            if (r.voice) q.ref_max = std::max(q.ref_max, r.ref_T);
+        q.prefix_cache = debug_env().no_prefix_cache ? nullptr : &prefix_cache_;
+    }
     // each lane runs a slot pool of its own; all of them take requests from the one queue
     const int L = int(lanes_.size());
     std::vector<int> pool((size_t)(L));

@@ -75,6 +75,54 @@ struct FreeDeleter {
 template <class T>
 using MallocPtr = std::unique_ptr<T, FreeDeleter>;  // std::malloc'd host memory
 
+// What a voice's reference leaves behind in the codec decoder's causal tail when it is decoded as the prefix of a streamed
+// request (CodecRunner::stream_save_row): taken the first time the voice is streamed with a geometry, put back with one launch
+// at every later admission instead of decoding the reference again. A voice is read-only, so the state depends on the voice,
+// on (chunk, window, lookahead) and on the codec path (two-plane / float16 / fp32 kernels; `bytes` guards the layout) alone --
+// not on the row, the row count or the lane. Kept beside the group's voices, read by any lane, dropped with the voice.
+struct PrefixCache {
+    struct Entry {
+        const Voice* voice = nullptr;
+        int chunk = 0, window = 0, lookahead = 0, path = 0;
+        size_t bytes = 0;
+        DevBuf<uint8_t> blob;
+        hipEvent_t ready = nullptr;  // behind the save: a restore on another stream waits for it
+        ~Entry() {
+            if (ready) (void)hipEventDestroy(ready);
+        }
+    };
+    std::mutex mu;
+    std::vector<std::shared_ptr<Entry>> entries;
+    std::atomic<int64_t> restored{0};  // admissions served from a saved state since the model was loaded (q3tts_debug_prefix_states)
+    std::shared_ptr<Entry> find(const Voice* v, int chunk, int window, int lookahead, int path, size_t bytes) {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& e : entries)
+            if (e->voice == v && e->chunk == chunk && e->window == window && e->lookahead == lookahead && e->path == path && e->bytes == bytes)
+                return e;
+        return nullptr;
+    }
+    void publish(std::shared_ptr<Entry> n) {  // (two lanes may have primed the same voice side by side: the first one stays)
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto& e : entries)
+            if (e->voice == n->voice && e->chunk == n->chunk && e->window == n->window && e->lookahead == n->lookahead && e->path == n->path &&
+                e->bytes == n->bytes)
+                return;
+        entries.push_back(std::move(n));
+    }
+    void drop(const Voice* v) {
+        std::lock_guard<std::mutex> lk(mu);
+        for (size_t i = entries.size(); i-- > 0;)
+            if (entries[i]->voice == v) entries.erase(entries.begin() + ptrdiff_t(i));
+    }
+    void stats(int32_t* n_entries, int64_t* bytes, int64_t* n_restored) {
+        std::lock_guard<std::mutex> lk(mu);
+        *n_entries = int32_t(entries.size());
+        *bytes = 0;
+        for (auto& e : entries) *bytes += int64_t(e->bytes);
+        *n_restored = restored.load();
+    }
+};
+
 // One q3tts_generate_queued call as the lanes see it: the resolved requests and the index of the next one to admit, which
 // every lane's slot pool takes from (a request's random stream is keyed by its index, so which lane serves it does not matter).
 struct QueueShared {
@@ -84,6 +132,11 @@ struct QueueShared {
     uint32_t row_base = 0;
     std::vector<SamplingParams> params;  // [n] every request's folded sampling parameters (an admission writes them to its slot)
     q3tts_result* results = nullptr;
+    // streamed audio for voice requests (q3tts_sampling.audio_stream_reference): the longest reference of the call (the
+    // stream's code rows hold reference ++ generated) and where the references' tail states are kept (nullptr: always decode them)
+    bool stream_reference = false;
+    int ref_max = 0;
+    PrefixCache* prefix_cache = nullptr;
 };
 
 class Engine {
@@ -137,6 +190,8 @@ class Engine {
                       int64_t* audio_lengths);
     void codec_decode_streamed(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, int chunk_frames, int window,
                                int lookahead, float* pcm);
+    void codec_decode_streamed_prefixed(const int32_t* codes, const int32_t* n_prefix, const int32_t* n_frames, int batch, int max_frames,
+                                        int chunk_frames, int window, int lookahead, float* pcm);
     // q3tts_debug_codec_stream_slots: the slotted stream of a streamed queue driven by the queue's schedule without the talker
     void debug_codec_stream_slots(const int32_t* codes, const int32_t* n_frames, int n_reqs, int max_frames, int slots, int burst,
                                   int chunk_frames, int window, int lookahead, float* pcm);
@@ -243,6 +298,8 @@ class Engine {
         std::vector<hipEvent_t> chunk_done;  // chunked decode (audio_chunk_frames > 0): one per chunk, behind its copy
         int n_chunks = 0, chunk_frames = 0;
         bool streamed = false;   // audio_window_frames > 0: chunks were decoded (and partly delivered) inside the frame loop
+        bool prefixed = false;   // streamed through a slotted stream with the clone rows' references in front (audio_stream_reference):
+                                 // rows of Fdec = max_frames + longest reference frames, a row's audio behind ref_T * up samples
         int chunks_fired = 0;    // AUDIO_CHUNK events already delivered for chunks [0, chunks_fired)
         double t_first_audio = 0;
         q3tts_timing timing{};
@@ -414,6 +471,7 @@ class EngineGroup {
     Voice* create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids);
     void free_voice(Voice* v);
     bool mine(const Voice* v) const;
+    PrefixCache& prefix_cache() { return prefix_cache_; }
     // Two-deep pipeline (Engine::begin / end); the job id names the context and its slot. With more than one lane a job runs
     // to completion inside begin.
     int begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user, bool more_follows);
@@ -439,6 +497,7 @@ class EngineGroup {
     std::mutex cb_mutex_;
     std::vector<std::unique_ptr<Engine>> lanes_;
     std::vector<std::unique_ptr<Voice>> voices_;
+    PrefixCache prefix_cache_;  // the voices' tail states for streamed requests; a voice's entries go with it (free_voice)
     void check_voices(const q3tts_request* reqs, int n, const Voice* const* voices) const;  // status 3 before any GPU work
     // one lane: the second job context (lanes_[0] is the first). A job takes a context without an outstanding job, the one
     // that was not used last first, so that plain q3tts_generate calls alternate and a host's warm-up calls warm both.

@@ -23,6 +23,8 @@ struct DebugEnv {
                              // equality tests of the background back half, engine.h)
     bool fail_back_half;     // Q3TTS_TEST_FAIL_BACK_HALF: a background job's back half throws on the host before it launches anything
                              // (tests: the error must come out of q3tts_generate_end and the job slot must be released)
+    bool no_prefix_cache;    // Q3TTS_NO_PREFIX_CACHE: a streamed voice request decodes its reference prefix at every admission instead
+                             // of restoring the tail state saved at the first one (A/B and equality tests, engine.h PrefixCache)
 };
 const DebugEnv& debug_env();
 void debug_env_reload();

@@ -254,25 +254,70 @@ __global__ __launch_bounds__(256) void stream_take_chunk_kernel(const float* fro
 }
 
 // slotted stream: roll_history over every tensor of the table in one launch, row by row: mode[b] 0 leaves row b alone, 1 moves
-// its last `hist` frames of the chunk into the margin, 2 zeroes the margin (a new request takes the row). mode == nullptr:
-// the launch is a reset of `only_row` alone (grid.y == 1), which also clears that row's non-finite flag.
+// the last `hist` frames of [old margin ++ the take[b] frames just written] into the margin, 2 zeroes the margin (a new request
+// takes the row). mode == nullptr: the launch is a reset of `only_row` alone (grid.y == 1), which also clears that row's
+// non-finite flag. take == nullptr or take[b] == chunk: the copy of a full chunk. A short chunk in mid-stream (the end of a
+// reference prefix, stream_plan.h) moves the row's frames down by take[b]; with take[b] < hist source and destination overlap,
+// so an element is moved by the one thread that owns its residue modulo the shift, front to back: position i is read before
+// the same thread overwrites it and no other thread touches it.
 __global__ __launch_bounds__(256) void roll_history_rows_kernel(const RollDesc* desc, int Tal, int hist, int chunk, const int32_t* mode,
-                                                                int only_row, int32_t* nonfinite) {
+                                                                const int32_t* take, int only_row, int32_t* nonfinite) {
     const int b = mode ? (int)blockIdx.y : only_row;
     const int m = mode ? mode[b] : 2;
     if (m == 0) return;
     if (!mode && nonfinite && blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) nonfinite[b] = 0;
     const RollDesc d = desc[blockIdx.z];
     float* row = d.base + (int64_t)b * Tal * d.frame_floats;
-    const int64_t keep = (int64_t)hist * d.frame_floats, from = (int64_t)chunk * d.frame_floats;
+    const int tk = (m == 1 && take) ? min(max(take[b], 0), chunk) : chunk;
+    if (tk == 0) return;  // nothing was written: the margin stands
+    const int64_t keep = (int64_t)hist * d.frame_floats, from = (int64_t)tk * d.frame_floats;
     const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
     if ((d.frame_floats & 3) == 0) {  // allocations are 256-byte aligned: whole float4s throughout
         float4* dst = reinterpret_cast<float4*>(row);
-        const float4* src = reinterpret_cast<const float4*>(row + from);
         const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int64_t i = i0; i < keep / 4; i += step) dst[i] = m == 1 ? src[i] : zero;
+        const int64_t keep4 = keep / 4, from4 = from / 4;
+        if (m != 1) {
+            for (int64_t i = i0; i < keep4; i += step) dst[i] = zero;
+        } else {
+            for (int64_t j = i0; j < min(from4, keep4); j += step)
+                for (int64_t i = j; i < keep4; i += from4) dst[i] = dst[i + from4];
+        }
+    } else if (m != 1) {
+        for (int64_t i = i0; i < keep; i += step) row[i] = 0.f;
     } else {
-        for (int64_t i = i0; i < keep; i += step) row[i] = m == 1 ? row[from + i] : 0.f;
+        for (int64_t j = i0; j < min(from, keep); j += step)
+            for (int64_t i = j; i < keep; i += from) row[i] = row[i + from];
+    }
+}
+
+// slotted stream: the state a row's request has left behind -- its margin (`hist` frames) in every tensor of the table -- to or
+// from one contiguous blob, RollDesc::state_off bytes into it for each tensor. load != 0 writes the blob into the margins and
+// clears the row's non-finite flag (a request whose reference prefix has been decoded before takes the row, codec.h). The
+// table counts frames in bytes here, so the fp32 tensors and the float16 ones of the codec_conv_h1 path are the same copy;
+// 16 bytes per lane wherever a frame is whole 16-byte words (blob offsets and allocations are 16-byte aligned).
+__global__ __launch_bounds__(256) void history_state_rows_kernel(const RollDesc* desc, int Tal, int hist, int row_index, uint8_t* blob, int load,
+                                                                 int32_t* nonfinite) {
+    if (load && nonfinite && blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) nonfinite[row_index] = 0;
+    const RollDesc d = desc[blockIdx.z];
+    const int64_t frame_bytes = d.frame_floats * 4;
+    uint8_t* margin = reinterpret_cast<uint8_t*>(d.base) + (int64_t)row_index * Tal * frame_bytes;
+    uint8_t* state = blob + d.state_off;
+    const int64_t bytes = (int64_t)hist * frame_bytes;
+    const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if ((frame_bytes & 15) == 0) {
+        uint4* m4 = reinterpret_cast<uint4*>(margin);
+        uint4* s4 = reinterpret_cast<uint4*>(state);
+        for (int64_t i = i0; i < bytes / 16; i += step) {
+            if (load) m4[i] = s4[i];
+            else s4[i] = m4[i];
+        }
+    } else {
+        uint32_t* m1 = reinterpret_cast<uint32_t*>(margin);
+        uint32_t* s1 = reinterpret_cast<uint32_t*>(state);
+        for (int64_t i = i0; i < bytes / 4; i += step) {
+            if (load) m1[i] = s1[i];
+            else s1[i] = m1[i];
+        }
     }
 }
 
@@ -287,12 +332,21 @@ void launch_stream_take_chunk(const float* front, int64_t front_bstride, float* 
 }
 
 void launch_roll_history_rows(const RollDesc* desc, int n_desc, int64_t max_frame_floats, int Tal, int hist, int chunk, const int32_t* mode,
-                              int only_row, int B, int32_t* nonfinite, hipStream_t st) {
+                              int only_row, int B, int32_t* nonfinite, hipStream_t st, const int32_t* take) {
     Q3_CHECK(chunk >= hist && Tal == hist + chunk, 3, "roll_history: chunk shorter than the history");
     Q3_CHECK(mode != nullptr || (only_row >= 0 && only_row < B), 3, "roll_history: row outside the stream");
     if (n_desc <= 0 || B <= 0 || hist <= 0) return;
     const int gx = int(std::max<int64_t>(1, std::min<int64_t>(64, (int64_t(hist) * max_frame_floats / 4 + 255) / 256)));
-    hipLaunchKernelGGL(roll_history_rows_kernel, dim3(gx, mode ? B : 1, n_desc), dim3(256), 0, st, desc, Tal, hist, chunk, mode, only_row, nonfinite);
+    hipLaunchKernelGGL(roll_history_rows_kernel, dim3(gx, mode ? B : 1, n_desc), dim3(256), 0, st, desc, Tal, hist, chunk, mode, take, only_row,
+                       nonfinite);
+}
+
+void launch_history_state_rows(const RollDesc* desc, int n_desc, int64_t max_frame_floats, int Tal, int hist, int row, int B, uint8_t* blob,
+                               bool load, int32_t* nonfinite, hipStream_t st) {
+    Q3_CHECK(row >= 0 && row < B && blob != nullptr, 3, "history_state: row outside the stream");
+    if (n_desc <= 0 || hist <= 0) return;
+    const int gx = int(std::max<int64_t>(1, std::min<int64_t>(64, (int64_t(hist) * max_frame_floats / 4 + 255) / 256)));
+    hipLaunchKernelGGL(history_state_rows_kernel, dim3(gx, 1, n_desc), dim3(256), 0, st, desc, Tal, hist, row, blob, load ? 1 : 0, nonfinite);
 }
 
 void launch_roll_history(float* cur, int64_t bstride, int64_t keep_floats, int64_t chunk_floats, int B, hipStream_t st) {

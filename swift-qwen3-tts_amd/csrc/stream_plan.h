@@ -5,6 +5,12 @@
 // [max(0, kC - W), min(n, (k+1)C + L)); it is decodable once the request has (k+1)C + L frames or is final. Rows of a queue
 // are admitted at different moments, so every row carries its own chunk index; a pass decodes one chunk for each row that has
 // one and leaves the others alone.
+//
+// A voice-clone row carries a reference prefix of R frames in front of its generated ones (include/q3tts.h, "streamed clone
+// rows"): its code row holds S = ref ++ gen. Prefix chunk j covers S[jC, min(R, (j+1)C)) with the window
+// [max(0, jC - W), min(R, (j+1)C + L)) -- lookahead stops at R, so the prefix depends on nothing but the reference -- is
+// decodable at once and emits nothing. Generated chunk k then covers S[R + kC, min(R + n, R + (k+1)C)) with the window
+// [max(0, R + kC - W), min(R + n, R + (k+1)C + L)), which reaches back into the reference while kC < W. R = 0 is the above.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -18,7 +24,9 @@ struct SlotPlanCfg {
 
 struct RowPlan {  // one row of one pass
     int part = 0;   // 1: the row decodes chunk k in this pass; 0: it is left alone (every length 0, not rolled)
-    int k = 0;      // chunk index
+    int k = 0;      // chunk index: among the generated chunks when emit, among the prefix chunks otherwise
+    int emit = 1;   // 0: a chunk of the row's reference prefix, whose samples are never delivered
+    // The frames below are positions in the row's code buffer, which holds the prefix in front of the generated frames.
     int f0 = 0;     // first frame of the chunk
     int w0 = 0;     // first frame of the pre-transformer window (the RVQ gather starts here)
     int wlen = 0;   // frames of the window: [w0, w0 + wlen)
@@ -31,19 +39,28 @@ class SlotPlanner {
         cfg_ = cfg;
         next_.assign(size_t(cfg.rows), 0);
         live_.assign(size_t(cfg.rows), 0);
+        prefix_.assign(size_t(cfg.rows), 0);
     }
     const SlotPlanCfg& cfg() const { return cfg_; }
     // a new request takes row b: its chunks count from 0 again. A row takes part in no pass before its first reset.
-    void reset_row(int b) {
+    // prefix > 0: the row's code buffer starts with that many reference frames, decoded first and never delivered.
+    void reset_row(int b, int prefix = 0) {
         next_[size_t(b)] = 0;
         live_[size_t(b)] = 1;
+        prefix_[size_t(b)] = std::max(0, prefix);
     }
-    int next_chunk(int b) const { return next_[size_t(b)]; }
+    // the row's prefix has been decoded before and its state put back (codec.h, stream_load_row): straight to generated chunk 0
+    void skip_prefix(int b) { next_[size_t(b)] = prefix_chunks(b); }
+    int next_chunk(int b) const { return next_[size_t(b)]; }  // prefix chunks count as well
+    int prefix_of(int b) const { return prefix_[size_t(b)]; }
+    int prefix_chunks(int b) const { return chunks_of(prefix_[size_t(b)]); }
+    bool in_prefix(int b) const { return live_[size_t(b)] && next_[size_t(b)] < prefix_chunks(b); }
     // chunks a request of n frames has
     int chunks_of(int n) const { return n <= 0 ? 0 : (n + cfg_.chunk - 1) / cfg_.chunk; }
     bool decodable(int b, int avail, bool fin) const {
         if (!live_[size_t(b)]) return false;
-        const int f0 = next_[size_t(b)] * cfg_.chunk;
+        if (in_prefix(b)) return true;  // the reference is there from the start
+        const int f0 = (next_[size_t(b)] - prefix_chunks(b)) * cfg_.chunk;
         if (avail <= f0 || f0 >= cfg_.max_frames) return false;
         return fin || avail >= std::min(cfg_.max_frames, f0 + cfg_.chunk + cfg_.lookahead);
     }
@@ -56,12 +73,15 @@ class SlotPlanner {
             const int a = std::min(avail[b], cfg_.max_frames);
             if (!decodable(b, a, fin && fin[b])) continue;
             RowPlan& r = out[size_t(b)];
+            const int R = prefix_[size_t(b)], P = prefix_chunks(b);
             r.part = 1;
-            r.k = next_[size_t(b)];
-            r.f0 = r.k * cfg_.chunk;
+            r.emit = next_[size_t(b)] >= P ? 1 : 0;
+            r.k = r.emit ? next_[size_t(b)] - P : next_[size_t(b)];
+            r.f0 = r.emit ? R + r.k * cfg_.chunk : r.k * cfg_.chunk;
+            const int end = r.emit ? R + a : R;  // the frames the chunk and its lookahead may reach
             r.w0 = std::max(0, r.f0 - cfg_.window);
-            r.wlen = std::min(a, r.f0 + cfg_.chunk + cfg_.lookahead) - r.w0;
-            r.take = std::min(a, r.f0 + cfg_.chunk) - r.f0;
+            r.wlen = std::min(end, r.f0 + cfg_.chunk + cfg_.lookahead) - r.w0;
+            r.take = std::min(end, r.f0 + cfg_.chunk) - r.f0;
             ++next_[size_t(b)];
             ++parts;
         }
@@ -70,7 +90,7 @@ class SlotPlanner {
 
   private:
     SlotPlanCfg cfg_;
-    std::vector<int> next_;
+    std::vector<int> next_, prefix_;
     std::vector<uint8_t> live_;
 };
 

@@ -56,7 +56,7 @@ class Sampling(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
                 ("repetition_penalty", C.c_float), ("seed", C.c_uint64), ("force_frames", C.c_int32), ("audio_chunk_frames", C.c_int32),
                 ("audio_window_frames", C.c_int32), ("audio_lookahead_frames", C.c_int32), ("row_base", C.c_uint32),
-                ("per_request", C.POINTER(RowSampling))]
+                ("per_request", C.POINTER(RowSampling)), ("audio_stream_reference", C.c_int32)]
 
 
 class GenInfo(C.Structure):
@@ -147,6 +147,11 @@ def lib() -> C.CDLL:
     L.q3tts_result_free.restype = None
     L.q3tts_codec_decode.argtypes = [vp, i32p, i32p, C.c_int32, C.c_int32, f32p, C.POINTER(C.c_int64)]
     L.q3tts_codec_decode_streamed.argtypes = [vp, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p]
+    if hasattr(L, "q3tts_codec_decode_streamed_prefixed"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_codec_decode_streamed_prefixed.argtypes = [vp, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                           f32p]
+    if hasattr(L, "q3tts_debug_prefix_states"):
+        L.q3tts_debug_prefix_states.argtypes = [vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "q3tts_debug_codec_stream_slots"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_codec_stream_slots.argtypes = [vp, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                      C.c_int32, f32p]

@@ -322,7 +322,7 @@ class Qwen3TTSModel:
 
     @classmethod
     def _sampling(cls, temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames=0,
-                  audio_window_frames=0, audio_lookahead_frames=4, row_base=0, reqs=None) -> L.Sampling:
+                  audio_window_frames=0, audio_lookahead_frames=4, row_base=0, reqs=None, audio_stream_reference=0) -> L.Sampling:
         """`reqs`: the call's requests; their `sampling` fields become per_request (the array rides on the returned struct,
         which therefore has to stay alive for as long as the library reads it: the call, or begin)."""
         s = L.Sampling()
@@ -335,22 +335,25 @@ class Qwen3TTSModel:
         s.audio_chunk_frames = audio_chunk_frames
         s.audio_window_frames, s.audio_lookahead_frames = audio_window_frames, audio_lookahead_frames
         s.row_base = row_base
+        s.audio_stream_reference = int(audio_stream_reference)
         return s
 
     def generate_batch(self, reqs: Sequence[GenerationRequest], temperature: float = 0.9, top_k: int = 50,
                        top_p: float = 1.0, repetition_penalty: float = 1.05, seed: int = 0, force_frames: int = 0,
                        on_event: Optional[Callable[[int, str, object], None]] = None,
                        audio_chunk_frames: int = 0, audio_window_frames: int = 0,
-                       audio_lookahead_frames: int = 4, row_base: int = 0) -> List[GenerationResult]:
+                       audio_lookahead_frames: int = 4, row_base: int = 0, audio_stream_reference: int = 0) -> List[GenerationResult]:
         """n utterances in one call (row-independent). `on_event(request_index, kind, payload)` receives
         ("token", id) / ("info", AudioGenerationInfo) / ("audio", ndarray) in the reference's order; with
         audio_chunk_frames > 0 also ("audio_chunk", (sample_offset, ndarray)) pieces of the final audio, in order,
         between the last token and info (the decoder's causal tail run chunk by chunk; same samples). With
         audio_window_frames > 0 as well the pieces leave while tokens are still being generated (q3tts.h: the
-        pre-transformer then sees a sliding window; the waveform is within a stated tolerance of the one-shot decode)."""
+        pre-transformer then sees a sliding window; the waveform is within a stated tolerance of the one-shot decode).
+        A batch with a voice-clone row is streamed that way only with audio_stream_reference=1: a clone row's reference then
+        goes in front of its stream (codec_decode_streamed_prefixed); without it such a batch is decoded one-shot."""
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
-                           audio_window_frames, audio_lookahead_frames, row_base, reqs=reqs)
+                           audio_window_frames, audio_lookahead_frames, row_base, reqs=reqs, audio_stream_reference=audio_stream_reference)
         cb = self._event_cb(on_event)
         res = (L.Result * len(reqs))()
         voices = self._voices(reqs)
@@ -365,18 +368,19 @@ class Qwen3TTSModel:
                         top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.05, seed: int = 0,
                         force_frames: int = 0, on_event: Optional[Callable[[int, str, object], None]] = None,
                         audio_chunk_frames: int = 0, audio_window_frames: int = 0, audio_lookahead_frames: int = 4,
-                        row_base: int = 0) -> List[GenerationResult]:
+                        row_base: int = 0, audio_stream_reference: int = 0) -> List[GenerationResult]:
         """Continuous batching (q3tts_generate_queued): any number of requests with at most `slots` rows in flight (default
         max_batch); a finished row's slot takes the next request. Result i is bit-identical to generate_batch([reqs[i]],
         row_base=row_base + i) with the same keywords. Events as generate_batch's, except that a request's ("info", ...) /
         ("audio", ...) arrive as soon as its audio is decoded. With audio_chunk_frames > 0 and audio_window_frames > 0 every
         request's audio is streamed as if it ran alone: ("audio_chunk", (offset, samples)) events carry its request index and
         leave while it generates, "info" / "audio" once its last chunk has landed. Refused: voice-clone requests that carry
-        ref_audio (requests that name a `voice` are served, q3tts_generate_queued_voices; not with streamed audio),
+        ref_audio (requests that name a `voice` are served, q3tts_generate_queued_voices; with streamed audio only when
+        audio_stream_reference=1, which puts a voice's reference in front of its request's stream),
         audio_chunk_frames > 0 without a window (audio_window_frames == 0) or below the decoder's history."""
         arr, keep = self._marshal(reqs)
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
-                           audio_window_frames, audio_lookahead_frames, row_base, reqs=reqs)
+                           audio_window_frames, audio_lookahead_frames, row_base, reqs=reqs, audio_stream_reference=audio_stream_reference)
         cb = self._event_cb(on_event)
         res = (L.Result * len(reqs))()
         n_slots = int(self.info.max_batch) if slots is None else int(slots)
@@ -603,6 +607,28 @@ class Qwen3TTSModel:
         self._check(self._lib.q3tts_codec_decode_streamed(self._h, codes.ctypes.data_as(L.i32p), nf.ctypes.data_as(L.i32p), B, F,
                                                           chunk_frames, window, lookahead, pcm.ctypes.data_as(L.f32p)))
         return pcm
+
+    def codec_decode_streamed_prefixed(self, codes: np.ndarray, n_prefix: Sequence[int], n_frames: Sequence[int], chunk_frames: int,
+                                       window: int, lookahead: int = 4) -> np.ndarray:
+        """The streamed decode of rows that carry a reference prefix, as a streamed voice-clone row is decoded
+        (q3tts_codec_decode_streamed_prefixed): codes [batch][max_frames][16] hold n_prefix[b] reference frames, then n_frames[b]
+        generated ones. Returns pcm [batch][max(n_frames) * 1920]: row b's first n_frames[b] * 1920 samples, the reference's cut."""
+        codes = np.ascontiguousarray(codes, np.int32)
+        B, F, G = codes.shape
+        npre, nf = np.asarray(n_prefix, np.int32), np.asarray(n_frames, np.int32)
+        assert npre.shape == (B,) and nf.shape == (B,) and G == 16
+        pcm = np.zeros((B, max(int(nf.max()), 0) * self.info.samples_per_frame), np.float32)
+        self._check(self._lib.q3tts_codec_decode_streamed_prefixed(self._h, codes.ctypes.data_as(L.i32p), npre.ctypes.data_as(L.i32p),
+                                                                   nf.ctypes.data_as(L.i32p), B, F, int(chunk_frames), int(window),
+                                                                   int(lookahead), pcm.ctypes.data_as(L.f32p)))
+        return pcm
+
+    def debug_prefix_states(self) -> Tuple[int, int, int]:
+        """The voices' saved tail states for streamed requests (q3tts_debug_prefix_states): how many are held, their device
+        bytes, and how many admissions have been served from one since the model was loaded."""
+        n, b, r = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.q3tts_debug_prefix_states(self._h, C.byref(n), C.byref(b), C.byref(r)))
+        return n.value, b.value, r.value
 
     def debug_codec_stream_slots(self, codes: np.ndarray, n_frames: Sequence[int], slots: int, burst: int, chunk_frames: int,
                                  window: int, lookahead: int) -> np.ndarray:

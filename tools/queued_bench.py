@@ -2,7 +2,7 @@
 """Continuous batching against static batches.
 
   python tools/queued_bench.py [--preset 1.7b] [--slots 32] [--requests 256] [--stream CHUNK,WINDOW,LOOKAHEAD] [--mixed-sampling]
-  python tools/queued_bench.py --preset 1.7b-base --voices 4 [--slots 32] [--requests 256]
+  python tools/queued_bench.py --preset 1.7b-base --voices 4 [--slots 32] [--requests 256] [--stream CHUNK,WINDOW,LOOKAHEAD]
 
 Two workloads on bench.py's synthetic checkpoint and request builder:
   ragged   max_tokens uniform in 50..400 (seeded), temperature 0.9, seed 1234: rows end at their caps (or EOS) at different frames
@@ -23,6 +23,10 @@ for bit, and the queue's rows now include top-p rows beside the others in every 
   static   pipelined batches whose requests carry their clip as ref_audio (every batch encodes its clips again)
   queued   one q3tts_generate_queued call whose requests name one of N voices made once by create_voice
 alternating --repeat times, with frames/s, frontend / prefill / codec milliseconds of each and the bit-identity of the two.
+--voices N --stream CHUNK,WINDOW,LOOKAHEAD then also streams the voices queue (audio_stream_reference = 1: a voice's reference goes in
+front of its request's stream): the voices' saved tail states against Q3TTS_NO_PREFIX_CACHE=1 (every admission decodes its
+reference again), alternating --repeat times, with frames/s and per request the time from admission to first AUDIO_CHUNK, median
+and worst, and whether the two agree bit for bit.
 """
 from __future__ import annotations
 
@@ -129,8 +133,44 @@ def run_voices(model, args):
     same = all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio)
                for x, y in zip(last["static"], last["queued"]))
     print(f"bit-identical codes + pcm, all {args.requests} requests, ref_audio batches against the queue with voices: {same}", flush=True)
+    if args.stream:
+        run_voices_streamed(model, args, as_voice, short(as_voice), kw)
     for v in voices:
         v.close()
+
+
+def run_voices_streamed(model, args, reqs, warm, kw):
+    """The voices queue with streamed audio: admissions served from the voices' saved tail states against admissions that decode
+    their reference prefix every time."""
+    from qwen3tts import _lib
+    c, w, l = (int(x) for x in args.stream.split(","))
+    skw = dict(kw, audio_chunk_frames=c, audio_window_frames=w, audio_lookahead_frames=l, audio_stream_reference=1)
+    run_queued_timed(model, warm, args.slots, skw)  # stream arena, pinned ring; every voice's state is saved here
+    n, b, _ = model.debug_prefix_states()
+    print(f"# streamed voices --stream {args.stream}: {n} saved tail states, {b} device bytes", flush=True)
+    last = {}
+    try:
+        for rep in range(args.repeat):
+            for name in ("restored", "primed"):
+                if name == "primed":
+                    os.environ["Q3TTS_NO_PREFIX_CACHE"] = "1"
+                else:
+                    os.environ.pop("Q3TTS_NO_PREFIX_CACHE", None)
+                _lib.reload_debug_env()
+                before = model.debug_prefix_states()[2]
+                out, dt, tm, lat = run_queued_timed(model, reqs, args.slots, skw)
+                frames = sum(int(r.codes.shape[0]) for r in out)
+                last[name] = out
+                print(f"run {rep} streamed voices {name:8s} frames {frames:7d}  wall {dt:8.3f} s  frames/s {frames / dt:9.1f}  "
+                      f"codec {tm.codec_ms:8.1f} ms  first_audio {tm.first_audio_ms:7.1f} ms  admission -> first AUDIO_CHUNK: median "
+                      f"{np.median(lat) * 1e3:7.1f} ms  worst {lat.max() * 1e3:7.1f} ms  admissions restored "
+                      f"{model.debug_prefix_states()[2] - before}  failed {sum(1 for r in out if r.status != 0)}", flush=True)
+    finally:
+        os.environ.pop("Q3TTS_NO_PREFIX_CACHE", None)
+        _lib.reload_debug_env()
+    same = all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio)
+               for x, y in zip(last["restored"], last["primed"]))
+    print(f"bit-identical codes + pcm, all {len(reqs)} requests, saved states against decoding every prefix: {same}", flush=True)
 
 
 def main():

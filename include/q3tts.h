@@ -39,7 +39,9 @@ typedef enum {
     Q3TTS_ERR_AUDIO_DECODING_FAILED = 4, /* .audioDecodingFailed                               */
     Q3TTS_ERR_AUDIO_ENCODING_FAILED = 5, /* .audioEncodingFailed                               */
     Q3TTS_ERR_IO = 6,     /* checkpoint/config read or parse failure (thrown Foundation errors) */
-    Q3TTS_ERR_DEVICE = 7  /* HIP runtime failure; the engine never falls back to the CPU        */
+    Q3TTS_ERR_DEVICE = 7, /* HIP runtime failure; the engine never falls back to the CPU        */
+    Q3TTS_ERR_CANCELLED = 8, /* new: the request was cancelled (q3tts_session_cancel / close without drain) */
+    Q3TTS_ERR_BUSY = 9       /* new: q3tts_session_submit: max_pending requests are already waiting */
 } q3tts_status;
 
 typedef struct {
@@ -415,6 +417,81 @@ q3tts_status q3tts_generate_voices(q3tts_model* m, const q3tts_request* reqs, co
 q3tts_status q3tts_generate_queued_voices(q3tts_model* m, const q3tts_request* reqs, const q3tts_voice* const* voices,
                                           int32_t n_reqs, int32_t slots, const q3tts_sampling* sampling, q3tts_event_cb cb,
                                           void* user, q3tts_result* results);
+
+/* Serving session (new: the reference generates one utterance per call). q3tts_generate_queued takes its whole request list up
+ * front; a session is the same slot loop with an open end: requests are submitted, cancelled and collected one by one while the
+ * loop runs. The frame step, the admission prefill and the decoder are the closed queue's.
+ * Tickets and determinism: the t-th ACCEPTED submit (t = 0, 1, ...) gets ticket t, and its result is bit-identical -- status,
+ * codes, pcm, n_frames, n_samples -- to q3tts_generate (q3tts_generate_voices for a voice) of that request alone with the
+ * session's sampling, `rs` folded in, and row_base = sampling->row_base + t: whatever its arrival time, its slot, what else was
+ * running, whether the session was idle before it, and whatever was cancelled around it. Equivalently it is results[t] of
+ * q3tts_generate_queued[_voices] over the same requests in ticket order. The streamed forms carry over, each request as if
+ * streamed alone: audio_chunk_frames > 0 with audio_window_frames > 0, and audio_stream_reference for voices, whose saved
+ * prefix states are reused as the closed queue reuses them. Events carry request_index = ticket (an int32: a session refuses
+ * submits past ticket 2^31 - 1) and are otherwise the closed queue's.
+ * Threads: q3tts_session_open starts one thread that the session owns. It runs the slot loop, and the event callbacks fire on
+ * it. submit, cancel, wait and get_stats may be called from any thread, concurrently: the session has a lock of its own and the
+ * one-caller-per-handle rule does not apply to them. submit and cancel may also be called from inside an event callback; they
+ * never wait for the loop. wait and close from inside a callback would wait for the thread they run on and are refused
+ * (INVALID_INPUT). open and close follow the one-caller-per-handle rule; no other session call may be running when close is.
+ *   q3tts_session_open: `slots` rows in flight, 1..max_batch. `max_pending`: accepted requests not yet admitted that the session
+ *     holds (0: 1024). `max_ref_frames`: the longest voice reference (frames) a submit may name; it sizes the voice rows of an
+ *     admission and, streamed, the stream's code rows once, here, so that no boundary allocates; 0: no voice requests. `sampling`
+ *     (NULL: defaults) holds for the whole session; per_request is ignored (a submit brings its own `rs`). Refused with
+ *     INVALID_INPUT: slots outside 1..max_batch, a q3tts_generate_begin job outstanding, a session already open, the streaming
+ *     fields a closed queue refuses, and, for now, a handle loaded with n_streams > 1 (lanes are not done).
+ *   q3tts_session_submit: checks the request on the calling thread exactly as q3tts_generate_queued checks each of its requests
+ *     (route, speaker, prompt length, max_tokens <= max_frames, RoPE range; ref_audio is refused; a voice must belong to the handle
+ *     and have ref_frames <= max_ref_frames; `rs`, or NULL, gets the checks of q3tts_sampling.per_request). A refused submit
+ *     consumes no ticket and leaves the session running. Q3TTS_ERR_BUSY when max_pending requests are waiting. The request and
+ *     everything it points at are copied before submit returns. While rows are running the request is admitted at the next
+ *     burst boundary; an idle session's thread sleeps on a condition variable -- no frame step, no spinning -- until a submit.
+ *   q3tts_session_cancel: a pending ticket is never admitted. A running one leaves its slot at the next burst boundary (one
+ *     launch marks the row finished and inactive on the device) and the slot is refilled like any freed slot; from that boundary
+ *     on no event fires for the ticket, a streamed request's chunks in flight are dropped, and its result has status
+ *     Q3TTS_ERR_CANCELLED and no codes or pcm. A ticket whose row has already been retired completes as it is. Cancelling a
+ *     completed or cancelled ticket returns OK and changes nothing; a ticket never given out is INVALID_INPUT. No other
+ *     ticket's result changes.
+ *   q3tts_session_wait: timeout_ms < 0 waits for ever. *ready = 1: the result is the caller's (q3tts_result_free) and the ticket
+ *     is forgotten -- a second wait on it is INVALID_INPUT. *ready = 0 (timeout): nothing is touched. The session holds a result
+ *     until it is waited for or the session is closed.
+ *   q3tts_session_get_stats: submitted = tickets given out; pending = accepted, not admitted; running = admitted, result not
+ *     filled yet; completed / cancelled = results filled with any other status / with CANCELLED; frame_steps and admissions
+ *     count since open.
+ *   q3tts_session_close: drain != 0 finishes everything accepted; drain == 0 cancels everything pending and running. Either way
+ *     it joins the thread and frees the unclaimed results, and the pointer is dead. q3tts_model_free closes an open session
+ *     first, without drain, and the pointer is dead after it as well: as with close, no other session call may be running, or
+ *     be started later, on a session that is being closed or whose model is being freed (such a call reads freed memory; it
+ *     is not answered with INVALID_INPUT). A server stops its submitting threads before it frees the model.
+ * While a session is open every other entry point that uses the engine (q3tts_generate*, q3tts_generate_begin, q3tts_codec_*,
+ * q3tts_voice_create / _free, q3tts_speaker_embedding, q3tts_debug_*, the arena calls) returns INVALID_INPUT ("a session is open")
+ * without touching the GPU, and the session goes on: voices are created before open. q3tts_model_get_info, q3tts_last_error,
+ * q3tts_voice_get_info, the tokenizer and q3tts_last_timing stay available.
+ * q3tts_last_error and the session calls: a submit, cancel, wait or get_stats that is refused keeps its message for the thread
+ * that made the call. q3tts_last_error(model) on that thread returns it until the thread's next call on the handle or session
+ * succeeds; other threads' refusals, which may happen at the same moment, do not disturb it, and the handle's own message (that
+ * of open, close and every other entry point) is not touched by them.
+ * Failure: a device error on the loop thread completes every pending and running ticket with that status; submit and close
+ * return it from then on, and q3tts_last_error carries the message (after submit: on the submitting thread, as above). */
+typedef struct q3tts_session q3tts_session;
+typedef struct {
+    int32_t slots;          /* rows in flight, 1..max_batch */
+    int32_t max_pending;    /* accepted but not yet admitted requests the session holds; 0 = default (1024) */
+    int32_t max_ref_frames; /* longest voice reference (frames) a submit may name; 0 = no voice requests */
+} q3tts_session_opts;
+typedef struct {
+    int64_t submitted, pending, running, completed, cancelled;
+    int64_t frame_steps, admissions; /* since open */
+} q3tts_session_stats;
+q3tts_status q3tts_session_open(q3tts_model* m, const q3tts_session_opts* opts, const q3tts_sampling* sampling, q3tts_event_cb cb,
+                                void* user, q3tts_session** out);
+q3tts_status q3tts_session_submit(q3tts_session* s, const q3tts_request* req, const q3tts_voice* voice /* or NULL */,
+                                  const q3tts_row_sampling* rs /* or NULL */, int64_t* ticket);
+q3tts_status q3tts_session_cancel(q3tts_session* s, int64_t ticket);
+q3tts_status q3tts_session_wait(q3tts_session* s, int64_t ticket, int32_t timeout_ms /* <0: for ever */, q3tts_result* out,
+                                int32_t* ready);
+q3tts_status q3tts_session_get_stats(const q3tts_session* s, q3tts_session_stats* out);
+q3tts_status q3tts_session_close(q3tts_session* s, int32_t drain);
 
 /* Qwen3TTSSpeechTokenizer.decode (Models/SpeechTokenizer.swift:823-836): codes
  * [batch][max_frames][num_code_groups] -> pcm [batch][max_frames*1920] (caller-allocated),

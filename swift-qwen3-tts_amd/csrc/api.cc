@@ -14,8 +14,13 @@
 
 using q3::EngineGroup;
 
+struct q3tts_session {  // the handle q3tts_session_open gives out: the model's one session (EngineGroup::session())
+    q3tts_model* m = nullptr;
+};
+
 struct q3tts_model {
     std::unique_ptr<EngineGroup> eng;
+    std::unique_ptr<q3tts_session> session;
     // "Calls on one handle are serialised by the caller" (q3tts.h; the reference's model object is not re-entrant either). The
     // contract is checked, not assumed: a call that finds the handle inside another thread's call fails with INVALID_INPUT instead
     // of racing on the engine's state. Nested calls from the SAME thread (an event callback asking for q3tts_model_info) pass.
@@ -29,6 +34,10 @@ struct q3tts_tokenizer {
 namespace {
 thread_local std::string g_load_error;
 thread_local const q3tts_model* g_refused = nullptr;  // this thread's last call on that handle found it in use (HandleUse)
+// submit / cancel / wait / get_stats run on any thread at once, so a refusal's message is kept per thread, not in the handle's
+// one string: q3tts_last_error gives a thread the message of ITS last refused session call until its next call on the handle
+thread_local std::string g_session_error;
+thread_local const q3tts_model* g_session_refused = nullptr;
 const char* const kBusyMsg =
     "Invalid input: the model handle is inside another thread's call (calls on one handle must be serialised by the caller)";
 
@@ -53,14 +62,20 @@ struct HandleUse {  // the handle's one-caller-at-a-time contract (struct q3tts_
 q3::Voice* voice_of(q3tts_voice* v) { return reinterpret_cast<q3::Voice*>(v); }
 const q3::Voice* voice_of(const q3tts_voice* v) { return reinterpret_cast<const q3::Voice*>(v); }
 
+// uses_engine: the call needs an engine, which an open session's loop thread owns: refused without touching the GPU
 template <class F>
-q3tts_status guarded(q3tts_model* m, F&& f) {
+q3tts_status guarded(q3tts_model* m, F&& f, bool uses_engine = true) {
     HandleUse use(m);
     if (m && !use.mine) {
         g_refused = m;  // (not written to the engine's last_error: that string belongs to the call that is running)
         return Q3TTS_ERR_INVALID_INPUT;
     }
     if (m && g_refused == m) g_refused = nullptr;
+    if (m && g_session_refused == m) g_session_refused = nullptr;
+    if (m && uses_engine && m->eng && m->eng->session()) {
+        m->eng->last_error = "Invalid input: a session is open on this model handle (q3tts_session_close must be called first)";
+        return Q3TTS_ERR_INVALID_INPUT;
+    }
     try {
         // every call on a handle runs with the handle's GPU current, whatever the calling thread had selected (a process may hold one
         // handle per GPU; allocations and per-device kernel attributes inside the call belong to THIS device)
@@ -76,6 +91,26 @@ q3tts_status guarded(q3tts_model* m, F&& f) {
         else g_load_error = e.what();
         return Q3TTS_ERR_DEVICE;
     }
+}
+// a session call that takes the session's own lock instead of the handle's one-caller check
+template <class F>
+q3tts_status session_call(const q3tts_session* s, F&& f) {
+    if (!s || !s->m || !s->m->eng || !s->m->eng->session()) return Q3TTS_ERR_INVALID_INPUT;
+    EngineGroup& g = *s->m->eng;
+    q3tts_status st = Q3TTS_OK;
+    try {
+        f(*g.session());
+        if (g_session_refused == s->m) g_session_refused = nullptr;
+        return Q3TTS_OK;
+    } catch (const q3::Error& e) {
+        g_session_error = e.what();
+        st = static_cast<q3tts_status>(e.status);
+    } catch (const std::exception& e) {
+        g_session_error = e.what();
+        st = Q3TTS_ERR_DEVICE;
+    }
+    g_session_refused = s->m;  // (the handle's own string is not touched: other threads' calls may be reading or writing theirs)
+    return st;
 }
 }  // namespace
 
@@ -136,11 +171,19 @@ q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts
 
 void q3tts_model_free(q3tts_model* m) {
     if (g_refused == m) g_refused = nullptr;  // (a later handle may be allocated at the same address)
+    if (g_session_refused == m) g_session_refused = nullptr;
+    if (m && m->eng) {  // an open session is closed first, without drain
+        try {
+            (void)m->eng->close_session(false);
+        } catch (const std::exception&) {
+        }
+    }
     delete m;
 }
 
 const char* q3tts_last_error(const q3tts_model* m) {
     if (m && g_refused == m) return kBusyMsg;
+    if (m && g_session_refused == m) return g_session_error.c_str();
     if (m && m->eng) return m->eng->last_error.c_str();
     return g_load_error.c_str();
 }
@@ -200,7 +243,7 @@ q3tts_status q3tts_model_get_info(const q3tts_model* m, q3tts_model_info* out) {
         out->samples_per_frame = c.has_codec ? c.codec.total_upsample() : c.decode_upsample_rate;
         out->max_batch = m->eng->opts().max_batch;
         out->weight_bytes = md.step_weight_bytes;
-    });
+    }, false);
 }
 
 int32_t q3tts_model_num_speakers(const q3tts_model* m) { return m ? int32_t(m->eng->speakers.size()) : 0; }
@@ -305,6 +348,58 @@ q3tts_status q3tts_generate_end(q3tts_model* m, q3tts_job* job, q3tts_result* re
             if (results[i].status == Q3TTS_ERR_GENERATION_FAILED)
                 m->eng->last_error = "Generation failed: No tokens generated";  // Qwen3.swift:940
     });
+}
+
+// ---- serving session: submit / cancel / wait / get_stats take the session's own lock, not the handle's one-caller check ----
+q3tts_status q3tts_session_open(q3tts_model* m, const q3tts_session_opts* opts, const q3tts_sampling* sampling, q3tts_event_cb cb,
+                                void* user, q3tts_session** out) {
+    if (out) *out = nullptr;
+    return guarded(m, [&] {
+        Q3_CHECK(m && opts && out, 3, "Invalid input: null argument");
+        q3tts_sampling sp;
+        if (sampling) sp = *sampling;
+        else q3tts_default_sampling(&sp);
+        m->eng->open_session(*opts, sp, cb, user);
+        m->session = std::make_unique<q3tts_session>();
+        m->session->m = m;
+        *out = m->session.get();
+    }, false);
+}
+
+q3tts_status q3tts_session_submit(q3tts_session* s, const q3tts_request* req, const q3tts_voice* voice, const q3tts_row_sampling* rs,
+                                  int64_t* ticket) {
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(req && ticket, 3, "Invalid input: null argument");
+        x.submit(*req, voice_of(voice), rs, ticket);
+    });
+}
+
+q3tts_status q3tts_session_cancel(q3tts_session* s, int64_t ticket) {
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(x.cancel(ticket) == Q3TTS_OK, 3, "Invalid input: no such ticket");
+    });
+}
+
+q3tts_status q3tts_session_wait(q3tts_session* s, int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready) {
+    return session_call(s, [&](q3::Session& x) { x.wait(ticket, timeout_ms, out, ready); });
+}
+
+q3tts_status q3tts_session_get_stats(const q3tts_session* s, q3tts_session_stats* out) {
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(out, 3, "Invalid input: null argument");
+        x.stats(out);
+    });
+}
+
+q3tts_status q3tts_session_close(q3tts_session* s, int32_t drain) {
+    if (!s || !s->m) return Q3TTS_ERR_INVALID_INPUT;
+    q3tts_model* m = s->m;
+    return guarded(m, [&] {
+        Q3_CHECK(m->session.get() == s && m->eng->session(), 3, "Invalid input: no such session");
+        const int st = m->eng->close_session(drain != 0);  // (throws from inside a callback: the session stays open)
+        m->session.reset();
+        if (st) throw q3::Error(st, m->eng->last_error);
+    }, false);
 }
 
 void q3tts_pcm_to_int16(const float* pcm, int64_t n_samples, int16_t* out) {

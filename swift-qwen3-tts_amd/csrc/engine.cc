@@ -1081,8 +1081,9 @@ struct Engine::SlotStream {
         int landed = 0;        // chunks taken from the ring
         int held_from = -1;    // first chunk held back
         bool complete = false;
+        bool dropped = false;  // cancelled (a session): its chunks in flight land nowhere
     };
-    std::vector<Out> out;         // by request index
+    std::unordered_map<int, Out> out;  // by request (its index in a closed call, its ticket in a session)
     std::vector<int> req_of_row;  // the request in row b, -1: none
     struct Flight {
         CodecRunner::SlotPass pass;
@@ -1097,8 +1098,8 @@ struct Engine::SlotStream {
     std::function<void(int, int, const float*, int64_t, int64_t)> on_chunk;  // request, chunk, samples, count, offset
     std::function<void(int)> on_complete;
 
-    SlotStream(Engine& eng, int rows, int n_reqs, int chunk, int window, int lookahead, int max_frames, bool overlapped, int max_prefix = 0)
-        : e(eng), C(chunk), up(eng.codec_->upsample()), out(size_t(n_reqs)), req_of_row(size_t(rows), -1) {
+    SlotStream(Engine& eng, int rows, int chunk, int window, int lookahead, int max_frames, bool overlapped, int max_prefix = 0)
+        : e(eng), C(chunk), up(eng.codec_->upsample()), req_of_row(size_t(rows), -1) {
         for (hipEvent_t* ev : {&ev_codes, &ev_pushed}) Q3_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
         cst = e.codec_stream(overlapped);
         CodecRunner::StreamCfg cfg;
@@ -1119,12 +1120,12 @@ struct Engine::SlotStream {
         if (state) e.codec_->stream_load_row(row, prefix, state);
         else e.codec_->stream_reset_row(row, prefix);
         req_of_row[size_t(row)] = req;
-        Out& o = out[size_t(req)];
+        Out& o = out[req];
         o.pcm.reset(static_cast<float*>(std::malloc(std::max<size_t>(size_t(cap_frames) * up * 4, 4))));
         Q3_CHECK(o.pcm != nullptr, 5, "out of host memory for the results");
     }
     void check_complete(int req) {
-        Out& o = out[size_t(req)];
+        Out& o = out[req];
         if (o.complete || o.frames < 0 || o.landed < e.codec_->stream_chunks_of(o.frames)) return;
         o.complete = true;
         if (on_complete) on_complete(req);
@@ -1152,7 +1153,8 @@ struct Engine::SlotStream {
             const RowPlan& r = f.pass.rows[b];
             if (!r.part || !r.emit) continue;  // (a chunk of a reference prefix delivers nothing)
             const int req = f.req[b];
-            Out& o = out[size_t(req)];
+            Out& o = out[req];
+            if (o.dropped) continue;
             if (hold && o.held_from < 0 && f.pass.nf[b]) o.held_from = r.k;
             if (o.held_from < 0) {
                 const int64_t off = int64_t(r.k) * C * up, n = int64_t(r.take) * up;
@@ -1181,8 +1183,22 @@ struct Engine::SlotStream {
     void retire(int row, int frames) {
         const int req = req_of_row[size_t(row)];
         req_of_row[size_t(row)] = -1;
-        out[size_t(req)].frames = frames;
+        out[req].frames = frames;
         check_complete(req);
+    }
+    // the request in `row` is cancelled: the row is free (its next occupant resets it), what is in flight for it is dropped
+    void drop(int row) {
+        const int req = req_of_row[size_t(row)];
+        req_of_row[size_t(row)] = -1;
+        Out& o = out[req];
+        o.dropped = true;
+        o.pcm.reset();
+    }
+    bool in_flight(int req) const {
+        for (const Flight& f : flights)
+            for (size_t b = 0; b < f.pass.rows.size(); ++b)
+                if (f.req[b] == req && f.pass.rows[b].part && f.pass.rows[b].emit) return true;
+        return false;
     }
     void finish() {  // every pass taken, the runner's stream closed
         while (take(true)) {}
@@ -1242,7 +1258,7 @@ struct Engine::StreamedDecode {
         J.Fdec = stride;
         J.dec_codes.grow(size_t(J.n) * stride * 16);
         J.pcm_host.grow(size_t(J.n) * stride * J.up);
-        ss = std::make_unique<SlotStream>(e, J.n, J.n, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
+        ss = std::make_unique<SlotStream>(e, J.n, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
                                           e.Fcap_, true, ref_max);
         sst = ss->cst;
         Q3_HIP(hipEventRecord(J.ev_codec[0], sst));
@@ -1319,7 +1335,7 @@ struct Engine::StreamedDecode {
         for (int b = 0; b < J.n; ++b) ss->retire(b, J.frames[size_t(b)]);
         ss->finish();
         for (int b = 0; b < J.n; ++b) {
-            const SlotStream::Out& o = ss->out[size_t(b)];
+            const SlotStream::Out& o = ss->out[b];
             Q3_CHECK(o.complete, 7, "internal error: a row of the streamed job was left incomplete");
             std::memcpy(J.pcm_host + (size_t(b) * stride + prefix[size_t(b)]) * J.up, o.pcm.get(), size_t(J.frames[size_t(b)]) * J.up * 4);
             J.held_from[size_t(b)] = o.held_from;
@@ -1747,6 +1763,7 @@ void Engine::Job::reset(int rows, int upsample) {
     target_tokens.assign(size_t(n), 0);
     ref_code0.assign(size_t(n), {});
     req_index.clear();  // (a queued call's decode batches used the slot with request indices of their own)
+    row_out.clear();
     row_span.clear();
     held_from.assign(size_t(n), -1);
     std::memset(nf_host, 0, nf_host.capacity() * 4);
@@ -2063,7 +2080,7 @@ void Engine::end(int job, q3tts_result* results) {
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
     // a queued decode batch: row b is request req_index[b], timed from its admission to its retirement
-    auto out = [&](int b) -> q3tts_result& { return results[J.req_index.empty() ? b : J.req_index[size_t(b)]]; };
+    auto out = [&](int b) -> q3tts_result& { return J.row_out.empty() ? results[b] : *J.row_out[size_t(b)]; };
     auto ev_index = [&](int b) { return J.request_base + (J.req_index.empty() ? b : J.req_index[size_t(b)]); };
     for (int b = 0; b < n; ++b) {
         q3tts_result& r = out(b);
@@ -2178,21 +2195,31 @@ void Engine::ensure_queue_ws() {
     qws_ = base;
 }
 
-int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained) {
+// One admitted request until its result is filled: what was resolved at its submission and, once its row is retired, what it
+// generated (streamed: until its last chunk has landed; otherwise until its decode batch is delivered).
+struct Engine::QLive {
+    ResolvedRequest rr;
+    int frames = 0;
+    double span = 0;             // admission -> retirement
+    std::vector<int32_t> codes;  // [frames][16]
+};
+
+void Engine::cancel_slots(uint64_t mask, int slots) { launch_cancel_rows(mask, finished_, active_, slots, st_); }
+
+int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int, QLive>& live) {
     std::vector<ResolvedRequest> rr;
     std::vector<int> slots, idx;
     std::vector<uint32_t> keys;
-    for (int s = 0; s < int(sl.size()) && !drained; ++s) {
+    std::vector<SamplingParams> params;
+    QueueItem item;
+    for (int s = 0; s < int(sl.size()); ++s) {
         if (sl[size_t(s)].req >= 0) continue;
-        const int i = q.next.fetch_add(1);
-        if (i >= q.n) {
-            drained = true;
-            break;
-        }
-        rr.push_back((*q.reqs)[size_t(i)]);
+        if (!q.src->take(item)) break;
+        rr.push_back(std::move(item.rr));
         slots.push_back(s);
-        idx.push_back(i);
-        keys.push_back(q.row_base + uint32_t(i));  // request i draws what q3tts_generate draws with row_base + i
+        idx.push_back(item.ticket);
+        keys.push_back(q.row_base + uint32_t(item.ticket));  // request t draws what q3tts_generate draws with row_base + t
+        params.push_back(item.params);
     }
     const int k = int(rr.size());
     if (k == 0) return 0;
@@ -2225,7 +2252,7 @@ int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained) {
         const int s = slots[size_t(j)];
         for (int i = 0; i < max_pages_; ++i) hbt[size_t(j) * max_pages_ + i] = s * max_pages_ + i;
         hnp[j] = np[size_t(j)];
-        hd[j] = AdmitDesc{s, nt[size_t(j)], rr[size_t(j)].max_frames, keys[size_t(j)], q.params[size_t(idx[size_t(j)])]};
+        hd[j] = AdmitDesc{s, nt[size_t(j)], rr[size_t(j)].max_frames, keys[size_t(j)], params[size_t(j)]};
     }
     Q3_HIP(hipMemcpyAsync(q_bt_, hbt, nbt * 4, hipMemcpyHostToDevice, st_));
     Q3_HIP(hipMemcpyAsync(q_kv_len_, hbt + nbt, size_t(k) * 4, hipMemcpyHostToDevice, st_));
@@ -2244,7 +2271,10 @@ int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained) {
     launch_admit_rows(a, k, st_);
     Q3_HIP(hipEventRecord(ev_[1], st_));
     const double now = now_s();
-    for (int j = 0; j < k; ++j) sl[size_t(slots[size_t(j)])] = QSlot{idx[size_t(j)], 0, 0, np[size_t(j)], now};
+    for (int j = 0; j < k; ++j) {
+        sl[size_t(slots[size_t(j)])] = QSlot{idx[size_t(j)], 0, 0, np[size_t(j)], now, rr[size_t(j)].max_frames};
+        live[idx[size_t(j)]].rr = std::move(rr[size_t(j)]);
+    }
     return k;
 }
 
@@ -2260,10 +2290,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     Q3_CHECK(!job_outstanding(), 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
     ensure_queue_ws();
     {   // an admission's voice rows go through extra_: room for S rows with the longest reference, so that no boundary allocates
-        int ref_max = -1;
-        for (const auto& r : *q.reqs)
-            if (r.voice) ref_max = std::max(ref_max, r.ref_T);
-        if (ref_max >= 0) extra_.grow(size_t(S) * (1 + ref_max) * m_->cfg.talker.hidden_size);
+        if (q.voice_ref_max >= 0) extra_.grow(size_t(S) * (1 + q.voice_ref_max) * m_->cfg.talker.hidden_size);
     }
     const double t_call = now_s();
     // every slot starts empty: finished, inactive, an empty cache in its own pages
@@ -2291,12 +2318,9 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     Q3_HIP(hipStreamSynchronize(st_));
 
     std::vector<QSlot> sl((size_t)(S));
-    struct Retired {
-        int req, frames;
-        double span;
-        std::vector<int32_t> codes;  // [frames][16]
-    };
-    std::deque<Retired> waiting;  // retired, decode not started
+    std::unordered_map<int, QLive> live;  // every admitted request whose result is not filled yet, by ticket
+    std::vector<int> settled;             // results filled since the last boundary: forgotten there
+    std::deque<int> waiting;              // retired, decode not started
     int dec = -1;                 // job slot of the decode batch in flight (all are free: no begin job is outstanding)
     struct DecodeGuard {          // an exception leaves no job slot behind
         Engine* e;
@@ -2315,25 +2339,33 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         }
         const int j = dec;
         dec = -1;
-        end(j, q.results);
+        const std::vector<int> batch = jobs_[j].req_index;
+        end(j, nullptr);
         codec_ms += timing.codec_ms;
+        for (int t : batch) {
+            q.src->complete(t);
+            live.erase(t);
+        }
     };
     auto decode = [&](bool overlapped) {  // every waiting row (up to max_batch) in one decode on the codec stream
         Job& J = jobs_[0];
         const int R = std::min(int(waiting.size()), Bm_);
         J.reset(R, codec_->upsample());
         J.req_index.assign(size_t(R), 0);
+        J.row_out.assign(size_t(R), nullptr);
         J.row_span.assign(size_t(R), 0);
         J.codes_host.assign(size_t(R) * Fcap_ * 16, 0);
         std::vector<int> dframes((size_t)(R), 0);  // frames the decoder sees per row: [reference ++] generated, as hand_off
         std::vector<const Voice*> voices((size_t)(R), nullptr);
         bool any_voice = false;
         for (int b = 0; b < R; ++b) {
-            const Retired& w = waiting[size_t(b)];
-            const ResolvedRequest& rq = (*q.reqs)[size_t(w.req)];
+            const QLive& w = live.at(waiting[size_t(b)]);
+            const ResolvedRequest& rq = w.rr;
             J.frames[size_t(b)] = w.frames;
             J.target_tokens[size_t(b)] = rq.target_token_count;
-            J.req_index[size_t(b)] = w.req;
+            J.req_index[size_t(b)] = waiting[size_t(b)];
+            J.row_out[size_t(b)] = q.src->result(waiting[size_t(b)]);
+            Q3_CHECK(J.row_out[size_t(b)] != nullptr, 7, "internal error: a retired request has no result to fill");
             J.row_span[size_t(b)] = w.span;
             std::copy(w.codes.begin(), w.codes.end(), J.codes_host.begin() + ptrdiff_t(size_t(b) * Fcap_ * 16));
             if (rq.voice) {  // compute_cuts then trims and cuts exactly as the static path does
@@ -2362,15 +2394,25 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     std::unique_ptr<SlotStream> ss;  // (its destructor closes the runner's stream whatever ends this call; it goes before scodes)
     std::vector<int> copied((size_t)(S), 0);   // frames [0, copied) of the slot's current request are in scodes
     std::vector<uint8_t> reused((size_t)(S), 0);  // the slot has had an earlier occupant whose codes the stream may still read
-    std::vector<Retired> gone;       // streamed: retired requests by index (codes, span) until they are complete
     std::vector<int> held;           // streamed: complete but held back, for the fp32 re-decode
     auto fill_result = [&](int req, q3tts_status status, float* pcm) {  // as end() fills a row; pcm: ownership passes
-        const Retired& w = gone[size_t(req)];
-        q3tts_result& r = q.results[req];
+        const QLive& w = live.at(req);
+        q3tts_result* rp = q.src->result(req);
+        Q3_CHECK(rp != nullptr, 7, "internal error: a streamed request has no result to fill");
+        q3tts_result& r = *rp;
+        struct Settle {  // however this ends, the result is the source's from here on
+            RequestSource* src;
+            std::vector<int>* settled;
+            int req;
+            ~Settle() {
+                src->complete(req);
+                settled->push_back(req);
+            }
+        } settle_req{q.src, &settled, req};
         std::memset(&r, 0, sizeof(r));
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
-        r.info.prompt_token_count = (*q.reqs)[size_t(req)].target_token_count;
+        r.info.prompt_token_count = w.rr.target_token_count;
         r.info.generation_token_count = w.frames;
         r.info.generate_time = w.span;
         r.info.tokens_per_second = w.span > 0 ? double(w.frames) / w.span : 0;
@@ -2412,11 +2454,21 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     DevBuf<DecodeRowDesc> ref_desc_dev;
     struct PendingState {  // a state saved at this call's admissions: published once its prefix is known to have stayed finite
         std::shared_ptr<PrefixCache::Entry> entry;
-        int flag = 0;  // index into state_flags
+        int32_t* flag = nullptr;  // its own entry of a block of state_flags
     };
     std::vector<PendingState> pending;
+    std::vector<int32_t*> free_flags;  // entries of state_flags no pending state owns
     std::vector<std::shared_ptr<PrefixCache::Entry>> in_use;  // states restored in this call stay alive until its stream has drained
-    PinnedBuf<int32_t> state_flags;
+    // Pinned flags in blocks of 2 * slots: a saved state owns one from its save to settle(), which gives it back. A block never moves
+    // (copies in flight write into it) and a further one is added when all are owned, so no admission ever waits for a flag.
+    std::deque<PinnedBuf<int32_t>> state_flags;
+    auto add_flags = [&] {
+        const size_t n = size_t(2) * S;
+        state_flags.emplace_back();
+        int32_t* b = state_flags.back().grow(n);
+        std::memset(b, 0, n * 4);
+        for (size_t i = n; i-- > 0;) free_flags.push_back(b + i);
+    };
     auto settle = [&](bool wait) {  // saved states whose save has run: into the cache, unless the prefix left the fp16 range
         for (size_t i = 0; i < pending.size();) {
             if (wait) {
@@ -2429,15 +2481,71 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                 }
                 Q3_HIP(pq);
             }
-            if (state_flags[pending[i].flag] == 0) q.prefix_cache->publish(pending[i].entry);
+            if (*pending[i].flag == 0) q.prefix_cache->publish(pending[i].entry);
+            free_flags.push_back(pending[i].flag);
             pending.erase(pending.begin() + ptrdiff_t(i));
         }
     };
-    if (streamed) {
-        gone.resize(size_t(q.n));
-        scodes.grow(size_t(S) * stride * 16);
-        if (q.prefix_cache) std::memset(state_flags.grow(size_t(q.n)), 0, size_t(q.n) * 4);
-        ss = std::make_unique<SlotStream>(*this, S, q.n, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
+    // (behind ss->finish(): the runner's stream is closed, `outs` holds the stream's requests)
+    auto redo_held = [&](std::unordered_map<int, SlotStream::Out>& outs) {
+        // ---- requests held back at a chunk that left the fp16 range: once more on the fp32 matrix cores, as redo_rows_fp32 does
+        // for a streamed job: chunks below the held one stay as delivered, the rest (events included) come from the exact decode
+        for (size_t h0 = 0; h0 < held.size(); h0 += size_t(Bm_)) {
+            const int R = int(std::min(held.size() - h0, size_t(Bm_)));
+            // (a voice request streamed behind its reference: the decoder sees reference ++ generated, as in every clone decode,
+            // and the request's samples start exactly ref_T frames in)
+            std::vector<int> dframes((size_t)(R)), refs((size_t)(R), 0);
+            int Fd = 0;
+            for (int i = 0; i < R; ++i) {
+                const ResolvedRequest& rq = live.at(held[h0 + i]).rr;
+                if (rq.voice && q.stream_reference) refs[size_t(i)] = rq.voice->ref_T;
+                Fd = std::max(Fd, dframes[size_t(i)] = refs[size_t(i)] + live.at(held[h0 + i]).frames);
+            }
+            PinnedBuf<int32_t> nf;
+            PinnedBuf<float> hpcm;
+            std::memset(nf.grow(size_t(R)), 0, size_t(R) * 4);
+            const bool widest = codec_->fp32_convs();  // already the fp32 kernels: nothing wider to fall back to
+            if (!widest) {
+                hipStream_t cst = codec_stream(false);
+                DevBuf<int32_t> dcodes;
+                dcodes.grow(size_t(R) * Fd * 16);
+                hpcm.grow(size_t(R) * Fd * up);
+                for (int i = 0; i < R; ++i) {
+                    const int ref = refs[size_t(i)];
+                    if (ref > 0)
+                        Q3_HIP(hipMemcpy(dcodes + size_t(i) * Fd * 16, live.at(held[h0 + i]).rr.voice->codes_host.data(), size_t(ref) * 64,
+                                         hipMemcpyHostToDevice));
+                    Q3_HIP(hipMemcpy(dcodes + (size_t(i) * Fd + ref) * 16, live.at(held[h0 + i]).codes.data(),
+                                     size_t(dframes[size_t(i)] - ref) * 64, hipMemcpyHostToDevice));
+                }
+                float* pcm_dev = nullptr;
+                codec_->decode(dcodes, Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
+                Q3_HIP(hipMemcpyAsync(hpcm, pcm_dev, size_t(R) * Fd * up * 4, hipMemcpyDeviceToHost, cst));
+                Q3_HIP(hipStreamSynchronize(cst));
+            }
+            for (int i = 0; i < R; ++i) {
+                const int req = held[h0 + i];
+                SlotStream::Out& o = outs.at(req);
+                if (widest || nf[i]) {  // never hand out a waveform with holes in it
+                    fill_result(req, Q3TTS_ERR_AUDIO_DECODING_FAILED, o.pcm.release());
+                    last_error = kCodecRangeMsg;
+                    continue;
+                }
+                const int64_t step = int64_t(sp.audio_chunk_frames) * up, ns = int64_t(dframes[size_t(i)] - refs[size_t(i)]) * up;
+                const int64_t from = std::min(ns, int64_t(o.held_from) * step);
+                std::memcpy(o.pcm.get() + from, hpcm + (size_t(i) * Fd + refs[size_t(i)]) * up + from, size_t(ns - from) * 4);
+                if (cb) {
+                    std::unique_lock<std::mutex> lk = cb_lock();
+                    for (int64_t lo = from; lo < ns; lo += step) audio_chunk(cb, user, req, o.pcm.get() + lo, std::min(step, ns - lo), lo);
+                }
+                fill_result(req, Q3TTS_OK, o.pcm.release());
+            }
+        }
+        held.clear();
+    };
+    auto open_stream = [&] {
+        ss.reset();
+        ss = std::make_unique<SlotStream>(*this, S, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
                                           Fcap_, true, q.ref_max);
         ss->t_call = t_call;
         if (cb)
@@ -2446,11 +2554,16 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                 audio_chunk(cb, user, req, pcm, n, off);
             };
         ss->on_complete = [&](int req) {
-            SlotStream::Out& o = ss->out[size_t(req)];
-            if (gone[size_t(req)].frames == 0) fill_result(req, Q3TTS_ERR_GENERATION_FAILED, o.pcm.release());  // Qwen3.swift:939-941
+            SlotStream::Out& o = ss->out[req];
+            if (live.at(req).frames == 0) fill_result(req, Q3TTS_ERR_GENERATION_FAILED, o.pcm.release());  // Qwen3.swift:939-941
             else if (o.held_from >= 0) held.push_back(req);
             else fill_result(req, Q3TTS_OK, o.pcm.release());
         };
+    };
+    if (streamed) {
+        scodes.grow(size_t(S) * stride * 16);
+        if (q.prefix_cache) add_flags();
+        open_stream();
     }
 
     const int burst_frames = std::max(1, max_inflight_frames / 2);
@@ -2458,15 +2571,52 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     std::vector<uint8_t> h_fin((size_t)(S), 0);
     int64_t kvb = 0;
     int launched = 0, served = 0;
-    bool drained = false;
     double prefill_ms = 0;
+    std::vector<int> cancels, zombies;  // zombies: cancelled streamed requests whose chunks may still be in flight
     Q3_HIP(hipEventRecord(ev_[2], st_));
     for (;;) {
+        // ---- results filled at the last boundary are forgotten; cancelled rows (a session) leave their slots ----
+        for (int t : settled) {
+            live.erase(t);
+            if (ss) ss->out.erase(t);
+        }
+        settled.clear();
+        for (size_t i = 0; i < zombies.size();)
+            if (!ss->in_flight(zombies[i])) {
+                ss->out.erase(zombies[i]);
+                zombies.erase(zombies.begin() + ptrdiff_t(i));
+            } else {
+                ++i;
+            }
+        if (q.src->has_cancels()) {
+            q.src->take_cancels(cancels);
+            uint64_t mask = 0;
+            for (int t : cancels) {
+                int s = -1;
+                for (int i = 0; i < S; ++i)
+                    if (sl[size_t(i)].req == t) s = i;
+                if (s >= 0) {  // running: its slot is an empty one from this boundary on, and no event of it fires any more
+                    mask |= uint64_t(1) << s;
+                    if (streamed) {
+                        ss->drop(s);
+                        zombies.push_back(t);
+                    }
+                    sl[size_t(s)] = QSlot{};
+                } else {
+                    auto w = std::find(waiting.begin(), waiting.end(), t);
+                    if (w == waiting.end()) continue;  // in a decode batch, or its last chunks are landing: it completes as it is
+                    waiting.erase(w);
+                }
+                live.erase(t);
+                q.src->complete_cancelled(t);
+            }
+            cancel_slots(mask, S);  // on st_: in front of the admissions below and of the next read of the flags
+        }
         // ---- admission: free slots in slot order take the next requests in request order ----
         std::vector<int> before;
         if (streamed)
             for (const QSlot& x : sl) before.push_back(x.req);
-        const int admitted = admit(q, sl, drained);
+        const int admitted = admit(q, sl, live);
         served += admitted;
         if (streamed) {  // a new occupant: the row's chunks, history margins and non-finite flag start over, in codec-stream order
             settle(false);
@@ -2474,7 +2624,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             bool any_ref = false, wait_pushed = false;
             for (int s = 0; s < S; ++s)
                 if (sl[size_t(s)].req >= 0 && before[size_t(s)] < 0) {
-                    const ResolvedRequest& rq = (*q.reqs)[size_t(sl[size_t(s)].req)];
+                    const ResolvedRequest& rq = live.at(sl[size_t(s)].req).rr;
                     fresh.push_back(s);
                     copied[size_t(s)] = 0;
                     prefix_of[size_t(s)] = rq.voice && q.stream_reference ? rq.ref_T : 0;
@@ -2491,7 +2641,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                 ref_desc.assign(size_t(S), DecodeRowDesc{});
                 for (int s : fresh) {
                     if (prefix_of[size_t(s)] == 0) continue;
-                    const Voice* v = (*q.reqs)[size_t(sl[size_t(s)].req)].voice;
+                    const Voice* v = live.at(sl[size_t(s)].req).rr.voice;
                     ref_desc[size_t(s)] = DecodeRowDesc{static_cast<const int32_t*>(v->codes_dev), codes_ + size_t(s) * Fcap_ * 16, v->ref_T, 1, s, 0};
                     reused[size_t(s)] = 1;
                 }
@@ -2503,7 +2653,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             const size_t state_bytes = codec_->stream_state_bytes();
             for (int s : fresh) {
                 const int req = sl[size_t(s)].req, R = prefix_of[size_t(s)];
-                const ResolvedRequest& rq = (*q.reqs)[size_t(req)];
+                const ResolvedRequest& rq = live.at(req).rr;
                 std::shared_ptr<PrefixCache::Entry> hit;
                 if (R > 0 && q.prefix_cache)
                     hit = q.prefix_cache->find(rq.voice, sp.audio_chunk_frames, sp.audio_window_frames, std::max(0, sp.audio_lookahead_frames),
@@ -2530,16 +2680,20 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                     if (!q.prefix_cache || state_bytes == 0) continue;
                     const int req = sl[size_t(s)].req;
                     auto e = std::make_shared<PrefixCache::Entry>();
-                    e->voice = (*q.reqs)[size_t(req)].voice;
+                    e->voice = live.at(req).rr.voice;
                     e->chunk = sp.audio_chunk_frames; e->window = sp.audio_window_frames; e->lookahead = std::max(0, sp.audio_lookahead_frames);
                     e->path = codec_->stream_path();
                     e->bytes = state_bytes;
                     e->blob.grow(state_bytes);
                     Q3_HIP(hipEventCreateWithFlags(&e->ready, hipEventDisableTiming));
+                    if (free_flags.empty()) add_flags();  // (settle(false) above returned what it could)
+                    int32_t* flag = free_flags.back();
+                    free_flags.pop_back();
+                    *flag = 0;
                     codec_->stream_save_row(s, e->blob);
-                    codec_->stream_row_flag(s, state_flags + req);
+                    codec_->stream_row_flag(s, flag);
                     Q3_HIP(hipEventRecord(e->ready, ss->cst));
-                    pending.push_back(PendingState{std::move(e), req});
+                    pending.push_back(PendingState{std::move(e), flag});
                 }
             }
         }
@@ -2548,15 +2702,39 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         for (const QSlot& x : sl)
             if (x.req >= 0) {
                 ++running;
-                burst = std::min(burst, (*q.reqs)[size_t(x.req)].max_frames - x.since);
+                burst = std::min(burst, x.cap - x.since);
             }
-        if (running == 0) break;
+        if (running == 0) {
+            if (!q.src->open_ended()) break;
+            // ---- a session with nothing running: everything retired is delivered, then the thread sleeps until a submit ----
+            while (dec >= 0 || !waiting.empty()) {
+                if (dec >= 0) deliver(true);
+                else decode(false);
+            }
+            if (streamed) {
+                while (ss->take(true)) {}
+                settle(true);
+                if (!held.empty()) {  // (the fp32 re-decode needs the runner: the slotted stream is closed around it)
+                    std::unordered_map<int, SlotStream::Out> outs = std::move(ss->out);
+                    ss->finish();
+                    in_use.clear();
+                    redo_held(outs);
+                    open_stream();
+                    zombies.clear();
+                    std::fill(reused.begin(), reused.end(), uint8_t(0));
+                }
+            }
+            if (!settled.empty()) continue;  // (forgotten at the top of the loop)
+            if (!q.src->wait_for_work()) break;
+            continue;
+        }
         burst = std::max(burst, 1);
         for (int f = 0; f < burst; ++f) {
             if (ge) Q3_HIP(hipGraphLaunch(ge, st_));
             else enqueue_frame(S, nullptr);
         }
         launched += burst;
+        q.src->progress(burst, admitted);
         Q3_HIP(hipMemcpyAsync(h_nframes.data(), n_frames_, size_t(S) * 4, hipMemcpyDeviceToHost, st_));
         Q3_HIP(hipMemcpyAsync(h_fin.data(), finished_, size_t(S), hipMemcpyDeviceToHost, st_));
         Q3_HIP(hipEventRecord(burst_ev_[0], st_));
@@ -2623,8 +2801,11 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             if (cb) emit_tokens(cb, user, s, x.req, nf, x.reported);
             if (!h_fin[size_t(s)]) continue;
             // copied out before the slot's next admission resets its row (stream order on st_)
-            Retired& w = streamed ? gone[size_t(x.req)] : (waiting.push_back(Retired{}), waiting.back());
-            w = Retired{x.req, nf, now - x.t0, std::vector<int32_t>((size_t)(nf) * 16)};
+            QLive& w = live.at(x.req);
+            if (!streamed) waiting.push_back(x.req);
+            w.frames = nf;
+            w.span = now - x.t0;
+            w.codes.assign((size_t)(nf) * 16, 0);
             if (nf > 0)
                 Q3_HIP(hipMemcpyAsync(w.codes.data(), codes_ + size_t(s) * Fcap_ * 16, size_t(nf) * 64, hipMemcpyDeviceToHost, st_));
             kvb += kv_bytes(x.np, nf);
@@ -2644,64 +2825,13 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     }
     double first_audio_ms = 0;
     if (streamed) {
+        zombies.clear();
         ss->finish();  // the passes still in flight; every request is complete behind this
         settle(true);
         in_use.clear();
         codec_ms = ss->codec_ms;
         first_audio_ms = ss->first_audio_ms;
-        // ---- requests held back at a chunk that left the fp16 range: once more on the fp32 matrix cores, as redo_rows_fp32 does
-        // for a streamed job: chunks below the held one stay as delivered, the rest (events included) come from the exact decode
-        for (size_t h0 = 0; h0 < held.size(); h0 += size_t(Bm_)) {
-            const int R = int(std::min(held.size() - h0, size_t(Bm_)));
-            // (a voice request streamed behind its reference: the decoder sees reference ++ generated, as in every clone decode,
-            // and the request's samples start exactly ref_T frames in)
-            std::vector<int> dframes((size_t)(R)), refs((size_t)(R), 0);
-            int Fd = 0;
-            for (int i = 0; i < R; ++i) {
-                const ResolvedRequest& rq = (*q.reqs)[size_t(held[h0 + i])];
-                if (rq.voice && q.stream_reference) refs[size_t(i)] = rq.voice->ref_T;
-                Fd = std::max(Fd, dframes[size_t(i)] = refs[size_t(i)] + gone[size_t(held[h0 + i])].frames);
-            }
-            PinnedBuf<int32_t> nf;
-            PinnedBuf<float> hpcm;
-            std::memset(nf.grow(size_t(R)), 0, size_t(R) * 4);
-            const bool widest = codec_->fp32_convs();  // already the fp32 kernels: nothing wider to fall back to
-            if (!widest) {
-                hipStream_t cst = codec_stream(false);
-                DevBuf<int32_t> dcodes;
-                dcodes.grow(size_t(R) * Fd * 16);
-                hpcm.grow(size_t(R) * Fd * up);
-                for (int i = 0; i < R; ++i) {
-                    const int ref = refs[size_t(i)];
-                    if (ref > 0)
-                        Q3_HIP(hipMemcpy(dcodes + size_t(i) * Fd * 16, (*q.reqs)[size_t(held[h0 + i])].voice->codes_host.data(), size_t(ref) * 64,
-                                         hipMemcpyHostToDevice));
-                    Q3_HIP(hipMemcpy(dcodes + (size_t(i) * Fd + ref) * 16, gone[size_t(held[h0 + i])].codes.data(),
-                                     size_t(dframes[size_t(i)] - ref) * 64, hipMemcpyHostToDevice));
-                }
-                float* pcm_dev = nullptr;
-                codec_->decode(dcodes, Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, nf, true);
-                Q3_HIP(hipMemcpyAsync(hpcm, pcm_dev, size_t(R) * Fd * up * 4, hipMemcpyDeviceToHost, cst));
-                Q3_HIP(hipStreamSynchronize(cst));
-            }
-            for (int i = 0; i < R; ++i) {
-                const int req = held[h0 + i];
-                SlotStream::Out& o = ss->out[size_t(req)];
-                if (widest || nf[i]) {  // never hand out a waveform with holes in it
-                    fill_result(req, Q3TTS_ERR_AUDIO_DECODING_FAILED, o.pcm.release());
-                    last_error = kCodecRangeMsg;
-                    continue;
-                }
-                const int64_t step = int64_t(sp.audio_chunk_frames) * up, ns = int64_t(dframes[size_t(i)] - refs[size_t(i)]) * up;
-                const int64_t from = std::min(ns, int64_t(o.held_from) * step);
-                std::memcpy(o.pcm.get() + from, hpcm + (size_t(i) * Fd + refs[size_t(i)]) * up + from, size_t(ns - from) * 4);
-                if (cb) {
-                    std::unique_lock<std::mutex> lk = cb_lock();
-                    for (int64_t lo = from; lo < ns; lo += step) audio_chunk(cb, user, req, o.pcm.get() + lo, std::min(step, ns - lo), lo);
-                }
-                fill_result(req, Q3TTS_OK, o.pcm.release());
-            }
-        }
+        redo_held(ss->out);
     }
     q3tts_timing tm{};
     float loop_ms = 0;
@@ -3035,7 +3165,7 @@ void Engine::codec_decode_streamed_prefixed(const int32_t* codes, const int32_t*
     DevBuf<int32_t> dcodes;
     dcodes.grow(size_t(batch) * max_frames * 16);
     Q3_HIP(hipMemcpy(dcodes, codes, size_t(batch) * max_frames * 16 * 4, hipMemcpyHostToDevice));
-    SlotStream ss(*this, batch, batch, chunk_frames, window, lookahead, std::max(Fmax, 1), false, Rmax);
+    SlotStream ss(*this, batch, chunk_frames, window, lookahead, std::max(Fmax, 1), false, Rmax);
     ss.hold = false;  // (as q3tts_codec_decode_streamed: the samples as the default kernels produce them)
     for (int b = 0; b < batch; ++b) ss.admit(b, b, std::max(Fmax, 1), n_prefix[b]);
     std::vector<int> avail((size_t)(batch));
@@ -3053,8 +3183,8 @@ void Engine::codec_decode_streamed_prefixed(const int32_t* codes, const int32_t*
     for (int b = 0; b < batch; ++b) ss.retire(b, n_frames[b]);
     ss.finish();
     for (int b = 0; b < batch; ++b) {
-        Q3_CHECK(ss.out[size_t(b)].complete, 7, "internal error: a row of the prefixed stream was left incomplete");
-        std::memcpy(pcm + size_t(b) * Fmax * up, ss.out[size_t(b)].pcm.get(), size_t(n_frames[b]) * up * 4);
+        Q3_CHECK(ss.out[b].complete, 7, "internal error: a row of the prefixed stream was left incomplete");
+        std::memcpy(pcm + size_t(b) * Fmax * up, ss.out[b].pcm.get(), size_t(n_frames[b]) * up * 4);
     }
 }
 
@@ -3080,7 +3210,7 @@ void Engine::debug_codec_stream_slots(const int32_t* codes, const int32_t* n_fra
     all.grow(size_t(n_reqs) * max_frames * 16);
     scodes.grow(size_t(slots) * max_frames * 16);
     Q3_HIP(hipMemcpy(all, codes, size_t(n_reqs) * max_frames * 16 * 4, hipMemcpyHostToDevice));
-    SlotStream ss(*this, slots, n_reqs, chunk_frames, window, lookahead, max_frames, false);
+    SlotStream ss(*this, slots, chunk_frames, window, lookahead, max_frames, false);
     ss.hold = false;  // (as q3tts_codec_decode_streamed: the samples as the default kernels produce them)
     std::vector<int> copied((size_t)(slots), 0);
     replay_queue_schedule(
@@ -3103,8 +3233,8 @@ void Engine::debug_codec_stream_slots(const int32_t* codes, const int32_t* n_fra
         });
     ss.finish();
     for (int i = 0; i < n_reqs; ++i) {
-        Q3_CHECK(ss.out[size_t(i)].complete, 7, "internal error: a request of the slotted stream was left incomplete");
-        std::memcpy(pcm + size_t(i) * max_frames * up, ss.out[size_t(i)].pcm.get(), size_t(n_frames[i]) * up * 4);
+        Q3_CHECK(ss.out[i].complete, 7, "internal error: a request of the slotted stream was left incomplete");
+        std::memcpy(pcm + size_t(i) * max_frames * up, ss.out[i].pcm.get(), size_t(n_frames[i]) * up * 4);
     }
 }
 
@@ -3153,6 +3283,7 @@ EngineGroup::EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& op
 }
 
 EngineGroup::~EngineGroup() {  // jobs begun and never ended: each engine lets its worker finish before its streams go
+    session_.reset();  // (an open session is closed without drain: its loop thread is joined before the engines go)
     ctx1_.reset();
     lanes_.clear();
 }
@@ -3315,9 +3446,28 @@ void EngineGroup::generate(const q3tts_request* reqs, int n, const q3tts_samplin
     }
 }
 
-void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
-                                  q3tts_result* results, const Voice* const* voices) {
-    Q3_CHECK(n >= 1, 3, "Invalid input: n_reqs must be at least 1");
+namespace {
+// q3tts_generate_queued's request source: the call's list, handed out in index order (every lane's loop takes from it)
+struct ClosedSource : RequestSource {
+    const std::vector<ResolvedRequest>* reqs = nullptr;
+    std::vector<SamplingParams> params;  // [n] every request's folded sampling parameters
+    q3tts_result* results = nullptr;
+    std::atomic<int> next{0};
+    bool take(QueueItem& out) override {
+        if (next.load() >= int(reqs->size())) return false;
+        const int i = next.fetch_add(1);
+        if (i >= int(reqs->size())) return false;
+        out.ticket = i;
+        out.rr = (*reqs)[size_t(i)];
+        out.params = params[size_t(i)];
+        return true;
+    }
+    q3tts_result* result(int ticket) override { return results + ticket; }
+};
+}  // namespace
+
+// what a closed queue and a session check alike before the slot loop starts (status 3, nothing touched)
+void EngineGroup::check_queue_open(int slots, const q3tts_sampling& sp) const {
     Q3_CHECK(slots >= 1 && slots <= opts_.max_batch, 3, "Invalid input: slots must be between 1 and max_batch");
     // chunks cut after a request's end (audio_window_frames == 0) give a queue nothing: its AUDIO already leaves as soon as it is decoded
     Q3_CHECK(sp.audio_chunk_frames == 0 || sp.audio_window_frames > 0, 3,
@@ -3328,10 +3478,16 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     outstanding = outstanding || (ctx1_ && ctx1_->job_outstanding());  // (the queued path itself runs on the first context alone)
     Q3_CHECK(!outstanding, 3, "Invalid input: a q3tts_generate_begin job is outstanding (q3tts_generate_end must be called first)");
     Q3_CHECK(model_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
-    check_row_sampling(sp, n);
-    check_voices(reqs, n, voices);
     Q3_CHECK(sp.audio_stream_reference == 0 || (sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0), 3,
              "Invalid input: audio_stream_reference needs audio_chunk_frames > 0 and audio_window_frames > 0 in q3tts_generate_queued");
+}
+
+void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
+                                  q3tts_result* results, const Voice* const* voices) {
+    Q3_CHECK(n >= 1, 3, "Invalid input: n_reqs must be at least 1");
+    check_queue_open(slots, sp);
+    check_row_sampling(sp, n);
+    check_voices(reqs, n, voices);
     if (voices && sp.audio_chunk_frames > 0 && sp.audio_stream_reference == 0)  // (only on request: the result differs from the one-shot
                                                                                  // clone decode in trim and cut, include/q3tts.h)
         for (int i = 0; i < n; ++i)
@@ -3349,16 +3505,18 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
     }
     if (sp.audio_chunk_frames > 0)  // a streamed queue: the causal tail's history must fit into a chunk (as a streamed q3tts_generate)
         lanes_[0]->check_stream_chunk(sp.audio_chunk_frames);
+    ClosedSource src;
+    src.reqs = &rr;
+    src.results = results;
+    for (int i = 0; i < n; ++i) src.params.push_back(fold_sampling(sp, i, 0u));  // (a queued slot keys on row_key_, not on row0)
     QueueShared q;
-    q.reqs = &rr;
-    q.n = n;
+    q.src = &src;
     q.row_base = sp.row_base;
-    for (int i = 0; i < n; ++i) q.params.push_back(fold_sampling(sp, i, 0u));  // (a queued slot keys on row_key_, not on row0)
-    q.results = results;
+    for (const auto& r : rr)
+        if (r.voice) q.voice_ref_max = std::max(q.voice_ref_max, r.ref_T);
     if (sp.audio_stream_reference != 0 && sp.audio_chunk_frames > 0) {
         q.stream_reference = true;
-        for (const auto& r : rr)
-            if (r.voice) q.ref_max = std::max(q.ref_max, r.ref_T);
+        q.ref_max = std::max(0, q.voice_ref_max);
         q.prefix_cache = debug_env().no_prefix_cache ? nullptr : &prefix_cache_;
     }
     // each lane runs a slot pool of its own; all of them take requests from the one queue
@@ -3382,6 +3540,139 @@ void EngineGroup::generate_queued(const q3tts_request* reqs, int n, int slots, c
         timing.kv_bytes_read += t.kv_bytes_read;
     }
     timing.rows = n;
+}
+
+// ------------------------------------------------------------------------------------------------
+// serving session (q3tts_session_*)
+// ------------------------------------------------------------------------------------------------
+static void free_one_result(q3tts_result* r) {
+    std::free(r->pcm);
+    std::free(r->codes);
+    r->pcm = nullptr;
+    r->codes = nullptr;
+}
+
+Session::Session(EngineGroup& g, Engine& lane, const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user)
+    : g_(g), lane_(lane), slots_(so.slots), max_ref_frames_(std::max(0, so.max_ref_frames)), sp_(sp), cb_(cb), user_(user),
+      queue_(so.max_pending, &free_one_result) {
+    sp_.per_request = nullptr;  // (a submit brings its own overrides)
+    thread_ = std::thread([this] { loop(); });
+}
+
+Session::~Session() {
+    try {
+        (void)close(false);
+    } catch (const std::exception&) {  // (destroyed from its own callback: nothing can join the thread from there)
+        if (thread_.joinable()) thread_.detach();
+    }
+}
+
+std::string Session::error() const {
+    std::lock_guard<std::mutex> lk(err_mu_);
+    return error_;
+}
+
+void Session::loop() {
+    int status = 0;
+    std::string what;
+    try {
+        QueueShared q;
+        q.src = this;
+        q.row_base = sp_.row_base;
+        q.voice_ref_max = max_ref_frames_ > 0 ? max_ref_frames_ : -1;
+        if (sp_.audio_stream_reference != 0 && sp_.audio_chunk_frames > 0) {
+            q.stream_reference = true;
+            q.ref_max = max_ref_frames_;
+            q.prefix_cache = debug_env().no_prefix_cache ? nullptr : &g_.prefix_cache();
+        }
+        lane_.run_queued(q, slots_, sp_, cb_, user_);
+    } catch (const Error& e) {
+        status = e.status;
+        what = e.what();
+    } catch (const std::exception& e) {
+        status = 7;
+        what = e.what();
+    }
+    if (status) {  // every pending and running ticket completes with it; submit and close return it from here on
+        {
+            std::lock_guard<std::mutex> lk(err_mu_);
+            error_ = what;
+        }
+        queue_.fail(status);
+    }
+}
+
+void Session::submit(const q3tts_request& r, const Voice* voice, const q3tts_row_sampling* rs, int64_t* ticket) {
+    if (voice) {
+        Q3_CHECK(g_.mine(voice), 3, "Invalid input: the voice was not created on this model handle (or has been freed)");
+        Q3_CHECK(r.ref_audio == nullptr && r.ref_text_ids == nullptr, 3,
+                 "Invalid input: the request names a voice and carries ref_audio / ref_text_ids as well");
+        Q3_CHECK(voice->ref_T <= max_ref_frames_, 3,
+                 "Invalid input: the voice's reference is longer than the session's max_ref_frames");
+        Q3_CHECK(sp_.audio_chunk_frames == 0 || sp_.audio_stream_reference != 0, 3,
+                 "Invalid input: streamed audio (audio_chunk_frames > 0) is not supported for voice requests unless the session "
+                 "was opened with audio_stream_reference");
+    }
+    q3tts_sampling one = sp_;
+    one.per_request = rs;
+    check_row_sampling(one, 1);
+    Item it;
+    it.rr = lane_.check_queued(r, sp_, voice);
+    it.params = fold_sampling(one, 0, 0u);  // (a queued slot keys on its ticket, not on row0)
+    const int st = queue_.submit(std::move(it), ticket);
+    if (st == Q3TTS_ERR_BUSY) throw Error(st, "Session busy: max_pending requests are already waiting");
+    if (st == Q3TTS_OK) return;
+    const std::string why = error();
+    throw Error(st, why.empty() ? std::string("Invalid input: the session is closing or has run out of tickets") : why);
+}
+
+void Session::wait(int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready) {
+    Q3_CHECK(!on_loop_thread(), 3, "Invalid input: q3tts_session_wait inside an event callback would wait for the thread it runs on");
+    Q3_CHECK(out && ready, 3, "Invalid input: null argument");
+    const int st = queue_.wait(ticket, timeout_ms, out, ready);
+    Q3_CHECK(st == Q3TTS_OK, st, "Invalid input: no such ticket (never given out, or its result has been collected)");
+}
+
+int Session::close(bool drain) {
+    Q3_CHECK(!on_loop_thread(), 3, "Invalid input: q3tts_session_close inside an event callback would join the thread it runs on");
+    queue_.close(drain);
+    if (thread_.joinable()) thread_.join();
+    return queue_.failed();
+}
+
+bool Session::take(QueueItem& out) {
+    int64_t t = -1;
+    Item it;
+    if (!queue_.take(&t, &it)) return false;
+    out.ticket = int(t);
+    out.rr = std::move(it.rr);
+    out.params = it.params;
+    return true;
+}
+
+void Session::take_cancels(std::vector<int>& out) {
+    std::vector<int64_t> t;
+    queue_.take_cancels(t);
+    out.assign(t.begin(), t.end());
+}
+
+Session* EngineGroup::open_session(const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user) {
+    Q3_CHECK(!session_, 3, "Invalid input: a session is already open on this model handle");
+    Q3_CHECK(lanes_.size() == 1, 3, "Invalid input: q3tts_session_open is not supported with n_streams > 1");
+    Q3_CHECK(so.max_pending >= 0 && so.max_ref_frames >= 0, 3, "Invalid input: max_pending / max_ref_frames must not be negative");
+    check_queue_open(so.slots, sp);
+    if (sp.audio_chunk_frames > 0) lanes_[0]->check_stream_chunk(sp.audio_chunk_frames);
+    lanes_[0]->drain();
+    session_ = std::make_unique<Session>(*this, *lanes_[0], so, sp, cb, user);
+    return session_.get();
+}
+
+int EngineGroup::close_session(bool drain) {
+    if (!session_) return 0;
+    const int st = session_->close(drain);  // (throws, and leaves the session open, when called from its own callback)
+    if (st) last_error = session_->error();
+    session_.reset();
+    return st;
 }
 
 }  // namespace q3

@@ -13,11 +13,13 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/q3tts.h"
 #include "kernels.h"
 #include "model.h"
+#include "session_queue.h"
 
 namespace q3 {
 
@@ -123,16 +125,41 @@ struct PrefixCache {
     }
 };
 
-// One q3tts_generate_queued call as the lanes see it: the resolved requests and the index of the next one to admit, which
-// every lane's slot pool takes from (a request's random stream is keyed by its index, so which lane serves it does not matter).
+// One request as the slot loop admits it: its ticket (the closed call: its index), what check_queued resolved, and its folded
+// sampling parameters (an admission writes them to its slot).
+struct QueueItem {
+    int ticket = -1;
+    ResolvedRequest rr;
+    SamplingParams params{};
+};
+
+// Where the slot loop (Engine::run_queued) gets its requests and leaves their results. q3tts_generate_queued implements it over
+// its request list; a session (q3tts_session_*) over a locked deque that other threads fill while the loop runs. A request's
+// random stream is keyed by its ticket, so which lane or slot serves it, and when, does not matter.
+struct RequestSource {
+    virtual ~RequestSource() = default;
+    // the next request in ticket order; false: none now (called from every lane's loop)
+    virtual bool take(QueueItem& out) = 0;
+    // where ticket's result goes: a stable address the loop alone writes until complete(ticket)
+    virtual q3tts_result* result(int ticket) = 0;
+    virtual void complete(int) {}
+    // ---- an open source (a session) ----
+    virtual bool open_ended() const { return false; }  // requests may arrive while the loop runs: an idle loop waits for them
+    // the loop has nothing running and has flushed everything: sleeps until a request waits (true) or the source ends (false)
+    virtual bool wait_for_work() { return false; }
+    virtual bool has_cancels() { return false; }
+    virtual void take_cancels(std::vector<int>& out) { out.clear(); }  // running tickets to drop at this boundary
+    virtual void complete_cancelled(int) {}
+    virtual void progress(int /*frame_steps*/, int /*admissions*/) {}
+};
+
+// What the lanes of one slot loop share: the request source and what was fixed before the loop started.
 struct QueueShared {
-    const std::vector<ResolvedRequest>* reqs = nullptr;
-    int n = 0;
-    std::atomic<int> next{0};
+    RequestSource* src = nullptr;
     uint32_t row_base = 0;
-    std::vector<SamplingParams> params;  // [n] every request's folded sampling parameters (an admission writes them to its slot)
-    q3tts_result* results = nullptr;
-    // streamed audio for voice requests (q3tts_sampling.audio_stream_reference): the longest reference of the call (the
+    int voice_ref_max = -1;  // longest reference (frames) of a voice request the source may hand out: sizes the voice rows of an
+                             // admission once, before the loop; -1: no voice requests
+    // streamed audio for voice requests (q3tts_sampling.audio_stream_reference): the longest reference (the
     // stream's code rows hold reference ++ generated) and where the references' tail states are kept (nullptr: always decode them)
     bool stream_reference = false;
     int ref_max = 0;
@@ -281,6 +308,7 @@ class Engine {
         int n = 0, Fdec = 0, up = 0;
         std::vector<int> frames, ref_T, target_tokens, n_prompt;
         std::vector<int> req_index;   // queued decode batch: row b is request req_index[b] (results / events); empty: row b
+        std::vector<q3tts_result*> row_out;  // queued decode batch: where row b's result goes (end() is given no array)
         std::vector<double> row_span; // queued decode batch: admission -> retirement of row b (generate_time); empty: the job's
         std::vector<std::vector<int32_t>> ref_code0;  // first code row of each reference (valid-length count)
         std::vector<int32_t> codes_host;  // [n][Fcap][16]
@@ -440,13 +468,18 @@ class Engine {
         int reported = 0;  // TOKEN events delivered
         int np = 0;
         double t0 = 0;     // admission (host clock)
+        int cap = 0;       // its max_frames
     };
     // free slots of `sl` in slot order take the next requests of q (prompts, prefill and admit_rows_kernel as a sub-batch of
-    // their own); returns how many were admitted, sets `drained` once q is empty
-    int admit(QueueShared& q, std::vector<QSlot>& sl, bool& drained);
+    // their own); returns how many were admitted. `live` takes every admitted request by ticket
+    struct QLive;
+    int admit(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int, QLive>& live);
+    void cancel_slots(uint64_t mask, int slots);  // one launch on st_: the listed slots are finished and inactive
     GemmArgs gemm_args(const LinearW& L, const uint16_t* x, int M) const;
 };
 
+
+class Session;
 
 // The object behind q3tts_model: the model plus its engines. With n_streams > 1 they are lanes: q3tts_generate splits its
 // rows contiguously over them, each lane driven by its own host thread on its own HIP stream. That never pays (a lane's
@@ -479,11 +512,19 @@ class EngineGroup {
     // q3tts_generate_queued: every request checked up front; `slots` rows split over the lanes, one shared queue
     void generate_queued(const q3tts_request* reqs, int n, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
                          q3tts_result* results, const Voice* const* voices = nullptr);
+    // q3tts_session_*: one session at a time; while it is open its loop thread owns the first context (api.cc refuses the
+    // entry points that would use an engine). close_session joins the thread and returns the status the loop failed with (0: none)
+    Session* open_session(const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
+    Session* session() const { return session_.get(); }
+    int close_session(bool drain);
     std::string last_error;
     q3tts_timing timing{};
     std::vector<std::string> speakers;
 
   private:
+    std::unique_ptr<Session> session_;
+    // what a closed queue and a session check alike before the slot loop starts
+    void check_queue_open(int slots, const q3tts_sampling& sp) const;
     // fn(i) for lanes 0..L-1, each on a thread of its own unless `serial`; then the first failed lane's Error is rethrown
     template <class F>
     static void run_lanes(int L, bool serial, F&& fn);
@@ -505,6 +546,50 @@ class EngineGroup {
     int last_ctx_ = 1;
     bool background_ = false;  // jobs without a callback run their back half on the context's worker (off: Q3TTS_SERIAL_JOBS)
     Engine* free_context();  // throws when both contexts have a job outstanding
+};
+
+// A serving session (q3tts_session_*): the slot loop of the first context on a thread of its own, fed from a SessionQueue that
+// any thread may submit to while the loop runs. The loop is Engine::run_queued, the one q3tts_generate_queued runs, with the
+// session as its request source: ticket t is what index t is to a closed call.
+class Session final : public RequestSource {
+  public:
+    struct Item {  // a submitted request as the queue holds it: self-contained (check_queued copied what the caller pointed at)
+        ResolvedRequest rr;
+        SamplingParams params{};
+    };
+    Session(EngineGroup& g, Engine& lane, const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
+    ~Session() override;  // closes without drain
+    // every check of a queued request on the calling thread; throws Error (3: refused, 9: max_pending waiting, or what the loop failed with)
+    void submit(const q3tts_request& r, const Voice* voice, const q3tts_row_sampling* rs, int64_t* ticket);
+    int cancel(int64_t ticket) { return queue_.cancel(ticket); }
+    void wait(int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready);
+    void stats(q3tts_session_stats* s) const { queue_.stats(s); }
+    int close(bool drain);  // joins the loop thread; the status it failed with, or 0
+    bool on_loop_thread() const { return std::this_thread::get_id() == thread_.get_id(); }
+    std::string error() const;
+
+    bool take(QueueItem& out) override;
+    q3tts_result* result(int ticket) override { return queue_.result(ticket); }
+    void complete(int ticket) override { queue_.complete(ticket); }
+    bool open_ended() const override { return true; }
+    bool wait_for_work() override { return queue_.wait_for_work(); }
+    bool has_cancels() override { return queue_.has_cancels(); }
+    void take_cancels(std::vector<int>& out) override;
+    void complete_cancelled(int ticket) override { queue_.complete_cancelled(ticket); }
+    void progress(int frame_steps, int admissions) override { queue_.progress(frame_steps, admissions); }
+
+  private:
+    void loop();
+    EngineGroup& g_;
+    Engine& lane_;
+    const int slots_, max_ref_frames_;
+    q3tts_sampling sp_;
+    q3tts_event_cb cb_;
+    void* user_;
+    SessionQueue<Item> queue_;
+    mutable std::mutex err_mu_;
+    std::string error_;  // what the loop thread failed with
+    std::thread thread_;
 };
 
 }  // namespace q3

@@ -257,6 +257,9 @@ struct AdmitArgs {
     uint8_t *finished, *active, *seen;
 };
 void launch_admit_rows(const AdmitArgs& a, int k, hipStream_t st);
+// A session's cancel (Engine::run_queued): the slots whose bit is set in `mask` become empty slots (finished = 1, active = 0)
+// in one launch; slots <= 64 (the bound on max_batch). Every other slot's row carries on.
+void launch_cancel_rows(uint64_t mask, uint8_t* finished, uint8_t* active, int slots, hipStream_t st);
 
 
 // prompt assembly (Qwen3.swift:371-406, 505-510): dst[dst_row[i]] = proj[a[i]] when b[i] == -1, else

@@ -218,6 +218,15 @@ __global__ __launch_bounds__(256) void admit_rows_kernel(AdmitArgs a) {
     }
 }
 
+// Continuous batching: the slots listed in `mask` (bit s: slot s) leave the frame step at once -- finished up, active down, the
+// state of an empty slot -- whatever their rows were doing. The slots around them are not touched. One launch, one wave.
+__global__ __launch_bounds__(64) void cancel_rows_kernel(unsigned long long mask, uint8_t* finished, uint8_t* active, int slots) {
+    const int s = threadIdx.x;
+    if (s >= slots || !((mask >> s) & 1ull)) return;
+    finished[s] = 1;
+    active[s] = 0;
+}
+
 // Diagnostics (Q3TTS_FRAME_STAMPS=1): slot[k] accumulates the time between this stamp and the previous one of the same
 // frame step, so that the phases of a REPLAYED graph can be timed (a tracing profiler perturbs a chain of 5 us launches).
 __global__ void stamp_kernel(unsigned long long* acc, unsigned long long* last, int k) {
@@ -325,6 +334,12 @@ void launch_advance_len(int32_t* kv_len, const uint8_t* active, int B, hipStream
 void launch_admit_rows(const AdmitArgs& a, int k, hipStream_t st) {
     if (k <= 0) return;
     hipLaunchKernelGGL(admit_rows_kernel, dim3(k), dim3(256), 0, st, a);
+}
+void launch_cancel_rows(uint64_t mask, uint8_t* finished, uint8_t* active, int slots, hipStream_t st) {
+    Q3_CHECK(slots >= 1 && slots <= 64, 7, "internal error: cancel_rows covers at most 64 slots");
+    if (slots < 64) mask &= (uint64_t(1) << slots) - 1;
+    if (mask == 0) return;
+    hipLaunchKernelGGL(cancel_rows_kernel, dim3(1), dim3(64), 0, st, (unsigned long long)mask, finished, active, slots);
 }
 void launch_frame_end(const FrameEndArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(frame_end_kernel, dim3(a.B), dim3(256), 0, st, a);

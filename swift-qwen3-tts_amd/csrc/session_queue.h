@@ -1,0 +1,261 @@
+// session_queue.h -- the host-only bookkeeping of a serving session (include/q3tts.h, q3tts_session_*): ticket assignment, the
+// pending requests, cancel marks, the result store and wait / notify. No HIP include, so
+// tests/native/session_queue_driver.cc compiles it with a plain C++ compiler and runs it under the sanitizers.
+//
+// Producers (any thread): submit, cancel, wait, stats, close. One consumer (the session's loop thread): take / wait_for_work /
+// take_cancels / result / complete / fail. A ticket is Pending (accepted, in the deque), Running (handed to the consumer) or Done
+// (its result is filled and waits to be claimed); a claimed ticket is forgotten.
+#pragma once
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
+#include <cstdint>
+#include <cstring>
+#include <deque>
+#include <map>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "../../include/q3tts.h"
+
+// gcc 11's thread sanitizer runtime does not see through pthread_cond_clockwait, which a steady-clock timed wait becomes, and then
+// reports the mutex as never released. A build under that sanitizer (the test driver's) waits against the system clock instead,
+// which is pthread_cond_timedwait; every other build waits against the steady clock, so that a step of the wall clock does not
+// stretch or shorten a timeout.
+#if defined(__SANITIZE_THREAD__)
+#define Q3_SESSION_WAIT_CLOCK std::chrono::system_clock
+#elif defined(__has_feature)
+#if __has_feature(thread_sanitizer)
+#define Q3_SESSION_WAIT_CLOCK std::chrono::system_clock
+#endif
+#endif
+#ifndef Q3_SESSION_WAIT_CLOCK
+#define Q3_SESSION_WAIT_CLOCK std::chrono::steady_clock
+#endif
+
+namespace q3 {
+
+template <class Req>
+class SessionQueue {
+  public:
+    using FreeFn = void (*)(q3tts_result*);  // frees what a result points at (q3tts_result_free of one result)
+    static constexpr int kDefaultPending = 1024;
+
+    SessionQueue(int max_pending, FreeFn free_fn) : max_pending_(max_pending > 0 ? max_pending : kDefaultPending), free_(free_fn) {}
+    ~SessionQueue() {  // unclaimed results go with the queue
+        for (auto& kv : entries_)
+            if (kv.second.state == Done) free_(&kv.second.res);
+    }
+    SessionQueue(const SessionQueue&) = delete;
+    SessionQueue& operator=(const SessionQueue&) = delete;
+
+    // ---- producers ----
+    // The t-th accepted submit gets ticket t. A refused one (BUSY, closing, failed) consumes no ticket.
+    int submit(Req&& r, int64_t* ticket) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (failed_) return failed_;
+            if (closing_) return Q3TTS_ERR_INVALID_INPUT;
+            if (next_ > int64_t(INT32_MAX)) return Q3TTS_ERR_INVALID_INPUT;  // events carry the ticket as an int32
+            if (int(pending_.size()) >= max_pending_) return Q3TTS_ERR_BUSY;
+            const int64_t t = next_++;
+            Entry& e = entries_[t];
+            e.req = std::move(r);
+            pending_.push_back(t);
+            ++submitted_;
+            if (ticket) *ticket = t;
+        }
+        work_cv_.notify_one();
+        return Q3TTS_OK;
+    }
+    // Pending: never handed out, Done at once with CANCELLED. Running: marked, the consumer completes it at its next boundary.
+    // Done, claimed or already marked: nothing changes. A ticket that was never given out: INVALID_INPUT.
+    int cancel(int64_t ticket) {
+        bool done = false;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (ticket < 0 || ticket >= next_) return Q3TTS_ERR_INVALID_INPUT;
+            auto it = entries_.find(ticket);
+            if (it == entries_.end()) return Q3TTS_OK;  // claimed
+            Entry& e = it->second;
+            if (e.state == Pending) {
+                pending_.erase(std::find(pending_.begin(), pending_.end(), ticket));
+                finish_locked(e, Q3TTS_ERR_CANCELLED, true);
+                done = true;
+            } else if (e.state == Running && !e.cancel) {
+                e.cancel = true;
+                cancels_.push_back(ticket);
+            }
+        }
+        if (done) done_cv_.notify_all();
+        return Q3TTS_OK;
+    }
+    // *ready = 1: the result is the caller's and the ticket is forgotten. *ready = 0 (timeout): nothing is touched.
+    int wait(int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready) {
+        if (ready) *ready = 0;
+        std::unique_lock<std::mutex> lk(mu_);
+        auto settled = [&] {
+            auto it = entries_.find(ticket);
+            return it == entries_.end() || it->second.state == Done;
+        };
+        if (entries_.find(ticket) == entries_.end()) return Q3TTS_ERR_INVALID_INPUT;
+        if (timeout_ms < 0) done_cv_.wait(lk, settled);
+        else done_cv_.wait_until(lk, Q3_SESSION_WAIT_CLOCK::now() + std::chrono::milliseconds(timeout_ms), settled);
+        auto it = entries_.find(ticket);
+        if (it == entries_.end()) return Q3TTS_ERR_INVALID_INPUT;  // (another waiter claimed it)
+        if (it->second.state != Done) return Q3TTS_OK;
+        if (out) *out = it->second.res;
+        else free_(&it->second.res);
+        entries_.erase(it);
+        if (ready) *ready = 1;
+        return Q3TTS_OK;
+    }
+    void stats(q3tts_session_stats* s) const {
+        std::lock_guard<std::mutex> lk(mu_);
+        std::memset(s, 0, sizeof(*s));
+        s->submitted = submitted_;
+        s->pending = int64_t(pending_.size());
+        s->running = running_;
+        s->completed = completed_;
+        s->cancelled = cancelled_;
+        s->frame_steps = frame_steps_;
+        s->admissions = admissions_;
+    }
+    // No submit is accepted any more. drain: everything accepted still runs; otherwise every pending ticket is cancelled at once
+    // and every running one is marked. The consumer's wait_for_work() returns false once nothing is pending.
+    void close(bool drain) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            closing_ = true;
+            if (!drain) {
+                for (int64_t t : pending_) finish_locked(entries_[t], Q3TTS_ERR_CANCELLED, true);
+                pending_.clear();
+                for (auto& kv : entries_)
+                    if (kv.second.state == Running && !kv.second.cancel) {
+                        kv.second.cancel = true;
+                        cancels_.push_back(kv.first);
+                    }
+            }
+        }
+        work_cv_.notify_all();
+        done_cv_.notify_all();
+    }
+    int failed() const {
+        std::lock_guard<std::mutex> lk(mu_);
+        return failed_;
+    }
+
+    // ---- the consumer ----
+    // the next pending request in ticket order (it is Running from here on); false: none is waiting now
+    bool take(int64_t* ticket, Req* out) {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (pending_.empty() || failed_) return false;
+        const int64_t t = pending_.front();
+        pending_.pop_front();
+        Entry& e = entries_[t];
+        e.state = Running;
+        *out = std::move(e.req);
+        e.req = Req();
+        *ticket = t;
+        ++running_;
+        return true;
+    }
+    // nothing is running: sleeps until a request is pending (true) or the queue is closing with none left (false)
+    bool wait_for_work() {
+        std::unique_lock<std::mutex> lk(mu_);
+        work_cv_.wait(lk, [&] { return !pending_.empty() || closing_ || failed_; });
+        return !pending_.empty() && !failed_;
+    }
+    bool has_cancels() const {
+        std::lock_guard<std::mutex> lk(mu_);
+        return !cancels_.empty();
+    }
+    void take_cancels(std::vector<int64_t>& out) {  // running tickets marked since the last call
+        std::lock_guard<std::mutex> lk(mu_);
+        out.assign(cancels_.begin(), cancels_.end());
+        cancels_.clear();
+    }
+    // A running ticket's result: a stable address that only the consumer writes until complete(). nullptr: not running.
+    q3tts_result* result(int64_t ticket) {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = entries_.find(ticket);
+        return it != entries_.end() && it->second.state == Running ? &it->second.res : nullptr;
+    }
+    void complete(int64_t ticket) {  // its result is filled (status included)
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            auto it = entries_.find(ticket);
+            if (it == entries_.end() || it->second.state != Running) return;
+            --running_;
+            finish_locked(it->second, it->second.res.status, false);
+        }
+        done_cv_.notify_all();
+    }
+    void complete_cancelled(int64_t ticket) {  // whatever the consumer had put into its result is freed
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            auto it = entries_.find(ticket);
+            if (it == entries_.end() || it->second.state != Running) return;
+            --running_;
+            finish_locked(it->second, Q3TTS_ERR_CANCELLED, true);
+        }
+        done_cv_.notify_all();
+    }
+    // the consumer has failed: every pending and running ticket completes with `status`, and every later submit returns it
+    void fail(int status) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            failed_ = status;
+            pending_.clear();
+            cancels_.clear();
+            for (auto& kv : entries_) {
+                Entry& e = kv.second;
+                if (e.state == Done) continue;
+                if (e.state == Running) --running_;
+                finish_locked(e, status, true);
+            }
+        }
+        work_cv_.notify_all();
+        done_cv_.notify_all();
+    }
+    void progress(int frame_steps, int admissions) {
+        std::lock_guard<std::mutex> lk(mu_);
+        frame_steps_ += frame_steps;
+        admissions_ += admissions;
+    }
+
+  private:
+    enum State { Pending, Running, Done };
+    struct Entry {
+        State state = Pending;
+        bool cancel = false;
+        Req req{};
+        q3tts_result res{};
+    };
+    void finish_locked(Entry& e, int status, bool wipe) {  // wipe: the result carries nothing but the status
+        e.state = Done;
+        e.req = Req();
+        if (wipe) {
+            free_(&e.res);
+            std::memset(&e.res, 0, sizeof(e.res));
+        }
+        e.res.status = static_cast<q3tts_status>(status);
+        if (status == Q3TTS_ERR_CANCELLED) ++cancelled_;
+        else ++completed_;
+    }
+
+    mutable std::mutex mu_;
+    std::condition_variable work_cv_, done_cv_;
+    const int max_pending_;
+    const FreeFn free_;
+    std::map<int64_t, Entry> entries_;  // every ticket that is not claimed yet
+    std::deque<int64_t> pending_;       // in ticket order
+    std::deque<int64_t> cancels_;
+    int64_t next_ = 0;
+    int64_t submitted_ = 0, running_ = 0, completed_ = 0, cancelled_ = 0, frame_steps_ = 0, admissions_ = 0;
+    bool closing_ = false;
+    int failed_ = 0;
+};
+
+}  // namespace q3

@@ -89,6 +89,18 @@ class VoiceInfo(C.Structure):  # q3tts_voice_info
                 ("device_bytes", C.c_int64)]
 
 
+class SessionOpts(C.Structure):  # q3tts_session_opts
+    _fields_ = [("slots", C.c_int32), ("max_pending", C.c_int32), ("max_ref_frames", C.c_int32)]
+
+
+class SessionStats(C.Structure):  # q3tts_session_stats
+    _fields_ = [("submitted", C.c_int64), ("pending", C.c_int64), ("running", C.c_int64), ("completed", C.c_int64),
+                ("cancelled", C.c_int64), ("frame_steps", C.c_int64), ("admissions", C.c_int64)]
+
+
+ERR_CANCELLED, ERR_BUSY = 8, 9  # q3tts_status: a cancelled request's result; submit with max_pending requests waiting
+
+
 class AttnDebug(C.Structure):  # q3tts_attn_debug
     _fields_ = [("n_heads", C.c_int32), ("n_kv", C.c_int32), ("B", C.c_int32), ("eps", C.c_float), ("scale", C.c_float),
                 ("max_pages", C.c_int32), ("fixed_len", C.c_int32), ("identity_pages", C.c_int32), ("chunk", C.c_int32),
@@ -138,6 +150,13 @@ def lib() -> C.CDLL:
                                         C.POINTER(Result)]
     L.q3tts_generate_queued_voices.argtypes = [vp, C.POINTER(Request), C.POINTER(vp), C.c_int32, C.c_int32, C.POINTER(Sampling),
                                                EVENT_CB, vp, C.POINTER(Result)]
+    if hasattr(L, "q3tts_session_open"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_session_open.argtypes = [vp, C.POINTER(SessionOpts), C.POINTER(Sampling), EVENT_CB, vp, C.POINTER(vp)]
+        L.q3tts_session_submit.argtypes = [vp, C.POINTER(Request), vp, C.POINTER(RowSampling), C.POINTER(C.c_int64)]
+        L.q3tts_session_cancel.argtypes = [vp, C.c_int64]
+        L.q3tts_session_wait.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(Result), i32p]
+        L.q3tts_session_get_stats.argtypes = [vp, C.POINTER(SessionStats)]
+        L.q3tts_session_close.argtypes = [vp, C.c_int32]
     L.q3tts_generate_begin.argtypes = [vp, C.POINTER(Request), C.c_int32, C.POINTER(Sampling), EVENT_CB, vp, C.c_int32, C.POINTER(vp)]
     L.q3tts_generate_end.argtypes = [vp, vp, C.POINTER(Result)]
     L.q3tts_pcm_to_int16.argtypes = [f32p, C.c_int64, C.POINTER(C.c_int16)]

@@ -414,7 +414,7 @@ class Qwen3TTSModel:
 
         return L.EVENT_CB(_cb)
 
-    def _collect(self, st, res, n) -> List[GenerationResult]:
+    def _collect(self, st, res, n, set_last: bool = True) -> List[GenerationResult]:
         """Results as numpy arrays that VIEW the library's buffers (49 MB of PCM per 32 x 16 s batch: no second copy); the
         buffers go back through q3tts_result_free when the last array over them is collected."""
         block = _ResultBlock(self._lib, res, n)
@@ -431,8 +431,28 @@ class Qwen3TTSModel:
             audio = np.asarray(_RowBuf(block, C.cast(r.pcm, C.c_void_p).value, (int(r.n_samples),), "<f4"))
             codes = np.asarray(_RowBuf(block, C.cast(r.codes, C.c_void_p).value, (int(r.n_frames), 16), "<i4"))
             out.append(GenerationResult(audio, codes, info, 0))
-        self.last_info = out[0].info if out else None
+        if set_last:
+            self.last_info = out[0].info if out else None
         return out
+
+    def open_session(self, slots: Optional[int] = None, max_pending: int = 0, max_ref_frames: int = 0,
+                     on_event: Optional[Callable[[int, str, object], None]] = None, temperature: float = 0.9, top_k: int = 50,
+                     top_p: float = 1.0, repetition_penalty: float = 1.05, seed: int = 0, force_frames: int = 0,
+                     audio_chunk_frames: int = 0, audio_window_frames: int = 0, audio_lookahead_frames: int = 4, row_base: int = 0,
+                     audio_stream_reference: int = 0) -> "Session":
+        """q3tts_session_open: the slot loop of generate_queued on a thread of its own, with an open end. Requests are
+        submitted, cancelled and collected one by one while it runs; ticket t's result is bit-identical to
+        generate_batch([request], row_base=row_base + t) with the session's keywords and the request's own `sampling`.
+        `on_event(ticket, kind, payload)` fires on the session's thread. While the session is open the model's other
+        generating calls are refused (status 3); voices are created before it is opened, and `max_ref_frames` bounds the
+        references a submit may name."""
+        s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
+                           audio_window_frames, audio_lookahead_frames, row_base, audio_stream_reference=audio_stream_reference)
+        o = L.SessionOpts(int(self.info.max_batch) if slots is None else int(slots), int(max_pending), int(max_ref_frames))
+        cb = self._event_cb(on_event)
+        h = C.c_void_p()
+        self._check(self._lib.q3tts_session_open(self._h, C.byref(o), C.byref(s), cb, None, C.byref(h)))
+        return Session(self, h, cb)
 
     def generate_batch_begin(self, reqs: Sequence[GenerationRequest], temperature: float = 0.9, top_k: int = 50,
                              top_p: float = 1.0, repetition_penalty: float = 1.05, seed: int = 0, force_frames: int = 0,
@@ -749,6 +769,75 @@ class Qwen3TTSModel:
         self._check(self._lib.q3tts_debug_codec_stage(self._h, codes.ctypes.data_as(L.i32p), F, stage.encode(),
                                                       out.ctypes.data_as(L.f32p), cap, C.byref(T), C.byref(Cc)))
         return out[: T.value * Cc.value].reshape(T.value, Cc.value).copy()
+
+
+class Session:
+    """An open serving session (Qwen3TTSModel.open_session). submit / result / cancel / stats may be called from any thread,
+    submit and cancel also from inside `on_event`; result and close may not (they would wait for the thread they run on)."""
+
+    def __init__(self, model: Qwen3TTSModel, handle: C.c_void_p, cb):
+        self._model, self._h, self._cb = model, handle, cb  # (the callback object lives as long as the session's thread)
+
+    def _handle(self):
+        if not self._h or not self._model._h:
+            raise Qwen3TTSError(3, "Invalid input: the session has been closed")
+        return self._h
+
+    def submit(self, request: GenerationRequest, **row_sampling) -> int:
+        """Returns the request's ticket. Keywords (temperature, top_k, top_p, repetition_penalty, seed) override
+        `request.sampling` for this submit; `request.voice` is honoured. Status 9 (Qwen3TTSError) when max_pending wait."""
+        m = self._model
+        arr, keep = m._marshal([request])
+        rs = RequestSampling(**row_sampling) if row_sampling else getattr(request, "sampling", None)
+        rows = m._row_sampling([rs])
+        voice = getattr(request, "voice", None)
+        if voice is not None and not voice._h:
+            raise Qwen3TTSError(3, "Invalid input: the voice of the request has been closed")
+        t = C.c_int64(-1)
+        st = m._lib.q3tts_session_submit(self._handle(), arr, voice._h if voice is not None else None,
+                                         rows if rows is not None else None, C.byref(t))
+        del keep
+        m._check(st)
+        return int(t.value)
+
+    def result(self, ticket: int, timeout: Optional[float] = None) -> GenerationResult:
+        """Waits for the ticket's result and takes it (a second call for the same ticket is status 3). A cancelled
+        request's result has status 8 and no audio. TimeoutError when `timeout` seconds pass first."""
+        m = self._model
+        res = (L.Result * 1)()
+        ready = C.c_int32(0)
+        ms = -1 if timeout is None else max(0, int(round(timeout * 1000)))
+        st = m._lib.q3tts_session_wait(self._handle(), int(ticket), ms, res, C.byref(ready))
+        if st == 0 and not ready.value:
+            raise TimeoutError("ticket %d was not ready after %s s" % (ticket, timeout))
+        if st != 0:
+            m._check(st)
+        return m._collect(0, res, 1, set_last=False)[0]
+
+    def cancel(self, ticket: int) -> None:
+        self._model._check(self._model._lib.q3tts_session_cancel(self._handle(), int(ticket)))
+
+    def stats(self) -> L.SessionStats:
+        s = L.SessionStats()
+        self._model._check(self._model._lib.q3tts_session_get_stats(self._handle(), C.byref(s)))
+        return s
+
+    def close(self, drain: bool = True) -> None:
+        """drain: everything accepted finishes first; otherwise whatever is pending or running is cancelled. Results not
+        collected before are gone."""
+        if self._h and self._model._h:
+            h, self._h = self._h, None
+            st = self._model._lib.q3tts_session_close(h, 1 if drain else 0)
+            if st == 3 and self._model._h:  # refused (called from on_event): the session is still open
+                self._h = h
+            self._model._check(st)
+        self._h = None if not self._model._h else self._h
+
+    def __enter__(self) -> "Session":
+        return self
+
+    def __exit__(self, *exc):
+        self.close(drain=exc[0] is None)
 
 
 class NativeTokenizer:

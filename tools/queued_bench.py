@@ -27,6 +27,13 @@ alternating --repeat times, with frames/s, frontend / prefill / codec millisecon
 front of its request's stream): the voices' saved tail states against Q3TTS_NO_PREFIX_CACHE=1 (every admission decodes its
 reference again), alternating --repeat times, with frames/s and per request the time from admission to first AUDIO_CHUNK, median
 and worst, and whether the two agree bit for bit.
+--session [--arrivals RATE] runs the ragged workload through a serving session (q3tts_session_*): requests are submitted one by
+one, open-loop, with exponential gaps of mean 1 / RATE seconds from a fixed seed (RATE = inf, the default: all at once), and
+collected by ticket. Printed: frames/s over the time from the first submit to the last completion, and per request the time from
+its submit to its completion (its AUDIO event; without a callback: when its result was collected, in ticket order) -- median, p95
+and max over the requests that succeeded; with --stream also from its submit to its first AUDIO_CHUNK. The same requests as one closed q3tts_generate_queued call, with the same callback, stand next
+to it (every request "submitted" at the call). With RATE = inf the session and the closed call also alternate --repeat times
+WITHOUT a callback, which is the saturated-throughput comparison, and their results are compared bit for bit.
 """
 from __future__ import annotations
 
@@ -94,6 +101,106 @@ def run_queued_timed(model, reqs, slots, kw):
     first = first_chunk if first_chunk else audio
     lat = [first[i] - (last_token[i] - out[i].info.generate_time) for i in range(len(reqs)) if i in first and i in last_token]
     return out, dt, tm, np.asarray(lat)
+
+
+def _pct(x):
+    x = np.asarray(x) * 1e3
+    return f"median {np.median(x):8.1f} ms  p95 {np.percentile(x, 95):8.1f} ms  max {x.max():8.1f} ms" if x.size else "none"
+
+
+def run_session(model, reqs, slots, kw, rate, timed):
+    """The requests through a session at `rate` arrivals per second (inf: all at once). Returns results, wall time, and, when
+    `timed`, per request submit -> completion and submit -> first AUDIO_CHUNK (seconds)."""
+    n = len(reqs)
+    submit_t, done_t, first_chunk = [0.0] * n, {}, {}
+
+    def on_event(i, kind, payload):
+        if kind == "audio_chunk":
+            first_chunk.setdefault(i, time.perf_counter())
+        elif kind == "audio":
+            done_t[i] = time.perf_counter()
+
+    gaps = np.random.default_rng(4321).exponential(1.0 / rate, size=n) if np.isfinite(rate) else np.zeros(n)
+    s = model.open_session(slots=slots, max_pending=n, on_event=on_event if timed else None, **kw)
+    try:
+        t0 = time.perf_counter()
+        due = t0
+        for i, r in enumerate(reqs):
+            due += gaps[i]
+            while True:  # open loop: the arrival times do not depend on how the session is doing
+                now = time.perf_counter()
+                if now >= due:
+                    break
+                time.sleep(min(due - now, 0.002))
+            submit_t[i] = time.perf_counter()
+            assert s.submit(r) == i
+        out = []
+        for i in range(n):
+            out.append(s.result(i, timeout=600))
+            if not timed:
+                done_t[i] = time.perf_counter()  # (no callback: when its result was collected)
+        dt = time.perf_counter() - t0
+        st = s.stats()
+        s.close()
+    finally:
+        s.close(drain=False)
+    done = np.asarray([done_t[i] - submit_t[i] for i in range(n) if i in done_t])  # (a failed request has no AUDIO event)
+    first = np.asarray([first_chunk[i] - submit_t[i] for i in range(n) if i in first_chunk])
+    return out, dt, st, done, first
+
+
+def run_closed_timed(model, reqs, slots, kw):
+    """The same requests as one closed call with the same stamps: every request counts as submitted when the call starts."""
+    done_t, first_chunk = {}, {}
+
+    def on_event(i, kind, payload):
+        if kind == "audio_chunk":
+            first_chunk.setdefault(i, time.perf_counter())
+        elif kind == "audio":
+            done_t[i] = time.perf_counter()
+
+    t0 = time.perf_counter()
+    out = model.generate_queued(reqs, slots=slots, on_event=on_event, **kw)
+    dt = time.perf_counter() - t0
+    done = np.asarray([done_t[i] - t0 for i in range(len(reqs)) if i in done_t])
+    first = np.asarray([first_chunk[i] - t0 for i in range(len(reqs)) if i in first_chunk])
+    return out, dt, done, first
+
+
+def run_session_bench(model, args, ragged, warm, sampling):
+    rate = float(args.arrivals)
+    kw = dict(sampling)
+    if args.stream:
+        c, w, l = (int(x) for x in args.stream.split(","))
+        kw.update(audio_chunk_frames=c, audio_window_frames=w, audio_lookahead_frames=l)
+    run_session(model, warm, args.slots, kw, float("inf"), True)  # warm-up: the session's thread, the stream arena
+    run_closed_timed(model, warm, args.slots, kw)
+    same = lambda a, b: all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio) for x, y in zip(a, b))
+    tag = f"--stream {args.stream}" if args.stream else "whole audio"
+    print(f"# session, {len(ragged)} ragged requests, slots {args.slots}, arrivals {args.arrivals}/s, {tag}", flush=True)
+    if not np.isfinite(rate):
+        for rep in range(args.repeat):  # saturated throughput: no callback on either side
+            a, da, _, _, _ = run_session(model, ragged, args.slots, kw, rate, False)
+            t0 = time.perf_counter()
+            b = model.generate_queued(ragged, slots=args.slots, **kw)
+            db = time.perf_counter() - t0
+            fa, fb = (sum(int(r.codes.shape[0]) for r in x) for x in (a, b))
+            print(f"run {rep} no callback: session frames/s {fa / da:9.1f} (wall {da:7.3f} s)   closed frames/s {fb / db:9.1f} (wall {db:7.3f} s)   "
+                  f"session / closed {(fa / da) / (fb / db):.4f}   bit-identical: {same(a, b)}", flush=True)
+    out, dt, st, done, first = run_session(model, ragged, args.slots, kw, rate, True)
+    frames = sum(int(r.codes.shape[0]) for r in out)
+    print(f"session  frames {frames:7d}  wall {dt:8.3f} s  frames/s {frames / dt:9.1f}  frame_steps {st.frame_steps:6d}  admissions {st.admissions:4d}  "
+          f"failed {sum(1 for r in out if r.status != 0)}", flush=True)
+    print(f"session  submit -> completion:        {_pct(done)}", flush=True)
+    if args.stream:
+        print(f"session  submit -> first AUDIO_CHUNK: {_pct(first)}", flush=True)
+    cout, cdt, cdone, cfirst = run_closed_timed(model, ragged, args.slots, kw)
+    cframes = sum(int(r.codes.shape[0]) for r in cout)
+    print(f"closed   frames {cframes:7d}  wall {cdt:8.3f} s  frames/s {cframes / cdt:9.1f}   (one q3tts_generate_queued call, same callback)", flush=True)
+    print(f"closed   call -> completion:          {_pct(cdone)}", flush=True)
+    if args.stream:
+        print(f"closed   call -> first AUDIO_CHUNK:   {_pct(cfirst)}", flush=True)
+    print(f"bit-identical codes + pcm, session against the closed call: {same(out, cout)}", flush=True)
 
 
 def run_voices(model, args):
@@ -182,7 +289,9 @@ def main():
     ap.add_argument("--mixed-sampling", action="store_true", help="ragged workload: four per-request parameter sets in turn")
     ap.add_argument("--stream", default=None, metavar="CHUNK,WINDOW,LOOKAHEAD", help="also run the ragged queue with streamed audio")
     ap.add_argument("--voices", type=int, default=0, metavar="N", help="Base checkpoint: voice-clone requests, N voices shared round-robin")
-    ap.add_argument("--repeat", type=int, default=3, help="--voices: how often the two paths alternate")
+    ap.add_argument("--repeat", type=int, default=3, help="--voices / --session: how often the two paths alternate")
+    ap.add_argument("--session", action="store_true", help="the ragged workload through a serving session (see --arrivals)")
+    ap.add_argument("--arrivals", default="inf", metavar="RATE", help="--session: requests per second, exponential gaps; inf: all at once")
     args = ap.parse_args()
     from qwen3tts import Qwen3TTSModel, RequestSampling
 
@@ -214,6 +323,10 @@ def main():
     run_static(model, warm, args.slots, sampling)
     run_queued(model, warm, args.slots, sampling)
 
+    if args.session:
+        run_session_bench(model, args, ragged, warm, sampling)
+        model.close()
+        return
     print(f"# {args.preset} bf16, {args.requests} requests, slots {args.slots}; frames/s = generated frames / wall time (codec included)")
     for name, reqs, kw in workloads:
         res = {}

@@ -493,6 +493,48 @@ q3tts_status q3tts_session_wait(q3tts_session* s, int64_t ticket, int32_t timeou
 q3tts_status q3tts_session_get_stats(const q3tts_session* s, q3tts_session_stats* out);
 q3tts_status q3tts_session_close(q3tts_session* s, int32_t drain);
 
+/* Open-text requests (new): a request whose text arrives while it is being spoken -- a voice agent whose text comes out of a
+ * language model token by token. The model does not need the text early: on the generate / CustomVoice / VoiceDesign routes the
+ * prompt holds only the first content token (Qwen3.swift:371-406) and every later one is consumed one per frame (:919-935).
+ * Contract: the result of an open-text ticket t is bit-identical -- status, codes, pcm, n_frames, n_samples -- to q3tts_generate of
+ * the ORDINARY request alone: the same role tokens, all the content tokens that were submitted and appended, any 5 tail tokens,
+ * target_token_count = the number of content tokens, the same sampling, row_base = sampling->row_base + t. This holds whatever
+ * the timing: text that all arrived before the admission, text appended from a TOKEN callback, text appended after the row had
+ * run dry, any number of pieces of any sizes. The streamed forms carry over as for every session request.
+ * Starvation: a row that needs a text row that has not arrived, and whose text is still open, starves: the frame in flight
+ * completes (its codes count, its TOKEN fires), and then the row forms no next input, takes no frame step, draws no random number
+ * and appends nothing to its cache until text arrives; it resumes at the first burst boundary after that with exactly the input
+ * the ordinary request would have formed. It never falls back to tts_pad, which is the reference's input for text that has ENDED.
+ * Streamed chunks that are decodable leave while a row is starved. When every running row is starved and nothing can be admitted
+ * the session thread sleeps on its condition variable like an idle session -- no frame step, no spinning -- until an append, a
+ * cancel, a submit or close.
+ *   q3tts_session_submit_open: text_ids = the 3 role tokens + >= 1 content tokens and NO 5-token tail (n_text_ids >= 4);
+ *     target_token_count is ignored. Every check of q3tts_session_submit for a request without a voice applies; ref_audio is
+ *     refused as there, and so is a voice, which this call cannot name (the ICL prompt of a clone holds the whole text,
+ *     Qwen3.swift:501-512). max_tokens (0 = 2048) must be <= max_frames: while the text is open it is the row's frame cap, and at
+ *     the close the cap becomes the reference's min(max_tokens, max(75, 6 * n_content)) (:822-823) -- which the row cannot have
+ *     passed, since starvation keeps its frames <= its content tokens.
+ *   q3tts_session_append_text: n >= 0 content token ids behind the ticket's text; final != 0 closes the text (n == 0 with final:
+ *     just close). Copied before it returns. Any thread, also from inside an event callback; it never waits for the loop.
+ *     INVALID_INPUT, with nothing changed and the session carrying on: a ticket never given out, a ticket from q3tts_session_submit,
+ *     a ticket whose text is closed, an id outside the text vocabulary, content beyond the trailing-text capacity (max_prompt rows,
+ *     the tts_eos row included: at most max_prompt content tokens), n < 0. A ticket that has completed or was cancelled
+ *     already (EOS sampled early, cap hit, cancel): OK, and the text is dropped, as cancel treats a completed ticket -- the race
+ *     is inherent. Text for a ticket that is still pending is joined to the stored request; one closed before its admission
+ *     is admitted as the ordinary request it now is.
+ *   q3tts_session_close(drain != 0) closes every open text first: such a ticket ends as if `final` had been sent. drain == 0 and
+ *     q3tts_session_cancel work as for every ticket; a starved row is cancellable.
+ *   q3tts_session_get_text_stats: open = tickets accepted whose text is not closed and whose result is not filled; starved =
+ *     running rows waiting for text now; appended_tokens = tokens accepted by append_text, starve_events = times a row ran dry,
+ *     both since open. */
+typedef struct {
+    int64_t open, starved, appended_tokens, starve_events;
+} q3tts_session_text_stats;
+q3tts_status q3tts_session_submit_open(q3tts_session* s, const q3tts_request* req, const q3tts_row_sampling* rs /* or NULL */,
+                                       int64_t* ticket);
+q3tts_status q3tts_session_append_text(q3tts_session* s, int64_t ticket, const int32_t* ids, int32_t n, int32_t final);
+q3tts_status q3tts_session_get_text_stats(const q3tts_session* s, q3tts_session_text_stats* out);
+
 /* Qwen3TTSSpeechTokenizer.decode (Models/SpeechTokenizer.swift:823-836): codes
  * [batch][max_frames][num_code_groups] -> pcm [batch][max_frames*1920] (caller-allocated),
  * audio_lengths[batch] = count(code0 > 0) * 1920. n_frames[b] <= max_frames are the valid rows. Every code of a valid row is
@@ -596,6 +638,16 @@ q3tts_status q3tts_debug_sample(q3tts_model* m, const uint16_t* logits, int32_t 
                                 const q3tts_sampling* sampling, const uint8_t* seen,
                                 int32_t suppress_lo, int32_t suppress_hi, int32_t eos_id,
                                 uint32_t row0, uint32_t draw, int32_t* tokens);
+
+/* The talker input a resumed open-text row gets against the one the end of its frame would have formed (q3tts_session_submit_open):
+ * tables [16][V][H] bf16 (codec embedding, then the 15 code-predictor tables), codes [16], text_row [H]; H a multiple of 128 up
+ * to 4096, V <= 4096. Row 1 of a two-row step runs (0) through the end-of-frame kernel with its text row there, (1) through it
+ * with its text open and no row -- it starves -- and (2) from that state through the append launch with text_row as the new
+ * text. out_h [3][H], out_ss [3] (the row's sum of squares; -1: not written), out_state [3][8] = n_frames, trailing_idx,
+ * n_trailing, finished, active, text_open, starved, cp_len after each. (0) and (2) must agree in every bit of h and ss. The call
+ * allocates its own device buffers and frees them; it touches neither the model's weights nor its caches. */
+q3tts_status q3tts_debug_text_resume(q3tts_model* m, int32_t H, int32_t V, const uint16_t* tables, const int32_t* codes,
+                                     const uint16_t* text_row, uint16_t* out_h, float* out_ss, int32_t* out_state);
 
 /* Skinny bf16 GEMM used by every Linear on the decode path (Talker.swift:183-186,413-415):
  * y[M][N] = x[M][K] W[N][K]^T (+bias), M <= 64. */

@@ -391,6 +391,24 @@ q3tts_status q3tts_session_get_stats(const q3tts_session* s, q3tts_session_stats
     });
 }
 
+q3tts_status q3tts_session_submit_open(q3tts_session* s, const q3tts_request* req, const q3tts_row_sampling* rs, int64_t* ticket) {
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(req && ticket, 3, "Invalid input: null argument");
+        x.submit_open(*req, rs, ticket);
+    });
+}
+
+q3tts_status q3tts_session_append_text(q3tts_session* s, int64_t ticket, const int32_t* ids, int32_t n, int32_t final) {
+    return session_call(s, [&](q3::Session& x) { x.append_text(ticket, ids, n, final != 0); });
+}
+
+q3tts_status q3tts_session_get_text_stats(const q3tts_session* s, q3tts_session_text_stats* out) {
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(out, 3, "Invalid input: null argument");
+        x.text_stats(out);
+    });
+}
+
 q3tts_status q3tts_session_close(q3tts_session* s, int32_t drain) {
     if (!s || !s->m) return Q3TTS_ERR_INVALID_INPUT;
     q3tts_model* m = s->m;
@@ -548,6 +566,14 @@ q3tts_status q3tts_debug_sample(q3tts_model* m, const uint16_t* logits, int32_t 
         Q3_CHECK(m && logits && sampling && tokens, 3, "Invalid input: null argument");
         q3::check_row_sampling(*sampling, rows);
         m->eng->lane0().debug_sample(logits, rows, V, *sampling, seen, suppress_lo, suppress_hi, eos_id, row0, draw, tokens);
+    });
+}
+
+q3tts_status q3tts_debug_text_resume(q3tts_model* m, int32_t H, int32_t V, const uint16_t* tables, const int32_t* codes,
+                                     const uint16_t* text_row, uint16_t* out_h, float* out_ss, int32_t* out_state) {
+    return guarded(m, [&] {
+        Q3_CHECK(m, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_text_resume(H, V, tables, codes, text_row, out_h, out_ss, out_state);
     });
 }
 

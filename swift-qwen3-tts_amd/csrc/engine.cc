@@ -152,6 +152,7 @@ Engine::~Engine() {
     }
     for (auto& g : graphs_) (void)hipGraphExecDestroy(g.second);
     for (auto& g : qgraphs_) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : ographs_) (void)hipGraphExecDestroy(g.second);
     if (qws_) (void)hipFree(qws_);
     codec_.reset();
     fe_.reset();
@@ -420,6 +421,19 @@ void Engine::enqueue_cp_pass(int B, bool from_talker, int head, int cp_pos, bool
     enqueue_layers(m_->cp, cp_, B, cp_kpool_, cp_vpool_, cp_kv_layer_stride_, cp_block_table_, 1, cp_len_, nullptr, ss_count, cp_pos, 1, nullptr, 0);
 }
 
+// The end-of-frame job's operands (row_jobs.h frame_end_job). The resume of a row that waited for its text
+// (launch_text_append_rows) forms the same input from the same operands.
+FrameEndArgs Engine::frame_end_args(int B) const {
+    const TalkerConfig& t = m_->cfg.talker;
+    FrameEndArgs fe{};
+    fe.cur_codes = cur_codes_; fe.codec_emb = m_->codec_emb; fe.cp_emb = m_->cp_emb_dev;
+    fe.trailing = trailing_; fe.n_trailing = n_trailing_; fe.trailing_idx = trailing_idx_; fe.Tmax = Tcap_;
+    fe.tts_pad = tts_pad_; fe.h = tk_.h; fe.hMB = Mp_ / 16; fe.ss_out = tk_.ss_a; fe.H = t.hidden_size; fe.B = B; fe.groups = t.num_code_groups;
+    fe.n_frames = n_frames_; fe.max_frames = max_frames_; fe.finished = finished_; fe.active = active_; fe.cp_len = cp_len_;
+    fe.text_open = frame_text_open_; fe.starved = frame_text_open_ ? starved_ : nullptr;  // (a session's open-text requests only)
+    return fe;
+}
+
 void Engine::enqueue_frame(int B, const DebugOpts* dbg) {
     struct Count {  // launches of this frame step, for q3tts_timing (the same count whether captured or launched eagerly)
         Engine* e;
@@ -497,11 +511,7 @@ void Engine::enqueue_frame(int B, const DebugOpts* dbg) {
             launch_copy_rows(reinterpret_cast<const uint16_t*>(cp_ss2_), 0, reinterpret_cast<uint16_t*>(cp_.ss_a), 0, 1, Mp_ * 2, counted());
         }
     }
-    FrameEndArgs fe{};
-    fe.cur_codes = cur_codes_; fe.codec_emb = m_->codec_emb; fe.cp_emb = m_->cp_emb_dev;
-    fe.trailing = trailing_; fe.n_trailing = n_trailing_; fe.trailing_idx = trailing_idx_; fe.Tmax = Tcap_;
-    fe.tts_pad = tts_pad_; fe.h = tk_.h; fe.hMB = MBL; fe.ss_out = tk_.ss_a; fe.H = H; fe.B = B; fe.groups = groups;
-    fe.n_frames = n_frames_; fe.max_frames = max_frames_; fe.finished = finished_; fe.active = active_; fe.cp_len = cp_len_;
+    const FrameEndArgs fe = frame_end_args(B);
     bool fe_done = false;
     for (int i = 0; i < groups - 1; ++i) {
         const bool second_of_pair = pair && i == 0;  // its stack forward already ran above; rows B..2B-1 hold it
@@ -548,7 +558,8 @@ void Engine::enqueue_frame(int B, const DebugOpts* dbg) {
 
 hipGraphExec_t Engine::frame_graph(int B) {
     // a queued frame step keys its samplers on row_key_ (frame_row_key_ set): a capture of its own
-    std::map<int, hipGraphExec_t>& graphs = frame_row_key_ ? qgraphs_ : graphs_;
+    // (and a session's, whose frame end reads text_open_, another one: the closed queue's step stays exactly what it was)
+    std::map<int, hipGraphExec_t>& graphs = frame_text_open_ ? ographs_ : frame_row_key_ ? qgraphs_ : graphs_;
     auto it = graphs.find(B);
     if (it != graphs.end()) return it->second;
     hipGraph_t g = nullptr;
@@ -767,9 +778,10 @@ void Engine::assemble_prompts(const std::vector<ResolvedRequest>& reqs, std::vec
             td.push_back(trow * Tcap_ + q);
             ++q;
         };
-        if (tl - 5 > 4)  // Qwen3.swift:394-406
-            for (int i = 4; i < tl - 5; ++i) pusht(text_off[size_t(b)] + i);
-        pusht(eos);
+        // (an open-text request carries no tail, n_tail = 0; while its text is open the tts_eos row is not there yet)
+        if (tl - r.n_tail > 4)  // Qwen3.swift:394-406
+            for (int i = 4; i < tl - r.n_tail; ++i) pusht(text_off[size_t(b)] + i);
+        if (!r.text_open) pusht(eos);
         Q3_CHECK(q <= Tcap_, 3, "Invalid input: text longer than max_prompt");
         n_trailing[size_t(b)] = q;
     }
@@ -2138,17 +2150,26 @@ bool Engine::job_outstanding() const {
 // resolve() plus every limit a request would otherwise hit inside the slot loop, on the host: the lengths are the ones
 // assemble_prompts produces -- for an ordinary request, or with `voice` for the ICL prompt of a voice-clone request (a
 // request that carries its clip as ref_audio is refused here: its front end has no place at a burst boundary)
-ResolvedRequest Engine::check_queued(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice) const {
+ResolvedRequest Engine::check_queued(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice, bool open_text) const {
     const TalkerConfig& t = m_->cfg.talker;
     Q3_CHECK(r.ref_audio == nullptr, 3, "Invalid input: voice-clone requests (ref_audio) are not supported by q3tts_generate_queued");
     ResolvedRequest o = resolve(r, sp, voice);
+    if (open_text) {  // role + content, no tail; the frame cap while the text is open is max_tokens (final_text_cap at the close)
+        Q3_CHECK(!o.clone, 3, "Invalid input: an open-text request cannot be a voice-clone request");
+        o.n_tail = 0;
+        o.text_open = true;
+        o.open_max_tokens = r.max_tokens > 0 ? r.max_tokens : 2048;
+        o.open_force_frames = sp.force_frames;
+        o.max_frames = sp.force_frames > 0 ? sp.force_frames : o.open_max_tokens;
+        o.target_token_count = int(o.text_ids.size()) - 3;
+    }
     Q3_CHECK(m_->has_codec, 1, "Model not initialized: Speech tokenizer not loaded");  // Qwen3.swift:799-801
     Q3_CHECK(o.max_frames <= Fcap_, 3, "Invalid input: max_tokens exceeds the configured max_frames");
     Q3_CHECK(o.language_id < t.vocab_size && o.speaker_token < t.vocab_size, 3, "Invalid input: codec prefix id out of range");
     const int tl = int(o.text_ids.size());
     int nc = (o.language_id < 0 ? 3 : 4) + (o.speaker_token >= 0 ? 1 : 0) + 2;  // codec prefix (Qwen3.swift:322-359)
     int np = int(o.instruct_ids.size()) + 3 + nc;                                // instruct, role, prefix, first text token
-    int nt = (tl - 5 > 4 ? tl - 9 : 0) + 1;                                      // trailing text + tts_eos (:394-406)
+    int nt = (tl - o.n_tail > 4 ? tl - o.n_tail - 4 : 0) + 1;                    // trailing text + tts_eos (:394-406)
     if (o.clone) {  // the ICL prompt (assemble_prompts): role, prefix with the x-vector, reference text, target text, tts_eos,
                     // codec_bos, one row per reference frame; the trailing text is tts_pad alone
         nc += m_->has_speaker_encoder ? 1 : 0;
@@ -2185,7 +2206,10 @@ void Engine::ensure_queue_ws() {
         q_n_prompt_ = b.take<int32_t>(size_t(Bm_));
         q_desc_ = b.take<AdmitDesc>(size_t(Bm_));
         row_key_ = b.take<uint32_t>(size_t(Bm_));
+        q_text_desc_ = b.take<TextAppendDesc>(size_t(Bm_));
         q_active_ = b.take<uint8_t>(size_t(Bm_));
+        text_open_ = b.take<uint8_t>(size_t(Bm_));
+        starved_ = b.take<uint8_t>(size_t(Bm_));
         if (!pass) {
             const size_t bytes = align_up(b.off, 256);
             Q3_HIP(hipMalloc(reinterpret_cast<void**>(&base), bytes));
@@ -2205,6 +2229,72 @@ struct Engine::QLive {
 };
 
 void Engine::cancel_slots(uint64_t mask, int slots) { launch_cancel_rows(mask, finished_, active_, slots, st_); }
+
+// What was appended to running open-text requests since the last boundary: the new ids go through text_projection like a
+// prompt's (project_rows; row 0 of the pass is tts_eos, for the closes) and one launch puts them behind the slots' trailing
+// text, closes the texts that ended and resumes the rows that waited (kernels.h TextAppendArgs). Text for a ticket that is in
+// no slot any more -- retired, cancelled -- is dropped: the caller cannot know.
+void Engine::apply_text_appends(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int, QLive>& live) {
+    std::vector<RequestSource::TextAppend> msgs;
+    q.src->take_appends(msgs);
+    const int S = int(sl.size());
+    struct Add {
+        std::vector<int32_t> ids;
+        bool close = false;
+    };
+    std::vector<Add> add((size_t)(S));
+    for (auto& m : msgs)
+        for (int s = 0; s < S; ++s)
+            if (sl[size_t(s)].req == m.ticket && sl[size_t(s)].open && !add[size_t(s)].close) {
+                add[size_t(s)].ids.insert(add[size_t(s)].ids.end(), m.ids.begin(), m.ids.end());
+                add[size_t(s)].close = m.final;
+            }
+    q_text_ids_.assign(1, m_->cfg.tts_eos_token_id);
+    q_text_desc_host_.clear();
+    for (int s = 0; s < S; ++s) {
+        Add& a = add[size_t(s)];
+        if (a.ids.empty() && !a.close) continue;
+        QSlot& x = sl[size_t(s)];
+        QLive& w = live.at(x.req);
+        const int n_new = int(a.ids.size());
+        // trailing rows = content - 1, + 1 for tts_eos at the close: at most Tcap_ content tokens (the session's append checked it)
+        Q3_CHECK(x.n_content + n_new <= Tcap_, 7, "internal error: appended text beyond the trailing-text rows");
+        TextAppendDesc d{};
+        d.slot = s;
+        d.src_row = int(q_text_ids_.size());
+        d.n_new = n_new;
+        q_text_ids_.insert(q_text_ids_.end(), a.ids.begin(), a.ids.end());
+        x.n_content += n_new;
+        w.rr.target_token_count = x.n_content;
+        if (a.close) {
+            // The cap the ordinary request would have had from its first frame on. The row cannot have passed it: a row forms
+            // frame f + 1's input from content token f + 1, so starvation keeps its frames <= its content tokens n, it is below
+            // max_tokens or it would have ended, and n < max(75, 6 n); with force_frames both caps are force_frames.
+            d.close = 1;
+            d.max_frames = final_text_cap(w.rr.open_max_tokens, w.rr.open_force_frames, x.n_content);
+            x.open = false;
+            x.cap = d.max_frames;
+            w.rr.max_frames = d.max_frames;
+            w.rr.text_open = false;
+        }
+        x.starved = false;  // (it has its next text row now -- a new one, or tts_eos: the launch below resumes it)
+        q_text_desc_host_.push_back(d);
+    }
+    const int k = int(q_text_desc_host_.size());
+    if (k > 0) {
+        project_rows(q_text_ids_, int(q_text_ids_.size()));
+        Q3_HIP(hipMemcpyAsync(q_text_desc_, q_text_desc_host_.data(), size_t(k) * sizeof(TextAppendDesc), hipMemcpyHostToDevice, st_));
+        TextAppendArgs ta{};
+        ta.desc = q_text_desc_; ta.src = proj_out_; ta.eos_row = proj_out_;
+        ta.trailing = trailing_; ta.n_trailing = n_trailing_; ta.text_open = text_open_; ta.max_frames = max_frames_; ta.slots = S;
+        ta.fe = frame_end_args(S);
+        launch_text_append_rows(ta, q_text_desc_host_.data(), k, st_);
+        Q3_HIP(hipStreamSynchronize(st_));  // (the staging vectors are reused by the next boundary; proj_out_ by the next admission)
+    }
+    int starved_now = 0;
+    for (const QSlot& x : sl) starved_now += x.req >= 0 && x.starved ? 1 : 0;
+    q.src->text_progress(starved_now, 0);
+}
 
 int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int, QLive>& live) {
     std::vector<ResolvedRequest> rr;
@@ -2252,7 +2342,7 @@ int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int
         const int s = slots[size_t(j)];
         for (int i = 0; i < max_pages_; ++i) hbt[size_t(j) * max_pages_ + i] = s * max_pages_ + i;
         hnp[j] = np[size_t(j)];
-        hd[j] = AdmitDesc{s, nt[size_t(j)], rr[size_t(j)].max_frames, keys[size_t(j)], params[size_t(j)]};
+        hd[j] = AdmitDesc{s, nt[size_t(j)], rr[size_t(j)].max_frames, keys[size_t(j)], rr[size_t(j)].text_open ? 1 : 0, params[size_t(j)]};
     }
     Q3_HIP(hipMemcpyAsync(q_bt_, hbt, nbt * 4, hipMemcpyHostToDevice, st_));
     Q3_HIP(hipMemcpyAsync(q_kv_len_, hbt + nbt, size_t(k) * 4, hipMemcpyHostToDevice, st_));
@@ -2268,11 +2358,19 @@ int Engine::admit(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int
     a.cp_len = cp_len_; a.trailing_idx = trailing_idx_; a.cur_codes = cur_codes_; a.codes = codes_; a.row_key = row_key_;
     a.sp = sp_dev_;
     a.finished = finished_; a.active = active_; a.seen = seen_;
+    a.text_open = text_open_; a.starved = starved_;
     launch_admit_rows(a, k, st_);
     Q3_HIP(hipEventRecord(ev_[1], st_));
     const double now = now_s();
     for (int j = 0; j < k; ++j) {
-        sl[size_t(slots[size_t(j)])] = QSlot{idx[size_t(j)], 0, 0, np[size_t(j)], now, rr[size_t(j)].max_frames};
+        QSlot& x = sl[size_t(slots[size_t(j)])];
+        x = QSlot{};
+        x.req = idx[size_t(j)];
+        x.np = np[size_t(j)];
+        x.t0 = now;
+        x.cap = rr[size_t(j)].max_frames;
+        x.open = rr[size_t(j)].text_open;
+        x.n_content = int(rr[size_t(j)].text_ids.size()) - 3 - rr[size_t(j)].n_tail;
         live[idx[size_t(j)]].rr = std::move(rr[size_t(j)]);
     }
     return k;
@@ -2311,9 +2409,15 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     build_cp_proj_tables();
     struct KeyScope {
         Engine* e;
-        ~KeyScope() { e->frame_row_key_ = nullptr; }
+        ~KeyScope() { e->frame_row_key_ = nullptr; e->frame_text_open_ = nullptr; }
     } key_scope{this};
     frame_row_key_ = row_key_;  // the samplers of every frame step below key on the slots' request indices
+    const bool open_text = q.src->open_text();
+    if (open_text) {  // (a session) rows may starve: the frame end reads text_open_ and raises starved_
+        Q3_HIP(hipMemsetAsync(text_open_, 0, size_t(S), st_));
+        Q3_HIP(hipMemsetAsync(starved_, 0, size_t(S), st_));
+        frame_text_open_ = text_open_;
+    }
     hipGraphExec_t ge = opts_.use_graph ? frame_graph(S) : nullptr;
     Q3_HIP(hipStreamSynchronize(st_));
 
@@ -2568,7 +2672,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
 
     const int burst_frames = std::max(1, max_inflight_frames / 2);
     std::vector<int32_t> h_nframes((size_t)(S), 0);
-    std::vector<uint8_t> h_fin((size_t)(S), 0);
+    std::vector<uint8_t> h_fin((size_t)(S), 0), h_starved((size_t)(S), 0);
     int64_t kvb = 0;
     int launched = 0, served = 0;
     double prefill_ms = 0;
@@ -2609,6 +2713,11 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                 }
                 live.erase(t);
                 q.src->complete_cancelled(t);
+            }
+            if (open_text) {  // (a cancelled row may have been one that waited for text)
+                int starved_now = 0;
+                for (const QSlot& x : sl) starved_now += x.req >= 0 && x.starved ? 1 : 0;
+                q.src->text_progress(starved_now, 0);
             }
             cancel_slots(mask, S);  // on st_: in front of the admissions below and of the next read of the flags
         }
@@ -2697,13 +2806,37 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
                 }
             }
         }
+        // ---- open-text requests: what has been appended since the last boundary, in front of the burst, in stream order on st_ ----
+        if (open_text && q.src->has_appends()) apply_text_appends(q, sl, live);
         // ---- burst: no longer than the first running row's remaining frames (its cap ends it on time) ----
-        int running = 0, burst = burst_frames;
+        int running = 0, runnable = 0, burst = burst_frames;
         for (const QSlot& x : sl)
             if (x.req >= 0) {
                 ++running;
-                burst = std::min(burst, x.cap - x.since);
+                if (x.starved) continue;  // (waits for text on the device: it takes no frame step whatever is launched)
+                ++runnable;
+                burst = std::min(burst, x.cap - x.since);  // (an open-text row: the open cap, max_tokens, until its close)
             }
+        if (running > 0 && runnable == 0) {
+            // ---- every running row waits for text and nothing could be admitted: no frame step is launched. What has landed is
+            // delivered -- decode batches of retired rows and, streamed, the chunks in flight (a starved row is not final: its
+            // last chunks wait with it) -- and the thread sleeps until an append, a cancel, a request it can admit, or close.
+            // (A streamed request held back for the fp32 re-decode waits until the session is idle: the stream cannot be closed
+            // around rows that are still in it.)
+            while (dec >= 0 || !waiting.empty()) {
+                if (dec >= 0) deliver(true);
+                else decode(false);
+            }
+            if (streamed) {
+                while (ss->take(true)) {}
+                settle(true);
+            }
+            if (!settled.empty()) continue;  // (forgotten at the top of the loop)
+            bool can_admit = false;
+            for (const QSlot& x : sl) can_admit = can_admit || x.req < 0;
+            q.src->wait_for_text(can_admit);
+            continue;
+        }
         if (running == 0) {
             if (!q.src->open_ended()) break;
             // ---- a session with nothing running: everything retired is delivered, then the thread sleeps until a submit ----
@@ -2737,6 +2870,7 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         q.src->progress(burst, admitted);
         Q3_HIP(hipMemcpyAsync(h_nframes.data(), n_frames_, size_t(S) * 4, hipMemcpyDeviceToHost, st_));
         Q3_HIP(hipMemcpyAsync(h_fin.data(), finished_, size_t(S), hipMemcpyDeviceToHost, st_));
+        if (open_text) Q3_HIP(hipMemcpyAsync(h_starved.data(), starved_, size_t(S), hipMemcpyDeviceToHost, st_));
         Q3_HIP(hipEventRecord(burst_ev_[0], st_));
         // ---- while the burst runs: deliver the decode batch that has landed, start the next one ----
         if (dec >= 0) deliver(false);
@@ -2752,6 +2886,22 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
             }
         }
         Q3_HIP(hipEventSynchronize(burst_ev_[0]));
+        if (open_text) {
+            // A starved row carries the finished flag of a parked row (row_jobs.h frame_end_job) without having ended: neither the
+            // retirement nor the stream's last chunks may take it for a finished one.
+            int starved_now = 0, events = 0;
+            for (int s = 0; s < S; ++s) {
+                QSlot& x = sl[size_t(s)];
+                const bool st = x.req >= 0 && h_starved[size_t(s)] != 0;
+                if (st) {
+                    h_fin[size_t(s)] = 0;
+                    ++starved_now;
+                    if (!x.starved) ++events;
+                }
+                x.starved = st;
+            }
+            q.src->text_progress(starved_now, events);
+        }
         if (streamed) {
             // ---- the new frames of every running slot into the stream's own code buffer, then every chunk they allow ----
             // A continuing request's new frames lie behind everything an issued pass reads (windows end at the frames that
@@ -2796,8 +2946,8 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
         for (int s = 0; s < S; ++s) {
             QSlot& x = sl[size_t(s)];
             if (x.req < 0) continue;
-            x.since += burst;
             const int nf = h_nframes[size_t(s)];
+            x.since = x.open || x.starved ? nf : x.since + burst;  // (a row that waited for text has taken fewer steps than were launched)
             if (cb) emit_tokens(cb, user, s, x.req, nf, x.reported);
             if (!h_fin[size_t(s)]) continue;
             // copied out before the slot's next admission resets its row (stream order on st_)
@@ -2910,6 +3060,93 @@ void Engine::debug_linear(const uint16_t* x, const uint16_t* W, const uint16_t* 
     Q3_HIP(hipMemcpy2D(y, size_t(N) * 2, dy, size_t(Np) * 2, size_t(N) * 2, size_t(M), hipMemcpyDeviceToHost));
     for (void* p : {(void*)dW, (void*)dWt, (void*)dx, (void*)dxl, (void*)dy, (void*)db})
         if (p) (void)hipFree(p);
+}
+
+// The end of a frame against the resume of a starved row, on the caller's tables (q3tts.h): row 1 of a two-row step, once through
+// frame_end_kernel with its text row there (run A), once with its text open and no row (it starves: run B1) and then through
+// text_append_rows_kernel with that row as the appended text (run B2). Nothing of the engine's own state is touched.
+void Engine::debug_text_resume(int H, int V, const uint16_t* tables, const int32_t* codes, const uint16_t* text, uint16_t* out_h,
+                               float* out_ss, int32_t* out_state) {
+    Q3_CHECK(H >= 128 && H <= 4096 && H % 128 == 0 && V >= 1 && V <= 4096, 3, "debug_text_resume: H must be a multiple of 128 up to 4096, V up to 4096");
+    Q3_CHECK(tables && codes && text && out_h && out_ss && out_state, 3, "Invalid input: null argument");
+    for (int g = 0; g < 16; ++g) Q3_CHECK(codes[g] >= 0 && codes[g] < V, 3, "debug_text_resume: code outside the tables");
+    constexpr int B = 2, row = 1, Tmax = 2;
+    DevBuf<uint16_t> d_tab, d_trailing, d_pad, d_h, d_hl, d_text;
+    DevBuf<const uint16_t*> d_cp;
+    DevBuf<int32_t> d_i32;  // cur_codes [2][16] | n_trailing | trailing_idx | n_frames | max_frames | cp_len  ([2] each)
+    DevBuf<uint8_t> d_u8;   // finished | active | text_open | starved ([2] each)
+    DevBuf<float> d_ss;
+    DevBuf<TextAppendDesc> d_desc;
+    d_tab.grow(size_t(16) * V * H);
+    d_trailing.grow(size_t(B) * Tmax * H);
+    d_pad.grow(size_t(H));
+    d_h.grow(size_t(16) * H);
+    d_hl.grow(size_t(16) * H);
+    d_text.grow(size_t(H));
+    d_cp.grow(15);
+    d_i32.grow(32 + 10);
+    d_u8.grow(8);
+    d_ss.grow(B);
+    d_desc.grow(1);
+    Q3_HIP(hipMemcpy(d_tab, tables, size_t(16) * V * H * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(d_text, text, size_t(H) * 2, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemset(d_pad, 0, size_t(H) * 2));
+    std::vector<const uint16_t*> cp(15);
+    for (int g = 1; g < 16; ++g) cp[size_t(g - 1)] = d_tab + size_t(g) * V * H;
+    Q3_HIP(hipMemcpy(d_cp, cp.data(), 15 * sizeof(const uint16_t*), hipMemcpyHostToDevice));
+    int32_t* cur = d_i32;
+    int32_t *n_tr = cur + 32, *t_idx = n_tr + 2, *n_fr = t_idx + 2, *max_fr = n_fr + 2, *cp_len = max_fr + 2;
+    uint8_t *fin = d_u8, *act = fin + 2, *topen = act + 2, *starved = topen + 2;
+    FrameEndArgs fe{};
+    fe.cur_codes = cur; fe.codec_emb = d_tab; fe.cp_emb = d_cp;
+    fe.trailing = d_trailing; fe.n_trailing = n_tr; fe.trailing_idx = t_idx; fe.Tmax = Tmax;
+    fe.tts_pad = d_pad; fe.h = d_h; fe.hMB = 1; fe.ss_out = d_ss; fe.H = H; fe.B = B; fe.groups = 16;
+    fe.n_frames = n_fr; fe.max_frames = max_fr; fe.finished = fin; fe.active = act; fe.cp_len = cp_len;
+    fe.text_open = topen; fe.starved = starved;
+    auto reset = [&](int n_trailing, int open) {  // row 0: an empty slot; row 1: running, its frame's 16 codes decided
+        std::vector<int32_t> hi(42, 0);
+        for (int g = 0; g < 16; ++g) hi[size_t(16 + g)] = codes[g];
+        hi[32 + row] = n_trailing;
+        hi[38] = hi[39] = 100;  // max_frames
+        hi[40] = hi[41] = 15;   // cp_len
+        const uint8_t hu[8] = {1, 0, 0, 1, 0, uint8_t(open), 0, 0};
+        const float hs[2] = {-1.f, -1.f};
+        Q3_HIP(hipMemcpy(d_i32, hi.data(), hi.size() * 4, hipMemcpyHostToDevice));
+        Q3_HIP(hipMemcpy(d_u8, hu, 8, hipMemcpyHostToDevice));
+        Q3_HIP(hipMemcpy(d_ss, hs, 8, hipMemcpyHostToDevice));
+        Q3_HIP(hipMemset(d_h, 0xEE, size_t(16) * H * 2));
+        Q3_HIP(hipMemset(d_trailing, 0, size_t(B) * Tmax * H * 2));
+    };
+    auto read = [&](int k) {
+        launch_untile_rows(d_h, 1, d_hl, H, 16, H, st_);
+        Q3_HIP(hipStreamSynchronize(st_));
+        Q3_HIP(hipMemcpy(out_h + size_t(k) * H, d_hl + size_t(row) * H, size_t(H) * 2, hipMemcpyDeviceToHost));
+        float hs[2];
+        int32_t hi[42];
+        uint8_t hu[8];
+        Q3_HIP(hipMemcpy(hs, d_ss, 8, hipMemcpyDeviceToHost));
+        Q3_HIP(hipMemcpy(hi, d_i32, sizeof(hi), hipMemcpyDeviceToHost));
+        Q3_HIP(hipMemcpy(hu, d_u8, 8, hipMemcpyDeviceToHost));
+        out_ss[k] = hs[row];
+        int32_t* o = out_state + size_t(k) * 8;
+        o[0] = hi[36 + row]; o[1] = hi[34 + row]; o[2] = hi[32 + row]; o[3] = hu[row]; o[4] = hu[2 + row]; o[5] = hu[4 + row];
+        o[6] = hu[6 + row]; o[7] = hi[40 + row];  // n_frames, trailing_idx, n_trailing, finished, active, text_open, starved, cp_len
+    };
+    reset(1, 0);  // A: the text row is there
+    Q3_HIP(hipMemcpy(d_trailing + size_t(row) * Tmax * H, d_text, size_t(H) * 2, hipMemcpyDeviceToDevice));
+    launch_frame_end(fe, st_);
+    read(0);
+    reset(0, 1);  // B1: it is not, and the text is open
+    launch_frame_end(fe, st_);
+    read(1);
+    TextAppendDesc d{};  // B2: it arrives
+    d.slot = row; d.src_row = 0; d.n_new = 1;
+    Q3_HIP(hipMemcpy(d_desc, &d, sizeof(d), hipMemcpyHostToDevice));
+    TextAppendArgs ta{};
+    ta.desc = d_desc; ta.src = d_text; ta.eos_row = d_pad; ta.trailing = d_trailing; ta.n_trailing = n_tr; ta.text_open = topen;
+    ta.max_frames = max_fr; ta.slots = B; ta.fe = fe;
+    launch_text_append_rows(ta, &d, 1, st_);
+    read(2);
 }
 
 // One launch_attn_decode on the caller's buffers (q3tts.h). Everything the kernels turn into an address -- cache lengths,
@@ -3626,6 +3863,48 @@ void Session::submit(const q3tts_request& r, const Voice* voice, const q3tts_row
     throw Error(st, why.empty() ? std::string("Invalid input: the session is closing or has run out of tickets") : why);
 }
 
+void Session::submit_open(const q3tts_request& r, const q3tts_row_sampling* rs, int64_t* ticket) {
+    Q3_CHECK(r.ref_audio == nullptr && r.ref_text_ids == nullptr, 3,
+             "Invalid input: an open-text request cannot be a voice-clone request (the ICL prompt holds the whole text)");
+    Q3_CHECK(r.text_ids && r.n_text_ids >= 4, 3,
+             "Invalid input: text_ids of an open-text request must hold the 3 role tokens and at least one content token (no tail)");
+    q3tts_sampling one = sp_;
+    one.per_request = rs;
+    check_row_sampling(one, 1);
+    Item it;
+    it.rr = lane_.check_queued(r, sp_, nullptr, true);
+    it.params = fold_sampling(one, 0, 0u);
+    const int n_content = int(it.rr.text_ids.size()) - 3;
+    const int st = queue_.submit(std::move(it), ticket, true, n_content, lane_.text_cap());
+    if (st == Q3TTS_ERR_BUSY) throw Error(st, "Session busy: max_pending requests are already waiting");
+    if (st == Q3TTS_OK) return;
+    const std::string why = error();
+    throw Error(st, why.empty() ? std::string("Invalid input: the session is closing or has run out of tickets") : why);
+}
+
+void Session::append_text(int64_t ticket, const int32_t* ids, int32_t n, bool final) {
+    Q3_CHECK(n >= 0 && (n == 0 || ids), 3, "Invalid input: n must not be negative (and ids not null)");
+    const int V = g_.model().cfg.talker.text_vocab_size;  // (the token map, where there is one, has an entry for each of them)
+    for (int32_t i = 0; i < n; ++i) Q3_CHECK(ids[i] >= 0 && ids[i] < V, 3, "Invalid input: text token id out of range");
+    std::string why;
+    const int st = queue_.append_text(ticket, ids, n, final, &why);
+    if (st == Q3TTS_OK) return;
+    if (why.empty()) why = error();
+    throw Error(st, why.empty() ? std::string("Invalid input: the append was refused") : why);
+}
+
+void Session::take_appends(std::vector<TextAppend>& out) {
+    std::vector<SessionQueue<Item>::TextMsg> msgs;
+    queue_.take_appends(msgs);
+    out.clear();
+    for (auto& m : msgs) {
+        out.emplace_back();
+        out.back().ticket = int(m.ticket);
+        out.back().ids = std::move(m.ids);
+        out.back().final = m.final;
+    }
+}
+
 void Session::wait(int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready) {
     Q3_CHECK(!on_loop_thread(), 3, "Invalid input: q3tts_session_wait inside an event callback would wait for the thread it runs on");
     Q3_CHECK(out && ready, 3, "Invalid input: null argument");
@@ -3643,7 +3922,16 @@ int Session::close(bool drain) {
 bool Session::take(QueueItem& out) {
     int64_t t = -1;
     Item it;
-    if (!queue_.take(&t, &it)) return false;
+    SessionQueue<Item>::TextTake text;
+    if (!queue_.take(&t, &it, &text)) return false;
+    if (text.open) {  // what was appended while it waited is part of its text; closed already: the ordinary request it now is
+        it.rr.text_ids.insert(it.rr.text_ids.end(), text.early.begin(), text.early.end());
+        it.rr.target_token_count = int(it.rr.text_ids.size()) - 3;
+        if (text.closed) {
+            it.rr.text_open = false;
+            it.rr.max_frames = final_text_cap(it.rr.open_max_tokens, it.rr.open_force_frames, it.rr.target_token_count);
+        }
+    }
     out.ticket = int(t);
     out.rr = std::move(it.rr);
     out.params = it.params;

@@ -61,7 +61,17 @@ struct ResolvedRequest {
     int extra_base = 0;   // first row of this request in extra_: speaker x-vector, then ref_T embedding sums
     int ref_off = 0;      // offset of this request's [16][ref_T] codes in ref_codes_dev_
     const Voice* voice = nullptr;  // clone row whose reference is a voice: no waveform, no front end (ref_T known at once)
+    // A session's open-text request (q3tts_session_submit_open): text_ids = role + the content so far, without the 5 tail tokens
+    // (n_tail = 0). text_open: the text may still grow; max_frames is then the open cap (max_tokens) and open_max_tokens /
+    // open_force_frames give final_text_cap() what it needs at the close.
+    int n_tail = 5;
+    bool text_open = false;
+    int open_max_tokens = 0, open_force_frames = 0;
 };
+// the reference's frame cap (Qwen3.swift:822-823) for n_content content tokens
+inline int final_text_cap(int max_tokens, int force_frames, int n_content) {
+    return force_frames > 0 ? force_frames : int(std::min<int64_t>(max_tokens, std::max<int64_t>(75, int64_t(n_content) * 6)));
+}
 
 // q3tts_sampling.per_request: the set fields of its n entries are checked on the host, before any GPU work (status 3)
 void check_row_sampling(const q3tts_sampling& sp, int n);
@@ -151,6 +161,18 @@ struct RequestSource {
     virtual void take_cancels(std::vector<int>& out) { out.clear(); }  // running tickets to drop at this boundary
     virtual void complete_cancelled(int) {}
     virtual void progress(int /*frame_steps*/, int /*admissions*/) {}
+    // ---- open-text requests (a session) ----
+    struct TextAppend {
+        int ticket = -1;
+        std::vector<int32_t> ids;  // content tokens, already checked
+        bool final = false;        // the text ends behind them
+    };
+    virtual bool open_text() const { return false; }  // requests may be admitted with their text still open
+    virtual bool has_appends() { return false; }
+    virtual void take_appends(std::vector<TextAppend>& out) { out.clear(); }  // for running tickets, in arrival order
+    // every running row waits for text: sleeps until a boundary has something to do (an append, a cancel, a request while can_admit, close)
+    virtual void wait_for_text(bool /*can_admit*/) {}
+    virtual void text_progress(int /*starved_now*/, int /*starve_events*/) {}
 };
 
 // What the lanes of one slot loop share: the request source and what was fixed before the loop started.
@@ -195,6 +217,7 @@ class Engine {
               bool background = false, const Voice* const* voices = nullptr);
     void end(int job, q3tts_result* results);
     bool job_outstanding() const;
+    int text_cap() const { return Tcap_; }  // rows of a slot's trailing text: the most content tokens an open-text request may hold
     void prepare_job_pair();  // at load, by an EngineGroup that will run background jobs on its two contexts
     void drain();             // returns once no back half is queued or running on the worker thread
     // Continuous batching (q3tts_generate_queued). check_queued resolves one request (with `voice`: a voice-clone request, whose
@@ -202,13 +225,16 @@ class Engine {
     // range) on the host, before any GPU work. run_queued keeps `slots`
     // rows in flight: at each burst boundary finished rows are retired (codes copied out, decode queued on the codec stream
     // beside the frame loop) and their slots take the next requests of `q`, prefilled as a sub-batch of their own.
-    ResolvedRequest check_queued(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice = nullptr) const;
+    ResolvedRequest check_queued(const q3tts_request& r, const q3tts_sampling& sp, const Voice* voice = nullptr,
+                                 bool open_text = false) const;  // open_text: a session's open-text request (role + content, no tail)
     void check_stream_chunk(int chunk_frames) const;  // a streamed decode's chunk must hold the causal tail's history
     void run_queued(QueueShared& q, int slots, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
     void debug_prepare_inputs(const q3tts_request& req, uint16_t* input_embeds, int cap_prompt, int* n_prompt,
                               uint16_t* trailing, int cap_trailing, int* n_trailing, uint16_t* tts_pad);
     void debug_sample(const uint16_t* logits, int rows, int V, const q3tts_sampling& sp, const uint8_t* seen,
                       int suppress_lo, int suppress_hi, int eos_id, uint32_t row0, uint32_t draw, int32_t* tokens);
+    void debug_text_resume(int H, int V, const uint16_t* tables, const int32_t* codes, const uint16_t* text, uint16_t* out_h,
+                           float* out_ss, int32_t* out_state);
     void debug_linear(const uint16_t* x, const uint16_t* W, const uint16_t* bias, int M, int K, int N, uint16_t* y);
     void debug_attention(const q3tts_attn_debug& a);
     void debug_build_decode_codes(const int32_t* refs, const int32_t* ref_T, const int32_t* gen, const int32_t* n_frames, int R,
@@ -449,6 +475,7 @@ class Engine {
     void enqueue_talker_step(int B, bool with_head);
     void enqueue_cp_pass(int B, bool from_talker, int head, int cp_pos, bool projected = false);  // head: lm_head index or -1; cp_pos: tokens already cached
     void enqueue_frame(int B, const DebugOpts* dbg);
+    FrameEndArgs frame_end_args(int B) const;
     hipGraphExec_t frame_graph(int B);
     // ---- continuous batching (run_queued) ----
     const uint32_t* frame_row_key_ = nullptr;  // non-null while a queued frame step is enqueued: the samplers key on it
@@ -460,6 +487,14 @@ class Engine {
     AdmitDesc* q_desc_ = nullptr;
     std::vector<AdmitDesc> q_desc_host_;
     uint32_t* row_key_ = nullptr;  // [max_batch] random key of every slot
+    // open-text requests (a session): the frame step reads text_open_ and raises starved_ (row_jobs.h frame_end_job) only while
+    // frame_text_open_ is set -- the closed queue, static batches and begin / end jobs pass nullptr and capture graphs of their own
+    uint8_t *text_open_ = nullptr, *starved_ = nullptr;  // [max_batch]
+    const uint8_t* frame_text_open_ = nullptr;
+    std::map<int, hipGraphExec_t> ographs_;  // frame_graph() while frame_text_open_ is set, keyed by slot count
+    TextAppendDesc* q_text_desc_ = nullptr;  // [max_batch]
+    std::vector<TextAppendDesc> q_text_desc_host_;
+    std::vector<int32_t> q_text_ids_;        // staging of a boundary's new ids (alive until the launch has been waited for)
     std::vector<int32_t> q_host_;  // staging of the sub-batch's arrays (alive until the next boundary's sync)
     void ensure_queue_ws();
     struct QSlot {
@@ -469,10 +504,15 @@ class Engine {
         int np = 0;
         double t0 = 0;     // admission (host clock)
         int cap = 0;       // its max_frames
+        // an open-text request: its text may still grow (open), its row waits for text on the device (starved)
+        bool open = false, starved = false;
+        int n_content = 0;  // content tokens so far
     };
+    struct QLive;
+    // a boundary's appends (run_queued): new text rows and closes for the slots' open-text requests, one launch on st_
+    void apply_text_appends(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int, QLive>& live);
     // free slots of `sl` in slot order take the next requests of q (prompts, prefill and admit_rows_kernel as a sub-batch of
     // their own); returns how many were admitted. `live` takes every admitted request by ticket
-    struct QLive;
     int admit(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int, QLive>& live);
     void cancel_slots(uint64_t mask, int slots);  // one launch on st_: the listed slots are finished and inactive
     GemmArgs gemm_args(const LinearW& L, const uint16_t* x, int M) const;
@@ -561,6 +601,10 @@ class Session final : public RequestSource {
     ~Session() override;  // closes without drain
     // every check of a queued request on the calling thread; throws Error (3: refused, 9: max_pending waiting, or what the loop failed with)
     void submit(const q3tts_request& r, const Voice* voice, const q3tts_row_sampling* rs, int64_t* ticket);
+    // open-text requests (include/q3tts.h): every check on the calling thread; throws Error 3 on a refusal, which changes nothing
+    void submit_open(const q3tts_request& r, const q3tts_row_sampling* rs, int64_t* ticket);
+    void append_text(int64_t ticket, const int32_t* ids, int32_t n, bool final);
+    void text_stats(q3tts_session_text_stats* s) const { queue_.text_stats(s); }
     int cancel(int64_t ticket) { return queue_.cancel(ticket); }
     void wait(int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready);
     void stats(q3tts_session_stats* s) const { queue_.stats(s); }
@@ -577,6 +621,11 @@ class Session final : public RequestSource {
     void take_cancels(std::vector<int>& out) override;
     void complete_cancelled(int ticket) override { queue_.complete_cancelled(ticket); }
     void progress(int frame_steps, int admissions) override { queue_.progress(frame_steps, admissions); }
+    bool open_text() const override { return true; }
+    bool has_appends() override { return queue_.has_appends(); }
+    void take_appends(std::vector<TextAppend>& out) override;
+    void wait_for_text(bool can_admit) override { queue_.wait_for_text(can_admit); }
+    void text_progress(int starved_now, int starve_events) override { queue_.text_progress(starved_now, starve_events); }
 
   private:
     void loop();

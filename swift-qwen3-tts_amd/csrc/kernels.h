@@ -146,6 +146,10 @@ struct FrameEndArgs {  // Qwen3.swift:919-935 + loop bookkeeping
     uint8_t* finished;
     uint8_t* active;
     int32_t* cp_len;              // [B] reset to 0
+    // open-text requests of a session (nullptr everywhere else: no row ever starves). Device arrays, so that a captured frame
+    // step does not depend on their values.
+    const uint8_t* text_open;     // [B] 1: more text may still arrive for the row -- it starves at the end of what has arrived
+    uint8_t* starved;             // [B] set with finished when the row starves (row_jobs.h frame_end_job)
 };
 void launch_frame_end(const FrameEndArgs& a, hipStream_t st);
 
@@ -238,6 +242,7 @@ void launch_advance_len_chunk(int32_t* kv_len, const int32_t* n_prompt, int r_ba
 struct AdmitDesc {
     int32_t slot, n_trailing, max_frames;
     uint32_t row_key;
+    int32_t text_open;  // 1: an open-text request (its trailing text ends without tts_eos and grows through launch_text_append_rows)
     SamplingParams sp;  // the request's parameters: the call's with its own overrides folded in
 };
 struct AdmitArgs {
@@ -255,11 +260,34 @@ struct AdmitArgs {
     uint32_t* row_key;
     SamplingParams* sp;        // [slots] the frame step's per-row sampling parameters
     uint8_t *finished, *active, *seen;
+    uint8_t *text_open, *starved;  // [slots] the slot's next occupant always gets its own values
 };
 void launch_admit_rows(const AdmitArgs& a, int k, hipStream_t st);
 // A session's cancel (Engine::run_queued): the slots whose bit is set in `mask` become empty slots (finished = 1, active = 0)
 // in one launch; slots <= 64 (the bound on max_batch). Every other slot's row carries on.
 void launch_cancel_rows(uint64_t mask, uint8_t* finished, uint8_t* active, int slots, hipStream_t st);
+// A session's open-text requests (Engine::run_queued), one launch at a burst boundary, one workgroup per slot with new text:
+//   - `n_new` projected text rows src[src_row ..] go behind the slot's trailing text, and on `close` the tts_eos row behind them;
+//     n_trailing follows; on close text_open is cleared and max_frames takes the request's final cap;
+//   - a slot that starved (frame_end_job) and now has its next text row gets the talker input its last frame could not form --
+//     by next_input_row, the device function frame_end_job calls, from cur_codes and that text row -- and runs again:
+//     trailing_idx + 1, cp_len 0, finished down, active up, starved down.
+// A descriptor whose rows would not fit the slot's Tmax rows is checked on the host (nothing is launched) and skipped on the device.
+struct TextAppendDesc {
+    int32_t slot, src_row, n_new, close, max_frames, pad_;
+};
+struct TextAppendArgs {
+    const TextAppendDesc* desc;  // [k]
+    const uint16_t* src;         // row-major [rows][H]: text_projection of the new ids
+    const uint16_t* eos_row;     // [H]: text_projection(tts_eos)
+    uint16_t* trailing;          // [slots][Tmax][H]
+    int32_t* n_trailing;
+    uint8_t* text_open;
+    int32_t* max_frames;
+    int slots;
+    FrameEndArgs fe;             // the frame step's own arguments (trailing_idx, cur_codes, tables, h, ss_out, flags, Tmax, H)
+};
+void launch_text_append_rows(const TextAppendArgs& a, const TextAppendDesc* host, int k, hipStream_t st);
 
 
 // prompt assembly (Qwen3.swift:371-406, 505-510): dst[dst_row[i]] = proj[a[i]] when b[i] == -1, else

@@ -215,6 +215,52 @@ __global__ __launch_bounds__(256) void admit_rows_kernel(AdmitArgs a) {
         a.trailing_idx[s] = 0;
         a.finished[s] = 0;
         a.active[s] = 1;
+        if (a.text_open) a.text_open[s] = d.text_open ? 1 : 0;
+        if (a.starved) a.starved[s] = 0;
+    }
+}
+
+// Open-text requests of a session: new trailing text for the slots listed in desc, and the resume of the ones that starved
+// (kernels.h TextAppendArgs). Only the listed slots' rows are written; the rows in flight around them carry on.
+__global__ __launch_bounds__(256) void text_append_rows_kernel(TextAppendArgs a) {
+    __shared__ float sh[4];
+    const TextAppendDesc d = a.desc[blockIdx.x];
+    const int s = d.slot, tid = threadIdx.x;
+    const FrameEndArgs& fe = a.fe;
+    if (s < 0 || s >= a.slots || d.n_new < 0) return;
+    const int nt = a.n_trailing[s];
+    const int add = d.n_new + (d.close ? 1 : 0);
+    if (nt < 0 || nt + add > fe.Tmax) return;  // (the host has checked it: nothing is ever written past the slot's rows)
+    uint16_t* dst = a.trailing + ((size_t)s * fe.Tmax + nt) * fe.H;
+    for (int r = 0; r < add; ++r) {
+        const uint4* from = reinterpret_cast<const uint4*>(r < d.n_new ? a.src + (size_t)(d.src_row + r) * fe.H : a.eos_row);
+        uint4* to = reinterpret_cast<uint4*>(dst + (size_t)r * fe.H);
+        for (int i = tid; i < fe.H / 8; i += 256) to[i] = from[i];
+    }
+    // A starved row stopped exactly at the end of what had arrived (trailing_idx == n_trailing): its next text row is the first
+    // new one, read from the source rather than from the copy just stored.
+    const int ti = fe.trailing_idx[s];
+    const bool resume = fe.starved[s] != 0 && add > 0 && ti == nt;  // block-uniform
+    float ss = 0.f;
+    if (resume) {
+        const uint16_t* text = d.n_new > 0 ? a.src + (size_t)d.src_row * fe.H : a.eos_row;
+        ss = next_input_row(fe, s, tid, fe.cur_codes + (size_t)s * 16, -1, text);
+    }
+    const float tot = block_sum_first256(ss, sh, tid);
+    if (tid == 0) {
+        a.n_trailing[s] = nt + add;
+        if (d.close) {
+            a.text_open[s] = 0;
+            a.max_frames[s] = d.max_frames;
+        }
+        if (resume) {
+            fe.ss_out[s] = tot;
+            fe.trailing_idx[s] = ti + 1;
+            fe.cp_len[s] = 0;
+            fe.starved[s] = 0;
+            fe.finished[s] = 0;
+            fe.active[s] = 1;
+        }
     }
 }
 
@@ -334,6 +380,15 @@ void launch_advance_len(int32_t* kv_len, const uint8_t* active, int B, hipStream
 void launch_admit_rows(const AdmitArgs& a, int k, hipStream_t st) {
     if (k <= 0) return;
     hipLaunchKernelGGL(admit_rows_kernel, dim3(k), dim3(256), 0, st, a);
+}
+void launch_text_append_rows(const TextAppendArgs& a, const TextAppendDesc* host, int k, hipStream_t st) {
+    if (k <= 0) return;
+    Q3_CHECK(a.fe.starved && a.text_open && a.fe.H % 8 == 0, 7, "internal error: text_append_rows without the open-text arrays");
+    for (int j = 0; j < k; ++j)
+        Q3_CHECK(host[j].slot >= 0 && host[j].slot < a.slots && host[j].n_new >= 0 && host[j].src_row >= 0 &&
+                     host[j].n_new + (host[j].close ? 1 : 0) <= a.fe.Tmax,
+                 7, "internal error: text_append_rows descriptor outside the slot's trailing text");
+    hipLaunchKernelGGL(text_append_rows_kernel, dim3(k), dim3(256), 0, st, a);
 }
 void launch_cancel_rows(uint64_t mask, uint8_t* finished, uint8_t* active, int slots, hipStream_t st) {
     Q3_CHECK(slots >= 1 && slots <= 64, 7, "internal error: cancel_rows covers at most 64 slots");

@@ -97,16 +97,13 @@ __device__ __forceinline__ void norm_row_job(const NormRowsArgs& a, int m, int t
     }
 }
 
-// End of a frame (Qwen3.swift:914-935): next talker input = text embed (next trailing text row or tts_pad) + sum of the 16
-// codebook embeddings, every add rounded to bf16 in the reference's left-to-right order; then the loop bookkeeping that the
-// Swift loop keeps on the host. `last_code` >= 0 replaces cur_codes[b][groups - 1] (the caller has just decided it and its
-// store may not be visible to the other threads yet).
-__device__ __forceinline__ void frame_end_job(const FrameEndArgs& a, int b, int tid, int last_code, float* sh /*[4]*/) {
-    const bool on = tid < 256;
-    const int32_t* cc = a.cur_codes + (size_t)b * 16;
-    const int ti = a.trailing_idx[b];
-    const bool has_text = ti < a.n_trailing[b];
-    const uint16_t* text = has_text ? a.trailing + ((size_t)b * a.Tmax + ti) * a.H : a.tts_pad;
+// The next talker input of row b (Qwen3.swift:919-935): text row + sum of the 16 codebook embeddings of `cc`, every add rounded
+// to bf16 in the reference's left-to-right order, stored to a.h; returns this thread's share of the row's sum of squares (the
+// caller adds the shares up with block_sum_first256). The one place this arithmetic lives: the end of a frame (frame_end_job) and
+// the resume of a row that waited for its text (text_append_rows_kernel, lm_misc.hip) both call it, so the two inputs cannot
+// differ in a bit. `last_code` >= 0 replaces cc[groups - 1]. Threads 0..255 work; the others return 0.
+__device__ __forceinline__ float next_input_row(const FrameEndArgs& a, int b, int tid, const int32_t* cc, int last_code,
+                                                const uint16_t* text) {
     const uint16_t* rows[16];
     rows[0] = a.codec_emb + (size_t)cc[0] * a.H;
 #pragma unroll
@@ -115,7 +112,7 @@ __device__ __forceinline__ void frame_end_job(const FrameEndArgs& a, int b, int 
         rows[g] = (g < a.groups) ? a.cp_emb[g - 1] + (size_t)code * a.H : rows[0];
     }
     float ss = 0.f;
-    if (on) {
+    if (tid < 256) {
         for (int i0 = tid * 8; i0 < a.H; i0 += 256 * 8) {
             uint4 e[16];
 #pragma unroll
@@ -142,15 +139,42 @@ __device__ __forceinline__ void frame_end_job(const FrameEndArgs& a, int b, int 
             *reinterpret_cast<uint4*>(a.h + act_tiled_offset(b, i0, a.hMB)) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
         }
     }
+    return ss;
+}
+
+// End of a frame (Qwen3.swift:914-935): next talker input = text embed (next trailing text row or tts_pad) + sum of the 16
+// codebook embeddings (next_input_row); then the loop bookkeeping that the Swift loop keeps on the host. `last_code` >= 0
+// replaces cur_codes[b][groups - 1] (the caller has just decided it and its store may not be visible to the other threads yet).
+//
+// A row whose text is still open (a.text_open[b], a session's open-text request) and whose next text row has not arrived
+// STARVES instead of falling back to tts_pad, which is the reference's input for text that has ENDED: the frame in flight counts
+// (n_frames + 1, the cap check), no input is formed, and the row is parked in the state of a finished row -- finished up, active
+// down -- which every kernel of the frame step leaves alone (no draw, no cache append, no length advance), with starved[b] up so
+// that the host can tell it from a row that has ended. launch_text_append_rows forms the missing input and reactivates it.
+__device__ __forceinline__ void frame_end_job(const FrameEndArgs& a, int b, int tid, int last_code, float* sh /*[4]*/) {
+    const int32_t* cc = a.cur_codes + (size_t)b * 16;
+    const int ti = a.trailing_idx[b];
+    const bool has_text = ti < a.n_trailing[b];
+    // (read from an address that is always valid, with the two loads above: under a branch on the pointer this byte would be a
+    // memory round trip of its own behind them)
+    const uint8_t open_raw = *(a.text_open ? a.text_open + b : a.finished + b);
+    const bool starve = !has_text && a.text_open && open_raw != 0;  // block-uniform
+    const uint16_t* text = has_text ? a.trailing + ((size_t)b * a.Tmax + ti) * a.H : a.tts_pad;
+    float ss = 0.f;
+    if (!starve) ss = next_input_row(a, b, tid, cc, last_code, text);
     const float tot = block_sum_first256(ss, sh, tid);  // (its barriers also order every thread's read of trailing_idx before the update)
     if (tid == 0) {
-        a.ss_out[b] = tot;
+        if (!starve) a.ss_out[b] = tot;
         if (has_text) a.trailing_idx[b] = ti + 1;
         const int nf = a.n_frames[b] + 1;
         a.n_frames[b] = nf;
         if (nf >= a.max_frames[b]) {  // for _ in 0..<effectiveMaxTokens (Qwen3.swift:847)
             a.finished[b] = 1;
             a.active[b] = 0;
+        } else if (starve) {
+            a.finished[b] = 1;
+            a.active[b] = 0;
+            a.starved[b] = 1;
         }
         a.cp_len[b] = 0;  // fresh code-predictor cache per frame (Qwen3.swift:879)
     }

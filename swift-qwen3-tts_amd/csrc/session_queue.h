@@ -5,6 +5,12 @@
 // Producers (any thread): submit, cancel, wait, stats, close. One consumer (the session's loop thread): take / wait_for_work /
 // take_cancels / result / complete / fail. A ticket is Pending (accepted, in the deque), Running (handed to the consumer) or Done
 // (its result is filled and waits to be claimed); a claimed ticket is forgotten.
+//
+// Open-text tickets (submit with open = true, q3tts_session_submit_open): the request's text grows through append_text until an
+// append closes it. Text for a Pending ticket is kept beside the stored request and handed out with it (take); text for a Running
+// one goes into the append mailbox, which the consumer empties at its boundaries (take_appends); text for a Done or claimed one is
+// dropped. The consumer sleeps in wait_for_text() while every row it runs waits for text; an append, a cancel, a submit it
+// could admit, or close wakes it.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -14,6 +20,7 @@
 #include <deque>
 #include <map>
 #include <mutex>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -52,7 +59,8 @@ class SessionQueue {
 
     // ---- producers ----
     // The t-th accepted submit gets ticket t. A refused one (BUSY, closing, failed) consumes no ticket.
-    int submit(Req&& r, int64_t* ticket) {
+    // open: an open-text ticket holding n_content content tokens so far, at most text_cap in all.
+    int submit(Req&& r, int64_t* ticket, bool open = false, int n_content = 0, int text_cap = 0) {
         {
             std::lock_guard<std::mutex> lk(mu_);
             if (failed_) return failed_;
@@ -62,6 +70,10 @@ class SessionQueue {
             const int64_t t = next_++;
             Entry& e = entries_[t];
             e.req = std::move(r);
+            e.open = open;
+            e.n_content = n_content;
+            e.text_cap = text_cap;
+            kind_.push_back(open ? kOpen : kPlain);
             pending_.push_back(t);
             ++submitted_;
             if (ticket) *ticket = t;
@@ -72,7 +84,7 @@ class SessionQueue {
     // Pending: never handed out, Done at once with CANCELLED. Running: marked, the consumer completes it at its next boundary.
     // Done, claimed or already marked: nothing changes. A ticket that was never given out: INVALID_INPUT.
     int cancel(int64_t ticket) {
-        bool done = false;
+        bool done = false, marked = false;
         {
             std::lock_guard<std::mutex> lk(mu_);
             if (ticket < 0 || ticket >= next_) return Q3TTS_ERR_INVALID_INPUT;
@@ -86,10 +98,61 @@ class SessionQueue {
             } else if (e.state == Running && !e.cancel) {
                 e.cancel = true;
                 cancels_.push_back(ticket);
+                marked = true;
             }
         }
+        if (marked) work_cv_.notify_all();  // (a consumer whose rows all wait for text sleeps on it)
         if (done) done_cv_.notify_all();
         return Q3TTS_OK;
+    }
+    // One append of an open-text request, and the wake-up of a consumer that waits for it.
+    struct TextMsg {
+        int64_t ticket = -1;
+        std::vector<int32_t> ids;
+        bool final = false;
+    };
+    // n >= 0 content tokens behind the ticket's text; final closes it. INVALID_INPUT, with nothing changed and *why saying so: a
+    // ticket never given out, one from a plain submit, one whose text is closed, n < 0, more content than text_cap. A ticket that is
+    // Done or claimed (it ended early, hit its cap or was cancelled -- the race is the caller's to lose): OK, and the text is dropped.
+    int append_text(int64_t ticket, const int32_t* ids, int32_t n, bool final, std::string* why = nullptr) {
+        auto refuse = [&](const char* w) {
+            if (why) *why = w;
+            return int(Q3TTS_ERR_INVALID_INPUT);
+        };
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (failed_) return failed_;
+            if (ticket < 0 || ticket >= next_) return refuse("Invalid input: no such ticket");
+            if (kind_[size_t(ticket)] == kPlain) return refuse("Invalid input: the ticket is not an open-text request");
+            if (kind_[size_t(ticket)] == kClosed) return refuse("Invalid input: the ticket's text has been closed");
+            if (n < 0 || (n > 0 && !ids)) return refuse("Invalid input: n must not be negative");
+            auto it = entries_.find(ticket);
+            if (it == entries_.end() || it->second.state == Done) return Q3TTS_OK;  // dropped
+            Entry& e = it->second;
+            if (e.n_content + int64_t(n) > int64_t(e.text_cap)) return refuse("Invalid input: text longer than max_prompt");
+            e.n_content += n;
+            appended_tokens_ += n;
+            if (final) kind_[size_t(ticket)] = kClosed;
+            if (e.state == Pending) {
+                e.early.insert(e.early.end(), ids, ids + n);
+            } else if (n > 0 || final) {
+                appends_.emplace_back();
+                appends_.back().ticket = ticket;
+                appends_.back().ids.assign(ids, ids + n);
+                appends_.back().final = final;
+            }
+        }
+        work_cv_.notify_all();
+        return Q3TTS_OK;
+    }
+    void text_stats(q3tts_session_text_stats* s) const {
+        std::lock_guard<std::mutex> lk(mu_);
+        std::memset(s, 0, sizeof(*s));
+        for (const auto& kv : entries_)
+            if (kv.second.open && kv.second.state != Done && kind_[size_t(kv.first)] == kOpen) ++s->open;
+        s->starved = starved_;
+        s->appended_tokens = appended_tokens_;
+        s->starve_events = starve_events_;
     }
     // *ready = 1: the result is the caller's and the ticket is forgotten. *ready = 0 (timeout): nothing is touched.
     int wait(int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready) {
@@ -128,6 +191,17 @@ class SessionQueue {
         {
             std::lock_guard<std::mutex> lk(mu_);
             closing_ = true;
+            if (drain) {  // every open text is closed first: the ticket then ends as if its last append had been final
+                for (auto& kv : entries_) {
+                    if (kv.second.state == Done || kind_[size_t(kv.first)] != kOpen) continue;
+                    kind_[size_t(kv.first)] = kClosed;
+                    if (kv.second.state == Running) {
+                        appends_.emplace_back();
+                        appends_.back().ticket = kv.first;
+                        appends_.back().final = true;
+                    }
+                }
+            }
             if (!drain) {
                 for (int64_t t : pending_) finish_locked(entries_[t], Q3TTS_ERR_CANCELLED, true);
                 pending_.clear();
@@ -148,7 +222,13 @@ class SessionQueue {
 
     // ---- the consumer ----
     // the next pending request in ticket order (it is Running from here on); false: none is waiting now
-    bool take(int64_t* ticket, Req* out) {
+    // An open-text ticket as take() hands it out: the content that arrived while it was pending, and whether its text is closed
+    // already (it is then an ordinary request). From here on its appends go through the mailbox.
+    struct TextTake {
+        bool open = false, closed = false;
+        std::vector<int32_t> early;
+    };
+    bool take(int64_t* ticket, Req* out, TextTake* text = nullptr) {
         std::lock_guard<std::mutex> lk(mu_);
         if (pending_.empty() || failed_) return false;
         const int64_t t = pending_.front();
@@ -157,6 +237,12 @@ class SessionQueue {
         e.state = Running;
         *out = std::move(e.req);
         e.req = Req();
+        if (text) {
+            text->open = e.open;
+            text->closed = kind_[size_t(t)] == kClosed;
+            text->early = std::move(e.early);
+        }
+        e.early = std::vector<int32_t>();
         *ticket = t;
         ++running_;
         return true;
@@ -166,6 +252,30 @@ class SessionQueue {
         std::unique_lock<std::mutex> lk(mu_);
         work_cv_.wait(lk, [&] { return !pending_.empty() || closing_ || failed_; });
         return !pending_.empty() && !failed_;
+    }
+    // Every running row waits for text: sleeps until there is something to do at a boundary -- an append or a cancel in the
+    // mailboxes, a pending request while `can_admit`, or the first look after close() -- and never spins: each of these is consumed by
+    // the boundary that follows.
+    void wait_for_text(bool can_admit) {
+        std::unique_lock<std::mutex> lk(mu_);
+        work_cv_.wait(lk, [&] {
+            return !appends_.empty() || !cancels_.empty() || (can_admit && !pending_.empty()) || (closing_ && !close_seen_) || failed_;
+        });
+        if (closing_) close_seen_ = true;
+    }
+    bool has_appends() const {
+        std::lock_guard<std::mutex> lk(mu_);
+        return !appends_.empty();
+    }
+    void take_appends(std::vector<TextMsg>& out) {  // in arrival order
+        std::lock_guard<std::mutex> lk(mu_);
+        out.assign(std::make_move_iterator(appends_.begin()), std::make_move_iterator(appends_.end()));
+        appends_.clear();
+    }
+    void text_progress(int starved_now, int starve_events) {
+        std::lock_guard<std::mutex> lk(mu_);
+        starved_ = starved_now;
+        starve_events_ += starve_events;
     }
     bool has_cancels() const {
         std::lock_guard<std::mutex> lk(mu_);
@@ -227,15 +337,20 @@ class SessionQueue {
 
   private:
     enum State { Pending, Running, Done };
+    enum Kind : uint8_t { kPlain, kOpen, kClosed };  // kOpen: an open-text ticket whose text is not closed yet
     struct Entry {
         State state = Pending;
         bool cancel = false;
+        bool open = false;           // submitted as an open-text request
+        int n_content = 0, text_cap = 0;
+        std::vector<int32_t> early;  // content appended while Pending
         Req req{};
         q3tts_result res{};
     };
     void finish_locked(Entry& e, int status, bool wipe) {  // wipe: the result carries nothing but the status
         e.state = Done;
         e.req = Req();
+        e.early = std::vector<int32_t>();
         if (wipe) {
             free_(&e.res);
             std::memset(&e.res, 0, sizeof(e.res));
@@ -252,6 +367,10 @@ class SessionQueue {
     std::map<int64_t, Entry> entries_;  // every ticket that is not claimed yet
     std::deque<int64_t> pending_;       // in ticket order
     std::deque<int64_t> cancels_;
+    std::deque<TextMsg> appends_;       // text for Running tickets, in arrival order
+    std::vector<uint8_t> kind_;         // by ticket, for every ticket ever given out (a claimed ticket is still refused correctly)
+    int64_t starved_ = 0, appended_tokens_ = 0, starve_events_ = 0;
+    bool close_seen_ = false;
     int64_t next_ = 0;
     int64_t submitted_ = 0, running_ = 0, completed_ = 0, cancelled_ = 0, frame_steps_ = 0, admissions_ = 0;
     bool closing_ = false;

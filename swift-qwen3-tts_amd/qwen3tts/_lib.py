@@ -98,6 +98,10 @@ class SessionStats(C.Structure):  # q3tts_session_stats
                 ("cancelled", C.c_int64), ("frame_steps", C.c_int64), ("admissions", C.c_int64)]
 
 
+class SessionTextStats(C.Structure):  # q3tts_session_text_stats
+    _fields_ = [("open", C.c_int64), ("starved", C.c_int64), ("appended_tokens", C.c_int64), ("starve_events", C.c_int64)]
+
+
 ERR_CANCELLED, ERR_BUSY = 8, 9  # q3tts_status: a cancelled request's result; submit with max_pending requests waiting
 
 
@@ -157,6 +161,11 @@ def lib() -> C.CDLL:
         L.q3tts_session_wait.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(Result), i32p]
         L.q3tts_session_get_stats.argtypes = [vp, C.POINTER(SessionStats)]
         L.q3tts_session_close.argtypes = [vp, C.c_int32]
+    if hasattr(L, "q3tts_session_submit_open"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_session_submit_open.argtypes = [vp, C.POINTER(Request), C.POINTER(RowSampling), C.POINTER(C.c_int64)]
+        L.q3tts_session_append_text.argtypes = [vp, C.c_int64, i32p, C.c_int32, C.c_int32]
+        L.q3tts_session_get_text_stats.argtypes = [vp, C.POINTER(SessionTextStats)]
+        L.q3tts_debug_text_resume.argtypes = [vp, C.c_int32, C.c_int32, u16p, i32p, u16p, u16p, f32p, i32p]
     L.q3tts_generate_begin.argtypes = [vp, C.POINTER(Request), C.c_int32, C.POINTER(Sampling), EVENT_CB, vp, C.c_int32, C.POINTER(vp)]
     L.q3tts_generate_end.argtypes = [vp, vp, C.POINTER(Result)]
     L.q3tts_pcm_to_int16.argtypes = [f32p, C.c_int64, C.POINTER(C.c_int16)]

@@ -715,6 +715,20 @@ class Qwen3TTSModel:
                                                  toks.ctypes.data_as(L.i32p)))
         return toks
 
+    def debug_text_resume(self, tables: np.ndarray, codes, text_row: np.ndarray):
+        """q3tts_debug_text_resume: tables [16][V][H] bf16 bits, codes [16], text_row [H] -> (h [3][H] uint16, ss [3], state [3][8])
+        for (0) the end of a frame with its text row, (1) the same frame starving, (2) its resume by the append launch."""
+        tables = np.ascontiguousarray(tables, np.uint16)
+        _, V, H = tables.shape
+        codes = np.ascontiguousarray(codes, np.int32)
+        text_row = np.ascontiguousarray(text_row, np.uint16)
+        assert tables.shape[0] == 16 and codes.shape == (16,) and text_row.shape == (H,)
+        h, ss, state = np.zeros((3, H), np.uint16), np.zeros(3, np.float32), np.zeros((3, 8), np.int32)
+        self._check(self._lib.q3tts_debug_text_resume(self._h, H, V, tables.ctypes.data_as(L.u16p), codes.ctypes.data_as(L.i32p),
+                                                      text_row.ctypes.data_as(L.u16p), h.ctypes.data_as(L.u16p),
+                                                      ss.ctypes.data_as(L.f32p), state.ctypes.data_as(L.i32p)))
+        return h, ss, state
+
     def debug_linear(self, x: np.ndarray, W: np.ndarray, bias: Optional[np.ndarray] = None) -> np.ndarray:
         x = np.ascontiguousarray(x, np.uint16)
         W = np.ascontiguousarray(W, np.uint16)
@@ -799,6 +813,39 @@ class Session:
         del keep
         m._check(st)
         return int(t.value)
+
+    def submit_open(self, request: GenerationRequest, **row_sampling) -> int:
+        """q3tts_session_submit_open: an open-text request. `request.text_ids` holds the 3 role tokens and the content that is
+        there already (at least one token) and NO 5-token tail; target_token_count is ignored. The rest of the text arrives
+        through append_text; the result equals the ordinary request over the whole text alone. A request with a voice or
+        reference audio is refused (status 3)."""
+        m = self._model
+        if getattr(request, "voice", None) is not None:
+            raise Qwen3TTSError(3, "Invalid input: an open-text request cannot name a voice (the ICL prompt holds the whole text)")
+        arr, keep = m._marshal([request])
+        rs = RequestSampling(**row_sampling) if row_sampling else getattr(request, "sampling", None)
+        rows = m._row_sampling([rs])
+        t = C.c_int64(-1)
+        st = m._lib.q3tts_session_submit_open(self._handle(), arr, rows if rows is not None else None, C.byref(t))
+        del keep
+        m._check(st)
+        return int(t.value)
+
+    def append_text(self, ticket: int, ids, final: bool = False) -> None:
+        """More content token ids for an open-text ticket; final=True closes its text. May be called from any thread and from
+        inside `on_event`. Text for a ticket that has already completed or was cancelled is dropped without an error."""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        self._model._check(self._model._lib.q3tts_session_append_text(self._handle(), int(ticket), a.ctypes.data_as(L.i32p),
+                                                                       int(a.size), 1 if final else 0))
+
+    def close_text(self, ticket: int) -> None:
+        """The ticket's text ends with what has been appended."""
+        self.append_text(ticket, [], final=True)
+
+    def text_stats(self) -> L.SessionTextStats:
+        s = L.SessionTextStats()
+        self._model._check(self._model._lib.q3tts_session_get_text_stats(self._handle(), C.byref(s)))
+        return s
 
     def result(self, ticket: int, timeout: Optional[float] = None) -> GenerationResult:
         """Waits for the ticket's result and takes it (a second call for the same ticket is status 3). A cancelled

@@ -316,6 +316,42 @@ public final class Qwen3TTSModel {
         return out
     }
 
+    /// Open-text requests of a serving session (q3tts_session_submit_open / q3tts_session_append_text; INTEGRATION.md section 2a):
+    /// `session` is the handle q3tts_session_open gave the host. The request starts with the beginning of its text -- at least one
+    /// token -- and gets the rest through `appendText`; its audio equals the whole text's, generated alone with the ticket as
+    /// row_base offset. Every piece is tokenised on its own: how the text is cut into pieces is the caller's affair.
+    public func submitOpenText(session: OpaquePointer, text: String, speaker: String? = nil, language: String = "auto",
+                               maxTokens: Int = 2048) throws -> Int64 {
+        guard let tokenizer else { throw AudioGenerationError.modelNotInitialized("Model not initialized: Tokenizer not loaded") }
+        // role tokens + the content so far, without the "<|im_end|>\n<|im_start|>assistant\n" tail of a whole request
+        let ids = tokenizer.encode(text: "<|im_start|>assistant\n\(text)").map(Int32.init)
+        var ticket: Int64 = -1
+        let st: q3tts_status = ids.withUnsafeBufferPointer { tp in
+            withOptionalCString(speaker) { sp in
+                language.withCString { lp in
+                    var req = q3tts_request()
+                    req.text_ids = tp.baseAddress; req.n_text_ids = Int32(tp.count)
+                    req.speaker = sp; req.language = lp
+                    req.max_tokens = Int32(maxTokens)
+                    return q3tts_session_submit_open(session, &req, nil, &ticket)
+                }
+            }
+        }
+        guard st == Q3TTS_OK else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
+        return ticket
+    }
+
+    /// More text for an open-text ticket; `final` closes it (an empty `text` with `final`: just close). Callable from any thread,
+    /// also from inside the session's event callback. Text for a ticket that has already ended is dropped without an error.
+    public func appendText(session: OpaquePointer, ticket: Int64, text: String, final: Bool = false) throws {
+        guard let tokenizer else { throw AudioGenerationError.modelNotInitialized("Model not initialized: Tokenizer not loaded") }
+        let ids = text.isEmpty ? [] : tokenizer.encode(text: text).map(Int32.init)
+        let st = ids.withUnsafeBufferPointer { tp in
+            q3tts_session_append_text(session, ticket, tp.baseAddress, Int32(tp.count), final ? 1 : 0)
+        }
+        guard st == Q3TTS_OK else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
+    }
+
     private func run(text: String, speaker: String?, instruct: String?, language: String, temperature: Float, topK: Int,
                      topP: Float, repetitionPenalty: Float, maxTokens: Int, seed: UInt64, route: Int32 = 0,
                      referenceAudio: [Float] = [], refTextIds: [Int32] = [], voice: Qwen3TTSVoice? = nil, chunkFrames: Int = 0,

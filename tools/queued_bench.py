@@ -34,12 +34,19 @@ its submit to its completion (its AUDIO event; without a callback: when its resu
 and max over the requests that succeeded; with --stream also from its submit to its first AUDIO_CHUNK. The same requests as one closed q3tts_generate_queued call, with the same callback, stand next
 to it (every request "submitted" at the call). With RATE = inf the session and the closed call also alternate --repeat times
 WITHOUT a callback, which is the saturated-throughput comparison, and their results are compared bit for bit.
+--session --text-rate TOK_PER_S feeds every request's text the way a language model would hand it over: content token j of each
+request arrives j / TOK_PER_S seconds after its first one, from a feeder thread. Two ways to serve that, alternating --repeat times:
+  open    q3tts_session_submit_open at the first token, q3tts_session_append_text for every later one (the last one final)
+  whole   q3tts_session_submit of the whole request once its last token has arrived -- what a caller can do without open text
+Printed per run: the time from a request's first token to its first AUDIO_CHUNK (--stream; its AUDIO otherwise), median, p95 and max,
+to its completion, the session's starve events, and whether the two ways agree bit for bit (they must: same tickets).
 """
 from __future__ import annotations
 
 import argparse
 import os
 import sys
+import threading
 import time
 
 import numpy as np
@@ -203,6 +210,95 @@ def run_session_bench(model, args, ragged, warm, sampling):
     print(f"bit-identical codes + pcm, session against the closed call: {same(out, cout)}", flush=True)
 
 
+def run_text_fed(model, reqs, slots, kw, rate, open_text):
+    """Every request's content token j arrives j / rate seconds after the run's start. open_text: submit_open at the first token and
+    one append per later token; otherwise plain submit once the last token is there. Returns results, first token -> first audio,
+    first token -> completion (seconds), and the session's text stats."""
+    from qwen3tts import GenerationRequest
+    n = len(reqs)
+    first_audio, done_t = {}, {}
+    first_kind = "audio_chunk" if kw.get("audio_chunk_frames", 0) > 0 else "audio"
+
+    def on_event(i, kind, payload):
+        t = time.perf_counter()
+        if kind == first_kind:
+            first_audio.setdefault(i, t)
+        if kind == "audio":
+            done_t[i] = t
+
+    content = [list(r.text_ids[3:-5]) for r in reqs]
+    longest = max(len(c) for c in content)
+    s = model.open_session(slots=slots, max_pending=n, on_event=on_event, **kw)
+    errors = []
+    try:
+        t0 = time.perf_counter()
+
+        def feeder():
+            try:
+                for j in range(longest):
+                    due = t0 + j / rate
+                    while True:
+                        now = time.perf_counter()
+                        if now >= due:
+                            break
+                        time.sleep(min(due - now, 0.001))
+                    for i, r in enumerate(reqs):
+                        c = content[i]
+                        if j >= len(c):
+                            continue
+                        last = j == len(c) - 1
+                        if open_text:
+                            if j == 0:
+                                head = GenerationRequest(list(r.text_ids[:4]), 0, r.instruct_ids, r.speaker, r.language, r.max_tokens)
+                                assert s.submit_open(head) == i
+                                if last:
+                                    s.close_text(i)
+                            else:
+                                s.append_text(i, c[j:j + 1], final=last)
+                        elif last:
+                            s.submit(r)
+            except Exception as e:  # (reported by the caller's thread)
+                errors.append(e)
+
+        th = threading.Thread(target=feeder)
+        th.start()
+        th.join()
+        if errors:
+            raise errors[0]
+        out = [s.result(i, timeout=600) for i in range(n)]
+        ts = s.text_stats()
+        s.close()
+    finally:
+        s.close(drain=False)
+    first = np.asarray([first_audio[i] - t0 for i in range(n) if i in first_audio])
+    done = np.asarray([done_t[i] - t0 for i in range(n) if i in done_t])
+    return out, first, done, ts
+
+
+def run_text_rate_bench(model, args, reqs, warm, sampling):
+    rate = float(args.text_rate)
+    kw = dict(sampling)
+    if args.stream:
+        c, w, l = (int(x) for x in args.stream.split(","))
+        kw.update(audio_chunk_frames=c, audio_window_frames=w, audio_lookahead_frames=l)
+    run_text_fed(model, warm, args.slots, kw, 1e9, True)  # warm-up: the session's graph, the stream arena
+    run_text_fed(model, warm, args.slots, kw, 1e9, False)
+    what = "first AUDIO_CHUNK" if args.stream else "AUDIO"
+    tag = f"--stream {args.stream}" if args.stream else "whole audio"
+    print(f"# session, {len(reqs)} requests of {len(reqs[0].text_ids) - 8} content tokens arriving at {args.text_rate} tokens/s each, "
+          f"slots {args.slots}, {tag}", flush=True)
+    same = lambda a, b: all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio) for x, y in zip(a, b))
+    for rep in range(args.repeat):
+        res = {}
+        for name, open_text in (("open", True), ("whole", False)):
+            out, first, done, ts = run_text_fed(model, reqs, args.slots, kw, rate, open_text)
+            res[name] = out
+            print(f"run {rep} {name:5s} first token -> {what}: {_pct(first)}", flush=True)
+            print(f"run {rep} {name:5s} first token -> completion:   {_pct(done)}   starve events {ts.starve_events}  "
+                  f"appended tokens {ts.appended_tokens}  failed {sum(1 for r in out if r.status != 0)}", flush=True)
+        print(f"run {rep} bit-identical codes + pcm, open text against whole submits: {same(res['open'], res['whole'])}", flush=True)
+
+
 def run_voices(model, args):
     """The ragged workload as voice-clone requests: static ref_audio batches against the queue with voices."""
     from qwen3tts import GenerationRequest, synth
@@ -292,6 +388,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=3, help="--voices / --session: how often the two paths alternate")
     ap.add_argument("--session", action="store_true", help="the ragged workload through a serving session (see --arrivals)")
     ap.add_argument("--arrivals", default="inf", metavar="RATE", help="--session: requests per second, exponential gaps; inf: all at once")
+    ap.add_argument("--text-rate", default=None, metavar="TOK_PER_S",
+                    help="--session: every request's content arrives at this rate; open-text requests against whole submits")
     args = ap.parse_args()
     from qwen3tts import Qwen3TTSModel, RequestSampling
 
@@ -323,6 +421,13 @@ def main():
     run_static(model, warm, args.slots, sampling)
     run_queued(model, warm, args.slots, sampling)
 
+    if args.session and args.text_rate:
+        # (an open-text request's target_token_count is its content count: the whole requests it is compared with say the same)
+        fed = [type(r)(r.text_ids, len(r.text_ids) - 8, r.instruct_ids, r.speaker, r.language, r.max_tokens) for r in ragged]
+        fed_warm = [type(r)(r.text_ids, len(r.text_ids) - 8, r.instruct_ids, r.speaker, r.language, 8) for r in base[:args.slots]]
+        run_text_rate_bench(model, args, fed, fed_warm, sampling)
+        model.close()
+        return
     if args.session:
         run_session_bench(model, args, ragged, warm, sampling)
         model.close()

@@ -691,6 +691,65 @@ typedef struct {
 } q3tts_attn_debug;
 q3tts_status q3tts_debug_attention(q3tts_model* m, const q3tts_attn_debug* a);
 
+/* One launch of the decode GEMM (csrc/kernels/gemm_decode.hip, gemm_prefill.hip) on caller-supplied host buffers, through the
+ * product's own launchers -- launch_gemm_skinny, or launch_gemm_skinny_with_norm_rows when a rider is given -- so that
+ * skinny_geometry / gemm_tall_takes pick the kernel instantiation exactly as a frame step would. Everything GemmArgs can
+ * express can be stated here. The weights are handed over as a checkpoint holds them and tiled by the loader's own
+ * launch_tile_weights / launch_tile_int4 with the loader's arguments (csrc/model.cc put_linear; epi 2: gate and up separately,
+ * eight rows per tile at tile rows 0 and 8). The call allocates its own device buffers and frees them; it touches neither the
+ * model's weights nor its caches. Every argument is checked on the host (INVALID_INPUT) before anything is launched:
+ *   K a multiple of 128 up to 8192; N a multiple of 16 (epi 2: of 8, N counts output columns); 1 <= M <= 1024;
+ *   16 * xMB >= Mpad (= M rounded up to 16), 16 * yMB >= Mpad, ss_ld >= Mpad; y_cols >= N, a multiple of 8, and of 128 where
+ *   y is fragment-major on the device (epi 2, epi 3, y_tiled); epi in {0, 2, 3}; bias / act_silu not with epi 2;
+ *   norm: norm_w, ss_in, 1 <= ss_count <= 4096, norm_dim >= 1; rider: 1 <= rider_M <= 16 * rider_MB <= 1024, rider_H a multiple
+ *   of 128 up to 4096, rider_ss_count in 1..256 when rider_ss_in is set.
+ * The caller sees every activation row-major; the call converts to and from the fragment-major device layouts itself.
+ *   x [16 * xMB][K] (rows >= M are uploaded too: the kernels must ignore them);
+ *   y [16 * yMB][y_cols] is uploaded whole as the caller filled it and returned whole (the hidden-state form, epi 3, is in
+ *   place), and so is ss_out [N / 16][ss_ld] when given: a sentinel shows what was and was not written;
+ *   rider_h [16 * rider_MB][rider_H], rider_out the same shape (in / out), rider_ss_out [16 * rider_MB] (in / out) or NULL,
+ *   rider_ss_in [rider_ss_count][16 * rider_MB] or NULL.
+ * mode 0: the GEMM (rider_M > 0: with the rider; `rode` reports whether the launch carried it -- if not, nothing was launched).
+ * mode 1: launch_norm_rows alone on the rider fields (the GEMM fields are ignored).
+ * geometry_only != 0: nothing is allocated or launched and no buffer pointer is read; only the geometry outputs are filled
+ * from norm / quant / has_bias and the sizes. This works without a GPU and with m == NULL. */
+typedef struct {
+    int32_t mode, geometry_only;
+    int32_t M, K, N;
+    int32_t xMB, yMB, ss_ld, y_cols;
+    int32_t epi, act_silu, resid, nt_weights, y_tiled;
+    int32_t norm, quant, has_bias;   /* which optional operands take part (the pointers below must agree) */
+    int32_t ss_count, norm_dim;
+    float norm_eps;
+    int32_t rider_M, rider_H, rider_MB, rider_ss_count;
+    float rider_eps;
+    /* outputs */
+    int32_t rode;                    /* mode 0 with a rider: 1 when launch_gemm_skinny_with_norm_rows launched */
+    int32_t tall;                    /* the tall form takes it: tall_shape 2 (128 x 64) or 3 (64 x 64); the rest is 0 */
+    int32_t tall_shape;
+    int32_t split, mbw, nw, ch, np, gx, ntw;  /* SkinnyGeom (csrc/kernels.h) */
+    /* inputs */
+    const uint16_t* x;
+    const void* W;                   /* bf16 [N][K], or uint32 [N][K / 8] with quant; epi 2: the gate matrix */
+    const uint16_t* scales;          /* quant: bf16 [N][K / 64] */
+    const uint16_t* biases;
+    const void* W_up;                /* epi 2: the up matrix, with its scales / biases */
+    const uint16_t* scales_up;
+    const uint16_t* biases_up;
+    const uint16_t* bias;            /* [N] */
+    const uint16_t* norm_w;          /* [K] */
+    const float* ss_in;              /* [ss_count][ss_ld] */
+    const uint16_t* rider_h;
+    const uint16_t* rider_w;         /* [rider_H] */
+    const float* rider_ss_in;
+    /* in / out */
+    uint16_t* y;
+    float* ss_out;                   /* or NULL */
+    uint16_t* rider_out;
+    float* rider_ss_out;             /* or NULL */
+} q3tts_gemm_debug;
+q3tts_status q3tts_debug_gemm(q3tts_model* m, q3tts_gemm_debug* a);
+
 /* Codec decoder with intermediate activations (SpeechTokenizer.swift:754-784) for one utterance:
  * stage names: "quantizer","pre_conv","pre_transformer","upsample0","upsample1","init_conv",
  * "block0".."block3". Output is channels-last [T][C] float32; *T,*C receive the shape. */

@@ -592,6 +592,20 @@ q3tts_status q3tts_debug_attention(q3tts_model* m, const q3tts_attn_debug* a) {
     });
 }
 
+q3tts_status q3tts_debug_gemm(q3tts_model* m, q3tts_gemm_debug* a) {
+    if (a && a->geometry_only) {  // host code only: no model, no GPU
+        return guarded(nullptr, [&] {
+            q3::GemmArgs ga{};
+            q3::NormRowsArgs na{};
+            q3::Engine::debug_gemm_check(*a, ga, na);
+        });
+    }
+    return guarded(m, [&] {
+        Q3_CHECK(m && a, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_gemm(*a);
+    });
+}
+
 q3tts_status q3tts_codec_decode_streamed(q3tts_model* m, const int32_t* codes, const int32_t* n_frames, int32_t batch, int32_t max_frames,
                                          int32_t chunk_frames, int32_t window, int32_t lookahead, float* pcm) {
     return guarded(m, [&] {

@@ -3261,6 +3261,191 @@ void Engine::debug_attention(const q3tts_attn_debug& d) {
     Q3_HIP(hipMemcpy(d.vpool, vp, pool * 2, hipMemcpyDeviceToHost));
 }
 
+// q3tts_debug_gemm (q3tts.h): everything the kernels turn into an address is checked here against the sizes the caller states.
+void Engine::debug_gemm_check(q3tts_gemm_debug& d, GemmArgs& ga, NormRowsArgs& na) {
+    static const uint16_t dummy16 = 0;  // geometry_only: "this operand takes part" without a buffer
+    static const uint32_t dummy32 = 0;
+    d.rode = d.tall = d.tall_shape = d.split = d.mbw = d.nw = d.ch = d.np = d.gx = d.ntw = 0;
+    Q3_CHECK(d.mode == 0 || d.mode == 1, 3, "debug_gemm: unknown mode");
+    const bool rider = d.mode == 1 || d.rider_M > 0;
+    if (rider) {
+        Q3_CHECK(d.rider_M >= 1 && d.rider_MB >= 1 && d.rider_MB <= 64 && d.rider_M <= 16 * d.rider_MB, 3, "debug_gemm: rider rows out of range");
+        Q3_CHECK(d.rider_H >= 128 && d.rider_H <= 4096 && d.rider_H % 128 == 0, 3, "debug_gemm: rider_H must be a multiple of 128 up to 4096");
+        Q3_CHECK(d.geometry_only || (d.rider_h && d.rider_w && d.rider_out), 3, "debug_gemm: null rider argument");
+        if (d.rider_ss_in) Q3_CHECK(d.rider_ss_count >= 1 && d.rider_ss_count <= 256, 3, "debug_gemm: at most 256 partial sums of squares per rider row");
+        na.hMB = na.outMB = d.rider_MB; na.eps = d.rider_eps; na.M = d.rider_M; na.H = d.rider_H;
+        na.ss_count = d.rider_ss_in ? d.rider_ss_count : 0; na.ss_ld = 16 * d.rider_MB;
+    }
+    if (d.mode == 1) return;
+    Q3_CHECK(d.epi == 0 || d.epi == 2 || d.epi == 3, 3, "debug_gemm: unknown epilogue");
+    Q3_CHECK(d.M >= 1 && d.M <= 1024, 3, "debug_gemm: M out of range");
+    Q3_CHECK(d.K >= 128 && d.K <= 8192 && d.K % 128 == 0, 3, "debug_gemm: K must be a multiple of 128 up to 8192");
+    Q3_CHECK(d.N >= 8 && d.N <= 65536 && d.N % (d.epi == 2 ? 8 : 16) == 0, 3, "debug_gemm: N must be a multiple of 16 (epi 2: of 8)");
+    const int Mp = int(align_up(size_t(d.M), 16));
+    const bool tiled = d.epi != 0 || d.y_tiled;
+    Q3_CHECK(d.xMB <= 64 && 16 * d.xMB >= Mp && d.yMB <= 64 && 16 * d.yMB >= Mp && d.ss_ld >= Mp && d.ss_ld <= 4096, 3,
+             "debug_gemm: allocation smaller than the padded batch");
+    Q3_CHECK(d.y_cols >= d.N && d.y_cols <= d.N + 1024 && d.y_cols % (tiled ? 128 : 8) == 0, 3, "debug_gemm: y_cols");
+    Q3_CHECK(d.epi != 2 || (!d.has_bias && !d.act_silu), 3, "debug_gemm: the gate/up epilogue takes no bias or activation");
+    Q3_CHECK(d.epi == 0 || !d.act_silu, 3, "debug_gemm: act_silu belongs to epi 0");
+    Q3_CHECK(d.epi == 3 || (!d.resid && !d.ss_out), 3, "debug_gemm: resid / ss_out belong to epi 3");
+    if (d.norm) Q3_CHECK(d.ss_count >= 1 && d.ss_count <= 4096 && d.norm_dim >= 1, 3, "debug_gemm: norm prologue sizes");
+    if (!d.geometry_only) {
+        Q3_CHECK(d.x && d.W && d.y, 3, "debug_gemm: null argument");
+        Q3_CHECK((d.epi == 2) == (d.W_up != nullptr), 3, "debug_gemm: W_up goes with epi 2");
+        Q3_CHECK((d.quant != 0) == (d.scales != nullptr) && (d.quant != 0) == (d.biases != nullptr), 3, "debug_gemm: scales / biases go with quant");
+        if (d.epi == 2) Q3_CHECK((d.quant != 0) == (d.scales_up != nullptr) && (d.quant != 0) == (d.biases_up != nullptr), 3, "debug_gemm: scales / biases go with quant");
+        Q3_CHECK((d.has_bias != 0) == (d.bias != nullptr), 3, "debug_gemm: bias goes with has_bias");
+        Q3_CHECK((d.norm != 0) == (d.norm_w != nullptr) && (d.norm != 0) == (d.ss_in != nullptr), 3, "debug_gemm: norm_w / ss_in go with norm");
+    }
+    ga.Wsb = d.quant ? &dummy32 : nullptr;
+    ga.xMB = d.xMB; ga.M = d.M; ga.Mpad = Mp; ga.N = d.N; ga.K = d.K; ga.epi = d.epi;
+    ga.ldy = d.y_cols; ga.y_tiled = d.y_tiled ? 1 : 0; ga.yMB = d.yMB;
+    ga.bias = d.has_bias ? &dummy16 : nullptr;
+    ga.act_silu = d.act_silu ? 1 : 0;
+    ga.norm_w = d.norm ? &dummy16 : nullptr;
+    ga.ss_count = d.norm ? d.ss_count : 0; ga.ss_ld = d.ss_ld; ga.norm_dim = d.norm_dim; ga.norm_eps = d.norm_eps;
+    ga.nt_weights = d.nt_weights ? 1 : 0; ga.resid = d.resid ? 1 : 0;
+    const SkinnyGeom g = skinny_geometry(ga);
+    d.tall = g.tall ? 1 : 0;
+    if (g.tall) {
+        d.tall_shape = gemm_tall_shape(ga);
+    } else {
+        Q3_CHECK(g.mbw >= 1 && g.mbw <= 4, 3, "debug_gemm: more than 4 row blocks per workgroup");
+        d.split = g.split; d.mbw = g.mbw; d.nw = g.nw; d.ch = g.ch; d.np = g.np; d.gx = g.gx; d.ntw = g.ntw ? 1 : 0;
+    }
+    if (rider) d.rode = gemm_norm_rows_rides(ga, na) ? 1 : 0;
+}
+
+namespace {
+// row-major [rows][cols] <-> the fragment-major activation layout (common.h act_tiled_offset); rows % 16 == 0, cols % 128 == 0
+void host_tile(const uint16_t* src, std::vector<uint16_t>& dst, int rows, int cols) {
+    dst.resize(size_t(rows) * cols);
+    for (int m = 0; m < rows; ++m)
+        for (int k = 0; k < cols; k += 8) std::memcpy(&dst[act_tiled_offset(m, k, rows / 16)], src + size_t(m) * cols + k, 16);
+}
+void host_untile(const std::vector<uint16_t>& src, uint16_t* dst, int rows, int cols) {
+    for (int m = 0; m < rows; ++m)
+        for (int k = 0; k < cols; k += 8) std::memcpy(dst + size_t(m) * cols + k, &src[act_tiled_offset(m, k, rows / 16)], 16);
+}
+}  // namespace
+
+void Engine::debug_gemm(q3tts_gemm_debug& d) {
+    GemmArgs ga{};
+    NormRowsArgs na{};
+    debug_gemm_check(d, ga, na);
+    DevBuf<uint16_t> dx, dy, dbias, dnw, dsrc, dsc, dbi, rh, rw, rout;
+    DevBuf<uint8_t> dWt;
+    DevBuf<uint32_t> dWq, dsb;
+    DevBuf<float> dssi, dsso, rssi, rsso;
+    std::vector<uint16_t> tmp;
+    auto up16 = [&](DevBuf<uint16_t>& b, const uint16_t* src, size_t n) {
+        b.grow(n);
+        Q3_HIP(hipMemcpy(b, src, n * 2, hipMemcpyHostToDevice));
+    };
+    const bool rider = d.mode == 1 || d.rider_M > 0;
+    const int rrows = 16 * d.rider_MB;
+    if (rider) {
+        host_tile(d.rider_h, tmp, rrows, d.rider_H);
+        up16(rh, tmp.data(), tmp.size());
+        host_tile(d.rider_out, tmp, rrows, d.rider_H);
+        up16(rout, tmp.data(), tmp.size());
+        up16(rw, d.rider_w, size_t(d.rider_H));
+        na.h = rh; na.w = rw; na.out = rout;
+        if (d.rider_ss_in) {
+            rssi.grow(size_t(d.rider_ss_count) * rrows);
+            Q3_HIP(hipMemcpy(rssi, d.rider_ss_in, size_t(d.rider_ss_count) * rrows * 4, hipMemcpyHostToDevice));
+            na.ss_in = rssi;
+        }
+        if (d.rider_ss_out) {
+            rsso.grow(size_t(rrows));
+            Q3_HIP(hipMemcpy(rsso, d.rider_ss_out, size_t(rrows) * 4, hipMemcpyHostToDevice));
+            na.ss_out = rsso;
+        }
+    }
+    const bool tiled = d.mode == 0 && (d.epi != 0 || d.y_tiled);
+    const int yrows = 16 * d.yMB, n_tiles = d.mode == 0 ? (d.epi == 2 ? d.N / 8 : d.N / 16) : 0, KC = d.K / 128;
+    const size_t n_ss_out = d.mode == 0 ? size_t(d.N / 16) * d.ss_ld : 0;
+    if (d.mode == 0) {
+        host_tile(d.x, tmp, 16 * d.xMB, d.K);
+        up16(dx, tmp.data(), tmp.size());
+        if (tiled) {
+            host_tile(d.y, tmp, yrows, d.y_cols);
+            up16(dy, tmp.data(), tmp.size());
+        } else {
+            up16(dy, d.y, size_t(yrows) * d.y_cols);
+        }
+        // the weights as the loader tiles them (model.cc put_linear): zeroed destination, one launch per source matrix
+        const size_t wbytes = d.quant ? size_t(n_tiles) * 16 * d.K / 2 : size_t(n_tiles) * 16 * d.K * 2;
+        dWt.grow(wbytes);
+        Q3_HIP(hipMemset(dWt, 0, wbytes));
+        if (d.quant) {
+            dsb.grow(size_t(n_tiles) * KC * 64);
+            Q3_HIP(hipMemset(dsb, 0, size_t(n_tiles) * KC * 64 * 4));
+        }
+        const int rpt = d.epi == 2 ? 8 : 16;
+        for (int part = 0; part < (d.epi == 2 ? 2 : 1); ++part) {
+            const void* W = part ? d.W_up : d.W;
+            if (d.quant) {
+                dWq.grow(size_t(d.N) * d.K / 8);
+                Q3_HIP(hipMemcpy(dWq, W, size_t(d.N) * d.K / 8 * 4, hipMemcpyHostToDevice));
+                up16(dsc, part ? d.scales_up : d.scales, size_t(d.N) * d.K / 64);
+                up16(dbi, part ? d.biases_up : d.biases, size_t(d.N) * d.K / 64);
+                launch_tile_int4(dWq, dsc, dbi, d.N, d.K, dWt, dsb, KC, 0, 1, st_, rpt, 8 * part);
+            } else {
+                up16(dsrc, static_cast<const uint16_t*>(W), size_t(d.N) * d.K);
+                launch_tile_weights(dsrc, d.N, d.K, reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(dWt)), KC, 0, 1, st_, rpt, 8 * part);
+            }
+            Q3_HIP(hipStreamSynchronize(st_));  // the staging buffers are reused
+        }
+        if (d.bias) up16(dbias, d.bias, size_t(d.N));
+        if (d.norm) {
+            up16(dnw, d.norm_w, size_t(d.K));
+            dssi.grow(size_t(d.ss_count) * d.ss_ld);
+            Q3_HIP(hipMemcpy(dssi, d.ss_in, size_t(d.ss_count) * d.ss_ld * 4, hipMemcpyHostToDevice));
+        }
+        if (d.ss_out) {
+            dsso.grow(n_ss_out);
+            Q3_HIP(hipMemcpy(dsso, d.ss_out, n_ss_out * 4, hipMemcpyHostToDevice));
+        }
+        ga.W = reinterpret_cast<const uint16_t*>(static_cast<uint8_t*>(dWt));
+        ga.Wsb = d.quant ? static_cast<uint32_t*>(dsb) : nullptr;
+        ga.x = dx; ga.y = dy;
+        ga.bias = d.bias ? static_cast<uint16_t*>(dbias) : nullptr;
+        ga.norm_w = d.norm ? static_cast<uint16_t*>(dnw) : nullptr;
+        ga.ss_in = d.norm ? static_cast<float*>(dssi) : nullptr;
+        ga.ss_out = d.ss_out ? static_cast<float*>(dsso) : nullptr;
+    }
+    bool launched = true;
+    if (d.mode == 1) {
+        launch_norm_rows(na, st_);
+    } else if (rider) {
+        launched = launch_gemm_skinny_with_norm_rows(ga, na, st_);
+        Q3_CHECK(launched == (d.rode != 0), 7, "debug_gemm: the rider launch disagrees with gemm_norm_rows_rides");
+    } else {
+        launch_gemm_skinny(ga, st_);
+    }
+    Q3_HIP(hipGetLastError());  // an instantiation the device cannot launch must not pass as "nothing written"
+    Q3_HIP(hipStreamSynchronize(st_));
+    if (!launched) return;
+    if (d.mode == 0) {
+        if (tiled) {
+            tmp.resize(size_t(yrows) * d.y_cols);
+            Q3_HIP(hipMemcpy(tmp.data(), dy, tmp.size() * 2, hipMemcpyDeviceToHost));
+            host_untile(tmp, d.y, yrows, d.y_cols);
+        } else {
+            Q3_HIP(hipMemcpy(d.y, dy, size_t(yrows) * d.y_cols * 2, hipMemcpyDeviceToHost));
+        }
+        if (d.ss_out) Q3_HIP(hipMemcpy(d.ss_out, dsso, n_ss_out * 4, hipMemcpyDeviceToHost));
+    }
+    if (rider) {
+        tmp.resize(size_t(rrows) * d.rider_H);
+        Q3_HIP(hipMemcpy(tmp.data(), rout, tmp.size() * 2, hipMemcpyDeviceToHost));
+        host_untile(tmp, d.rider_out, rrows, d.rider_H);
+        if (d.rider_ss_out) Q3_HIP(hipMemcpy(d.rider_ss_out, rsso, size_t(rrows) * 4, hipMemcpyDeviceToHost));
+    }
+}
+
 // Codes a CALLER hands in (q3tts_codec_decode, q3tts_codec_decode_streamed) index the RVQ tables on the GPU: every code of every frame
 // that will be decoded is checked against the tables as loaded. (Codes the engine sampled itself are inside by construction:
 // the samplers draw below the vocabulary, the tables have at least that many rows.)

@@ -237,6 +237,10 @@ class Engine {
                            float* out_ss, int32_t* out_state);
     void debug_linear(const uint16_t* x, const uint16_t* W, const uint16_t* bias, int M, int K, int N, uint16_t* y);
     void debug_attention(const q3tts_attn_debug& a);
+    // q3tts_debug_gemm: the host checks and the geometry need neither an engine nor a GPU (geometry_only); returns the GemmArgs
+    // and NormRowsArgs the launch will carry, still without pointers
+    static void debug_gemm_check(q3tts_gemm_debug& d, GemmArgs& ga, NormRowsArgs& na);
+    void debug_gemm(q3tts_gemm_debug& d);
     void debug_build_decode_codes(const int32_t* refs, const int32_t* ref_T, const int32_t* gen, const int32_t* n_frames, int R,
                                   int gen_stride, int Fdec, bool misalign, int32_t* out);
     void codec_decode(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, float* pcm,

@@ -91,10 +91,12 @@ SkinnyGeom skinny_geometry(const GemmArgs& a);
 // otherwise. A kernel of its own: the riders' dispatch test must not sit in front of every other GEMM's first load (as a
 // field of GemmArgs it cost 0.28 us per launch, 500 launches per frame step).
 bool launch_gemm_skinny_with_norm_rows(const GemmArgs& a, const NormRowsArgs& n, hipStream_t st);
+bool gemm_norm_rows_rides(const GemmArgs& a, const NormRowsArgs& n);  // whether it would launch (same test, nothing enqueued)
 // More than 64 rows, plain bf16 weights, no prologue / bias: the tall form (gemm_prefill.hip), bit-identical to the skinny one.
 // launch_gemm_skinny tries it first; false = nothing launched (shape or options it does not take).
 bool launch_gemm_tall(const GemmArgs& a, hipStream_t st);
 bool gemm_tall_takes(const GemmArgs& a);  // whether launch_gemm_tall would launch (same test, nothing enqueued)
+int gemm_tall_shape(const GemmArgs& a);   // the tile shape it takes: 2 (128 x 64 rows) or 3 (64 x 64)
 
 
 // ---- QK-norm + RoPE + KV append + paged decode attention (attn_decode.hip) ---------------------

@@ -185,7 +185,7 @@ SkinnyGeom skinny_geometry(const GemmArgs& a) {
 }
 
 // whether launch_gemm_skinny_with_norm_rows launches for these arguments
-static bool gemm_norm_rows_rides(const GemmArgs& a, const NormRowsArgs& n) {
+bool gemm_norm_rows_rides(const GemmArgs& a, const NormRowsArgs& n) {
     if (a.epi != 0 || !a.norm_w || a.nt_weights || n.M <= 0 || n.H > 4096) return false;
     if (a.K % 128 != 0 || a.N % 16 != 0) return false;
     const SkinnyGeom g = skinny_geometry(a);

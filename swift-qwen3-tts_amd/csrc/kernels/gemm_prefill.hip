@@ -241,10 +241,7 @@ bool gemm_tall_takes(const GemmArgs& a) {
     return true;
 }
 
-bool launch_gemm_tall(const GemmArgs& a, hipStream_t st) {
-    if (!gemm_tall_takes(a)) return false;
-    const int KC = a.K / 128;
-    const int nphase = KC <= 4 ? 4 : 8;  // gemm_decode.hip launch_mb: waves that split K
+int gemm_tall_shape(const GemmArgs& a) {
     const int n_tiles = a.epi == 2 ? a.N / 8 : a.N / 16;
     const int MBt = a.Mpad / 16;
     // 128 activation rows x 64 weight rows where that still gives (nearly) every CU a workgroup, else 64 x 64. Measured per
@@ -256,7 +253,15 @@ bool launch_gemm_tall(const GemmArgs& a, hipStream_t st) {
     auto wgs = [&](int tm, int tn) { return ((MBt + tm - 1) / tm) * ((n_tiles + tn - 1) / tn); };
     int shape = wgs(8, 4) >= 192 ? 2 : 3;
     if (force == 2 || force == 3) shape = force;
-    if (shape == 2) launch_shape<2, 2, 4, 2, 4>(a, n_tiles, nphase, st);
+    return shape;
+}
+
+bool launch_gemm_tall(const GemmArgs& a, hipStream_t st) {
+    if (!gemm_tall_takes(a)) return false;
+    const int KC = a.K / 128;
+    const int nphase = KC <= 4 ? 4 : 8;  // gemm_decode.hip launch_mb: waves that split K
+    const int n_tiles = a.epi == 2 ? a.N / 8 : a.N / 16;
+    if (gemm_tall_shape(a) == 2) launch_shape<2, 2, 4, 2, 4>(a, n_tiles, nphase, st);
     else launch_shape<2, 2, 2, 2, 8>(a, n_tiles, nphase, st);
     return true;
 }

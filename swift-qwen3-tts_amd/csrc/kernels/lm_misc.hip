@@ -302,6 +302,9 @@ __global__ __launch_bounds__(256) void frame_end_kernel(FrameEndArgs a) {
 
 void launch_norm_rows(const NormRowsArgs& a, hipStream_t st) {
     Q3_CHECK(a.H % 128 == 0 && a.H <= 4096, 3, "norm_rows: H must be a multiple of 128, at most 4096");
+    // norm_row_job folds 32 partials per thread on 8 threads; the GEMM prologue's tail loop would take more, and the two
+    // must add up the same partials
+    Q3_CHECK(!a.ss_in || (a.ss_count >= 1 && a.ss_count <= 256), 3, "norm_rows: at most 256 partial sums of squares per row");
     hipLaunchKernelGGL(norm_rows_kernel, dim3(a.M), dim3(256), 0, st, a);
 }
 void launch_gather_rows(const uint16_t* table, int ld, const int32_t* ids, const int32_t* token_map, int n,

@@ -114,6 +114,23 @@ class AttnDebug(C.Structure):  # q3tts_attn_debug
                 ("kpool", u16p), ("vpool", u16p), ("out", u16p)]
 
 
+class GemmDebug(C.Structure):  # q3tts_gemm_debug
+    _fields_ = [("mode", C.c_int32), ("geometry_only", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("N", C.c_int32),
+                ("xMB", C.c_int32), ("yMB", C.c_int32), ("ss_ld", C.c_int32), ("y_cols", C.c_int32),
+                ("epi", C.c_int32), ("act_silu", C.c_int32), ("resid", C.c_int32), ("nt_weights", C.c_int32), ("y_tiled", C.c_int32),
+                ("norm", C.c_int32), ("quant", C.c_int32), ("has_bias", C.c_int32), ("ss_count", C.c_int32), ("norm_dim", C.c_int32),
+                ("norm_eps", C.c_float),
+                ("rider_M", C.c_int32), ("rider_H", C.c_int32), ("rider_MB", C.c_int32), ("rider_ss_count", C.c_int32),
+                ("rider_eps", C.c_float),
+                ("rode", C.c_int32), ("tall", C.c_int32), ("tall_shape", C.c_int32),
+                ("split", C.c_int32), ("mbw", C.c_int32), ("nw", C.c_int32), ("ch", C.c_int32), ("np", C.c_int32), ("gx", C.c_int32),
+                ("ntw", C.c_int32),
+                ("x", u16p), ("W", C.c_void_p), ("scales", u16p), ("biases", u16p), ("W_up", C.c_void_p), ("scales_up", u16p),
+                ("biases_up", u16p), ("bias", u16p), ("norm_w", u16p), ("ss_in", f32p), ("rider_h", u16p), ("rider_w", u16p),
+                ("rider_ss_in", f32p),
+                ("y", u16p), ("ss_out", f32p), ("rider_out", u16p), ("rider_ss_out", f32p)]
+
+
 _lib = None
 
 
@@ -204,11 +221,27 @@ def lib() -> C.CDLL:
                                      C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, i32p]
     L.q3tts_debug_linear.argtypes = [vp, u16p, u16p, u16p, C.c_int32, C.c_int32, C.c_int32, u16p]
     L.q3tts_debug_attention.argtypes = [vp, C.POINTER(AttnDebug)]
+    if hasattr(L, "q3tts_debug_gemm"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_debug_gemm.argtypes = [vp, C.POINTER(GemmDebug)]
     if hasattr(L, "q3tts_debug_build_decode_codes"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_build_decode_codes.argtypes = [vp, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
     L.q3tts_debug_codec_stage.argtypes = [vp, i32p, C.c_int32, C.c_char_p, f32p, C.c_int64, i32p, i32p]
     _lib = L
     return L
+
+
+GEOM_FIELDS = ("rode", "tall", "tall_shape", "split", "mbw", "nw", "ch", "np", "gx", "ntw")
+
+
+def gemm_geometry(**kw) -> dict:
+    """q3tts_debug_gemm with geometry_only = 1: the launch skinny_geometry / gemm_tall_takes choose for these sizes and options
+    (GemmDebug's scalar fields as keywords). Host code only: needs neither a model nor a GPU. Raises ValueError on
+    INVALID_INPUT."""
+    a = GemmDebug(geometry_only=1, **kw)
+    st = lib().q3tts_debug_gemm(None, C.byref(a))
+    if st != 0:
+        raise ValueError("q3tts_debug_gemm refused the arguments (status %d): %r" % (st, kw))
+    return {f: int(getattr(a, f)) for f in GEOM_FIELDS}
 
 
 def reload_debug_env() -> None:

@@ -774,6 +774,67 @@ class Qwen3TTSModel:
         self._check(self._lib.q3tts_debug_attention(self._h, C.byref(a)))
         return out, kpool, vpool
 
+    def debug_gemm(self, *, x=None, W=None, y=None, M=0, epi=0, W_up=None, scales=None, biases=None, scales_up=None, biases_up=None,
+                   bias=None, norm_w=None, ss_in=None, norm_dim=0, norm_eps=1e-6, ss_out=None, act_silu=0, resid=0, nt_weights=0,
+                   y_tiled=0, N=None, rider=None, mode=0):
+        """One launch of the decode GEMM on these host buffers (q3tts_debug_gemm); bf16 operands as uint16 bit patterns.
+        x [16 * xMB][K]; W [N][K] bf16, or uint32 [N][K / 8] with scales / biases [N][K / 64] (int4); epi 2: W the gate and W_up
+        the up matrix; y [16 * yMB][y_cols] and ss_out [N / 16][ss_ld] as the caller filled them (copied, returned as the launch
+        left them); ss_in [ss_count][ss_ld]. N defaults to W's rows. rider: dict(h [16 * MB][H], w [H], out like h, M, eps,
+        ss_in [count][16 * MB] or None, ss_out [16 * MB] or None); mode 1 runs launch_norm_rows alone on it.
+        Returns a dict: y, ss_out, rider_out, rider_ss_out (those that apply) and the geometry fields (_lib.GEOM_FIELDS)."""
+        u16 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint16)
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+        ptr = lambda v, t: None if v is None else v.ctypes.data_as(t)
+        a = L.GemmDebug(mode=mode)
+        keep = []
+        if mode == 0:
+            quant = scales is not None
+            x, y = u16(x), u16(y).copy()
+            Wg = np.ascontiguousarray(W, np.uint32 if quant else np.uint16)
+            Wu = None if W_up is None else np.ascontiguousarray(W_up, np.uint32 if quant else np.uint16)
+            K = x.shape[1]
+            N = Wg.shape[0] if N is None else N
+            if Wg.shape != (N, K // 8 if quant else K) or (Wu is not None and Wu.shape != Wg.shape) or x.shape[0] % 16 or y.shape[0] % 16:
+                raise ValueError("debug_gemm: operand shape")
+            sc, bi, scu, biu, bias, norm_w = u16(scales), u16(biases), u16(scales_up), u16(biases_up), u16(bias), u16(norm_w)
+            for v in (sc, bi, scu, biu):
+                if v is not None and v.shape != (N, K // 64):
+                    raise ValueError("debug_gemm: scales / biases shape")
+            ss_in, ss_out = f32(ss_in), (None if ss_out is None else f32(ss_out).copy())
+            ss_ld = ss_in.shape[1] if ss_in is not None else (ss_out.shape[1] if ss_out is not None else y.shape[0])
+            if (bias is not None and bias.shape != (N,)) or (norm_w is not None and norm_w.shape != (K,)) or \
+                    (ss_out is not None and ss_out.shape != (N // 16, ss_ld)) or (ss_in is not None and ss_in.ndim != 2):
+                raise ValueError("debug_gemm: per-column / per-row operand shape")
+            a.M, a.K, a.N, a.xMB, a.yMB, a.ss_ld, a.y_cols = M, K, N, x.shape[0] // 16, y.shape[0] // 16, ss_ld, y.shape[1]
+            a.epi, a.act_silu, a.resid, a.nt_weights, a.y_tiled = epi, act_silu, resid, nt_weights, y_tiled
+            a.norm, a.quant, a.has_bias = int(norm_w is not None), int(quant), int(bias is not None)
+            a.ss_count, a.norm_dim, a.norm_eps = (ss_in.shape[0] if ss_in is not None else 0), norm_dim, norm_eps
+            a.x, a.W, a.scales, a.biases = ptr(x, L.u16p), Wg.ctypes.data_as(C.c_void_p), ptr(sc, L.u16p), ptr(bi, L.u16p)
+            a.W_up = None if Wu is None else Wu.ctypes.data_as(C.c_void_p)
+            a.scales_up, a.biases_up, a.bias, a.norm_w = ptr(scu, L.u16p), ptr(biu, L.u16p), ptr(bias, L.u16p), ptr(norm_w, L.u16p)
+            a.ss_in, a.y, a.ss_out = ptr(ss_in, L.f32p), ptr(y, L.u16p), ptr(ss_out, L.f32p)
+            keep += [x, y, Wg, Wu, sc, bi, scu, biu, bias, norm_w, ss_in, ss_out]
+        r_out = r_sso = None
+        if rider is not None:
+            rh, rw, r_out = u16(rider["h"]), u16(rider["w"]), u16(rider["out"]).copy()
+            r_ssi = f32(rider.get("ss_in"))
+            r_sso = None if rider.get("ss_out") is None else f32(rider["ss_out"]).copy()
+            H = rh.shape[1]
+            if rh.shape[0] % 16 or r_out.shape != rh.shape or rw.shape != (H,) or (r_ssi is not None and r_ssi.shape[1:] != (rh.shape[0],)) \
+                    or (r_sso is not None and r_sso.shape != (rh.shape[0],)):
+                raise ValueError("debug_gemm: rider shape")
+            a.rider_M, a.rider_H, a.rider_MB, a.rider_eps = rider["M"], H, rh.shape[0] // 16, rider.get("eps", 1e-6)
+            a.rider_ss_count = r_ssi.shape[0] if r_ssi is not None else 0
+            a.rider_h, a.rider_w, a.rider_ss_in = ptr(rh, L.u16p), ptr(rw, L.u16p), ptr(r_ssi, L.f32p)
+            a.rider_out, a.rider_ss_out = ptr(r_out, L.u16p), ptr(r_sso, L.f32p)
+            keep += [rh, rw, r_ssi]
+        self._check(self._lib.q3tts_debug_gemm(self._h, C.byref(a)))
+        del keep
+        res = {f: int(getattr(a, f)) for f in L.GEOM_FIELDS}
+        res.update(y=y if mode == 0 else None, ss_out=ss_out if mode == 0 else None, rider_out=r_out, rider_ss_out=r_sso)
+        return res
+
     def debug_codec_stage(self, codes: np.ndarray, stage: str) -> np.ndarray:
         codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
         F = codes.shape[0]

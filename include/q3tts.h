@@ -750,6 +750,73 @@ typedef struct {
 } q3tts_gemm_debug;
 q3tts_status q3tts_debug_gemm(q3tts_model* m, q3tts_gemm_debug* a);
 
+/* One launch of a codec-decoder convolution (csrc/kernels/codec_conv.hip, codec_conv_h1.hip, the out-convs of codec_misc.hip and
+ * codec_conv_h1.hip) on caller-supplied host buffers, through the product's own launcher, so that the launcher's dispatch picks
+ * the kernel instantiation exactly as a decode would. kind:
+ *   0  launch_conv_gemm      split == 0: conv_gemm_kernel (fp32 MFMA); split != 0: the two fp16 planes and row scales are attached
+ *                            (conv_gemm_h2_kernel, its prologue form, or conv_pw_h2_kernel for K == 1 without a prologue)
+ *   1  launch_resunit        out = x + conv2(act2(conv1(act1(x)))); Cin == N == C, ldx == ldo == C; w conv1 [C][K][C], w2 conv2 [C][C],
+ *                            bias / bias2, snake_* = act1, act2_*, post_* [C] for out2
+ *   2  launch_conv_gemm_h1   float16 tensors as uint16 bit patterns (x fp32 with x_f32); w, bias hold float16-exact values
+ *   3  launch_resunit_h1     kind 1 on float16 tensors (K == 7, C == 96)
+ *   4  launch_out_conv       SnakeBeta(snake_*) -> k7 conv Cin -> 1 (w [7][Cin], bias [1]) -> clip: pcm [B][Tmax], nonfinite [B] or NULL
+ *   5  launch_out_conv_h1    kind 4 on a float16 tensor (bias optional)
+ * Everything ConvGemmArgs, ResUnitArgs, ConvH1Args and ResUnitH1Args (csrc/codec_kernels.h) express can be stated. The weights
+ * are handed over as a checkpoint holds them -- fp32 [N][K][Cin] -- and SnakeBeta as raw alpha / beta; the call packs them with
+ * the loader's own code (csrc/model.cc pack_conv_h2, pack_conv_h2_perm, pack_conv_h1, pack_conv_h1_perm, snake_params,
+ * snake_params_f16). It allocates its own device buffers and frees them; it touches neither the model's weights nor its caches.
+ * Buffers, as a streamed decode lays them out: every activation is [B][Tmax][ld] where Tmax counts the ALLOCATION's rows; row 0 of
+ * a sequence sits `margin` >= hist rows in (the last `hist` rows in front of it are what a causal conv reads as the previous
+ * chunk's last rows; rows in front of those must not be read), batch entry b has frames[b] * ppf valid positions and
+ * margin + frames[b] * ppf <= Tmax. pcm [B][Tmax] is indexed like the rows. x, x2 ([Tmax][ldx2], B == 1)
+ * and res are uploaded whole; out, out2, pcm and nonfinite are uploaded as the caller filled them and returned whole, so that a
+ * sentinel shows what was and was not written. res_is_out != 0: the residual is read from out's device buffer (res is ignored).
+ * Every argument is checked on the host (INVALID_INPUT) before anything is launched: the launchers' own conditions
+ * ((K - 1) * dil <= 56; Cin, N, ldx, ldo, ldr, ldx2 multiples of 4, for kinds 2 / 3 Cin and ldx of 8; x2 only with B == 1;
+ * out2 with post_alpha, post_beta and post_C > 0, a multiple of 4 dividing N; kind 2: K in {1, 2, 7}, x_f32 only with K == 7 and
+ * a 128-wide tile; kinds 1 / 3: the fused units' supported (C, K, dil) and out != x), ld >= channels, act in 0..5, pre_act in
+ * 0..1, 0 <= shift <= (K - 1) * dil, prologue fields only with kind 0, reflect only where every mirrored index stays inside
+ * [0, T) for every row, and the sizes above.
+ * geometry_only != 0: nothing is allocated or launched and no buffer is read (pointers only say which operands take part); the
+ * geometry outputs are filled from the code the launchers switch on (ConvDispatch). Works without a GPU and with m == NULL. */
+typedef struct {
+    int32_t kind, geometry_only, split;
+    int32_t B, Tmax, ppf, hist, margin;
+    int32_t Cin, N, K, dil;
+    int32_t ldx, ldo, ldr, ldx2;
+    int32_t act, pre_act, shift, reflect, post_C;
+    int32_t x_f32, res_is_out;
+    /* outputs: the launch (csrc/codec_kernels.h ConvDispatch) */
+    int32_t family;                  /* 0 conv_gemm_kernel, 1 conv_gemm_h2_kernel, 2 conv_pw_h2_kernel, 3 resunit_h2_kernel,
+                                        4 conv_gemm_h1_kernel, 5 resunit_h1_kernel, 6 out_conv_kernel, 7 out_conv_h1_kernel */
+    int32_t BN;                      /* output channels per workgroup */
+    int32_t pro, pw_depth, KT, X32, CT2, PT, wdb;  /* the template arguments that apply to the family, else 0 */
+    int32_t grid_x, grid_y, grid_z;
+    int64_t lds_bytes;               /* dynamic LDS */
+    /* inputs */
+    const int32_t* frames;           /* [B] */
+    const void* x;
+    const float* x2;
+    const float* w;
+    const float* w2;
+    const float* bias;
+    const float* bias2;
+    const float* scale;              /* kind 0: [N] */
+    const float* snake_alpha;        /* [Cin]: the prologue (kind 0), act1 (1, 3), the out-conv's SnakeBeta (4, 5) */
+    const float* snake_beta;
+    const float* act2_alpha;         /* [C], kinds 1 and 3 */
+    const float* act2_beta;
+    const float* post_alpha;         /* [post_C] (kinds 1, 3: [C]) */
+    const float* post_beta;
+    const void* res;
+    /* in / out */
+    void* out;
+    void* out2;
+    float* pcm;
+    int32_t* nonfinite;
+} q3tts_conv_debug;
+q3tts_status q3tts_debug_conv(q3tts_model* m, q3tts_conv_debug* a);
+
 /* Codec decoder with intermediate activations (SpeechTokenizer.swift:754-784) for one utterance:
  * stage names: "quantizer","pre_conv","pre_transformer","upsample0","upsample1","init_conv",
  * "block0".."block3". Output is channels-last [T][C] float32; *T,*C receive the shape. */

@@ -6,6 +6,22 @@
 
 namespace q3 {
 
+// What a launcher dispatches for a set of arguments: the kernel instantiation, the grid and the dynamic LDS size. The
+// *_dispatch functions are host code and hold the launchers' argument checks; each launcher switches on its descriptor and
+// q3tts_debug_conv (q3tts.h) reports it, so a test's case table is checked against the very code that launches.
+struct ConvDispatch {
+    enum Family { F32 = 0, H2 = 1, PW_H2 = 2, RESUNIT_H2 = 3, H1 = 4, RESUNIT_H1 = 5, OUT = 6, OUT_H1 = 7 };
+    int family = 0;
+    int BN = 0;             // output channels per workgroup (fused units: C)
+    int pro = 0;            // H2: conv_gemm_h2_kernel<BN, true> (a prologue, a shift or reflect padding)
+    int pw_depth = 0;       // PW_H2: the register ring's depth D
+    int KT = 0, X32 = 0;    // H1: taps, fp32 input
+    int CT2 = 0, PT = 0;    // fused units: 16-channel tiles, 16-position tiles per wave
+    int wdb = 0;            // RESUNIT_H2: conv1's weight tiles double-buffered
+    unsigned gx = 0, gy = 0, gz = 0;  // all zero: an empty batch, nothing is launched
+    size_t lds = 0;
+};
+
 // Rows are addressed as base + b*bstride + t*ld (channels-last). Row b has frames[b]*ppf valid
 // positions; the grid covers Tmax positions and skips the rest.
 struct ConvGemmArgs {
@@ -42,6 +58,7 @@ struct ConvGemmArgs {
     int reflect;            // 1: rows outside [0,T) are mirrored (reflectPad1d, SpeakerEncoder.swift:26-40), else zero
     int hist;               // streamed decode: rows -hist .. -1 in front of x are the previous chunk's last rows (else zero padding)
 };
+ConvDispatch conv_gemm_dispatch(const ConvGemmArgs& a);
 void launch_conv_gemm(const ConvGemmArgs& a, hipStream_t st);
 
 // The MainDecoder's convs on a float16 speech tokenizer (kernels/codec_conv_h1.hip): float16 activations in HBM, one matrix-core
@@ -67,6 +84,7 @@ struct ConvH1Args {
     int ppf, Tmax, B, Cin, N, K, dil;
     int hist;              // streamed decode: rows -hist .. -1 in front of x are the previous chunk's last rows (else zero padding)
 };
+ConvDispatch conv_gemm_h1_dispatch(const ConvH1Args& a);
 void launch_conv_gemm_h1(const ConvH1Args& a, hipStream_t st);
 // DecoderResidualUnit (SpeechTokenizer.swift:430-437) on float16 tensors in one launch (kernels/codec_conv_h1.hip resunit_h1_kernel):
 // out = y + conv2(act2(conv1(act1(y)))), C = 96, conv1 seven taps. y is read once (+ halo), the sum written once.
@@ -89,6 +107,7 @@ struct ResUnitH1Args {
     int hist;             // as ConvH1Args::hist, for y
 };
 bool resunit_h1_supported(int C, int K, int dil);
+ConvDispatch resunit_h1_dispatch(const ResUnitH1Args& a);
 void launch_resunit_h1(const ResUnitH1Args& a, hipStream_t st);
 // SnakeBeta -> k7 conv C -> 1 -> clip on a float16 tensor (kernels/codec_conv_h1.hip)
 void launch_out_conv_h1(const uint16_t* x, int C, const float* ea16, const float* ib16, const float* w, const float* bias,
@@ -119,6 +138,7 @@ struct ResUnitArgs {
     int wdb;              // set by launch_resunit: conv1's weight tiles double-buffered in LDS
 };
 bool resunit_supported(int C, int K, int dil);
+ConvDispatch resunit_dispatch(const ResUnitArgs& a);  // (wdb is an output here; the launcher copies it into the arguments)
 void launch_resunit(const ResUnitArgs& a, hipStream_t st);
 
 // Split-RVQ gather (SpeechTokenizer.swift:214-226, 81-96): out[b][f] = [cb_first[c0] | sum_j cb_rest[j][c_{j+1}]]
@@ -143,6 +163,7 @@ void launch_attn_full_f32(const float* qkv, int heads, const int32_t* frames, in
 void launch_out_conv(const float* x, int C, const float* ea, const float* ib, const float* w, const float* bias,
                      const int32_t* frames, int ppf, int Tmax, int B, float* pcm, hipStream_t st, int hist = 0,
                      int32_t* nonfinite = nullptr);  // nonfinite[b] |= 1 when row b's pre-clip waveform holds an inf / NaN
+ConvDispatch out_conv_dispatch(int C, int Tmax, int B, bool h1);  // launch_out_conv's and launch_out_conv_h1's grid and LDS
 // streamed decode: rows [chunk_rows - keep_rows, chunk_rows) of every batch row move to [-keep_rows, 0) (history of the next chunk)
 void launch_roll_history(float* cur, int64_t bstride, int64_t keep_floats, int64_t chunk_floats, int B, hipStream_t st);
 // ---- slotted stream (rows of a queue at chunk phases of their own, codec.h) ----

@@ -241,6 +241,9 @@ class Engine {
     // and NormRowsArgs the launch will carry, still without pointers
     static void debug_gemm_check(q3tts_gemm_debug& d, GemmArgs& ga, NormRowsArgs& na);
     void debug_gemm(q3tts_gemm_debug& d);
+    // q3tts_debug_conv (conv_debug.cc): likewise -- the check fills the geometry outputs from the launchers' dispatch functions
+    static void debug_conv_check(q3tts_conv_debug& d);
+    void debug_conv(q3tts_conv_debug& d);
     void debug_build_decode_codes(const int32_t* refs, const int32_t* ref_T, const int32_t* gen, const int32_t* n_frames, int R,
                                   int gen_stride, int Fdec, bool misalign, int32_t* out);
     void codec_decode(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, float* pcm,

@@ -1055,12 +1055,68 @@ bool resunit_supported(int C, int K, int dil) {
     return (C == 32 || C == 64 || C == 96 || C == 192) && K >= 1 && (K - 1) * dil <= MAX_HALO;
 }
 
+// ---- dispatch: which instantiation, grid and LDS size a set of arguments gets. The launchers below switch on the descriptor
+//      and q3tts_debug_conv reports it, so that a test's case table is checked against the code that launches. Host code. ----
+ConvDispatch resunit_dispatch(const ResUnitArgs& a) {
+    Q3_CHECK(resunit_supported(a.C, a.K, a.dil) && a.out != a.y, 3, "resunit: unsupported geometry");
+    Q3_CHECK(a.w1h && a.w2ph && a.wsc1 && a.wsc2, 3, "resunit: incomplete fp16x2 weights");
+    ConvDispatch d;
+    if (a.Tmax <= 0 || a.B <= 0) return d;
+    const int bmu = a.C == 96 ? 256 : 128;  // positions per workgroup (64 PT)
+    const int rows = bmu + (a.K - 1) * a.dil;
+    d.family = ConvDispatch::RESUNIT_H2;
+    d.BN = a.C;
+    d.CT2 = a.C / 16;
+    d.PT = bmu / 64;
+    // conv1's weight tiles are double-buffered (one barrier per tap instead of two) where two workgroups still share a CU
+    d.wdb = size_t(rows + 2 * a.C) * ROWH * sizeof(uint32_t) <= 80 * 1024 ? 1 : 0;
+    d.lds = size_t(rows + (d.wdb ? 2 : 1) * a.C) * ROWH * sizeof(uint32_t);
+    d.gx = 1; d.gy = unsigned((a.Tmax + bmu - 1) / bmu); d.gz = unsigned(a.B);
+    return d;
+}
+
+constexpr int PWD = 2;  // conv_pw_h2_kernel's ring depth
+
+ConvDispatch conv_gemm_dispatch(const ConvGemmArgs& a) {
+    Q3_CHECK((a.K - 1) * a.dil <= MAX_HALO, 3, "conv_gemm: receptive field too large");
+    Q3_CHECK(!a.x2 || (a.B == 1 && a.ldx2 % 4 == 0), 3, "conv_gemm: the pre-add input is single-row only");
+    Q3_CHECK(a.Cin % 4 == 0 && a.N % 4 == 0 && a.ldx % 4 == 0 && a.ldo % 4 == 0, 3, "conv_gemm: channels must be multiples of 4");
+    // (snake_pass loads float4 at n % post_C)
+    Q3_CHECK(!a.out2 || (a.post_ea && a.post_ib && a.post_C > 0 && a.post_C % 4 == 0), 3, "conv_gemm: activated output without its parameters");
+    ConvDispatch d;
+    const int mt = (a.Tmax + BM - 1) / BM;
+    if (mt <= 0 || a.B <= 0) return d;
+    // tile width: 128 when it divides evenly, 96 for the 96/192/288-channel stages, else 64 (masked tail)
+    int BN = 64;
+    if (a.N % 128 == 0) BN = 128;
+    else if (a.N % 96 == 0) BN = 96;
+    else if (a.N > 128 && (a.N % 64) != 0) BN = 128;
+    d.BN = BN;
+    d.gx = unsigned((a.N + BN - 1) / BN); d.gy = unsigned(mt); d.gz = unsigned(a.B);
+    if (a.wh) {
+        Q3_CHECK(a.wsc != nullptr, 3, "conv_gemm: fp16x2 weights without their row scales");
+        const bool pro = a.x2 || a.pre_act || a.snake_ea || a.shift || a.reflect;
+        if (!pro && a.K == 1 && !debug_env().conv_no_pw) {  // pointwise: both tiles requested PWD steps ahead (kernel)
+            d.family = ConvDispatch::PW_H2;
+            d.pw_depth = PWD;
+            d.lds = size_t(BM + BN) * ROWH * sizeof(uint32_t);
+        } else {
+            d.family = ConvDispatch::H2;
+            d.pro = pro ? 1 : 0;
+            d.lds = size_t(BM + (a.K - 1) * a.dil + 2 * BN) * ROWH * sizeof(uint32_t);
+        }
+    } else {
+        d.family = ConvDispatch::F32;
+        d.lds = size_t(BM + (a.K - 1) * a.dil + 2 * BN) * LDS_LD * sizeof(float);
+    }
+    return d;
+}
+
 void launch_resunit(const ResUnitArgs& a0, hipStream_t st) {
     static std::once_flag attr_once[kMaxDevices];
     ResUnitArgs a = a0;
-    Q3_CHECK(resunit_supported(a.C, a.K, a.dil) && a.out != a.y, 3, "resunit: unsupported geometry");
-    Q3_CHECK(a.w1h && a.w2ph && a.wsc1 && a.wsc2, 3, "resunit: incomplete fp16x2 weights");
-    if (a.Tmax <= 0 || a.B <= 0) return;
+    const ConvDispatch d = resunit_dispatch(a);
+    if (!d.gx) return;
     // once per DEVICE (a process may hold one handle per GPU; the attribute belongs to the device's copy of the kernel) and
     // thread-safe (lanes launch from their own threads)
     std::call_once(device_once(attr_once), [] {
@@ -1068,33 +1124,21 @@ void launch_resunit(const ResUnitArgs& a0, hipStream_t st) {
         for (auto k : ks)
             Q3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     });
-    const int bmu = a.C == 96 ? 256 : 128;  // positions per workgroup (64 PT)
-    const int rows = bmu + (a.K - 1) * a.dil;
-    // conv1's weight tiles are double-buffered (one barrier per tap instead of two) where two workgroups still share a CU
-    a.wdb = size_t(rows + 2 * a.C) * ROWH * sizeof(uint32_t) <= 80 * 1024 ? 1 : 0;
-    const size_t smemh = size_t(rows + (a.wdb ? 2 : 1) * a.C) * ROWH * sizeof(uint32_t);
-    dim3 grid(1, (a.Tmax + bmu - 1) / bmu, a.B), block(256);
-    switch (a.C) {
-        case 32: hipLaunchKernelGGL((resunit_h2_kernel<2, 2>), grid, block, smemh, st, a); break;
-        case 64: hipLaunchKernelGGL((resunit_h2_kernel<4, 2>), grid, block, smemh, st, a); break;
-        case 96: hipLaunchKernelGGL((resunit_h2_kernel<6, 4>), grid, block, smemh, st, a); break;
-        default: hipLaunchKernelGGL((resunit_h2_kernel<12, 2>), grid, block, smemh, st, a); break;
+    a.wdb = d.wdb;
+    const dim3 grid(d.gx, d.gy, d.gz), block(256);
+    switch (d.CT2) {
+        case 2: hipLaunchKernelGGL((resunit_h2_kernel<2, 2>), grid, block, d.lds, st, a); break;
+        case 4: hipLaunchKernelGGL((resunit_h2_kernel<4, 2>), grid, block, d.lds, st, a); break;
+        case 6: hipLaunchKernelGGL((resunit_h2_kernel<6, 4>), grid, block, d.lds, st, a); break;
+        default: hipLaunchKernelGGL((resunit_h2_kernel<12, 2>), grid, block, d.lds, st, a); break;
     }
 }
 
 void launch_conv_gemm(const ConvGemmArgs& a, hipStream_t st) {
     static std::once_flag attr_once[kMaxDevices];
-    Q3_CHECK((a.K - 1) * a.dil <= MAX_HALO, 3, "conv_gemm: receptive field too large");
-    Q3_CHECK(!a.x2 || (a.B == 1 && a.ldx2 % 4 == 0), 3, "conv_gemm: the pre-add input is single-row only");
-    Q3_CHECK(a.Cin % 4 == 0 && a.N % 4 == 0 && a.ldx % 4 == 0 && a.ldo % 4 == 0, 3, "conv_gemm: channels must be multiples of 4");
-    const int mt = (a.Tmax + BM - 1) / BM;
-    if (mt <= 0 || a.B <= 0) return;
-    // tile width: 128 when it divides evenly, 96 for the 96/192/288-channel stages, else 64 (masked tail)
-    int BN = 64;
-    if (a.N % 128 == 0) BN = 128;
-    else if (a.N % 96 == 0) BN = 96;
-    else if (a.N > 128 && (a.N % 64) != 0) BN = 128;
-    dim3 grid((a.N + BN - 1) / BN, mt, a.B), block(256);
+    const ConvDispatch d = conv_gemm_dispatch(a);
+    if (!d.gx) return;
+    const dim3 grid(d.gx, d.gy, d.gz), block(256);
     // once per DEVICE (a process may hold one handle per GPU; the attribute belongs to the device's copy of the kernel) and
     // thread-safe (lanes launch from their own threads)
     std::call_once(device_once(attr_once), [] {  // 160 KiB of LDS per CU on gfx950; the default static cap is 64 KiB
@@ -1107,33 +1151,28 @@ void launch_conv_gemm(const ConvGemmArgs& a, hipStream_t st) {
         for (auto k : h2_kernels)
             Q3_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
     });
-    if (a.wh) {
-        Q3_CHECK(a.wsc != nullptr, 3, "conv_gemm: fp16x2 weights without their row scales");
-        const size_t smemh = size_t(BM + (a.K - 1) * a.dil + 2 * BN) * ROWH * sizeof(uint32_t);
-        const bool pro = a.x2 || a.pre_act || a.snake_ea || a.shift || a.reflect;
-        if (!pro && a.K == 1 && !debug_env().conv_no_pw) {  // pointwise: both tiles requested PWD steps ahead (kernel)
-            constexpr int PWD = 2;
-            const size_t smpw = size_t(BM + BN) * ROWH * sizeof(uint32_t);
-            switch (BN) {
-                case 128: hipLaunchKernelGGL((conv_pw_h2_kernel<128, PWD>), grid, block, smpw, st, a); break;
-                case 96: hipLaunchKernelGGL((conv_pw_h2_kernel<96, PWD>), grid, block, smpw, st, a); break;
-                default: hipLaunchKernelGGL((conv_pw_h2_kernel<64, PWD>), grid, block, smpw, st, a); break;
+    auto go = [&](void (*kern)(ConvGemmArgs)) { hipLaunchKernelGGL(kern, grid, block, d.lds, st, a); };
+    switch (d.family) {
+        case ConvDispatch::PW_H2:
+            switch (d.BN) {
+                case 128: go(&conv_pw_h2_kernel<128, PWD>); break;
+                case 96: go(&conv_pw_h2_kernel<96, PWD>); break;
+                default: go(&conv_pw_h2_kernel<64, PWD>); break;
             }
-            return;
-        }
-        auto go = [&](void (*kern)(ConvGemmArgs)) { hipLaunchKernelGGL(kern, grid, block, smemh, st, a); };
-        switch (BN) {
-            case 128: pro ? go(&conv_gemm_h2_kernel<128, true>) : go(&conv_gemm_h2_kernel<128, false>); break;
-            case 96: pro ? go(&conv_gemm_h2_kernel<96, true>) : go(&conv_gemm_h2_kernel<96, false>); break;
-            default: pro ? go(&conv_gemm_h2_kernel<64, true>) : go(&conv_gemm_h2_kernel<64, false>); break;
-        }
-        return;
-    }
-    const size_t smem = size_t(BM + (a.K - 1) * a.dil + 2 * BN) * LDS_LD * sizeof(float);
-    switch (BN) {
-        case 128: hipLaunchKernelGGL(conv_gemm_kernel<128>, grid, block, smem, st, a); break;
-        case 96: hipLaunchKernelGGL(conv_gemm_kernel<96>, grid, block, smem, st, a); break;
-        default: hipLaunchKernelGGL(conv_gemm_kernel<64>, grid, block, smem, st, a); break;
+            break;
+        case ConvDispatch::H2:
+            switch (d.BN) {
+                case 128: d.pro ? go(&conv_gemm_h2_kernel<128, true>) : go(&conv_gemm_h2_kernel<128, false>); break;
+                case 96: d.pro ? go(&conv_gemm_h2_kernel<96, true>) : go(&conv_gemm_h2_kernel<96, false>); break;
+                default: d.pro ? go(&conv_gemm_h2_kernel<64, true>) : go(&conv_gemm_h2_kernel<64, false>); break;
+            }
+            break;
+        default:
+            switch (d.BN) {
+                case 128: go(&conv_gemm_kernel<128>); break;
+                case 96: go(&conv_gemm_kernel<96>); break;
+                default: go(&conv_gemm_kernel<64>); break;
+            }
     }
 }
 

@@ -78,6 +78,7 @@ __device__ __forceinline__ float sin_mod_pi(float t) {
 // float16 ALU: every mul / add below IS one float16 op with one rounding (x * alpha, s * s, (1 / beta) * q, x + r); the sine is
 // taken in fp32 and rounded once. ea / ib: the float16-rounded exp(alpha) and 1 / exp(beta) (model.cc put_snake).
 __device__ __forceinline__ h2v snake_h2(h2v x, h2v ea, h2v ib) {
+#pragma clang fp contract(off)  // x + ib * q stays two ops: as one v_pk_fma_f16, (1 / beta) * q loses its rounding (four roundings, not five)
     const h2v t = x * ea;
     const f32x2v tf = __builtin_convertvector(t, f32x2v);
     const f32x2v sf = {sin_mod_pi(tf[0]), sin_mod_pi(tf[1])};
@@ -597,32 +598,45 @@ __global__ __launch_bounds__(256) void out_conv_h1_kernel(const uint16_t* x, int
 
 }  // namespace
 
-void launch_conv_gemm_h1(const ConvH1Args& a, hipStream_t st) {
+// Which instantiation, grid and LDS size these arguments get (codec_kernels.h ConvDispatch): launch_conv_gemm_h1 switches on it
+ConvDispatch conv_gemm_h1_dispatch(const ConvH1Args& a) {
     Q3_CHECK((a.K - 1) * a.dil <= MAX_HALO, 3, "conv_gemm_h1: receptive field too large");
     Q3_CHECK(a.Cin % 8 == 0 && a.N % 4 == 0 && a.ldx % 8 == 0 && a.ldo % 4 == 0, 3, "conv_gemm_h1: channel counts must be multiples of 8 / 4");
     Q3_CHECK(!a.out2 || (a.post_ea && a.post_ib && a.post_C > 0 && a.post_C % 4 == 0), 3, "conv_gemm_h1: activated output without its parameters");
+    ConvDispatch d;
     const int mt = (a.Tmax + BM - 1) / BM;
-    if (mt <= 0 || a.B <= 0) return;
+    if (mt <= 0 || a.B <= 0) return d;
     int BN = 64;
     if (a.N % 128 == 0) BN = 128;
     else if (a.N % 96 == 0) BN = 96;
     else if (a.N > 128 && (a.N % 64) != 0) BN = 128;
-    const dim3 grid((a.N + BN - 1) / BN, mt, a.B), block(256);
     // LDS: the input tile, or the SnakeBeta pass's stash (4 waves x CT x 64 uint2) + parameters, whichever is larger
     const size_t tiles = size_t(BM + (a.K - 1) * a.dil) * RH * sizeof(uint32_t);
     const size_t pass = size_t(4 * (BN / 32) * 64 + 2 * (BN / 4)) * sizeof(uint2);
-    const size_t smem = std::max(tiles, pass);
-    Q3_CHECK(smem <= 64 * 1024, 3, "conv_gemm_h1: tile does not fit the static LDS limit");
+    d.lds = std::max(tiles, pass);
+    Q3_CHECK(d.lds <= 64 * 1024, 3, "conv_gemm_h1: tile does not fit the static LDS limit");
     Q3_CHECK(a.K == 1 || a.K == 2 || a.K == 7, 3, "conv_gemm_h1: 1, 2 or 7 taps (the MainDecoder's convs)");
     Q3_CHECK(!a.x_f32 || (a.K == 7 && BN == 128), 3, "conv_gemm_h1: the fp32-input form is initConv's");
-#define Q3_H1(BNv)                                                                                              \
-    do {                                                                                                        \
-        if (a.x_f32) hipLaunchKernelGGL((conv_gemm_h1_kernel<128, 7, true>), grid, block, smem, st, a);         \
-        else if (a.K == 7) hipLaunchKernelGGL((conv_gemm_h1_kernel<BNv, 7, false>), grid, block, smem, st, a);  \
-        else if (a.K == 2) hipLaunchKernelGGL((conv_gemm_h1_kernel<BNv, 2, false>), grid, block, smem, st, a);  \
-        else hipLaunchKernelGGL((conv_gemm_h1_kernel<BNv, 1, false>), grid, block, smem, st, a);                \
+    d.family = ConvDispatch::H1;
+    d.BN = BN;
+    d.KT = a.K;
+    d.X32 = a.x_f32 ? 1 : 0;
+    d.gx = unsigned((a.N + BN - 1) / BN); d.gy = unsigned(mt); d.gz = unsigned(a.B);
+    return d;
+}
+
+void launch_conv_gemm_h1(const ConvH1Args& a, hipStream_t st) {
+    const ConvDispatch d = conv_gemm_h1_dispatch(a);
+    if (!d.gx) return;
+    const dim3 grid(d.gx, d.gy, d.gz), block(256);
+#define Q3_H1(BNv)                                                                                               \
+    do {                                                                                                         \
+        if (d.X32) hipLaunchKernelGGL((conv_gemm_h1_kernel<128, 7, true>), grid, block, d.lds, st, a);           \
+        else if (d.KT == 7) hipLaunchKernelGGL((conv_gemm_h1_kernel<BNv, 7, false>), grid, block, d.lds, st, a); \
+        else if (d.KT == 2) hipLaunchKernelGGL((conv_gemm_h1_kernel<BNv, 2, false>), grid, block, d.lds, st, a); \
+        else hipLaunchKernelGGL((conv_gemm_h1_kernel<BNv, 1, false>), grid, block, d.lds, st, a);                \
     } while (0)
-    switch (BN) {
+    switch (d.BN) {
         case 128: Q3_H1(128); break;
         case 96: Q3_H1(96); break;
         default: Q3_H1(64); break;
@@ -636,23 +650,33 @@ void launch_conv_gemm_h1(const ConvH1Args& a, hipStream_t st) {
 // kernels, four waves fetching the same ones -- not instantiated; the 192-channel units stay two launches each.
 bool resunit_h1_supported(int C, int K, int dil) { return C == 96 && K == 7 && 6 * dil <= MAX_HALO; }
 
-void launch_resunit_h1(const ResUnitH1Args& a, hipStream_t st) {
+ConvDispatch resunit_h1_dispatch(const ResUnitH1Args& a) {
     Q3_CHECK(resunit_h1_supported(a.C, 7, a.dil) && a.out != a.y, 3, "resunit_h1: unsupported geometry");
     Q3_CHECK(a.w1 && a.w2p && a.ea1 && a.ib1 && a.ea2 && a.ib2, 3, "resunit_h1: incomplete float16 weights");
     Q3_CHECK(!a.out2 || (a.post_ea && a.post_ib), 3, "resunit_h1: activated output without its parameters");
-    if (a.Tmax <= 0 || a.B <= 0) return;
+    ConvDispatch d;
+    if (a.Tmax <= 0 || a.B <= 0) return d;
     const int bmu = a.C == 96 ? 256 : 128;  // positions per workgroup (64 PT)
+    d.family = ConvDispatch::RESUNIT_H1;
+    d.BN = a.C;
+    d.CT2 = a.C / 16;
+    d.PT = bmu / 64;
     // LDS: the input tile of one chunk, or the SnakeBeta pass's stash (4 waves x 6 tiles x 64 uint2), whichever is larger
-    const size_t smem = std::max(size_t(bmu + 6 * a.dil) * RH * sizeof(uint32_t), size_t(4 * 6 * 64) * sizeof(uint2));
-    const dim3 grid(1, (a.Tmax + bmu - 1) / bmu, a.B), block(256);
-    hipLaunchKernelGGL((resunit_h1_kernel<6, 4>), grid, block, smem, st, a);
+    d.lds = std::max(size_t(bmu + 6 * a.dil) * RH * sizeof(uint32_t), size_t(4 * 6 * 64) * sizeof(uint2));
+    d.gx = 1; d.gy = unsigned((a.Tmax + bmu - 1) / bmu); d.gz = unsigned(a.B);
+    return d;
+}
+
+void launch_resunit_h1(const ResUnitH1Args& a, hipStream_t st) {
+    const ConvDispatch d = resunit_h1_dispatch(a);
+    if (!d.gx) return;
+    hipLaunchKernelGGL((resunit_h1_kernel<6, 4>), dim3(d.gx, d.gy, d.gz), dim3(256), d.lds, st, a);
 }
 
 void launch_out_conv_h1(const uint16_t* x, int C, const float* ea, const float* ib, const float* w, const float* bias,
                         const int32_t* frames, int ppf, int Tmax, int B, float* pcm, hipStream_t st, int32_t* nonfinite, int hist) {
-    const size_t smem = size_t(70 * (C + 4) + 7 * C) * sizeof(float);
-    Q3_CHECK(smem <= 64 * 1024 && C % 4 == 0 && C >= 4 && C <= 1024, 3, "out_conv_h1: unsupported channel count");
-    hipLaunchKernelGGL(out_conv_h1_kernel, dim3((Tmax + 63) / 64, B), dim3(256), smem, st, x, C, ea, ib, w, bias, frames, ppf, Tmax, pcm,
+    const ConvDispatch d = out_conv_dispatch(C, Tmax, B, true);
+    hipLaunchKernelGGL(out_conv_h1_kernel, dim3(d.gx, d.gy), dim3(256), d.lds, st, x, C, ea, ib, w, bias, frames, ppf, Tmax, pcm,
                        nonfinite, hist);
 }
 

@@ -382,11 +382,19 @@ void launch_attn_full_f32(const float* qkv, int heads, const int32_t* frames, in
     hipLaunchKernelGGL(attn_full_f32_kernel, dim3((Tmax + 63) / 64, heads, B), dim3(64), 0, st, qkv, heads, frames, Tmax,
                        out);
 }
+// grid and LDS of the two out-conv kernels (this file's and codec_conv_h1.hip's: the same tile), with the launchers' check
+ConvDispatch out_conv_dispatch(int C, int Tmax, int B, bool h1) {
+    ConvDispatch d;
+    d.family = h1 ? ConvDispatch::OUT_H1 : ConvDispatch::OUT;
+    d.lds = (size_t(70) * (C + 4) + size_t(7) * C) * sizeof(float);
+    Q3_CHECK(d.lds <= 64 * 1024 && C % 4 == 0 && C >= 4 && C <= 1024, 3, h1 ? "out_conv_h1: unsupported channel count" : "out_conv: unsupported channel count");
+    d.gx = unsigned((Tmax + 63) / 64); d.gy = unsigned(B); d.gz = 1;
+    return d;
+}
 void launch_out_conv(const float* x, int C, const float* ea, const float* ib, const float* w, const float* bias,
                      const int32_t* frames, int ppf, int Tmax, int B, float* pcm, hipStream_t st, int hist, int32_t* nonfinite) {
-    const size_t smem = (size_t(70) * (C + 4) + size_t(7) * C) * sizeof(float);
-    Q3_CHECK(smem <= 64 * 1024 && C % 4 == 0 && C >= 4 && C <= 1024, 3, "out_conv: unsupported channel count");
-    hipLaunchKernelGGL(out_conv_kernel, dim3((Tmax + 63) / 64, B), dim3(256), smem, st, x, C, ea, ib, w, bias, frames, ppf,
+    const ConvDispatch d = out_conv_dispatch(C, Tmax, B, false);
+    hipLaunchKernelGGL(out_conv_kernel, dim3(d.gx, d.gy), dim3(256), d.lds, st, x, C, ea, ib, w, bias, frames, ppf,
                        Tmax, pcm, hist, nonfinite);
 }
 

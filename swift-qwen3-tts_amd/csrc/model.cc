@@ -566,94 +566,122 @@ inline void split_h2(float w, int s, uint16_t& hi, uint16_t& lo) {
     hi = f32_to_f16_bits(ws);
     lo = f32_to_f16_bits(ws - f16_bits_to_f32(hi));
 }
-void put_row_scales(Builder& b, ConvW& c, const std::vector<int>& s, bool have) {
-    std::vector<float> sc;
-    if (have) {
-        sc.resize(size_t(c.N));
-        for (int nn = 0; nn < c.N; ++nn) sc[size_t(nn)] = std::ldexp(1.0f, -s[size_t(nn)]);
-    }
-    c.wsc = b.put<float>(sc.empty() ? nullptr : sc.data(), size_t(c.N));
-}
+}  // namespace
 
+// ---- the packers themselves: pure host functions (the Builder wrappers below upload what they fill; q3tts_debug_conv packs a
+//      caller's weights with the same code) ----
 // w [N][K][Cin] fp32 -> [K][chunks of 32 input channels][N][2 planes][32] fp16 (zero beyond Cin) + 2^-s per row
-void attach_h2(Builder& b, ConvW& c, const std::vector<float>& w) {
-    if (!b.split3) return;
+void pack_conv_h2(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& p, std::vector<float>& sc) {
     const int chunks = (c.Cin + 31) / 32;
-    const size_t n = size_t(c.K) * chunks * c.N * 64;
-    const bool have = !b.dry && b.fill && !w.empty();
-    std::vector<uint16_t> p;
-    std::vector<int> s;
-    if (have) {
-        s = row_shifts(c, w);
-        p.assign(n, 0);
-        for (int nn = 0; nn < c.N; ++nn)
-            for (int tap = 0; tap < c.K; ++tap)
-                for (int ci = 0; ci < c.Cin; ++ci) {
-                    uint16_t* d = &p[((size_t(tap) * chunks + ci / 32) * c.N + nn) * 64 + (ci % 32)];
-                    split_h2(w[(size_t(nn) * c.K + tap) * c.Cin + ci], s[size_t(nn)], d[0], d[32]);
-                }
-    }
-    c.wh = b.put<uint16_t>(p.empty() ? nullptr : p.data(), n);
-    put_row_scales(b, c, s, have);
+    const std::vector<int> s = row_shifts(c, w);
+    p.assign(size_t(c.K) * chunks * c.N * 64, 0);
+    for (int nn = 0; nn < c.N; ++nn)
+        for (int tap = 0; tap < c.K; ++tap)
+            for (int ci = 0; ci < c.Cin; ++ci) {
+                uint16_t* d = &p[((size_t(tap) * chunks + ci / 32) * c.N + nn) * 64 + (ci % 32)];
+                split_h2(w[(size_t(nn) * c.K + tap) * c.Cin + ci], s[size_t(nn)], d[0], d[32]);
+            }
+    sc.resize(size_t(c.N));
+    for (int nn = 0; nn < c.N; ++nn) sc[size_t(nn)] = std::ldexp(1.0f, -s[size_t(nn)]);
 }
 
 // conv2 of a residual unit for the fused kernel: k slot s = 8q + 4e + j of chunk m holds input channel 32m + 16e + 4q + j,
 // i.e. what lane group q of an MFMA accumulator pair (tiles 2m, 2m+1) carries in registers j of tile e; shares wsc with
-// attach_h2's copy
-void attach_h2_perm(Builder& b, ConvW& c, const std::vector<float>& w) {
-    if (!b.split3 || c.K != 1 || c.Cin % 32 != 0) return;
+// pack_conv_h2's copy
+void pack_conv_h2_perm(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& p) {
     const int chunks = c.Cin / 32;
-    const size_t n = size_t(chunks) * c.N * 64;
-    std::vector<uint16_t> p;
-    if (!b.dry && b.fill && !w.empty()) {
-        const std::vector<int> s = row_shifts(c, w);
-        p.assign(n, 0);
-        for (int nn = 0; nn < c.N; ++nn)
-            for (int m = 0; m < chunks; ++m)
-                for (int sl = 0; sl < 32; ++sl) {
-                    const int q = sl >> 3, e = (sl >> 2) & 1, j = sl & 3;
-                    const int ci = 32 * m + 16 * e + 4 * q + j;
-                    uint16_t* d = &p[(size_t(m) * c.N + nn) * 64 + sl];
-                    split_h2(w[size_t(nn) * c.Cin + ci], s[size_t(nn)], d[0], d[32]);
-                }
-    }
-    c.whp = b.put<uint16_t>(p.empty() ? nullptr : p.data(), n);
+    const std::vector<int> s = row_shifts(c, w);
+    p.assign(size_t(chunks) * c.N * 64, 0);
+    for (int nn = 0; nn < c.N; ++nn)
+        for (int m = 0; m < chunks; ++m)
+            for (int sl = 0; sl < 32; ++sl) {
+                const int q = sl >> 3, e = (sl >> 2) & 1, j = sl & 3;
+                const int ci = 32 * m + 16 * e + 4 * q + j;
+                uint16_t* d = &p[(size_t(m) * c.N + nn) * 64 + sl];
+                split_h2(w[size_t(nn) * c.Cin + ci], s[size_t(nn)], d[0], d[32]);
+            }
 }
 
 // float16 checkpoints: w [N][K][Cin] (float16-exact values) -> [K][chunks of 32 input channels][N][32] fp16, zero beyond Cin
 // (codec_conv_h1.hip conv_gemm_h1_kernel: one matrix-core product per block, no row scaling -- the values ARE float16)
-void attach_h1(Builder& b, ConvW& c, const std::vector<float>& w) {
-    if (!b.h1) return;
+void pack_conv_h1(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& p) {
     const int chunks = (c.Cin + 31) / 32;
-    const size_t n = size_t(c.K) * chunks * c.N * 32;
-    std::vector<uint16_t> p;
-    if (!b.dry && b.fill && !w.empty()) {
-        p.assign(n, 0);
-        for (int nn = 0; nn < c.N; ++nn)
-            for (int tap = 0; tap < c.K; ++tap)
-                for (int ci = 0; ci < c.Cin; ++ci)
-                    p[((size_t(tap) * chunks + ci / 32) * c.N + nn) * 32 + (ci % 32)] = f32_to_f16_bits(w[(size_t(nn) * c.K + tap) * c.Cin + ci]);
-    }
-    c.w1 = b.put<uint16_t>(p.empty() ? nullptr : p.data(), n);
+    p.assign(size_t(c.K) * chunks * c.N * 32, 0);
+    for (int nn = 0; nn < c.N; ++nn)
+        for (int tap = 0; tap < c.K; ++tap)
+            for (int ci = 0; ci < c.Cin; ++ci)
+                p[((size_t(tap) * chunks + ci / 32) * c.N + nn) * 32 + (ci % 32)] = f32_to_f16_bits(w[(size_t(nn) * c.K + tap) * c.Cin + ci]);
 }
 
 // conv2 of a residual unit for the fused float16 kernel (codec_conv_h1.hip resunit_h1_kernel): k slot s = 8q + 4e + j of chunk m
 // holds input channel 32m + 16e + 4q + j -- what lane group q of an accumulator pair (tiles 2m, 2m + 1) carries in registers j of
-// tile e (the order of attach_h2_perm)
+// tile e (the order of pack_conv_h2_perm)
+void pack_conv_h1_perm(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& p) {
+    const int chunks = c.Cin / 32;
+    p.assign(size_t(chunks) * c.N * 32, 0);
+    for (int nn = 0; nn < c.N; ++nn)
+        for (int m = 0; m < chunks; ++m)
+            for (int sl = 0; sl < 32; ++sl) {
+                const int q = sl >> 3, e = (sl >> 2) & 1, j = sl & 3;
+                p[(size_t(m) * c.N + nn) * 32 + sl] = f32_to_f16_bits(w[size_t(nn) * c.Cin + 32 * m + 16 * e + 4 * q + j]);
+            }
+}
+
+// SnakeBeta's parameters as the kernels take them (SpeechTokenizer.swift:246-253): exp(alpha), 1 / (exp(beta) + 1e-9)
+void snake_params(const std::vector<float>& al, const std::vector<float>& be, std::vector<float>& ea, std::vector<float>& ib) {
+    ea.resize(al.size());
+    ib.resize(be.size());
+    for (size_t i = 0; i < al.size(); ++i) {
+        ea[i] = expf(al[i]);
+        ib[i] = 1.0f / (expf(be[i]) + 1e-9f);
+    }
+}
+// the same parameters the way MLX forms them on float16 arrays (SpeechTokenizer.swift:247-248, 252): exp(alpha) and
+// exp(beta) rounded to float16, + eps (a Float 1e-9 is 0 in float16), 1 / . rounded again (codec_conv_h1.hip snake_h)
+void snake_params_f16(const std::vector<float>& al, const std::vector<float>& be, std::vector<float>& ea16, std::vector<float>& ib16) {
+    auto r16 = [](float v) { return f16_bits_to_f32(f32_to_f16_bits(v)); };
+    ea16.resize(al.size());
+    ib16.resize(be.size());
+    for (size_t i = 0; i < al.size(); ++i) {
+        ea16[i] = r16(expf(r16(al[i])));
+        ib16[i] = r16(1.0f / r16(expf(r16(be[i]))));
+    }
+}
+
+namespace {
+
+void attach_h2(Builder& b, ConvW& c, const std::vector<float>& w) {
+    if (!b.split3) return;
+    const int chunks = (c.Cin + 31) / 32;
+    const size_t n = size_t(c.K) * chunks * c.N * 64;
+    std::vector<uint16_t> p;
+    std::vector<float> sc;
+    if (!b.dry && b.fill && !w.empty()) pack_conv_h2(c, w, p, sc);
+    c.wh = b.put<uint16_t>(p.empty() ? nullptr : p.data(), n);
+    c.wsc = b.put<float>(sc.empty() ? nullptr : sc.data(), size_t(c.N));
+}
+
+void attach_h2_perm(Builder& b, ConvW& c, const std::vector<float>& w) {
+    if (!b.split3 || c.K != 1 || c.Cin % 32 != 0) return;
+    const size_t n = size_t(c.Cin / 32) * c.N * 64;
+    std::vector<uint16_t> p;
+    if (!b.dry && b.fill && !w.empty()) pack_conv_h2_perm(c, w, p);
+    c.whp = b.put<uint16_t>(p.empty() ? nullptr : p.data(), n);
+}
+
+void attach_h1(Builder& b, ConvW& c, const std::vector<float>& w) {
+    if (!b.h1) return;
+    const size_t n = size_t(c.K) * ((c.Cin + 31) / 32) * c.N * 32;
+    std::vector<uint16_t> p;
+    if (!b.dry && b.fill && !w.empty()) pack_conv_h1(c, w, p);
+    c.w1 = b.put<uint16_t>(p.empty() ? nullptr : p.data(), n);
+}
+
 void attach_h1_perm(Builder& b, ConvW& c, const std::vector<float>& w) {
     if (!b.h1 || c.K != 1 || c.Cin % 32 != 0) return;
-    const int chunks = c.Cin / 32;
-    const size_t n = size_t(chunks) * c.N * 32;
+    const size_t n = size_t(c.Cin / 32) * c.N * 32;
     std::vector<uint16_t> p;
-    if (!b.dry && b.fill && !w.empty()) {
-        p.assign(n, 0);
-        for (int nn = 0; nn < c.N; ++nn)
-            for (int m = 0; m < chunks; ++m)
-                for (int sl = 0; sl < 32; ++sl) {
-                    const int q = sl >> 3, e = (sl >> 2) & 1, j = sl & 3;
-                    p[(size_t(m) * c.N + nn) * 32 + sl] = f32_to_f16_bits(w[size_t(nn) * c.Cin + 32 * m + 16 * e + 4 * q + j]);
-                }
-    }
+    if (!b.dry && b.fill && !w.empty()) pack_conv_h1_perm(c, w, p);
     c.w1p = b.put<uint16_t>(p.empty() ? nullptr : p.data(), n);
 }
 
@@ -750,27 +778,14 @@ SnakeW put_snake(Builder& b, const TMap& t, const std::string& name) {
     HostTensor ea, ib;
     ea.shape = al.shape;
     ib.shape = be.shape;
-    if (!al.data.empty()) {
-        ea.data.resize(al.data.size());
-        ib.data.resize(be.data.size());
-        for (size_t i = 0; i < al.data.size(); ++i) {  // SnakeBeta, SpeechTokenizer.swift:246-253
-            ea.data[i] = expf(al.data[i]);
-            ib.data[i] = 1.0f / (expf(be.data[i]) + 1e-9f);
-        }
-    }
+    if (!al.data.empty()) snake_params(al.data, be.data, ea.data, ib.data);
     SnakeW s;
     s.C = int(al.shape[0]);
     s.ea = b.put_f32(ea);
     s.ib = b.put_f32(ib);
     if (b.h1) {
-        // the same parameters the way MLX forms them on float16 arrays (SpeechTokenizer.swift:247-248, 252): exp(alpha) and
-        // exp(beta) rounded to float16, + eps (a Float 1e-9 is 0 in float16), 1 / . rounded again (codec_conv_h1.hip snake_h)
-        auto r16 = [](float v) { return f16_bits_to_f32(f32_to_f16_bits(v)); };
-        HostTensor ea16 = ea, ib16 = ib;
-        for (size_t i = 0; i < ea16.data.size(); ++i) {
-            ea16.data[i] = r16(expf(r16(al.data[i])));
-            ib16.data[i] = r16(1.0f / r16(expf(r16(be.data[i]))));
-        }
+        HostTensor ea16 = ea, ib16 = ib;  // (shapes; empty when the weights arrive by broadcast)
+        if (!al.data.empty()) snake_params_f16(al.data, be.data, ea16.data, ib16.data);
         s.ea16 = b.put_f32(ea16);
         s.ib16 = b.put_f32(ib16);
     }

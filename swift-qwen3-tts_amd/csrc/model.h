@@ -67,6 +67,15 @@ struct SnakeW {
     int C = 0;
 };
 
+// The loader's packers as pure host functions (model.cc; only N, K and Cin of `c` are read). The loader uploads what they fill;
+// q3tts_debug_conv packs a caller's weights with them, so that no layout is stated twice.
+void pack_conv_h2(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& planes, std::vector<float>& wsc);  // ConvW::wh, wsc
+void pack_conv_h2_perm(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& planes);                     // ConvW::whp
+void pack_conv_h1(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& tiles);                           // ConvW::w1
+void pack_conv_h1_perm(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& tiles);                      // ConvW::w1p
+void snake_params(const std::vector<float>& alpha, const std::vector<float>& beta, std::vector<float>& ea, std::vector<float>& ib);
+void snake_params_f16(const std::vector<float>& alpha, const std::vector<float>& beta, std::vector<float>& ea16, std::vector<float>& ib16);
+
 struct CodecW {
     // RVQ (SpeechTokenizer.swift:175-227): codebooks [size][inner], output projections fused
     const float* cb_first = nullptr;               // [semantic_size][inner]

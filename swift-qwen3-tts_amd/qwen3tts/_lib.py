@@ -131,6 +131,22 @@ class GemmDebug(C.Structure):  # q3tts_gemm_debug
                 ("y", u16p), ("ss_out", f32p), ("rider_out", u16p), ("rider_ss_out", f32p)]
 
 
+class ConvDebug(C.Structure):  # q3tts_conv_debug
+    _fields_ = [("kind", C.c_int32), ("geometry_only", C.c_int32), ("split", C.c_int32),
+                ("B", C.c_int32), ("Tmax", C.c_int32), ("ppf", C.c_int32), ("hist", C.c_int32), ("margin", C.c_int32),
+                ("Cin", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("dil", C.c_int32),
+                ("ldx", C.c_int32), ("ldo", C.c_int32), ("ldr", C.c_int32), ("ldx2", C.c_int32),
+                ("act", C.c_int32), ("pre_act", C.c_int32), ("shift", C.c_int32), ("reflect", C.c_int32), ("post_C", C.c_int32),
+                ("x_f32", C.c_int32), ("res_is_out", C.c_int32),
+                ("family", C.c_int32), ("BN", C.c_int32), ("pro", C.c_int32), ("pw_depth", C.c_int32), ("KT", C.c_int32),
+                ("X32", C.c_int32), ("CT2", C.c_int32), ("PT", C.c_int32), ("wdb", C.c_int32),
+                ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32), ("lds_bytes", C.c_int64),
+                ("frames", i32p), ("x", C.c_void_p), ("x2", f32p), ("w", f32p), ("w2", f32p), ("bias", f32p), ("bias2", f32p),
+                ("scale", f32p), ("snake_alpha", f32p), ("snake_beta", f32p), ("act2_alpha", f32p), ("act2_beta", f32p),
+                ("post_alpha", f32p), ("post_beta", f32p), ("res", C.c_void_p),
+                ("out", C.c_void_p), ("out2", C.c_void_p), ("pcm", f32p), ("nonfinite", i32p)]
+
+
 _lib = None
 
 
@@ -223,6 +239,8 @@ def lib() -> C.CDLL:
     L.q3tts_debug_attention.argtypes = [vp, C.POINTER(AttnDebug)]
     if hasattr(L, "q3tts_debug_gemm"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_gemm.argtypes = [vp, C.POINTER(GemmDebug)]
+    if hasattr(L, "q3tts_debug_conv"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_debug_conv.argtypes = [vp, C.POINTER(ConvDebug)]
     if hasattr(L, "q3tts_debug_build_decode_codes"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_build_decode_codes.argtypes = [vp, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
     L.q3tts_debug_codec_stage.argtypes = [vp, i32p, C.c_int32, C.c_char_p, f32p, C.c_int64, i32p, i32p]
@@ -242,6 +260,41 @@ def gemm_geometry(**kw) -> dict:
     if st != 0:
         raise ValueError("q3tts_debug_gemm refused the arguments (status %d): %r" % (st, kw))
     return {f: int(getattr(a, f)) for f in GEOM_FIELDS}
+
+
+CONV_GEOM_FIELDS = ("family", "BN", "pro", "pw_depth", "KT", "X32", "CT2", "PT", "wdb", "grid_x", "grid_y", "grid_z", "lds_bytes")
+CONV_OPERANDS = ("x2", "bias", "bias2", "scale", "snake", "act2", "post", "res", "out", "out2", "w2", "pcm", "nonfinite")
+
+
+def conv_geometry(frames=None, **kw) -> dict:
+    """q3tts_debug_conv with geometry_only = 1: the launch the conv launchers' dispatch functions choose (ConvDebug's scalar fields
+    as keywords; the names of CONV_OPERANDS as truthy keywords say which optional operands take part; frames: the rows' frame
+    counts, checked when given). Host code only: needs neither a model nor a GPU. Raises ValueError on INVALID_INPUT."""
+    ops = {k: kw.pop(k, False) for k in CONV_OPERANDS}
+    a = ConvDebug(geometry_only=1, **kw)
+    one = (C.c_float * 4)()
+    fp = C.cast(one, f32p)
+    a.w = fp
+    for name in ("x2", "bias", "bias2", "scale", "w2", "pcm"):
+        if ops[name]:
+            setattr(a, name, fp)
+    for name in ("snake", "act2", "post"):
+        if ops[name]:
+            setattr(a, name + "_alpha", fp)
+            setattr(a, name + "_beta", fp)
+    for name in ("res", "out", "out2"):
+        if ops[name]:
+            setattr(a, name, C.cast(one, C.c_void_p))
+    if ops["nonfinite"]:
+        a.nonfinite = C.cast(one, i32p)
+    fr = None
+    if frames is not None:
+        fr = (C.c_int32 * len(frames))(*frames)
+        a.frames = C.cast(fr, i32p)
+    st = lib().q3tts_debug_conv(None, C.byref(a))
+    if st != 0:
+        raise ValueError("q3tts_debug_conv refused the arguments (status %d): %r" % (st, kw))
+    return {f: int(getattr(a, f)) for f in CONV_GEOM_FIELDS}
 
 
 def reload_debug_env() -> None:

@@ -835,6 +835,63 @@ class Qwen3TTSModel:
         res.update(y=y if mode == 0 else None, ss_out=ss_out if mode == 0 else None, rider_out=r_out, rider_ss_out=r_sso)
         return res
 
+    def debug_conv(self, kind, *, frames, x, w, K, dil=1, ppf=1, hist=0, margin=None, split=0, Cin=None, N=None, w2=None, bias=None, bias2=None,
+                   scale=None, snake=None, act2=None, post=None, post_C=0, res=None, res_is_out=0, out=None, out2=None, x2=None,
+                   act=0, pre_act=0, shift=0, reflect=0, x_f32=0, pcm=None, nonfinite=None):
+        """One launch of a codec conv launcher on these host buffers (q3tts_debug_conv; kind as in q3tts.h). x [B][Tmax][ldx]
+        (float32, or float16 bit patterns as uint16 for kinds 2 / 3 / 5 without x_f32), Tmax = the allocation's rows with the
+        sequences `margin` (default hist) rows in; w float32 [N][K][Cin]; snake / act2 / post: (alpha, beta) pairs of raw SnakeBeta parameters;
+        out / out2 [B][Tmax][ldo], pcm [B][Tmax] and nonfinite [B] as the caller filled them (copied, returned as the launch left
+        them). Cin / N default to w's shape. Returns a dict: out, out2, pcm, nonfinite (those given) and _lib.CONV_GEOM_FIELDS."""
+        f32 = lambda v: None if v is None else np.ascontiguousarray(v, np.float32)
+        h1 = kind in (2, 3, 5)
+        act_t = lambda v, f=False: None if v is None else np.ascontiguousarray(v, np.float32 if (f or not h1) else np.uint16)
+        ptr = lambda v, t=L.f32p: None if v is None else v.ctypes.data_as(t)
+        x, w, w2, bias, bias2, scale, x2 = act_t(x, bool(x_f32)), f32(w), f32(w2), f32(bias), f32(bias2), f32(scale), f32(x2)
+        res = act_t(res)
+        out, out2 = (None if out is None else act_t(out).copy()), (None if out2 is None else act_t(out2).copy())
+        pcm = None if pcm is None else f32(pcm).copy()
+        nonfinite = None if nonfinite is None else np.ascontiguousarray(nonfinite, np.int32).copy()
+        frames = np.ascontiguousarray(frames, np.int32)
+        if x.ndim != 3 or x.shape[0] != frames.shape[0] or w.ndim != 3 or w.shape[1] != K:
+            raise ValueError("debug_conv: operand shape")
+        B, Tmax, ldx = x.shape
+        Cin = w.shape[2] if Cin is None else Cin
+        N = w.shape[0] if N is None else N
+        for v in (out, out2, res):
+            if v is not None and (v.ndim != 3 or v.shape[:2] != (B, Tmax)):
+                raise ValueError("debug_conv: out / out2 / res shape")
+        if (out is not None and out2 is not None and out.shape != out2.shape) or (x2 is not None and (x2.ndim != 2 or x2.shape[0] != Tmax)) or \
+                (pcm is not None and pcm.shape != (B, Tmax)) or (nonfinite is not None and nonfinite.shape != (B,)) or \
+                (w2 is not None and w2.shape != (N, N)) or w.shape != (1 if kind >= 4 else N, K, Cin):
+            raise ValueError("debug_conv: operand shape")
+        pairs = []
+        for pr, n in ((snake, Cin), (act2, N), (post, N if kind in (1, 3) else post_C)):
+            if pr is None:
+                pairs += [None, None]
+                continue
+            al, be = f32(pr[0]), f32(pr[1])
+            if al.shape != (n,) or be.shape != (n,):
+                raise ValueError("debug_conv: SnakeBeta parameter shape")
+            pairs += [al, be]
+        for v, n in ((bias, 1 if kind >= 4 else N), (bias2, N), (scale, N)):
+            if v is not None and v.shape != (n,):
+                raise ValueError("debug_conv: per-channel operand shape")
+        o = out if out is not None else out2
+        a = L.ConvDebug(kind=kind, split=split, B=B, Tmax=Tmax, ppf=ppf, hist=hist, margin=hist if margin is None else margin, Cin=Cin, N=N, K=K, dil=dil, ldx=ldx,
+                        ldo=0 if o is None else o.shape[2], ldr=(o.shape[2] if res_is_out else (0 if res is None else res.shape[2])),
+                        ldx2=0 if x2 is None else x2.shape[1], act=act, pre_act=pre_act, shift=shift, reflect=reflect, post_C=post_C,
+                        x_f32=x_f32, res_is_out=res_is_out)
+        vp = C.c_void_p
+        a.frames, a.x, a.x2, a.w, a.w2 = ptr(frames, L.i32p), ptr(x, vp), ptr(x2), ptr(w), ptr(w2)
+        a.bias, a.bias2, a.scale = ptr(bias), ptr(bias2), ptr(scale)
+        a.snake_alpha, a.snake_beta, a.act2_alpha, a.act2_beta, a.post_alpha, a.post_beta = [ptr(v) for v in pairs]
+        a.res, a.out, a.out2, a.pcm, a.nonfinite = ptr(res, vp), ptr(out, vp), ptr(out2, vp), ptr(pcm), ptr(nonfinite, L.i32p)
+        self._check(self._lib.q3tts_debug_conv(self._h, C.byref(a)))
+        r = {f: int(getattr(a, f)) for f in L.CONV_GEOM_FIELDS}
+        r.update(out=out, out2=out2, pcm=pcm, nonfinite=nonfinite)
+        return r
+
     def debug_codec_stage(self, codes: np.ndarray, stage: str) -> np.ndarray:
         codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
         F = codes.shape[0]

@@ -76,6 +76,23 @@ typedef struct {
                            time) instead of fp16 matrix cores with every fp32 operand split into two fp16 planes (same accuracy,
                            activations limited to |x| < 65504: a decode that leaves that range reports
                            Q3TTS_ERR_AUDIO_DECODING_FAILED for the row instead of a waveform). Default 0 */
+    int32_t output_sample_rate; /* new (the reference speaks 24 kHz only): the rate of every waveform this handle hands out.
+                           0 (default) or 24000: the decoder's own rate -- nothing is added, the samples are what a handle
+                           loaded without this field gives, bit for bit. 8000, 12000, 16000, 22050, 32000, 44100 or 48000:
+                           the decoder's causal tail gets one more causal stage, the polyphase FIR defined under "Sample
+                           rates" below, in its causal form, and q3tts_model_info.sample_rate / .samples_per_frame report
+                           the rate and 1920 * rate / 24000 (640, 960, 1280, 1764, 2560, 3528, 3840). Everything this header
+                           counts in samples or states as "* 1920" then counts samples at that rate with that many per
+                           frame: pcm buffers and AUDIO_CHUNK.sample_offset, the end trim count(code0 > 0) * samples_per_frame,
+                           the clone cut R * samples_per_frame. Every guarantee in this header holds unchanged at the
+                           handle's rate -- streamed equals one-shot (window < 0), queued equals alone, session equals queued,
+                           bit for bit -- because the stage carries its history from chunk to chunk like the other causal
+                           convs of the tail, and the one-shot decode uses the same causal form. The output is therefore
+                           delayed by K input samples (K: below): 2.1 ms at 8 kHz, 0.7 ms at 48 kHz. The result is clipped to
+                           [-1, 1] again (the FIR overshoots). Non-finite flags still come from the 24 kHz signal. A saved
+                           prefix state of a voice grows by the stage's margin, 3 x 1920 x 4 bytes. Per handle, not per
+                           call: every buffer behind the tail is sized at load by samples per frame. Any other value is
+                           Q3TTS_ERR_INVALID_INPUT at load */
 } q3tts_load_opts;
 
 void q3tts_default_load_opts(q3tts_load_opts* o);
@@ -95,13 +112,13 @@ q3tts_status q3tts_model_arena(q3tts_model* m, void** device_ptr, size_t* bytes)
 
 typedef struct {
     char tts_model_type[32]; /* Qwen3TTSModel.ttsModelType (Qwen3.swift:1269-1271) */
-    int32_t sample_rate;     /* .sampleRate (Qwen3.swift:1262-1264) */
+    int32_t sample_rate;     /* .sampleRate (Qwen3.swift:1262-1264): 24000, or q3tts_load_opts.output_sample_rate when set */
     int32_t supports_voice_cloning; /* .supportsVoiceCloning (Qwen3.swift:1210-1214) */
     int32_t has_voice_cloning;      /* .hasVoiceCloning (Qwen3.swift:61-63) */
     int32_t hidden_size, num_layers, vocab_size, text_vocab_size, num_code_groups;
     int32_t cp_hidden_size, cp_num_layers, cp_vocab_size;
     int32_t codec_eos_token_id;
-    int32_t samples_per_frame; /* decodeUpsampleRate, 1920 */
+    int32_t samples_per_frame; /* decodeUpsampleRate, 1920; at another output rate 1920 * sample_rate / 24000 */
     int32_t max_batch;
     int64_t weight_bytes;      /* distinct bytes streamed per decode step (roofline accounting) */
     int32_t speaker_embedding_dim; /* enc_dim of the speaker encoder, 0 when absent */
@@ -144,7 +161,8 @@ typedef struct {
     /* Voice clone -- generateVoiceClone(text:referenceAudio:referenceText:language:...) (Qwen3.swift:1009-1020).
      * ref_audio != NULL selects it; speaker / instruct_ids are then ignored, as in the reference.
      *   ref_audio     = reference waveform, 24 kHz mono float32 (host memory, read during the call; a NaN or infinite
-     *                   sample is Q3TTS_ERR_INVALID_INPUT)
+     *                   sample is Q3TTS_ERR_INVALID_INPUT). A clip at another rate goes through a voice
+     *                   (q3tts_voice_create_rate) or through q3tts_resample first: this field has no rate of its own
      *   ref_text_ids  = tokens of "<|im_start|>assistant\n{referenceText}<|im_end|>\n" (:448-449)
      * The reference's default repetition penalty on this path is 1.5 (:1017), against 1.05 for generate(): a batch that mixes
      * both gives each request its own through q3tts_sampling.per_request (Q3TTS_ROW_REPETITION_PENALTY).
@@ -274,7 +292,7 @@ typedef void (*q3tts_event_cb)(void* user, const q3tts_event* ev);
 
 typedef struct {
     q3tts_status status; /* per-request outcome (e.g. GENERATION_FAILED "No tokens generated") */
-    float* pcm;          /* 24 kHz mono float32, trimmed as Qwen3.swift:954-959; engine-owned */
+    float* pcm;          /* mono float32 at q3tts_model_info.sample_rate (24 kHz by default), trimmed as Qwen3.swift:954-959; engine-owned */
     int64_t n_samples;
     int32_t* codes;      /* [n_frames][num_code_groups]; engine-owned */
     int32_t n_frames;
@@ -406,10 +424,16 @@ q3tts_status q3tts_generate_queued(q3tts_model* m, const q3tts_request* reqs, in
 typedef struct q3tts_voice q3tts_voice;
 q3tts_status q3tts_voice_create(q3tts_model* m, const float* ref_audio, int64_t n_ref_samples, const int32_t* ref_text_ids,
                                 int32_t n_ref_text_ids, q3tts_voice** out);
+/* The same for a clip at `sample_rate` Hz (8000, 12000, 16000, 22050, 32000, 44100 or 48000; 24000 is q3tts_voice_create): the
+ * clip is uploaded at its own rate, resampled to 24 kHz on the device -- the centred form of "Sample rates" below, no delay, no
+ * clip -- and handed to the same front end. What q3tts_voice_create(q3tts_resample(clip)) gives, without the round trip.
+ * Another rate is Q3TTS_ERR_INVALID_INPUT. q3tts_voice_info.n_ref_samples counts 24 kHz samples: ceil(n * 24000 / rate). */
+q3tts_status q3tts_voice_create_rate(q3tts_model* m, const float* ref_audio, int64_t n_ref_samples, int32_t sample_rate,
+                                     const int32_t* ref_text_ids, int32_t n_ref_text_ids, q3tts_voice** out);
 void q3tts_voice_free(q3tts_model* m, q3tts_voice* v);
 typedef struct {
     int32_t ref_frames, ref_text_tokens;
-    int64_t n_ref_samples, device_bytes;
+    int64_t n_ref_samples, device_bytes; /* n_ref_samples: of the 24 kHz clip the encoders saw */
 } q3tts_voice_info;
 q3tts_status q3tts_voice_get_info(const q3tts_voice* v, q3tts_voice_info* out);
 q3tts_status q3tts_generate_voices(q3tts_model* m, const q3tts_request* reqs, const q3tts_voice* const* voices, int32_t n_reqs,
@@ -534,6 +558,29 @@ q3tts_status q3tts_session_submit_open(q3tts_session* s, const q3tts_request* re
                                        int64_t* ticket);
 q3tts_status q3tts_session_append_text(q3tts_session* s, int64_t ticket, const int32_t* ids, int32_t n, int32_t final);
 q3tts_status q3tts_session_get_text_stats(const q3tts_session* s, q3tts_session_text_stats* out);
+
+/* ---- Sample rates (new: the reference speaks and hears 24 kHz only) -----------------------------------------------------
+ * One polyphase FIR serves the output side (q3tts_load_opts.output_sample_rate) and the input side (q3tts_voice_create_rate,
+ * q3tts_resample). Supported pairs: one side is 24000, the other 8000, 12000, 16000, 22050, 32000, 44100 or 48000.
+ * For in -> out Hz: g = gcd(in, out), L = out / g, M = in / g, s = 0.945 * min(1, L / M), half width K = ceil(16 / s) input
+ * samples (17 .. 51), 2K taps per phase. Tap i (0 .. 2K-1) of phase r (0 .. L-1) belongs to k = i - K + 1 and sits at
+ * t = k - r / L:   g(t) = s * sinc(s t) * I0(8.6 * sqrt(1 - (t / K)^2)) / I0(8.6) for |t| < K, otherwise 0, with
+ * sinc(x) = sin(pi x) / (pi x); computed in double, each phase normalised to sum 1 in double, then rounded to fp32.
+ * Output sample n has q = floor(n M / L) and r = (n M) mod L:
+ *     centred: y[n] = sum_i tab[r][i] * x[q - K + 1 + i]          causal: y[n] = sum_i tab[r][i] * x[q - 2K + 1 + i]
+ * The causal form is the centred one delayed by K input samples and reads nothing beyond x[q]. Samples outside the signal are
+ * zero; the output has ceil(n_in * L / M) samples. The sum runs in fp32 with fmaf, one accumulator, i ascending: every output
+ * has one fixed arithmetic order, whatever the launch geometry. 16 zero crossings, Kaiser beta 8.6 and roll-off 0.945 are a
+ * design choice: pass-band ripple at most 0.0101 dB up to 0.40 x the lower rate, at least 71.6 dB of attenuation from 0.55 x the
+ * lower rate upward, -16 dB at exactly half the lower rate (the transition band straddles Nyquist).
+ *
+ * q3tts_resample: `in` (host, n_in >= 1 samples at in_rate) through the device kernel to `out` (host, `cap` samples of room);
+ * *n_out = ceil(n_in * L / M). centred != 0: the centred form (no delay; what a reference clip gets); 0: the causal form with
+ * nothing in front of the clip (what the decoder's output stage computes for a whole utterance, without its clip to [-1, 1]).
+ * Q3TTS_ERR_INVALID_INPUT, the engine staying usable: an unsupported pair, a NaN or infinite sample, cap < *n_out (which is
+ * still set). One engine entry point like q3tts_codec_decode: one caller per handle, refused while a session is open. */
+q3tts_status q3tts_resample(q3tts_model* m, const float* in, int64_t n_in, int32_t in_rate, int32_t out_rate, int32_t centred,
+                            float* out, int64_t cap, int64_t* n_out);
 
 /* Qwen3TTSSpeechTokenizer.decode (Models/SpeechTokenizer.swift:823-836): codes
  * [batch][max_frames][num_code_groups] -> pcm [batch][max_frames*1920] (caller-allocated),

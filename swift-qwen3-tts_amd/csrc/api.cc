@@ -127,6 +127,7 @@ void q3tts_default_load_opts(q3tts_load_opts* o) {
     o->n_streams = 0;
     o->codec_overlap_cus = 0;
     o->codec_fp32 = 0;
+    o->output_sample_rate = 0;
 }
 
 void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
@@ -158,6 +159,8 @@ q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts
         hipError_t e = hipGetDeviceCount(&ndev);
         Q3_CHECK(e == hipSuccess && ndev > 0, 7, "no HIP device available: this engine has no CPU fallback");
         Q3_CHECK(o.device >= 0 && o.device < ndev, 3, "Invalid input: device ordinal out of range");
+        Q3_CHECK(o.output_sample_rate == 0 || o.output_sample_rate == q3::kResampleNative || q3::resample_rate_supported(o.output_sample_rate), 3,
+                 "Invalid input: output_sample_rate must be 0, 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000");
         q3::LoadOptions lo;
         lo.device = o.device;
         lo.max_pos_talker = o.max_prompt + o.max_frames + 8;
@@ -226,7 +229,9 @@ q3tts_status q3tts_model_get_info(const q3tts_model* m, q3tts_model_info* out) {
         const q3::Model& md = m->eng->model();
         const q3::ModelConfig& c = md.cfg;
         std::strncpy(out->tts_model_type, c.tts_model_type.c_str(), sizeof(out->tts_model_type) - 1);
-        out->sample_rate = c.sample_rate;
+        // the handle's output side: what the codec runner hands out (q3tts_load_opts.output_sample_rate)
+        const q3::CodecRunner* cr = m->eng->codec_runner();
+        out->sample_rate = cr ? cr->output_rate() : c.sample_rate;
         // supportsVoiceCloning: base model with a codec encoder (Qwen3.swift:1210-1214); hasVoiceCloning: speaker encoder (:61-63)
         out->supports_voice_cloning = (c.tts_model_type == "base" && md.has_codec && md.has_codec_encoder) ? 1 : 0;
         out->has_voice_cloning = md.has_speaker_encoder ? 1 : 0;
@@ -240,7 +245,7 @@ q3tts_status q3tts_model_get_info(const q3tts_model* m, q3tts_model_info* out) {
         out->cp_num_layers = c.talker.cp.num_hidden_layers;
         out->cp_vocab_size = c.talker.cp.vocab_size;
         out->codec_eos_token_id = c.talker.codec_eos_token_id;
-        out->samples_per_frame = c.has_codec ? c.codec.total_upsample() : c.decode_upsample_rate;
+        out->samples_per_frame = cr ? cr->upsample() : (c.has_codec ? c.codec.total_upsample() : c.decode_upsample_rate);
         out->max_batch = m->eng->opts().max_batch;
         out->weight_bytes = md.step_weight_bytes;
     }, false);
@@ -289,6 +294,23 @@ q3tts_status q3tts_voice_create(q3tts_model* m, const float* ref_audio, int64_t 
     return guarded(m, [&] {
         Q3_CHECK(m && out, 3, "Invalid input: null argument");
         *out = reinterpret_cast<q3tts_voice*>(m->eng->create_voice(ref_audio, n_ref_samples, ref_text_ids, n_ref_text_ids));
+    });
+}
+
+q3tts_status q3tts_voice_create_rate(q3tts_model* m, const float* ref_audio, int64_t n_ref_samples, int32_t sample_rate,
+                                     const int32_t* ref_text_ids, int32_t n_ref_text_ids, q3tts_voice** out) {
+    if (out) *out = nullptr;
+    return guarded(m, [&] {
+        Q3_CHECK(m && out, 3, "Invalid input: null argument");
+        *out = reinterpret_cast<q3tts_voice*>(m->eng->create_voice(ref_audio, n_ref_samples, ref_text_ids, n_ref_text_ids, sample_rate));
+    });
+}
+
+q3tts_status q3tts_resample(q3tts_model* m, const float* in, int64_t n_in, int32_t in_rate, int32_t out_rate, int32_t centred, float* out,
+                            int64_t cap, int64_t* n_out) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && in && out && n_out, 3, "Invalid input: null argument");
+        m->eng->lane0().resample(in, n_in, in_rate, out_rate, centred != 0, out, cap, n_out);
     });
 }
 

@@ -16,8 +16,23 @@ size_t kScratchBudget = size_t(24) << 30;  // activation scratch per group of ro
 }
 void CodecRunner::set_scratch_budget(size_t bytes) { kScratchBudget = bytes ? bytes : (size_t(24) << 30); }
 
-CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs) : m_(m), st_(st) {
-    up_ = m.cfg.codec.total_upsample();
+CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate) : m_(m), st_(st) {
+    native_ = up_ = m.cfg.codec.total_upsample();
+    if (output_rate != 0 && output_rate != kResampleNative) {
+        Q3_CHECK(resample_rate_supported(output_rate), 3,
+                 "Invalid input: output_sample_rate must be 0, 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000");
+        out_plan_ = make_resample_plan(kResampleNative, output_rate);
+        Q3_CHECK((int64_t(native_) * out_plan_.L) % out_plan_.M == 0, 3,
+                 "Invalid input: the codec's frame does not hold a whole number of samples at output_sample_rate");
+        // the stage reads 2K - 1 samples back: they must lie inside the margin every streamed tail tensor carries
+        Q3_CHECK(out_plan_.taps() - 1 <= hist_frames() * native_, 7, "internal error: resampler history beyond the stream's margin");
+        up_ = int(int64_t(native_) * out_plan_.L / out_plan_.M);
+        resample_ = true;
+        const size_t n = align_up(out_plan_.tab.size(), 4);
+        std::vector<float> padded(n, 0.0f);
+        std::copy(out_plan_.tab.begin(), out_plan_.tab.end(), padded.begin());
+        Q3_HIP(hipMemcpy(out_tab_.grow(n), padded.data(), n * 4, hipMemcpyHostToDevice));
+    }
     Q3_CHECK(m.cfg.codec.head_dim == 64, 6, "codec transformer head_dim must be 64");
     const char* e = std::getenv("Q3TTS_CODEC_FP32");  // tests switch per model load without touching the load options
     fp32_mfma_ = fp32_convs || (e && e[0] == '1');
@@ -73,6 +88,7 @@ int CodecRunner::tail_context_frames() const {
         ctx += 6.0 * (1 + 3 + 9) / rate;  // three residual units, k7 with dilation 1, 3, 9
     }
     ctx += 6.0 / rate;      // outConv k7
+    if (resample_) ctx += double(out_plan_.taps() - 1) / rate;  // the causal polyphase FIR behind it: 2K - 1 samples back
     return int(ctx) + 2;
 }
 
@@ -277,7 +293,8 @@ void* CodecRunner::Stream::get(size_t frame_bytes, bool reads_back) {
 
 // Steps 5-7 (SpeechTokenizer.swift:767-781): the causal tail. In: [nb][Trows][latent] with fr[b] valid frames per row behind
 // ps.hist_frames frames of history; out: pcm [nb][Trows * upsample] (row stride Trows * upsample). Every tensor is addressed as
-// base + hist_frames * elements per frame; the one-shot decode has no margin.
+// base + hist_frames * elements per frame; the one-shot decode has no margin. With an output rate other than the decoder's
+// own, out_conv's 24 kHz signal goes to one more tail tensor and the causal polyphase FIR (resample_plan.h) writes pcm.
 template <class Mem>
 void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float* pcm) {
     const CodecW& w = m_.codec;
@@ -371,19 +388,35 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
             capture(ps, ("block" + std::to_string(i)).c_str(), y, T, Bk.Cout);
         }
         // 7. outSnake -> outConv -> clip (:687-688, :781)
+        // (a resampled decode: out_conv's own clip stays, the flags of a non-finite waveform come from it as before)
+        float* p24 = resample_ ? static_cast<float*>(mem.get(size_t(ppf) * sizeof(float), true)) : nullptr;
         launch([&] {
             const E* x = y + size_t(H) * ppf * w.out_C;
-            float* out = pcm + size_t(H) * ppf;
+            float* out = (resample_ ? p24 : pcm) + size_t(H) * ppf;
             if constexpr (f16)
                 launch_out_conv_h1(x, w.out_C, w.out_snake.ea16, w.out_snake.ib16, w.out_w, w.out_b, fr, ppf, T, nb, out, st_, nf_dev_ + ps.row0, H * ppf);
             else
                 launch_out_conv(x, w.out_C, w.out_snake.ea, w.out_snake.ib, w.out_w, w.out_b, fr, ppf, T, nb, out, st_, H * ppf, nf_dev_ + ps.row0);
         });
         mem.put(y);
+        if (resample_) {
+            // Output frame f depends on input up to the end of frame f alone (q = floor(n M / L) stays inside the frame), and
+            // the phase of a chunk's first sample is 0: the rows are addressed frame by frame like every other tensor.
+            launch([&] {
+                ResampleArgs a{};
+                a.x = p24 + size_t(H) * ppf; a.x_bstride = int64_t(T);
+                a.y = pcm + size_t(H) * up_; a.y_bstride = int64_t(Trows) * up_;
+                a.len = fr; a.len_mul = ppf; a.max_in = int64_t(Trows - H) * ppf;
+                a.tab = out_tab_; a.L = out_plan_.L; a.M = out_plan_.M; a.K = out_plan_.K;
+                a.hist = H * ppf; a.centred = 0; a.clamp = 1; a.B = nb;
+                launch_resample(a, st_);
+            });
+            mem.put(p24);
+        }
     };
     if (w.f16_main && !fp32_mfma_ && !no_h1_) main_decoder(uint16_t{});
     else main_decoder(float{});
-    Q3_CHECK(ppf == up_, 7, "internal error: codec upsampling mismatch");
+    Q3_CHECK(ppf == native_, 7, "internal error: codec upsampling mismatch");
 }
 
 int CodecRunner::decode(const int32_t* codes_dev, int code_stride_frames, const std::vector<int>& frames, float** pcm_dev,

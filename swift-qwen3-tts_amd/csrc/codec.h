@@ -1,18 +1,24 @@
-// codec.h -- neural codec decoder runner (codes -> 24 kHz PCM) on the HIP kernels in
-// kernels/codec_conv.hip and kernels/codec_misc.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
+// codec.h -- neural codec decoder runner (codes -> PCM at 24 kHz or at the handle's output rate) on the HIP kernels in
+// kernels/codec_conv.hip, kernels/codec_misc.hip and kernels/resample.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
 // (/root/reference/Sources/Qwen3TTS/Models/SpeechTokenizer.swift:754-784).
 #pragma once
 #include <string>
 #include <vector>
 
 #include "model.h"
+#include "resample_plan.h"
 #include "stream_plan.h"
 
 namespace q3 {
 
 class CodecRunner {
   public:
-    CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false);
+    // output_rate: 0 or 24000 -- the decoder's own rate, nothing is added to the tail. Another supported rate
+    // (resample_plan.h): out_conv writes the 24 kHz signal into one more tail tensor and the causal polyphase FIR behind it
+    // writes the PCM, `upsample()` samples per frame at that rate. Being one more causal conv of the tail, the stage carries
+    // its history from chunk to chunk like the others: every statement below about samples, strides and bit-identity holds
+    // with upsample() counting output samples.
+    CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false, int output_rate = 0);
     // codes_dev: [B][code_stride_frames][16] int32 on the device; rows decode frames[b] frames.
     // pcm_dev receives [B][Fmax*upsample] float32 (Fmax = max(frames)); returns Fmax.
     // If `stage` is non-empty the activation after that stage is copied to stage_out ([B][T][C]).
@@ -103,7 +109,9 @@ class CodecRunner {
     static constexpr int kQuietSlots = 8;
     bool streaming() const { return stream_.open; }
     int hist_frames() const;
-    int upsample() const { return up_; }
+    int upsample() const { return up_; }            // PCM samples per frame at the output rate
+    int native_upsample() const { return native_; }  // the decoder's own samples per frame (1920)
+    int output_rate() const { return resample_ ? out_plan_.out_rate : kResampleNative; }
     hipStream_t stream() const { return st_; }
     void set_stream(hipStream_t st) { st_ = st; }  // the caller drains the old stream first (shared scratch)
 
@@ -196,7 +204,11 @@ class CodecRunner {
     static constexpr int kMaxRows = 4096;
     const Model& m_;
     hipStream_t st_;
-    int up_ = 1920;
+    int up_ = 1920;      // samples per frame of the PCM handed out (== native_ unless an output rate was asked for)
+    int native_ = 1920;  // samples per frame behind out_conv
+    bool resample_ = false;
+    ResamplePlan out_plan_;   // 24000 -> output rate
+    DevBuf<float> out_tab_;   // its phase table on the device
     bool no_h1_ = false;      // Q3TTS_CODEC_NO_F16=1: a float16 speech tokenizer through the up-cast (fp32-equivalent) path
     bool no_fuse_ = false;    // Q3TTS_CODEC_NO_FUSE=1: residual units of the narrow blocks as two launches each
     bool fp32_mfma_ = false;  // Q3TTS_CODEC_FP32=1: contract on the fp32 matrix-core path instead of the split one

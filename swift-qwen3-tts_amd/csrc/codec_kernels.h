@@ -188,6 +188,28 @@ void launch_roll_history_rows(const RollDesc* desc, int n_desc, int64_t max_fram
 void launch_history_state_rows(const RollDesc* desc, int n_desc, int64_t max_frame_floats, int Tal, int hist, int row, int B, uint8_t* blob,
                                bool load, int32_t* nonfinite, hipStream_t st);
 
+// ---- polyphase resampler (kernels/resample.hip; the filter and its index arithmetic: resample_plan.h) ----
+// Row b's input starts at x + b * x_bstride (16-byte aligned) and has len[b] * len_mul valid samples; its ceil(n_in L / M)
+// outputs go to y + b * y_bstride. A row of length 0 touches nothing. Causal mode (centred == 0): `hist` samples exist in
+// memory in front of every row's first one (a stream's margin; 0: they are taken as zero). Centred mode reads nothing in front
+// of a row. Samples at and behind n_in are never read either way. clamp: clip the result to [-1, 1].
+struct ResampleArgs {
+    const float* x;
+    int64_t x_bstride;
+    float* y;
+    int64_t y_bstride;
+    const int32_t* len;  // device [B]
+    int len_mul;
+    const float* tab;    // device [L][2K], padded to whole float4s
+    int L, M, K;
+    int hist;
+    int centred, clamp;
+    int B;
+    int64_t max_in;      // the longest row's input samples: sizes the grid
+};
+void launch_resample(const ResampleArgs& a, hipStream_t st);
+size_t resample_lds_bytes(int L, int M, int K);
+
 // ---- voice-clone front end (kernels/voice_frontend.hip) ------------------------------------------
 // first SEANet conv: 1 -> C channels, causal k taps (SpeechTokenizerEncoder.swift:404-414). w [C][K], out [S][C]
 void launch_enc_init_conv(const float* audio, int64_t S, int B, const float* w, const float* bias, int C, int K, float* out,

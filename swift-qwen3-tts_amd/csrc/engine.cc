@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "codec.h"
+#include "codec_kernels.h"
 #include "frontend.h"
 
 namespace q3 {
@@ -101,7 +102,7 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
         Q3_HIP(hipMalloc(reinterpret_cast<void**>(&stamps_), 64 * 8));
         Q3_HIP(hipMemset(stamps_, 0, 64 * 8));
     }
-    if (m_->has_codec) codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0);
+    if (m_->has_codec) codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0, opts.output_sample_rate);
     if (m_->has_codec_encoder || m_->has_speaker_encoder) fe_ = std::make_unique<VoiceFrontEnd>(*m_, st_);
 }
 
@@ -937,9 +938,66 @@ void Engine::speaker_embedding(const float* audio, int64_t n_samples, float* out
     timing.frontend_ms = ms;
 }
 
-std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids) {
+const Engine::ResamplerDev& Engine::resampler(int in_rate, int out_rate) {
+    Q3_CHECK(resample_pair_supported(in_rate, out_rate), 3,
+             "Invalid input: unsupported sample-rate pair (one rate must be 24000, the other 8000, 12000, 16000, 22050, 32000, 44100 or 48000)");
+    for (const auto& r : resamplers_)
+        if (r->plan.in_rate == in_rate && r->plan.out_rate == out_rate) return *r;
+    auto r = std::make_unique<ResamplerDev>();
+    r->plan = make_resample_plan(in_rate, out_rate);
+    const size_t n = align_up(r->plan.tab.size(), 4);
+    std::vector<float> padded(n, 0.0f);
+    std::copy(r->plan.tab.begin(), r->plan.tab.end(), padded.begin());
+    Q3_HIP(hipMemcpy(r->tab.grow(n), padded.data(), n * 4, hipMemcpyHostToDevice));
+    resamplers_.push_back(std::move(r));
+    return *resamplers_.back();
+}
+
+const float* Engine::resample_upload(const float* audio, int64_t n, int in_rate, int out_rate, bool centred, int64_t* n_out) {
+    const ResamplerDev& r = resampler(in_rate, out_rate);
+    Q3_CHECK(audio && n > 0 && n <= (int64_t(1) << 28), 3, "Invalid input: resampling takes between 1 and 2^28 samples");
+    const int64_t no = r.plan.out_len(n);
+    const float* a = upload_audio(audio, n);
+    if (size_t(no) > rs_out_dev_.capacity()) Q3_HIP(hipStreamSynchronize(st_));  // the old buffer may still be read
+    rs_out_dev_.grow(size_t(no));
+    rs_len_dev_.grow(1);
+    const int32_t len = int32_t(n);
+    Q3_HIP(hipStreamSynchronize(st_));  // `len` is pageable stack memory, and the device word may still feed an earlier launch
+    Q3_HIP(hipMemcpy(rs_len_dev_, &len, 4, hipMemcpyHostToDevice));
+    ResampleArgs ra{};
+    ra.x = a; ra.x_bstride = 0;
+    ra.y = rs_out_dev_; ra.y_bstride = 0;
+    ra.len = rs_len_dev_; ra.len_mul = 1; ra.max_in = n;
+    ra.tab = r.tab; ra.L = r.plan.L; ra.M = r.plan.M; ra.K = r.plan.K;
+    ra.hist = 0; ra.centred = centred ? 1 : 0; ra.clamp = 0; ra.B = 1;
+    launch_resample(ra, st_);
+    *n_out = no;
+    return rs_out_dev_;
+}
+
+void Engine::resample(const float* in, int64_t n_in, int in_rate, int out_rate, bool centred, float* out, int64_t cap, int64_t* n_out) {
+    const ResamplerDev& r = resampler(in_rate, out_rate);  // (the pair is refused first, whatever else is wrong)
+    Q3_CHECK(in && out && n_out && n_in > 0, 3, "Invalid input: empty audio");
+    Q3_CHECK(n_in <= (int64_t(1) << 28), 3, "Invalid input: resampling takes between 1 and 2^28 samples");
+    const int64_t no = r.plan.out_len(n_in);
+    *n_out = no;
+    Q3_CHECK(cap >= no, 3, "Invalid input: output buffer too small for the resampled audio");
+    bool finite = true;
+    for (int64_t i = 0; i < n_in; ++i) finite = finite && (std::fabs(in[i]) <= 3.0e38f);
+    Q3_CHECK(finite, 3, "Invalid input: audio holds non-finite samples");
+    int64_t got = 0;
+    const float* y = resample_upload(in, n_in, in_rate, out_rate, centred, &got);
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy(out, y, size_t(got) * 4, hipMemcpyDeviceToHost));
+}
+
+std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids,
+                                            int sample_rate) {
     const TalkerConfig& t = m_->cfg.talker;
     const int H = t.hidden_size;
+    if (sample_rate != kResampleNative)
+        Q3_CHECK(resample_pair_supported(sample_rate, kResampleNative), 3,
+                 "Invalid input: a voice's sample_rate must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000");
     check_reference(audio, n_samples, ref_text_ids, n_ref_text_ids);
     Q3_CHECK(fe_ != nullptr, 1, "Model not initialized: Speech tokenizer encoder not available");
     Q3_CHECK(m_->codec_enc.bins <= t.vocab_size && m_->codec_enc.bins <= t.cp.vocab_size, 3,
@@ -947,6 +1005,9 @@ std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_sample
     for (int i = 0; i < n_ref_text_ids; ++i)
         Q3_CHECK(ref_text_ids[i] >= 0 && ref_text_ids[i] < t.text_vocab_size, 3, "Invalid input: reference text token id out of range");
     auto v = std::make_unique<Voice>();
+    const float* a = nullptr;
+    if (sample_rate != kResampleNative) a = resample_upload(audio, n_samples, sample_rate, kResampleNative, true, &n_samples);
+    else a = upload_audio(audio, n_samples);
     const int T = fe_->encoded_frames(n_samples);
     v->ref_T = T;
     v->n_ref_samples = n_samples;
@@ -954,7 +1015,6 @@ std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_sample
     v->codes_dev.grow(size_t(16) * T);
     v->rows_dev.grow(size_t(1 + T) * H);
     v->device_bytes = int64_t(size_t(16) * T * 4 + size_t(1 + T) * H * 2);
-    const float* a = upload_audio(audio, n_samples);
     Q3_HIP(hipEventRecord(ev_fe_[0], st_));
     fe_->encode(a, n_samples, v->codes_dev);
     if (m_->has_speaker_encoder) {  // fp32 x-vector, then the talker's storage dtype like every other prompt row (prepare_clone_rows)
@@ -3782,8 +3842,8 @@ void EngineGroup::run_lanes(int L, bool serial, F&& fn) {
         if (codes[size_t(i)]) throw Error(codes[size_t(i)], errs[size_t(i)]);
 }
 
-Voice* EngineGroup::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids) {
-    std::unique_ptr<Voice> v = lane0().create_voice(audio, n_samples, ref_text_ids, n_ref_text_ids);
+Voice* EngineGroup::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids, int sample_rate) {
+    std::unique_ptr<Voice> v = lane0().create_voice(audio, n_samples, ref_text_ids, n_ref_text_ids, sample_rate);
     timing = lanes_[0]->timing;
     v->owner = this;
     voices_.push_back(std::move(v));

@@ -19,6 +19,7 @@
 #include "../../include/q3tts.h"
 #include "kernels.h"
 #include "model.h"
+#include "resample_plan.h"
 #include "session_queue.h"
 
 namespace q3 {
@@ -261,10 +262,16 @@ class Engine {
     int encoded_frames(int64_t n_samples) const;
     void speaker_embedding(const float* audio, int64_t n_samples, float* out, int cap);
     // q3tts_voice_create: what prepare_clone_rows runs for one clip, into buffers the voice owns; synchronises before it returns
-    std::unique_ptr<Voice> create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids);
+    // sample_rate != 24000: the clip is uploaded at its own rate and resampled on the device (centred form, no clamp) in front
+    // of the encoders; Voice::n_ref_samples counts 24 kHz samples
+    std::unique_ptr<Voice> create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids,
+                                        int sample_rate = 24000);
+    // q3tts_resample: host buffers through kernels/resample.hip; one of the rates is 24000 (resample_plan.h)
+    void resample(const float* in, int64_t n_in, int in_rate, int out_rate, bool centred, float* out, int64_t cap, int64_t* n_out);
     void debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C);
 
     std::vector<std::string> speakers;  // sorted (Qwen3.swift:965-971)
+    const CodecRunner* codec_runner() const { return codec_.get(); }  // nullptr: the checkpoint has no codec decoder
 
   private:
     Model* m_;
@@ -434,6 +441,17 @@ class Engine {
     };
     std::vector<FeLane> fe_lanes_;
     const float* upload_audio(const float* audio, int64_t n);
+    // the polyphase filters this engine has been asked for, tables on the device (built on first use)
+    struct ResamplerDev {
+        ResamplePlan plan;
+        DevBuf<float> tab;
+    };
+    std::vector<std::unique_ptr<ResamplerDev>> resamplers_;
+    DevBuf<float> rs_out_dev_;
+    DevBuf<int32_t> rs_len_dev_;
+    const ResamplerDev& resampler(int in_rate, int out_rate);
+    // `audio` (host, n samples at in_rate, finite) -> device buffer of *n_out samples at out_rate, queued on st_
+    const float* resample_upload(const float* audio, int64_t n, int in_rate, int out_rate, bool centred, int64_t* n_out);
     bool prepare_clone_rows(std::vector<ResolvedRequest>& reqs);  // true: the front end ran (some row carried a waveform)
 
     void alloc_workspace();
@@ -543,12 +561,13 @@ class EngineGroup {
         return *lanes_[0];
     }
     int n_lanes() const { return int(lanes_.size()); }
+    const CodecRunner* codec_runner() const { return lanes_[0]->codec_runner(); }  // (every lane's runner has the same geometry)
     const q3tts_load_opts& opts() const { return opts_; }
     void generate(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3tts_event_cb cb, void* user,
                   q3tts_result* results, const DebugOpts* dbg, const Voice* const* voices = nullptr);
     // q3tts_voice_create / _free: the group owns its voices (whatever is still alive goes with it). A voice of another group,
     // or one already freed, is not `mine`
-    Voice* create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids);
+    Voice* create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids, int sample_rate = 24000);
     void free_voice(Voice* v);
     bool mine(const Voice* v) const;
     PrefixCache& prefix_cache() { return prefix_cache_; }

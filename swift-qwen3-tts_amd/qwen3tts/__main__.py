@@ -4,7 +4,8 @@ audio seconds / generation seconds (:303), 16-bit WAV output (:134-165), peak me
 
     python -m qwen3tts --model DIR --text "..." [--speaker NAME] [--instruct "..."] [--language auto]
                        [--temperature 0.9] [--top-k 50] [--max-tokens 2048] [--output output.wav]
-                       [--reference-audio clip.wav --reference-text "..."]
+                       [--reference-audio clip.wav --reference-text "..." [--resample-reference]]
+                       [--output-sample-rate 8000|12000|16000|22050|24000|32000|44100|48000]
 
 The model directory must hold the tokenizer files the checkpoints ship (tokenizer.json or vocab.json + merges.txt),
 as the reference's postLoadHook requires (Qwen3.swift:1456-1459)."""
@@ -30,6 +31,10 @@ def main(argv=None) -> int:
     ap.add_argument("--reference-text", default=None)
     ap.add_argument("--seed", type=int, default=0, help="new: the reference has no seed")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--output-sample-rate", type=int, default=0,
+                    help="new: rate of the written audio (0 = 24000); resampled on the device behind the decoder")
+    ap.add_argument("--resample-reference", action="store_true",
+                    help="new: resample a reference clip that is not 24 kHz on the device instead of feeding it in as it is")
     a = ap.parse_args(argv)
 
     from . import Qwen3TTSModel
@@ -51,7 +56,7 @@ def main(argv=None) -> int:
     print("Loading model...")
     t0 = time.time()
     model = Qwen3TTSModel.from_pretrained(a.model, device=a.device, max_batch=1, max_frames=min(a.max_tokens, 2048) + 8,
-                                          max_prompt=1024)
+                                          max_prompt=1024, output_sample_rate=a.output_sample_rate)
     print(f"Model loaded in {time.time() - t0:.2f}s")
     print()
     print("Generating audio...")
@@ -62,11 +67,12 @@ def main(argv=None) -> int:
             return 1
         print("Mode: Voice Cloning")
         sr, ref = read_wav(a.reference_audio)
-        if sr != 24000:
+        if sr != 24000 and not a.resample_reference:
             print(f"Warning: Reference audio is {sr}Hz, expected 24000Hz. Results may vary.")
         audio = model.generate_voice_clone(text=a.text, reference_audio=ref, reference_text=a.reference_text,
                                            language=a.language, temperature=a.temperature, top_k=a.top_k,
-                                           max_tokens=a.max_tokens, seed=a.seed)
+                                           max_tokens=a.max_tokens, seed=a.seed,
+                                           sample_rate=sr if a.resample_reference else None)
     else:
         audio = model.generate(text=a.text, speaker=a.speaker, instruct=a.instruct, language=a.language,
                                temperature=a.temperature, top_k=a.top_k, max_tokens=a.max_tokens, seed=a.seed)

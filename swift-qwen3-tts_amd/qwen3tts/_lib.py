@@ -19,7 +19,8 @@ u8p = C.POINTER(C.c_uint8)
 class LoadOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_batch", C.c_int32), ("max_frames", C.c_int32),
                 ("max_prompt", C.c_int32), ("use_graph", C.c_int32), ("weights_from_broadcast", C.c_int32),
-                ("n_streams", C.c_int32), ("codec_overlap_cus", C.c_int32), ("codec_fp32", C.c_int32)]
+                ("n_streams", C.c_int32), ("codec_overlap_cus", C.c_int32), ("codec_fp32", C.c_int32),
+                ("output_sample_rate", C.c_int32)]
 
 
 class CommId(C.Structure):  # q3tts_comm_id == ncclUniqueId
@@ -180,6 +181,9 @@ def lib() -> C.CDLL:
     L.q3tts_generate_queued.argtypes = [vp, C.POINTER(Request), C.c_int32, C.c_int32, C.POINTER(Sampling), EVENT_CB, vp,
                                         C.POINTER(Result)]
     L.q3tts_voice_create.argtypes = [vp, f32p, C.c_int64, i32p, C.c_int32, C.POINTER(vp)]
+    if hasattr(L, "q3tts_resample"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_voice_create_rate.argtypes = [vp, f32p, C.c_int64, C.c_int32, i32p, C.c_int32, C.POINTER(vp)]
+        L.q3tts_resample.argtypes = [vp, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int64, C.POINTER(C.c_int64)]
     L.q3tts_voice_free.argtypes = [vp, vp]
     L.q3tts_voice_free.restype = None
     L.q3tts_voice_get_info.argtypes = [vp, C.POINTER(VoiceInfo)]

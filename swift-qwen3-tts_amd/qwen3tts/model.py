@@ -9,6 +9,7 @@ Core/GenerationTypes.swift:51-58. Tokenisation stays outside the engine like in 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Callable, Iterator, List, Optional, Sequence, Tuple
@@ -80,7 +81,7 @@ class GenerationRequest:
 
 @dataclass
 class GenerationResult:
-    audio: np.ndarray  # float32 [n_samples] @ 24 kHz
+    audio: np.ndarray  # float32 [n_samples] at the model's sample_rate (24 kHz by default)
     codes: np.ndarray  # int32 [n_frames][16]
     info: AudioGenerationInfo
     status: int = 0
@@ -160,7 +161,10 @@ class Qwen3TTSModel:
     def from_pretrained(cls, model_path: str, device: int = 0, max_batch: int = 1, max_frames: int = 2048,
                         max_prompt: int = 512, use_graph: bool = True,
                         weights_from_broadcast: bool = False, n_streams: int = 0,
-                        codec_overlap_cus: int = 0, codec_fp32: bool = False) -> "Qwen3TTSModel":
+                        codec_overlap_cus: int = 0, codec_fp32: bool = False,
+                        output_sample_rate: int = 0) -> "Qwen3TTSModel":
+        """output_sample_rate (q3tts_load_opts.output_sample_rate): 0 = 24000; 8000, 12000, 16000, 22050, 32000, 44100 or
+        48000 make every waveform of this handle leave at that rate (sample_rate and info.samples_per_frame report it)."""
         lib = L.lib()
         o = L.LoadOpts()
         lib.q3tts_default_load_opts(C.byref(o))
@@ -170,6 +174,7 @@ class Qwen3TTSModel:
         o.n_streams = n_streams
         o.codec_overlap_cus = codec_overlap_cus
         o.codec_fp32 = 1 if codec_fp32 else 0
+        o.output_sample_rate = int(output_sample_rate)
         h = C.c_void_p()
         st = lib.q3tts_model_load(model_path.encode(), C.byref(o), C.byref(h))
         if st != 0:
@@ -239,15 +244,32 @@ class Qwen3TTSModel:
         self._check(self._lib.q3tts_model_arena_checksum(self._h, C.byref(v)))
         return int(v.value)
 
-    def create_voice(self, ref_audio: np.ndarray, ref_text_ids: Sequence[int]) -> Voice:
-        """q3tts_voice_create: encodes the reference clip (24 kHz mono float32) once -- codec encoder, speaker encoder, the
-        prompt rows made of them -- and keeps the result on the device. ref_text_ids as GenerationRequest.ref_text_ids."""
+    def create_voice(self, ref_audio: np.ndarray, ref_text_ids: Sequence[int], sample_rate: int = 24000) -> Voice:
+        """q3tts_voice_create / _create_rate: encodes the reference clip (mono float32 at sample_rate) once -- codec encoder,
+        speaker encoder, the prompt rows made of them -- and keeps the result on the device. A clip at another supported rate
+        than 24000 is resampled on the device first (centred form). ref_text_ids as GenerationRequest.ref_text_ids."""
         ra = np.ascontiguousarray(np.asarray(ref_audio, np.float32).reshape(-1))
         rt = np.ascontiguousarray(ref_text_ids, np.int32)
         h = C.c_void_p()
-        self._check(self._lib.q3tts_voice_create(self._h, ra.ctypes.data_as(L.f32p), ra.size, rt.ctypes.data_as(L.i32p), rt.size,
-                                                 C.byref(h)))
+        if int(sample_rate) == 24000:
+            self._check(self._lib.q3tts_voice_create(self._h, ra.ctypes.data_as(L.f32p), ra.size, rt.ctypes.data_as(L.i32p),
+                                                     rt.size, C.byref(h)))
+        else:
+            self._check(self._lib.q3tts_voice_create_rate(self._h, ra.ctypes.data_as(L.f32p), ra.size, int(sample_rate),
+                                                          rt.ctypes.data_as(L.i32p), rt.size, C.byref(h)))
         return Voice(self, h)
+
+    def resample(self, audio: np.ndarray, in_rate: int, out_rate: int, centred: bool = True) -> np.ndarray:
+        """q3tts_resample: the engine's polyphase FIR on the device (include/q3tts.h, "Sample rates"). One of the rates is
+        24000. centred: no delay (reference clips); otherwise the causal form the decoder's output stage uses."""
+        a = np.ascontiguousarray(np.asarray(audio, np.float32).reshape(-1))
+        g = math.gcd(int(in_rate), int(out_rate)) if in_rate > 0 and out_rate > 0 else 1
+        cap = max(1, -(-a.size * (int(out_rate) // g) // max(1, int(in_rate) // g)))
+        out = np.zeros(cap, np.float32)
+        n = C.c_int64(0)
+        self._check(self._lib.q3tts_resample(self._h, a.ctypes.data_as(L.f32p), a.size, int(in_rate), int(out_rate),
+                                             1 if centred else 0, out.ctypes.data_as(L.f32p), out.size, C.byref(n)))
+        return out[: n.value]
 
     @staticmethod
     def _voices(reqs: Sequence[GenerationRequest]):
@@ -556,9 +578,12 @@ class Qwen3TTSModel:
                              top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.5,
                              max_tokens: int = 2048, *, seed: int = 0, text_ids: Optional[Sequence[int]] = None,
                              ref_text_ids: Optional[Sequence[int]] = None,
-                             target_token_count: Optional[int] = None) -> np.ndarray:
+                             target_token_count: Optional[int] = None, sample_rate: Optional[int] = None) -> np.ndarray:
         """generateVoiceClone(text:referenceAudio:referenceText:language:...) (Qwen3.swift:1009-1203): repetition
-        penalty defaults to 1.5 on this path. Returns the audio of `text` only."""
+        penalty defaults to 1.5 on this path. Returns the audio of `text` only. sample_rate: the reference clip's rate; given
+        and not 24000, the clip is resampled on the device first (without it the clip is taken as 24 kHz, as before)."""
+        if sample_rate is not None and int(sample_rate) != 24000:
+            reference_audio = self.resample(reference_audio, int(sample_rate), 24000, centred=True)
         if text_ids is None:
             if self.tokenizer is None:
                 raise Qwen3TTSError(1, "Model not initialized: Tokenizer not loaded")  # Qwen3.swift:424-426

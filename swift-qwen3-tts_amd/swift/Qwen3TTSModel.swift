@@ -128,8 +128,11 @@ public final class Qwen3TTSModel {
     }
     deinit { q3tts_model_free(handle) }
 
-    /// fromPretrained(_:) -- Qwen3.swift:1382
-    public static func fromPretrained(_ modelPath: String, device: Int32 = 0, maxBatch: Int32 = 1) async throws -> Qwen3TTSModel {
+    /// fromPretrained(_:) -- Qwen3.swift:1382. `outputSampleRate` (new; 0 = 24000): 8000, 12000, 16000, 22050, 32000, 44100 or
+    /// 48000 make every waveform of this model leave at that rate, resampled on the device behind the decoder
+    /// (q3tts_load_opts.output_sample_rate); `sampleRate` reports it.
+    public static func fromPretrained(_ modelPath: String, device: Int32 = 0, maxBatch: Int32 = 1,
+                                      outputSampleRate: Int32 = 0) async throws -> Qwen3TTSModel {
         // Qwen3.swift:1386-1388: the same decode of the same file (a malformed config fails here, before the engine sees it)
         let configData = try Data(contentsOf: URL(fileURLWithPath: modelPath).appendingPathComponent("config.json"))
         let config = try JSONDecoder().decode(Qwen3TTSModelConfig.self, from: configData)
@@ -137,6 +140,7 @@ public final class Qwen3TTSModel {
         q3tts_default_load_opts(&opts)
         opts.device = device
         opts.max_batch = maxBatch
+        opts.output_sample_rate = outputSampleRate
         var h: OpaquePointer?
         let st = q3tts_model_load(modelPath, &opts, &h)
         guard st == Q3TTS_OK, let h else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(nil))) }
@@ -283,18 +287,35 @@ public final class Qwen3TTSModel {
     }
 
     /// The reference of a voice-clone request, encoded once (q3tts_voice_create): codec encoder, speaker encoder and the prompt
-    /// rows made of them run here and never again for the requests that name the voice.
-    public func createVoice(referenceAudio: [Float], referenceText: String) throws -> Qwen3TTSVoice {
+    /// rows made of them run here and never again for the requests that name the voice. A clip whose `sampleRate` is not 24000
+    /// (8000, 12000, 16000, 22050, 32000, 44100 or 48000) is resampled on the device first (q3tts_voice_create_rate).
+    public func createVoice(referenceAudio: [Float], referenceText: String, sampleRate: Int = 24000) throws -> Qwen3TTSVoice {
         guard let tokenizer else { throw AudioGenerationError.modelNotInitialized("Model not initialized: Tokenizer not loaded") }
         let refIds = tokenizer.encode(text: "<|im_start|>assistant\n\(referenceText)<|im_end|>\n").map(Int32.init)   // Qwen3.swift:448-449
         var v: OpaquePointer?
         let st = referenceAudio.withUnsafeBufferPointer { ra in
             refIds.withUnsafeBufferPointer { rt in
-                q3tts_voice_create(handle, ra.baseAddress, Int64(ra.count), rt.baseAddress, Int32(rt.count), &v)
+                sampleRate == 24000
+                    ? q3tts_voice_create(handle, ra.baseAddress, Int64(ra.count), rt.baseAddress, Int32(rt.count), &v)
+                    : q3tts_voice_create_rate(handle, ra.baseAddress, Int64(ra.count), Int32(sampleRate), rt.baseAddress, Int32(rt.count), &v)
             }
         }
         guard st == Q3TTS_OK, let v else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
         return Qwen3TTSVoice(model: self, handle: v)
+    }
+
+    /// q3tts_resample: the engine's polyphase FIR on the device (q3tts.h, "Sample rates"); one of the rates is 24000.
+    /// `centred`: no delay (reference clips); otherwise the causal form of the decoder's output stage.
+    public func resample(_ audio: [Float], from inRate: Int, to outRate: Int, centred: Bool = true) throws -> [Float] {
+        func gcd(_ a: Int, _ b: Int) -> Int { b == 0 ? a : gcd(b, a % b) }
+        let g = max(1, gcd(max(inRate, 1), max(outRate, 1)))
+        var out = [Float](repeating: 0, count: max(1, (audio.count * (outRate / g) + (inRate / g) - 1) / max(1, inRate / g)))
+        var n: Int64 = 0
+        let st = audio.withUnsafeBufferPointer { a in
+            q3tts_resample(handle, a.baseAddress, Int64(a.count), Int32(inRate), Int32(outRate), centred ? 1 : 0, &out, Int64(out.count), &n)
+        }
+        guard st == Q3TTS_OK else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
+        return Array(out.prefix(Int(n)))
     }
 
     /// generateVoiceClone with a voice made by `createVoice` instead of the clip: the same audio, bit for bit, without the front end

@@ -390,16 +390,20 @@ def main():
     ap.add_argument("--arrivals", default="inf", metavar="RATE", help="--session: requests per second, exponential gaps; inf: all at once")
     ap.add_argument("--text-rate", default=None, metavar="TOK_PER_S",
                     help="--session: every request's content arrives at this rate; open-text requests against whole submits")
+    ap.add_argument("--output-sample-rate", type=int, default=0, metavar="R",
+                    help="load the model with q3tts_load_opts.output_sample_rate = R (0: the decoder's own 24000)")
+    ap.add_argument("--only-stream", action="store_true", help="with --stream: skip the static / queued comparison in front of it")
     args = ap.parse_args()
     from qwen3tts import Qwen3TTSModel, RequestSampling
+    rate_kw = dict(output_sample_rate=args.output_sample_rate) if args.output_sample_rate else {}
 
     ckpt = bench.ensure_checkpoint(args.preset, 0, None)
     if args.voices > 0:  # (an ICL prompt carries the reference text and one row per reference frame: 3 s are 38 frames)
-        model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=192)
+        model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=192, **rate_kw)
         run_voices(model, args)
         model.close()
         return
-    model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=128)
+    model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=128, **rate_kw)
     n_instruct = 16 if args.preset == "1.7b" else 0
     base = bench.build_requests(args.preset, 0, args.requests, args.n_text, n_instruct)
     rng = np.random.default_rng(1234)
@@ -432,8 +436,9 @@ def main():
         run_session_bench(model, args, ragged, warm, sampling)
         model.close()
         return
-    print(f"# {args.preset} bf16, {args.requests} requests, slots {args.slots}; frames/s = generated frames / wall time (codec included)")
-    for name, reqs, kw in workloads:
+    print(f"# {args.preset} bf16, {args.requests} requests, slots {args.slots}, output {model.sample_rate} Hz "
+          f"({model.info.samples_per_frame} samples per frame); frames/s = generated frames / wall time (codec included)")
+    for name, reqs, kw in ([] if args.only_stream and args.stream else workloads):
         res = {}
         for path, fn in (("static", run_static), ("queued", run_queued)):
             out, dt, steps, pre, codec, _ = fn(model, reqs, args.slots, kw)

@@ -93,6 +93,23 @@ typedef struct {
                            prefix state of a voice grows by the stage's margin, 3 x 1920 x 4 bytes. Per handle, not per
                            call: every buffer behind the tail is sized at load by samples per frame. Any other value is
                            Q3TTS_ERR_INVALID_INPUT at load */
+    float speed;        /* new (the reference has no speaking rate): how fast this handle speaks, pitch preserved. 0 (default) or
+                           1.0: off -- nothing is added, the samples are what a handle loaded without this field gives, bit for
+                           bit. 0.5 .. 2.0: the decoder's causal tail gets the time stretch defined under "Speaking rate"
+                           below, in its causal form, behind out_conv and in front of the output-rate stage. The synthesis hop
+                           Hs is the integer in [240, 960] nearest to 480 / speed (ties toward 480) for which a frame holds a
+                           whole number of samples at output_sample_rate (4 * Hs * L % M == 0; without an output rate every
+                           integer); q3tts_model_get_speed reports it and the effective speed 480 / Hs. A frame then yields
+                           4 * Hs samples at 24 kHz: q3tts_model_info.samples_per_frame is 4 * Hs * rate / 24000 and everything
+                           this header counts in samples follows it, as with output_sample_rate. Every guarantee holds unchanged
+                           -- streamed equals one-shot (window < 0), the chunked exact decode equals one-shot, queued equals
+                           alone, session equals queued, a voice's saved prefix state continues identically, bit for bit: the
+                           stage carries its input's margin and one int32 per row (the last hop's offset) from chunk to chunk.
+                           The causal form delays the audio by D 24 kHz samples (0 at 2x, 80 at 1.5x, 480 at 0.8x, 1200 at
+                           0.5x): a waveform starts with about D * Hs / 480 samples of silence and its last D input samples are
+                           not spoken (no flush). Hs == 480 is off. Per handle, not per request: the rows of one pass share one
+                           samples-per-frame. Outside [0.5, 2.0], NaN or infinite: Q3TTS_ERR_INVALID_INPUT at load, before any
+                           GPU work */
 } q3tts_load_opts;
 
 void q3tts_default_load_opts(q3tts_load_opts* o);
@@ -581,6 +598,31 @@ q3tts_status q3tts_session_get_text_stats(const q3tts_session* s, q3tts_session_
  * still set). One engine entry point like q3tts_codec_decode: one caller per handle, refused while a session is open. */
 q3tts_status q3tts_resample(q3tts_model* m, const float* in, int64_t n_in, int32_t in_rate, int32_t out_rate, int32_t centred,
                             float* out, int64_t cap, int64_t* n_out);
+
+/* ---- Speaking rate (new: the reference has none) ---------------------------------------------------------------------------
+ * WSOLA in crossfade form at 24 kHz (q3tts_load_opts.speed, q3tts_time_stretch). Analysis hop Ha = 480 (4 per frame), search
+ * radius Delta = 240, synthesis hop Hs in [240, 960]: speed = Ha / Hs. Fade f[n] = 0.5 - 0.5 cos(pi (n + 0.5) / Hs), n < Hs,
+ * in double, rounded to fp32. Delay D = max(0, Delta + Hs - Ha, Delta + 2 Hs - 2 Ha) in the causal form, 0 in the whole form.
+ * Hop m = 0, 1, ...:   cont[n] = x[p_{m-1} + Hs + n], p_{-1} = -D - Hs, d_0 = 0; for m > 0 and d in [-Delta, Delta]
+ * c(d) = sum_n cont[n] * x[m Ha + d - D + n] (fp32, one accumulator, fmaf, n ascending); d_m is the best c with the candidates
+ * visited as 0, -1, +1, -2, +2, ... and replaced on strictly greater only (ties: smallest |d|, then the negative one; a NaN
+ * never wins); p_m = m Ha + d_m - D; y[m Hs + n] = fmaf(f[n], x[p_m + n] - cont[n], cont[n]). Every sample is a convex
+ * combination of two input samples, rounded once: the [-1, 1] range of the decoder's output survives. With D as above hop m
+ * reads nothing beyond x[m Ha + Ha - 1], so output frame f depends on input up to the end of frame f alone.
+ * Causal form: samples in front of the signal are zero, floor(n_in / Ha) hops, floor(n_in / Ha) * Hs samples out; the output
+ * is the input delayed by D, so it starts with about D Hs / Ha samples of silence and the last D input samples are lost.
+ * Whole form: D = 0, reads behind the end are zero, ceil(n_in / Ha) hops, cut to ceil(n_in Hs / Ha) samples.
+ *
+ * q3tts_model_get_speed: the handle's effective speed 480 / Hs (1.0: off), Hs (480: off) and D (any pointer may be NULL).
+ * q3tts_time_stretch: `in` (host, n_in >= 1 samples at 24 kHz) through the device kernel to `out` (host, `cap` samples of
+ * room); Hs is the integer nearest to 480 / speed (ties toward 480; the handle's output rate plays no part; speed 1.0 is
+ * Hs = 480, which still aligns and crossfades). causal != 0: the causal form with nothing in front (what the decoder's stage
+ * computes for a whole utterance); 0: the whole form. Q3TTS_ERR_INVALID_INPUT, the engine staying usable: speed outside
+ * [0.5, 2.0], NaN or infinite (refused before any GPU work), a NaN or infinite sample, n_in above 2^26, cap < *n_out (which
+ * is still set). One engine entry point like q3tts_resample: one caller per handle, refused while a session is open. */
+q3tts_status q3tts_model_get_speed(const q3tts_model* m, float* effective_speed, int32_t* hs, int32_t* delay_samples);
+q3tts_status q3tts_time_stretch(q3tts_model* m, const float* in, int64_t n_in, float speed, int32_t causal, float* out, int64_t cap,
+                                int64_t* n_out);
 
 /* Qwen3TTSSpeechTokenizer.decode (Models/SpeechTokenizer.swift:823-836): codes
  * [batch][max_frames][num_code_groups] -> pcm [batch][max_frames*1920] (caller-allocated),

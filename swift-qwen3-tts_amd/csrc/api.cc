@@ -128,6 +128,7 @@ void q3tts_default_load_opts(q3tts_load_opts* o) {
     o->codec_overlap_cus = 0;
     o->codec_fp32 = 0;
     o->output_sample_rate = 0;
+    o->speed = 0.0f;
 }
 
 void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
@@ -155,6 +156,8 @@ q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts
         else q3tts_default_load_opts(&o);
         Q3_CHECK(o.max_batch >= 1 && o.max_batch <= 64, 3, "Invalid input: max_batch must be in 1..64");
         Q3_CHECK(o.max_frames >= 1 && o.max_prompt >= 16, 3, "Invalid input: max_frames / max_prompt too small");
+        // (a NaN fails every comparison: refused like a value out of range, and before the first call into the GPU runtime)
+        Q3_CHECK(o.speed == 0.0f || (o.speed >= 0.5f && o.speed <= 2.0f), 3, "Invalid input: speed must be 0 (off) or between 0.5 and 2.0");
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         Q3_CHECK(e == hipSuccess && ndev > 0, 7, "no HIP device available: this engine has no CPU fallback");
@@ -311,6 +314,25 @@ q3tts_status q3tts_resample(q3tts_model* m, const float* in, int64_t n_in, int32
     return guarded(m, [&] {
         Q3_CHECK(m && in && out && n_out, 3, "Invalid input: null argument");
         m->eng->lane0().resample(in, n_in, in_rate, out_rate, centred != 0, out, cap, n_out);
+    });
+}
+
+q3tts_status q3tts_model_get_speed(const q3tts_model* m, float* effective_speed, int32_t* hs, int32_t* delay_samples) {
+    return guarded(const_cast<q3tts_model*>(m), [&] {
+        Q3_CHECK(m, 3, "Invalid input: null argument");
+        const q3::CodecRunner* cr = m->eng->codec_runner();
+        const int h = cr ? cr->stretch_hs() : q3::kStretchHa;
+        if (effective_speed) *effective_speed = float(double(q3::kStretchHa) / double(h));
+        if (hs) *hs = h;
+        if (delay_samples) *delay_samples = cr ? cr->stretch_delay_samples() : 0;
+    }, false);
+}
+
+q3tts_status q3tts_time_stretch(q3tts_model* m, const float* in, int64_t n_in, float speed, int32_t causal, float* out, int64_t cap,
+                                int64_t* n_out) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && in && out && n_out, 3, "Invalid input: null argument");
+        m->eng->lane0().time_stretch(in, n_in, speed, causal != 0, out, cap, n_out);
     });
 }
 

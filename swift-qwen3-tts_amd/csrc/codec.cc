@@ -16,17 +16,39 @@ size_t kScratchBudget = size_t(24) << 30;  // activation scratch per group of ro
 }
 void CodecRunner::set_scratch_budget(size_t bytes) { kScratchBudget = bytes ? bytes : (size_t(24) << 30); }
 
-CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate) : m_(m), st_(st) {
-    native_ = up_ = m.cfg.codec.total_upsample();
+CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate, float speed) : m_(m), st_(st) {
+    native_ = mid_ = up_ = m.cfg.codec.total_upsample();
+    if (speed != 0.0f && speed != 1.0f) {
+        Q3_CHECK(speed >= 0.5f && speed <= 2.0f, 3, "Invalid input: speed must be 0 (off) or between 0.5 and 2.0");
+        Q3_CHECK(native_ % kStretchHa == 0, 3, "Invalid input: the codec's frame is not a whole number of 480-sample hops: no speed other than 1");
+        const int hops = native_ / kStretchHa;
+        int L = 1, M = 1;
+        if (output_rate != 0 && output_rate != kResampleNative && resample_rate_supported(output_rate)) {
+            const int g = resample_detail::gcd(kResampleNative, output_rate);
+            L = output_rate / g;
+            M = kResampleNative / g;
+        }
+        const int hs = stretch_choose_hs(double(speed), hops, L, M);
+        Q3_CHECK(hs != 0, 3, "Invalid input: no synthesis hop for this speed and output_sample_rate");
+        if (hs != kStretchHa) {
+            st_plan_ = make_stretch_plan(hs);
+            // the stage reads this far in front of a frame's first sample: inside the margin every streamed tail tensor carries
+            Q3_CHECK(stretch_lookback(hs) <= hist_frames() * native_, 7, "internal error: time stretch history beyond the stream's margin");
+            mid_ = up_ = hops * hs;
+            stretch_ = true;
+            Q3_HIP(hipMemcpy(st_fade_.grow(size_t(hs)), st_plan_.fade.data(), size_t(hs) * 4, hipMemcpyHostToDevice));
+        }
+    }
     if (output_rate != 0 && output_rate != kResampleNative) {
         Q3_CHECK(resample_rate_supported(output_rate), 3,
                  "Invalid input: output_sample_rate must be 0, 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000");
         out_plan_ = make_resample_plan(kResampleNative, output_rate);
-        Q3_CHECK((int64_t(native_) * out_plan_.L) % out_plan_.M == 0, 3,
+        // (with a time stretch in front, mid_ is its frame: stretch_choose_hs took only hops that pass this)
+        Q3_CHECK((int64_t(mid_) * out_plan_.L) % out_plan_.M == 0, 3,
                  "Invalid input: the codec's frame does not hold a whole number of samples at output_sample_rate");
         // the stage reads 2K - 1 samples back: they must lie inside the margin every streamed tail tensor carries
-        Q3_CHECK(out_plan_.taps() - 1 <= hist_frames() * native_, 7, "internal error: resampler history beyond the stream's margin");
-        up_ = int(int64_t(native_) * out_plan_.L / out_plan_.M);
+        Q3_CHECK(out_plan_.taps() - 1 <= hist_frames() * mid_, 7, "internal error: resampler history beyond the stream's margin");
+        up_ = int(int64_t(mid_) * out_plan_.L / out_plan_.M);
         resample_ = true;
         const size_t n = align_up(out_plan_.tab.size(), 4);
         std::vector<float> padded(n, 0.0f);
@@ -68,6 +90,7 @@ size_t CodecRunner::floats_per_frame() const {
         C /= 2;
         per_frame = std::max(per_frame, size_t(ppf) * C);
     }
+    if (stretch_) per_frame = std::max(per_frame, size_t(mid_));  // the stretched signal in front of the resampler
     return per_frame;
 }
 
@@ -88,6 +111,9 @@ int CodecRunner::tail_context_frames() const {
         ctx += 6.0 * (1 + 3 + 9) / rate;  // three residual units, k7 with dilation 1, 3, 9
     }
     ctx += 6.0 / rate;      // outConv k7
+    // the time stretch reads its look-back from the recomputed context (its state word and the resampler's input behind it
+    // are carried instead, decode_chunked)
+    if (stretch_) ctx += double(stretch_lookback(st_plan_.hs)) / rate;
     if (resample_) ctx += double(out_plan_.taps() - 1) / rate;  // the causal polyphase FIR behind it: 2K - 1 samples back
     return int(ctx) + 2;
 }
@@ -295,6 +321,7 @@ void* CodecRunner::Stream::get(size_t frame_bytes, bool reads_back) {
 // ps.hist_frames frames of history; out: pcm [nb][Trows * upsample] (row stride Trows * upsample). Every tensor is addressed as
 // base + hist_frames * elements per frame; the one-shot decode has no margin. With an output rate other than the decoder's
 // own, out_conv's 24 kHz signal goes to one more tail tensor and the causal polyphase FIR (resample_plan.h) writes pcm.
+// With a speed, the time stretch (stretch_plan.h) sits between the two: 24 kHz in, 4 Hs samples per frame out.
 template <class Mem>
 void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float* pcm) {
     const CodecW& w = m_.codec;
@@ -389,30 +416,84 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
         }
         // 7. outSnake -> outConv -> clip (:687-688, :781)
         // (a resampled decode: out_conv's own clip stays, the flags of a non-finite waveform come from it as before)
-        float* p24 = resample_ ? static_cast<float*>(mem.get(size_t(ppf) * sizeof(float), true)) : nullptr;
+        const bool post = resample_ || stretch_;  // stages behind out_conv: its signal goes to one more tail tensor
+        float* p24 = post ? static_cast<float*>(mem.get(size_t(ppf) * sizeof(float), true)) : nullptr;
         launch([&] {
             const E* x = y + size_t(H) * ppf * w.out_C;
-            float* out = (resample_ ? p24 : pcm) + size_t(H) * ppf;
+            float* out = (post ? p24 : pcm) + size_t(H) * ppf;
             if constexpr (f16)
                 launch_out_conv_h1(x, w.out_C, w.out_snake.ea16, w.out_snake.ib16, w.out_w, w.out_b, fr, ppf, T, nb, out, st_, nf_dev_ + ps.row0, H * ppf);
             else
                 launch_out_conv(x, w.out_C, w.out_snake.ea, w.out_snake.ib, w.out_w, w.out_b, fr, ppf, T, nb, out, st_, H * ppf, nf_dev_ + ps.row0);
         });
         mem.put(y);
+        // X: decode_chunked with a time stretch -- recomputed context frames in front of the new ones; the stages below run on
+        // the new frames (frn) and find their input's history in the context (0 everywhere else)
+        const int X = stretch_ ? ps.ctx_frames : 0;
+        const int32_t* frn = (stretch_ && ps.fr_new) ? ps.fr_new : fr;
+        // the resampler's input: its first new sample, row stride, samples in memory in front of it, samples per frame
+        float* rin = p24 ? p24 + size_t(H) * ppf : nullptr;
+        int64_t rin_stride = int64_t(T);
+        int rin_hist = H * ppf, rin_frame = ppf;
+        float* mid = nullptr;
+        if (stretch_) {
+            // 8. the time stretch (stretch_plan.h): output frame f depends on input up to the end of frame f alone, and on one
+            // word of state per row. A stream keeps the word in a tensor of its own, one entry per frame: the stage reads the
+            // entry of the frame in front of the chunk (the margin's last: zero behind a reset, i.e. hop 0 comes next) and
+            // writes one behind every frame, so the margin machinery carries it like samples.
+            int32_t* words = H > 0 ? static_cast<int32_t*>(mem.get(size_t(kStateWords) * sizeof(int32_t), true)) : nullptr;
+            float* sy = nullptr;
+            int64_t sy_stride = 0;
+            if (!resample_) {
+                sy = pcm ? pcm + size_t(H + X) * up_ : nullptr;  // (no memory behind the tensors in stream_open's counting pass)
+                sy_stride = int64_t(Trows) * up_;
+            } else if (ps.mid_carry) {
+                sy = ps.mid_carry + mid_;
+                sy_stride = ps.mid_stride;
+                rin_hist = mid_;
+            } else {
+                mid = static_cast<float*>(mem.get(size_t(mid_) * sizeof(float), true));
+                sy = mid ? mid + size_t(H) * mid_ : nullptr;
+                sy_stride = int64_t(Trows) * mid_;
+                rin_hist = H * mid_;
+            }
+            launch([&] {
+                StretchArgs a{};
+                a.x = p24 + size_t(H + X) * ppf; a.x_bstride = int64_t(T);
+                a.y = sy; a.y_bstride = sy_stride;
+                a.len = frn; a.len_mul = ppf;
+                a.fade = st_fade_; a.hs = st_plan_.hs; a.delay = st_plan_.delay;
+                a.hist = (H + X) * ppf; a.causal = 1; a.B = nb;
+                if (words) {
+                    a.state_in = words + size_t(H - 1) * kStateWords; a.state_in_bstride = int64_t(Trows) * kStateWords;
+                    a.state_frames = words + size_t(H) * kStateWords; a.state_frames_bstride = int64_t(Trows) * kStateWords;
+                    a.frame_hops = ppf / kStretchHa; a.state_frame_words = kStateWords;
+                } else if (ps.carry) {
+                    a.state_in = ps.carry; a.state_in_bstride = 1;
+                    a.state_out = ps.carry; a.state_out_bstride = 1;
+                }
+                launch_stretch(a, st_);
+            });
+            if (words) mem.put(words);
+            rin = sy;
+            rin_stride = sy_stride;
+            rin_frame = mid_;
+        }
         if (resample_) {
             // Output frame f depends on input up to the end of frame f alone (q = floor(n M / L) stays inside the frame), and
             // the phase of a chunk's first sample is 0: the rows are addressed frame by frame like every other tensor.
             launch([&] {
                 ResampleArgs a{};
-                a.x = p24 + size_t(H) * ppf; a.x_bstride = int64_t(T);
-                a.y = pcm + size_t(H) * up_; a.y_bstride = int64_t(Trows) * up_;
-                a.len = fr; a.len_mul = ppf; a.max_in = int64_t(Trows - H) * ppf;
+                a.x = rin; a.x_bstride = rin_stride;
+                a.y = pcm + size_t(H + X) * up_; a.y_bstride = int64_t(Trows) * up_;
+                a.len = frn; a.len_mul = rin_frame; a.max_in = int64_t(Trows - H - X) * rin_frame;
                 a.tab = out_tab_; a.L = out_plan_.L; a.M = out_plan_.M; a.K = out_plan_.K;
-                a.hist = H * ppf; a.centred = 0; a.clamp = 1; a.B = nb;
+                a.hist = rin_hist; a.centred = 0; a.clamp = 1; a.B = nb;
                 launch_resample(a, st_);
             });
-            mem.put(p24);
         }
+        if (mid) mem.put(mid);
+        if (post) mem.put(p24);
     };
     if (w.f16_main && !fp32_mfma_ && !no_h1_) main_decoder(uint16_t{});
     else main_decoder(float{});
@@ -490,13 +571,25 @@ int CodecRunner::decode_chunked(const int32_t* codes_dev, int code_stride_frames
     float* bufs[4];
     for (int i = 0; i < 4; ++i) bufs[i] = reinterpret_cast<float*>(buf_ + pcm_bytes + front_bytes + size_t(i) * big);
     // row lengths: the whole rows for the front, then per chunk the frames of [h0, f1) each row still has
-    std::vector<int32_t> lens((size_t)(B) * (1 + n_chunks));
+    // (a time stretch: then the frames of [f0, f1) alone, for the stages that carry their state instead of recomputing it)
+    std::vector<int32_t> lens((size_t)(B) * (1 + (stretch_ ? 2 : 1) * n_chunks));
     for (int b = 0; b < B; ++b) lens[size_t(b)] = frames[size_t(b)];
     for (int k = 0; k < n_chunks; ++k) {
         const int f0 = k * chunk_frames, f1 = std::min(Fmax, f0 + chunk_frames), h0 = std::max(0, f0 - H);
         for (int b = 0; b < B; ++b) lens[size_t(1 + k) * B + b] = std::max(0, std::min(frames[size_t(b)], f1) - h0);
+        if (stretch_)
+            for (int b = 0; b < B; ++b) lens[size_t(1 + n_chunks + k) * B + b] = std::max(0, std::min(frames[size_t(b)], f1) - f0);
     }
     upload_lens(lens.data(), int(lens.size()));
+    // The time stretch cannot recompute its state word from left context: the word is carried from chunk to chunk, reset here
+    // for chunk 0, and with it the stretched signal's last frame for the resampler behind it.
+    const int64_t mid_stride = int64_t(1 + chunk_frames) * mid_;
+    if (stretch_) {
+        if (size_t(B) > ch_words_.capacity() || (resample_ && size_t(B) * size_t(mid_stride) > ch_mid_.capacity()))
+            Q3_HIP(hipStreamSynchronize(st_));  // the old buffers may still be read
+        Q3_HIP(hipMemsetAsync(ch_words_.grow(size_t(B)), 0, size_t(B) * 4, st_));
+        if (resample_) Q3_HIP(hipMemsetAsync(ch_mid_.grow(size_t(B) * size_t(mid_stride)), 0, size_t(B) * size_t(mid_stride) * 4, st_));
+    }
     while (int(chunk_done.size()) < n_chunks) {
         hipEvent_t e = nullptr;
         Q3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -517,8 +610,19 @@ int CodecRunner::decode_chunked(const int32_t* codes_dev, int code_stride_frames
             ps.nb = std::min(G, B - r0); ps.row0 = r0; ps.fr = lens_dev_ + size_t(1 + k) * B + r0; ps.stage = &none;
             Q3_HIP(hipMemcpy2DAsync(bufs[0], size_t(T) * row_in, x_all + (size_t(r0) * Fmax + h0) * dc.latent_dim, size_t(Fmax) * row_in,
                                     size_t(T) * row_in, size_t(ps.nb), hipMemcpyDeviceToDevice, st_));
+            if (stretch_) {
+                ps.ctx_frames = f0 - h0;
+                ps.fr_new = lens_dev_ + size_t(1 + n_chunks + k) * B + r0;
+                ps.carry = ch_words_ + r0;
+                if (resample_) {
+                    ps.mid_carry = ch_mid_ + size_t(r0) * size_t(mid_stride);
+                    ps.mid_stride = mid_stride;
+                }
+            }
             Ring ring(bufs, big, size_t(ps.nb) * T);
             run_tail(ps, ring, bufs[0], T, pcm);
+            if (ps.mid_carry && f1 - f0 == chunk_frames)  // (a short chunk is the last one)
+                launch_roll_history(ps.mid_carry + mid_, mid_stride, int64_t(mid_), int64_t(chunk_frames) * mid_, ps.nb, st_);
             Q3_HIP(hipMemcpy2DAsync(pcm_host + (size_t(r0) * Fmax + f0) * up_, size_t(Fmax) * up_ * sizeof(float), pcm + size_t(f0 - h0) * up_,
                                     size_t(T) * up_ * sizeof(float), size_t(f1 - f0) * up_ * sizeof(float), size_t(ps.nb),
                                     hipMemcpyDeviceToHost, st_));

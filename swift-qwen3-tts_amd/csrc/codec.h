@@ -1,5 +1,5 @@
 // codec.h -- neural codec decoder runner (codes -> PCM at 24 kHz or at the handle's output rate) on the HIP kernels in
-// kernels/codec_conv.hip, kernels/codec_misc.hip and kernels/resample.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
+// kernels/codec_conv.hip, kernels/codec_misc.hip, kernels/stretch.hip and kernels/resample.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
 // (/root/reference/Sources/Qwen3TTS/Models/SpeechTokenizer.swift:754-784).
 #pragma once
 #include <string>
@@ -8,6 +8,7 @@
 #include "model.h"
 #include "resample_plan.h"
 #include "stream_plan.h"
+#include "stretch_plan.h"
 
 namespace q3 {
 
@@ -18,7 +19,13 @@ class CodecRunner {
     // writes the PCM, `upsample()` samples per frame at that rate. Being one more causal conv of the tail, the stage carries
     // its history from chunk to chunk like the others: every statement below about samples, strides and bit-identity holds
     // with upsample() counting output samples.
-    CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false, int output_rate = 0);
+    // speed: 0 or 1 -- off, nothing is added. Otherwise (0.5 .. 2; stretch_plan.h chooses the synthesis hop Hs, the one nearest
+    // to 480 / speed that leaves whole samples per frame at the output rate) the time stretch sits behind out_conv and in front
+    // of the resampler: one more causal stage, 4 Hs samples per frame, whose state besides its input's margin is one word per
+    // row (d of the last hop). In a stream the word lives in a tail tensor of its own, one 16-byte entry per frame, so whatever
+    // rolls, zeroes, saves or restores margins carries it like any other history; decode_chunked, which recomputes its left
+    // context, cannot recompute the word and carries it (and the resampler's input margin) from chunk to chunk.
+    CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false, int output_rate = 0, float speed = 0.0f);
     // codes_dev: [B][code_stride_frames][16] int32 on the device; rows decode frames[b] frames.
     // pcm_dev receives [B][Fmax*upsample] float32 (Fmax = max(frames)); returns Fmax.
     // If `stage` is non-empty the activation after that stage is copied to stage_out ([B][T][C]).
@@ -112,6 +119,9 @@ class CodecRunner {
     int upsample() const { return up_; }            // PCM samples per frame at the output rate
     int native_upsample() const { return native_; }  // the decoder's own samples per frame (1920)
     int output_rate() const { return resample_ ? out_plan_.out_rate : kResampleNative; }
+    // the time stretch of this handle: synthesis hop (480: off), effective speed 480 / Hs, delay D in 24 kHz samples
+    int stretch_hs() const { return stretch_ ? st_plan_.hs : kStretchHa; }
+    int stretch_delay_samples() const { return stretch_ ? st_plan_.delay : 0; }
     hipStream_t stream() const { return st_; }
     void set_stream(hipStream_t st) { st_ = st; }  // the caller drains the old stream first (shared scratch)
 
@@ -121,6 +131,13 @@ class CodecRunner {
         int row0 = 0;         // first row of this pass in the call's batch (non-finite flags)
         int hist_frames = 0;  // streamed decode: tensors carry this many frames of history in front of their first row
         const int32_t* fr = nullptr;  // device: valid frames per row
+        // decode_chunked with a time stretch: the first ctx_frames frames of every row are recomputed context. The stages with
+        // carried state run on the fr_new[b] frames behind them alone, the context supplying their input's history.
+        int ctx_frames = 0;
+        const int32_t* fr_new = nullptr;  // device: new frames per row
+        int32_t* carry = nullptr;         // device [nb]: the stretch's state word per row, read and written
+        float* mid_carry = nullptr;       // the resampler's input: [nb][mid_stride], one frame of margin in front of the new frames
+        int64_t mid_stride = 0;
         const std::string* stage = nullptr;
         std::vector<float>* stage_out = nullptr;
         int* stage_T = nullptr;
@@ -209,6 +226,13 @@ class CodecRunner {
     bool resample_ = false;
     ResamplePlan out_plan_;   // 24000 -> output rate
     DevBuf<float> out_tab_;   // its phase table on the device
+    int mid_ = 1920;          // samples per frame behind the time stretch == in front of the resampler (4 Hs, or native_)
+    bool stretch_ = false;
+    StretchPlan st_plan_;
+    DevBuf<float> st_fade_;   // its fade table on the device
+    static constexpr int kStateWords = 4;  // int32s per frame of the stretch's state tensor (the word and padding to 16 bytes)
+    DevBuf<int32_t> ch_words_;  // decode_chunked: [B] state words carried from chunk to chunk
+    DevBuf<float> ch_mid_;      // decode_chunked: [B][(1 + chunk) * mid_] stretched signal with one frame of margin
     bool no_h1_ = false;      // Q3TTS_CODEC_NO_F16=1: a float16 speech tokenizer through the up-cast (fp32-equivalent) path
     bool no_fuse_ = false;    // Q3TTS_CODEC_NO_FUSE=1: residual units of the narrow blocks as two launches each
     bool fp32_mfma_ = false;  // Q3TTS_CODEC_FP32=1: contract on the fp32 matrix-core path instead of the split one

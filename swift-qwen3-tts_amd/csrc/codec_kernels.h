@@ -210,6 +210,36 @@ struct ResampleArgs {
 void launch_resample(const ResampleArgs& a, hipStream_t st);
 size_t resample_lds_bytes(int L, int M, int K);
 
+// ---- time stretch (kernels/stretch.hip; the definition: stretch_plan.h) ----
+// Row b's input starts at x + b * x_bstride and has len[b] * len_mul valid samples at 24 kHz; its outputs (causal:
+// floor(n_in / 480) * hs, whole: ceil(n_in * hs / 480)) go to y + b * y_bstride. A row of length 0 touches nothing, its state
+// included. Causal form: `hist` samples exist in memory in front of every row's first one (0: they are taken as zero) and
+// `delay` is stretch_delay(hs). Samples at and behind n_in are never read. The row's state word (stretch_plan.h), all
+// optional: state_in[b * state_in_bstride] is read on entry (nullptr: the row starts at hop 0), the word as it stands behind
+// every frame_hops-th hop goes to state_frames[b * state_frames_bstride + frame * state_frame_words], the word behind the last
+// hop to state_out[b * state_out_bstride] (which may be state_in: one workgroup owns the row).
+struct StretchArgs {
+    const float* x;
+    int64_t x_bstride;
+    float* y;
+    int64_t y_bstride;
+    const int32_t* len;  // device [B]
+    int len_mul;
+    const float* fade;   // device [hs]
+    int hs, delay;
+    int hist;
+    int causal;
+    int B;
+    const int32_t* state_in;
+    int64_t state_in_bstride;
+    int32_t* state_frames;
+    int64_t state_frames_bstride;
+    int frame_hops, state_frame_words;
+    int32_t* state_out;
+    int64_t state_out_bstride;
+};
+void launch_stretch(const StretchArgs& a, hipStream_t st);
+
 // ---- voice-clone front end (kernels/voice_frontend.hip) ------------------------------------------
 // first SEANet conv: 1 -> C channels, causal k taps (SpeechTokenizerEncoder.swift:404-414). w [C][K], out [S][C]
 void launch_enc_init_conv(const float* audio, int64_t S, int B, const float* w, const float* bias, int C, int K, float* out,

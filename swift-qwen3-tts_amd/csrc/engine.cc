@@ -102,7 +102,7 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
         Q3_HIP(hipMalloc(reinterpret_cast<void**>(&stamps_), 64 * 8));
         Q3_HIP(hipMemset(stamps_, 0, 64 * 8));
     }
-    if (m_->has_codec) codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0, opts.output_sample_rate);
+    if (m_->has_codec) codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0, opts.output_sample_rate, opts.speed);
     if (m_->has_codec_encoder || m_->has_speaker_encoder) fe_ = std::make_unique<VoiceFrontEnd>(*m_, st_);
 }
 
@@ -989,6 +989,46 @@ void Engine::resample(const float* in, int64_t n_in, int in_rate, int out_rate, 
     const float* y = resample_upload(in, n_in, in_rate, out_rate, centred, &got);
     Q3_HIP(hipStreamSynchronize(st_));
     Q3_HIP(hipMemcpy(out, y, size_t(got) * 4, hipMemcpyDeviceToHost));
+}
+
+void Engine::time_stretch(const float* in, int64_t n_in, float speed, bool causal, float* out, int64_t cap, int64_t* n_out) {
+    // (the speed is refused first, whatever else is wrong, and before any GPU work)
+    const int hs = stretch_choose_hs(double(speed));
+    Q3_CHECK(hs != 0, 3, "Invalid input: speed must lie between 0.5 and 2.0");
+    Q3_CHECK(in && out && n_out && n_in > 0, 3, "Invalid input: empty audio");
+    Q3_CHECK(n_in <= (int64_t(1) << 26), 3, "Invalid input: time stretch takes between 1 and 2^26 samples");
+    StretchDev* sd = nullptr;
+    for (const auto& s : stretchers_)
+        if (s->plan.hs == hs) sd = s.get();
+    if (!sd) {
+        auto s = std::make_unique<StretchDev>();
+        s->plan = make_stretch_plan(hs);
+        Q3_HIP(hipMemcpy(s->fade.grow(size_t(hs)), s->plan.fade.data(), size_t(hs) * 4, hipMemcpyHostToDevice));
+        stretchers_.push_back(std::move(s));
+        sd = stretchers_.back().get();
+    }
+    const int64_t no = sd->plan.out_len(n_in, causal);
+    *n_out = no;
+    Q3_CHECK(cap >= no, 3, "Invalid input: output buffer too small for the stretched audio");
+    bool finite = true;
+    for (int64_t i = 0; i < n_in; ++i) finite = finite && (std::fabs(in[i]) <= 3.0e38f);
+    Q3_CHECK(finite, 3, "Invalid input: audio holds non-finite samples");
+    if (no == 0) return;  // (causal form of less than one hop)
+    const float* a = upload_audio(in, n_in);
+    if (size_t(no) > rs_out_dev_.capacity()) Q3_HIP(hipStreamSynchronize(st_));  // the old buffer may still be read
+    rs_out_dev_.grow(size_t(no));
+    rs_len_dev_.grow(1);
+    const int32_t len = int32_t(n_in);
+    Q3_HIP(hipStreamSynchronize(st_));  // `len` is pageable stack memory, and the device word may still feed an earlier launch
+    Q3_HIP(hipMemcpy(rs_len_dev_, &len, 4, hipMemcpyHostToDevice));
+    StretchArgs sa{};
+    sa.x = a; sa.y = rs_out_dev_;
+    sa.len = rs_len_dev_; sa.len_mul = 1;
+    sa.fade = sd->fade; sa.hs = hs; sa.delay = causal ? sd->plan.delay : 0;
+    sa.causal = causal ? 1 : 0; sa.B = 1;
+    launch_stretch(sa, st_);
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy(out, rs_out_dev_, size_t(no) * 4, hipMemcpyDeviceToHost));
 }
 
 std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids,

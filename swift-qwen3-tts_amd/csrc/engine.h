@@ -21,6 +21,7 @@
 #include "model.h"
 #include "resample_plan.h"
 #include "session_queue.h"
+#include "stretch_plan.h"
 
 namespace q3 {
 
@@ -268,6 +269,8 @@ class Engine {
                                         int sample_rate = 24000);
     // q3tts_resample: host buffers through kernels/resample.hip; one of the rates is 24000 (resample_plan.h)
     void resample(const float* in, int64_t n_in, int in_rate, int out_rate, bool centred, float* out, int64_t cap, int64_t* n_out);
+    // q3tts_time_stretch: a 24 kHz host buffer through kernels/stretch.hip (stretch_plan.h); causal: the decoder stage's form
+    void time_stretch(const float* in, int64_t n_in, float speed, bool causal, float* out, int64_t cap, int64_t* n_out);
     void debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C);
 
     std::vector<std::string> speakers;  // sorted (Qwen3.swift:965-971)
@@ -449,6 +452,11 @@ class Engine {
     std::vector<std::unique_ptr<ResamplerDev>> resamplers_;
     DevBuf<float> rs_out_dev_;
     DevBuf<int32_t> rs_len_dev_;
+    struct StretchDev {  // the same for the synthesis hops q3tts_time_stretch has been asked for
+        StretchPlan plan;
+        DevBuf<float> fade;
+    };
+    std::vector<std::unique_ptr<StretchDev>> stretchers_;
     const ResamplerDev& resampler(int in_rate, int out_rate);
     // `audio` (host, n samples at in_rate, finite) -> device buffer of *n_out samples at out_rate, queued on st_
     const float* resample_upload(const float* audio, int64_t n, int in_rate, int out_rate, bool centred, int64_t* n_out);

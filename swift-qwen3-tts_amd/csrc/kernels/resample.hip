@@ -78,6 +78,7 @@ void launch_resample(const ResampleArgs& a, hipStream_t st) {
     const int64_t max_out = (a.max_in * a.L + a.M - 1) / a.M;
     const int64_t gx = (max_out + kTile - 1) / kTile;
     Q3_CHECK(gx <= 0x7fffffff && a.B <= 65535, 3, "Invalid input: too many samples or rows in one resampling call");
+    (void)hipGetLastError();  // the runtime's last-error slot is sticky: an earlier, handled failure must not be read as this launch's
     hipLaunchKernelGGL(resample_kernel, dim3(unsigned(gx), unsigned(a.B)), dim3(kTile), lds, st, a);
     Q3_HIP(hipGetLastError());
 }

@@ -5,7 +5,7 @@ audio seconds / generation seconds (:303), 16-bit WAV output (:134-165), peak me
     python -m qwen3tts --model DIR --text "..." [--speaker NAME] [--instruct "..."] [--language auto]
                        [--temperature 0.9] [--top-k 50] [--max-tokens 2048] [--output output.wav]
                        [--reference-audio clip.wav --reference-text "..." [--resample-reference]]
-                       [--output-sample-rate 8000|12000|16000|22050|24000|32000|44100|48000]
+                       [--output-sample-rate 8000|12000|16000|22050|24000|32000|44100|48000] [--speed 0.5..2.0]
 
 The model directory must hold the tokenizer files the checkpoints ship (tokenizer.json or vocab.json + merges.txt),
 as the reference's postLoadHook requires (Qwen3.swift:1456-1459)."""
@@ -33,6 +33,8 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--output-sample-rate", type=int, default=0,
                     help="new: rate of the written audio (0 = 24000); resampled on the device behind the decoder")
+    ap.add_argument("--speed", type=float, default=0.0,
+                    help="new: speaking rate, pitch preserved (0 or 1 = off, 0.5 .. 2.0); stretched on the device behind the decoder")
     ap.add_argument("--resample-reference", action="store_true",
                     help="new: resample a reference clip that is not 24 kHz on the device instead of feeding it in as it is")
     a = ap.parse_args(argv)
@@ -56,8 +58,11 @@ def main(argv=None) -> int:
     print("Loading model...")
     t0 = time.time()
     model = Qwen3TTSModel.from_pretrained(a.model, device=a.device, max_batch=1, max_frames=min(a.max_tokens, 2048) + 8,
-                                          max_prompt=1024, output_sample_rate=a.output_sample_rate)
+                                          max_prompt=1024, output_sample_rate=a.output_sample_rate,
+                                          speed=a.speed)
     print(f"Model loaded in {time.time() - t0:.2f}s")
+    if a.speed not in (0.0, 1.0):
+        print(f"Speed: {model.speed:.4f}x (synthesis hop {model.stretch_hs}, delay {model.stretch_delay_samples} samples)")
     print()
     print("Generating audio...")
     t1 = time.time()

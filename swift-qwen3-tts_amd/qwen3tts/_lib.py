@@ -20,7 +20,7 @@ class LoadOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_batch", C.c_int32), ("max_frames", C.c_int32),
                 ("max_prompt", C.c_int32), ("use_graph", C.c_int32), ("weights_from_broadcast", C.c_int32),
                 ("n_streams", C.c_int32), ("codec_overlap_cus", C.c_int32), ("codec_fp32", C.c_int32),
-                ("output_sample_rate", C.c_int32)]
+                ("output_sample_rate", C.c_int32), ("speed", C.c_float)]
 
 
 class CommId(C.Structure):  # q3tts_comm_id == ncclUniqueId
@@ -184,6 +184,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "q3tts_resample"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_voice_create_rate.argtypes = [vp, f32p, C.c_int64, C.c_int32, i32p, C.c_int32, C.POINTER(vp)]
         L.q3tts_resample.argtypes = [vp, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, f32p, C.c_int64, C.POINTER(C.c_int64)]
+    if hasattr(L, "q3tts_time_stretch"):  # (the same)
+        L.q3tts_model_get_speed.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.q3tts_time_stretch.argtypes = [vp, f32p, C.c_int64, C.c_float, C.c_int32, f32p, C.c_int64, C.POINTER(C.c_int64)]
     L.q3tts_voice_free.argtypes = [vp, vp]
     L.q3tts_voice_free.restype = None
     L.q3tts_voice_get_info.argtypes = [vp, C.POINTER(VoiceInfo)]

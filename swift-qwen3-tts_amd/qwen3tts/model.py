@@ -162,9 +162,12 @@ class Qwen3TTSModel:
                         max_prompt: int = 512, use_graph: bool = True,
                         weights_from_broadcast: bool = False, n_streams: int = 0,
                         codec_overlap_cus: int = 0, codec_fp32: bool = False,
-                        output_sample_rate: int = 0) -> "Qwen3TTSModel":
+                        output_sample_rate: int = 0, speed: float = 0.0) -> "Qwen3TTSModel":
         """output_sample_rate (q3tts_load_opts.output_sample_rate): 0 = 24000; 8000, 12000, 16000, 22050, 32000, 44100 or
-        48000 make every waveform of this handle leave at that rate (sample_rate and info.samples_per_frame report it)."""
+        48000 make every waveform of this handle leave at that rate (sample_rate and info.samples_per_frame report it).
+        speed (q3tts_load_opts.speed): 0 or 1.0 = off; 0.5 .. 2.0 make this handle speak that much faster, pitch preserved,
+        through the time stretch in the decoder's tail (`speed`, `stretch_hs` and `stretch_delay_samples` report what was
+        chosen, info.samples_per_frame follows)."""
         lib = L.lib()
         o = L.LoadOpts()
         lib.q3tts_default_load_opts(C.byref(o))
@@ -175,6 +178,7 @@ class Qwen3TTSModel:
         o.codec_overlap_cus = codec_overlap_cus
         o.codec_fp32 = 1 if codec_fp32 else 0
         o.output_sample_rate = int(output_sample_rate)
+        o.speed = float(speed)
         h = C.c_void_p()
         st = lib.q3tts_model_load(model_path.encode(), C.byref(o), C.byref(h))
         if st != 0:
@@ -204,6 +208,26 @@ class Qwen3TTSModel:
     @property
     def sample_rate(self) -> int:
         return self.info.sample_rate
+
+    def _speed(self):
+        s, hs, d = C.c_float(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.q3tts_model_get_speed(self._h, C.byref(s), C.byref(hs), C.byref(d)))
+        return float(s.value), int(hs.value), int(d.value)
+
+    @property
+    def speed(self) -> float:
+        """The effective speaking rate 480 / Hs of this handle (1.0: the time stretch is off)."""
+        return self._speed()[0]
+
+    @property
+    def stretch_hs(self) -> int:
+        """The time stretch's synthesis hop Hs (480: off); a frame yields 4 * Hs samples at 24 kHz."""
+        return self._speed()[1]
+
+    @property
+    def stretch_delay_samples(self) -> int:
+        """The delay D of the causal time stretch in 24 kHz samples (q3tts.h, "Speaking rate")."""
+        return self._speed()[2]
 
     @property
     def tts_model_type(self) -> str:
@@ -269,6 +293,16 @@ class Qwen3TTSModel:
         n = C.c_int64(0)
         self._check(self._lib.q3tts_resample(self._h, a.ctypes.data_as(L.f32p), a.size, int(in_rate), int(out_rate),
                                              1 if centred else 0, out.ctypes.data_as(L.f32p), out.size, C.byref(n)))
+        return out[: n.value]
+
+    def time_stretch(self, audio: np.ndarray, speed: float, causal: bool = False) -> np.ndarray:
+        """q3tts_time_stretch: the engine's pitch-preserving time stretch on the device, for 24 kHz audio (include/q3tts.h,
+        "Speaking rate"). causal: the delayed form the decoder's stage uses; otherwise the whole form (no delay)."""
+        a = np.ascontiguousarray(np.asarray(audio, np.float32).reshape(-1))
+        out = np.zeros(max(1, 2 * a.size + 960), np.float32)  # (Hs <= 960 = 2 Ha, one hop of rounding)
+        n = C.c_int64(0)
+        self._check(self._lib.q3tts_time_stretch(self._h, a.ctypes.data_as(L.f32p), a.size, float(speed), 1 if causal else 0,
+                                                 out.ctypes.data_as(L.f32p), out.size, C.byref(n)))
         return out[: n.value]
 
     @staticmethod

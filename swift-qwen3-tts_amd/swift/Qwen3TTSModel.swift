@@ -130,9 +130,11 @@ public final class Qwen3TTSModel {
 
     /// fromPretrained(_:) -- Qwen3.swift:1382. `outputSampleRate` (new; 0 = 24000): 8000, 12000, 16000, 22050, 32000, 44100 or
     /// 48000 make every waveform of this model leave at that rate, resampled on the device behind the decoder
-    /// (q3tts_load_opts.output_sample_rate); `sampleRate` reports it.
+    /// (q3tts_load_opts.output_sample_rate); `sampleRate` reports it. `speed` (new; 0 or 1 = off): 0.5 ... 2.0 make the model
+    /// speak that much faster, pitch preserved, through the time stretch in the decoder's tail (q3tts_load_opts.speed);
+    /// `speed` / `stretchDelaySamples` report what was chosen.
     public static func fromPretrained(_ modelPath: String, device: Int32 = 0, maxBatch: Int32 = 1,
-                                      outputSampleRate: Int32 = 0) async throws -> Qwen3TTSModel {
+                                      outputSampleRate: Int32 = 0, speed: Float = 0) async throws -> Qwen3TTSModel {
         // Qwen3.swift:1386-1388: the same decode of the same file (a malformed config fails here, before the engine sees it)
         let configData = try Data(contentsOf: URL(fileURLWithPath: modelPath).appendingPathComponent("config.json"))
         let config = try JSONDecoder().decode(Qwen3TTSModelConfig.self, from: configData)
@@ -141,6 +143,7 @@ public final class Qwen3TTSModel {
         opts.device = device
         opts.max_batch = maxBatch
         opts.output_sample_rate = outputSampleRate
+        opts.speed = speed
         var h: OpaquePointer?
         let st = q3tts_model_load(modelPath, &opts, &h)
         guard st == Q3TTS_OK, let h else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(nil))) }
@@ -152,6 +155,10 @@ public final class Qwen3TTSModel {
     }
 
     public var sampleRate: Int { Int(info.sample_rate) }                                    // Qwen3.swift:1262
+    /// The effective speaking rate 480 / Hs of this model (1.0: the time stretch is off) -- q3tts_model_get_speed
+    public var speed: Float { var s: Float = 1; q3tts_model_get_speed(handle, &s, nil, nil); return s }
+    /// The delay of the causal time stretch in 24 kHz samples (0: off)
+    public var stretchDelaySamples: Int { var d: Int32 = 0; q3tts_model_get_speed(handle, nil, nil, &d); return Int(d) }
     public var ttsModelType: String { withUnsafeBytes(of: info.tts_model_type) { String(cString: $0.bindMemory(to: CChar.self).baseAddress!) } }
     public var supportsVoiceCloning: Bool { info.supports_voice_cloning != 0 }                // Qwen3.swift:1210
     public var hasVoiceCloning: Bool { info.has_voice_cloning != 0 }                          // Qwen3.swift:61
@@ -313,6 +320,18 @@ public final class Qwen3TTSModel {
         var n: Int64 = 0
         let st = audio.withUnsafeBufferPointer { a in
             q3tts_resample(handle, a.baseAddress, Int64(a.count), Int32(inRate), Int32(outRate), centred ? 1 : 0, &out, Int64(out.count), &n)
+        }
+        guard st == Q3TTS_OK else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
+        return Array(out.prefix(Int(n)))
+    }
+
+    /// q3tts_time_stretch: the engine's pitch-preserving time stretch on the device, for 24 kHz audio (q3tts.h, "Speaking
+    /// rate"). `causal`: the delayed form of the decoder's stage; otherwise the whole form (no delay).
+    public func timeStretch(_ audio: [Float], speed: Float, causal: Bool = false) throws -> [Float] {
+        var out = [Float](repeating: 0, count: max(1, 2 * audio.count + 960))
+        var n: Int64 = 0
+        let st = audio.withUnsafeBufferPointer { a in
+            q3tts_time_stretch(handle, a.baseAddress, Int64(a.count), speed, causal ? 1 : 0, &out, Int64(out.count), &n)
         }
         guard st == Q3TTS_OK else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(handle))) }
         return Array(out.prefix(Int(n)))

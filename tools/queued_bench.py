@@ -392,10 +392,14 @@ def main():
                     help="--session: every request's content arrives at this rate; open-text requests against whole submits")
     ap.add_argument("--output-sample-rate", type=int, default=0, metavar="R",
                     help="load the model with q3tts_load_opts.output_sample_rate = R (0: the decoder's own 24000)")
+    ap.add_argument("--speed", type=float, default=0.0, metavar="S",
+                    help="load the model with q3tts_load_opts.speed = S (0: off; 0.5 .. 2.0: the time stretch in the decoder's tail)")
     ap.add_argument("--only-stream", action="store_true", help="with --stream: skip the static / queued comparison in front of it")
     args = ap.parse_args()
     from qwen3tts import Qwen3TTSModel, RequestSampling
     rate_kw = dict(output_sample_rate=args.output_sample_rate) if args.output_sample_rate else {}
+    if args.speed:
+        rate_kw["speed"] = args.speed
 
     ckpt = bench.ensure_checkpoint(args.preset, 0, None)
     if args.voices > 0:  # (an ICL prompt carries the reference text and one row per reference frame: 3 s are 38 frames)

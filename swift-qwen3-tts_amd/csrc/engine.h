@@ -7,6 +7,7 @@
 #pragma once
 #include <atomic>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <memory>
 #include <condition_variable>
@@ -19,6 +20,7 @@
 #include "../../include/q3tts.h"
 #include "kernels.h"
 #include "model.h"
+#include "queue_slots.h"
 #include "resample_plan.h"
 #include "session_queue.h"
 #include "stretch_plan.h"
@@ -95,10 +97,15 @@ using MallocPtr = std::unique_ptr<T, FreeDeleter>;  // std::malloc'd host memory
 // on (chunk, window, lookahead) and on the codec path (two-plane / float16 / fp32 kernels; `bytes` guards the layout) alone --
 // not on the row, the row count or the lane. Kept beside the group's voices, read by any lane, dropped with the voice.
 struct PrefixCache {
-    struct Entry {
+    struct Key {
         const Voice* voice = nullptr;
         int chunk = 0, window = 0, lookahead = 0, path = 0;
         size_t bytes = 0;
+        bool operator==(const Key& o) const {
+            return voice == o.voice && chunk == o.chunk && window == o.window && lookahead == o.lookahead && path == o.path && bytes == o.bytes;
+        }
+    };
+    struct Entry : Key {
         DevBuf<uint8_t> blob;
         hipEvent_t ready = nullptr;  // behind the save: a restore on another stream waits for it
         ~Entry() {
@@ -108,19 +115,16 @@ struct PrefixCache {
     std::mutex mu;
     std::vector<std::shared_ptr<Entry>> entries;
     std::atomic<int64_t> restored{0};  // admissions served from a saved state since the model was loaded (q3tts_debug_prefix_states)
-    std::shared_ptr<Entry> find(const Voice* v, int chunk, int window, int lookahead, int path, size_t bytes) {
+    std::shared_ptr<Entry> find(const Key& k) {
         std::lock_guard<std::mutex> lk(mu);
         for (auto& e : entries)
-            if (e->voice == v && e->chunk == chunk && e->window == window && e->lookahead == lookahead && e->path == path && e->bytes == bytes)
-                return e;
+            if (*e == k) return e;
         return nullptr;
     }
     void publish(std::shared_ptr<Entry> n) {  // (two lanes may have primed the same voice side by side: the first one stays)
         std::lock_guard<std::mutex> lk(mu);
         for (auto& e : entries)
-            if (e->voice == n->voice && e->chunk == n->chunk && e->window == n->window && e->lookahead == n->lookahead && e->path == n->path &&
-                e->bytes == n->bytes)
-                return;
+            if (*e == *n) return;
         entries.push_back(std::move(n));
     }
     void drop(const Voice* v) {
@@ -407,6 +411,17 @@ class Engine {
     // rows whose waveform left the fp16 range of the default codec kernels are decoded again on the fp32 matrix cores
     // (the reference's range) before end() hands them out; returns the rows that are non-finite even then
     std::vector<int> redo_rows_fp32(Job& J);
+    // its mechanical part, shared with a streamed queue's held requests: rows of dframes[i] frames, whose codes place(i, dst,
+    // cst) puts on the device, through the exact decode on codec_stream(false); returns with the PCM on the host
+    struct ExactDecode {
+        PinnedBuf<float> pcm;   // [rows][Fd * upsample]
+        PinnedBuf<int32_t> nf;  // [rows]: non-finite even so
+        int Fd = 0;
+    };
+    ExactDecode decode_rows_fp32(const std::vector<int>& dframes, const std::function<void(int, int32_t*, hipStream_t)>& place);
+    // a streamed request held back at the chunk that starts at sample `at`: samples [at, ns) of its audio from the exact decode
+    // (src: its sample 0 there), then the AUDIO_CHUNK events it is still owed, in steps of `step` samples
+    void refire_held(float* own, const float* src, int64_t at, int64_t ns, int64_t step, q3tts_event_cb cb, void* user, int index);
     void staging_loop();
     std::thread stager_;
     std::mutex stage_mu_;
@@ -530,17 +545,7 @@ class Engine {
     std::vector<int32_t> q_text_ids_;        // staging of a boundary's new ids (alive until the launch has been waited for)
     std::vector<int32_t> q_host_;  // staging of the sub-batch's arrays (alive until the next boundary's sync)
     void ensure_queue_ws();
-    struct QSlot {
-        int req = -1;      // request in this slot, -1: empty
-        int since = 0;     // frame steps since its admission
-        int reported = 0;  // TOKEN events delivered
-        int np = 0;
-        double t0 = 0;     // admission (host clock)
-        int cap = 0;       // its max_frames
-        // an open-text request: its text may still grow (open), its row waits for text on the device (starved)
-        bool open = false, starved = false;
-        int n_content = 0;  // content tokens so far
-    };
+    struct QueueRun;  // the slot loop of one run_queued call (engine_queue.cc); its slots are QSlot (queue_slots.h)
     struct QLive;
     // a boundary's appends (run_queued): new text rows and closes for the slots' open-text requests, one launch on st_
     void apply_text_appends(QueueShared& q, std::vector<QSlot>& sl, std::unordered_map<int, QLive>& live);

@@ -12,7 +12,7 @@ from conftest import tiny_request
 
 pytestmark = pytest.mark.gpu
 
-BURST = 9  # frame steps per burst of a one-lane engine (engine.cc: max_inflight_frames / 2); EOS is seen at a burst boundary
+BURST = 9  # frame steps per burst of a one-lane engine (engine_queue.cc: max_inflight_frames / 2); EOS is seen at a burst boundary
 
 
 def _req(row, n_text, max_tokens, speaker="aiden", language="english", n_instruct=0):

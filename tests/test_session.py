@@ -15,7 +15,7 @@ from conftest import tiny_request
 
 pytestmark = pytest.mark.gpu
 
-BURST = 9   # frame steps per burst of a one-lane engine (engine.cc: max_inflight_frames / 2)
+BURST = 9   # frame steps per burst of a one-lane engine (engine_queue.cc: max_inflight_frames / 2)
 WAIT = 60   # seconds: every result() below
 SPF = 1920
 C_, W_, L_ = 8, 32, 4

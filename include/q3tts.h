@@ -906,6 +906,68 @@ typedef struct {
 } q3tts_conv_debug;
 q3tts_status q3tts_debug_conv(q3tts_model* m, q3tts_conv_debug* a);
 
+/* One launch of a non-GEMM row kernel of the codec decoder (csrc/kernels/codec_misc.hip) or of the voice-clone front end
+ * (csrc/kernels/voice_frontend.hip) on caller-supplied host buffers, through the product's own launch_* function. The call
+ * allocates its own device buffers and frees them; it touches neither the model's weights nor its caches. Read-only operands
+ * (in[]) are uploaded whole; every output and in/out buffer (io[]) is uploaded as the caller filled it and returned whole, so
+ * that a sentinel shows what was and was not written. Device tables of pointers (cb_rest, cb / c2, RollDesc) are built from
+ * offsets the caller gives into one pool; rvq_encode's codebooks are handed over as a checkpoint holds them ([bins][dim]) and
+ * transposed with the loader's own code (csrc/model.h transpose_codebook). A slot an op does not name must be NULL; a named
+ * slot holds exactly the bytes its shape states ("pool": any whole number of floats) unless marked optional ("?").
+ * Per op: p[] and f[] in order, then the in[] and io[] slots in order. Sizes in elements; fp32 unless stated; i32 / i64 = int32_t /
+ * int64_t.
+ *    0 rvq_gather          p: B, Fmax, code_stride_frames (csf), n_rest, inner, rows_first, rows_rest
+ *                          in: codes i32 [B][csf][16], cb_first [rows_first][inner], cb_rest pool, frames i32 [B], first_frame? i32 [B],
+ *                          cb_rest offsets i64 [n_rest]; io: out [B][Fmax][2 inner]
+ *    1 rmsnorm_f32         p: B, Tmax, ppf, C; f: eps; in: x [B][Tmax][C], w [C], frames i32 [B]; io: out [B][Tmax][C]
+ *    2 dwconv_ln           p: B, Tmax, ppf, C, hist, margin; f: eps; in: x [B][Tmax][C], dw_w [C][7], dw_b [C], ln_w [C], ln_b [C],
+ *                          frames i32 [B]; io: out [B][Tmax][C]
+ *    3 silu_mul_f32        p: B, Tmax, ppf, I; in: gu [B][Tmax][2 I], frames i32 [B]; io: out [B][Tmax][I]
+ *    4 attn_full_f32       p: B, Tmax, heads; in: qkv [B][Tmax][3 heads 64], frames i32 [B]; io: out [B][Tmax][heads 64]
+ *    5 roll_history        p: B, bstride, keep, chunk; io: buf [(B - 1) bstride + keep + chunk]
+ *    6 roll_history_rows   p: B, Tal, hist, chunk, n_desc, only_row; in: desc i64 [n_desc][3], mode? i32 [B], take? i32 [B];
+ *                          io: pool, nonfinite? i32 [B]
+ *    7 history_state_rows  p: B, Tal, hist, n_desc, row, load; in: desc i64 [n_desc][3]; io: pool, blob pool (bytes), nonfinite? i32 [B]
+ *    8 stream_take_chunk   p: B, front_bstride, lat_bstride, latent, max_take, lat_off; in: front [B][front_bstride], off i32 [B],
+ *                          take i32 [B]; io: lat [B][lat_bstride]
+ *    9 enc_init_conv       p: B, S, C, K, out_bstride; in: audio [B][S], w [C][K], bias [C]; io: out [B][out_bstride]
+ *   10 layernorm_f32       p: B, T, C, x_bstride, out_bstride; f: eps; in: x [B][x_bstride], w [C], b [C]; io: out [B][out_bstride]
+ *   11 rope_qk_f32         p: B, T, heads; in: cos [T][32], sin [T][32]; io: qkv [B][T][3 heads 64]
+ *   12 attn_causal_f32     p: B, T, heads; in: qkv [B][T][3 heads 64]; io: out [B][T][heads 64]
+ *   13 rvq_encode          p: B, Tmax, ldx, x_bstride, dim, bins, n_layers, layer0, xcol; in: x [B][x_bstride], valid i32 [B],
+ *                          code_off i64 [B], cb pool, c2 pool, cb offsets i64 [n_layers], c2 offsets i64 [n_layers]; io: codes i32 pool
+ *   14 log_mel             p: T, ld, nfreq, n_mels; in: spec [T][ld], fb [nfreq][n_mels]; io: out [T][n_mels]
+ *   15 time_stats          p: T, C, ld; f: eps; in: x [T][ld]; io: mean [C], std? [C]
+ *   16 scale_res           p: T, C, ldx, ldr, ldo; in: x [T][ldx], se [C], res [T][ldr]; io: out [T][ldo]
+ *   17 asp_concat          p: T, C; in: x [T][C], mean [C], std [C]; io: out [T][3 C]
+ *   18 asp_pool            p: T, C; f: eps; in: att [T][C], x [T][C]; io: pooled [2 C]
+ *   19 mask_tail           p: B, Tpad, C, bstride; in: valid i32 [B]; io: x [B][bstride]
+ *   20 copy2d_f32          p: T, C, lds, ldd; in: src [T][lds]; io: dst [T][ldd]
+ * Layouts as a decode has them. Ops 1-4: batch entry b has frames[b] * ppf valid rows (op 4: frames[b]). Op 2: row 0 of a
+ * sequence sits `margin` >= hist rows into the allocation's Tmax rows, margin + frames[b] * ppf <= Tmax; out is laid out the same.
+ * Op 5: row b's `keep` margin floats start at b * bstride, its chunk behind them. Ops 6, 7: desc[i] = {offset of tensor i in
+ * the pool (floats), frame_floats, state_off (bytes into the blob)}, tensor i is [B][Tal][frame_floats]; mode / take / nonfinite
+ * given or NULL as launch_roll_history_rows takes them. Op 8: lat row b starts lat_off floats into its lat_bstride. Op 13: the
+ * kernel reads columns xcol .. xcol + dim of x's rows; cb offsets point at [bins][dim] tables in the cb pool, c2 offsets at
+ * [bins] in the c2 pool; row b owns codes[code_off[b] .. code_off[b] + (layer0 + n_layers) * valid[b]).
+ * Every argument that becomes an address, a grid size or an LDS size is checked on the host before anything is launched
+ * (Q3TTS_ERR_INVALID_INPUT): the slot sizes against the strides and counts given; the launchers' own conditions (dwconv_ln
+ * C <= 4096, enc_init_conv K <= 17, rvq_encode dim <= 4096, latent % 4, keep % 4, chunk >= hist && Tal == hist + chunk, head width
+ * 64 by construction); 16-byte alignment of whatever a kernel loads as float4 (strides, offsets, keep, chunk in whole float4s);
+ * off + take inside the front buffer; code ranges disjoint and inside codes; table ranges inside their pools; dynamic LDS
+ * (dim, nfreq floats) <= 64 KiB; frames / valid / take / mode / first_frame values inside the buffers they index.
+ * check_only != 0 runs only these checks: no GPU is needed and m may be NULL. */
+typedef struct {
+    int32_t op, check_only;
+    int32_t p[16];
+    float f[4];
+    const void* in[8];
+    int64_t in_bytes[8];
+    void* io[4];
+    int64_t io_bytes[4];
+} q3tts_rowop_debug;
+q3tts_status q3tts_debug_rowop(q3tts_model* m, q3tts_rowop_debug* a);
+
 /* Codec decoder with intermediate activations (SpeechTokenizer.swift:754-784) for one utterance:
  * stage names: "quantizer","pre_conv","pre_transformer","upsample0","upsample1","init_conv",
  * "block0".."block3". Output is channels-last [T][C] float32; *T,*C receive the shape. */

@@ -216,6 +216,9 @@ __global__ __launch_bounds__(256) void rvq_encode_kernel(const float* x, int ldx
                     v = bv[w];
                     i = bi[w];
                 }
+            // no distance below +inf (a frame of NaN / inf from a damaged checkpoint or an overflow upstream): `<` never fired and
+            // the index is still the initial one, which must become neither a code nor a row of embt. Bin 0, as the sampler's rule.
+            if (i == 0x7fffffff) i = 0;
             best_s = i;
             codes[(size_t)layer * T + t] = i;
         }

@@ -570,6 +570,12 @@ inline void split_h2(float w, int s, uint16_t& hi, uint16_t& lo) {
 
 // ---- the packers themselves: pure host functions (the Builder wrappers below upload what they fill; q3tts_debug_conv packs a
 //      caller's weights with the same code) ----
+// [bins][dim] -> [dim][bins]: the search kernel reads one dimension of 64 consecutive codes per wave load
+void transpose_codebook(const float* emb, int bins, int dim, std::vector<float>& embt) {
+    embt.resize(size_t(bins) * dim);
+    for (int r = 0; r < bins; ++r)
+        for (int d = 0; d < dim; ++d) embt[size_t(d) * bins + r] = emb[size_t(r) * dim + d];
+}
 // w [N][K][Cin] fp32 -> [K][chunks of 32 input channels][N][2 planes][32] fp16 (zero beyond Cin) + 2^-s per row
 void pack_conv_h2(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& p, std::vector<float>& sc) {
     const int chunks = (c.Cin + 31) / 32;
@@ -1023,11 +1029,7 @@ void build_codec_encoder(Builder& b, const TMap& t, const CodecEncoderConfig& ec
         }
         HostTensor embt;  // [dim][bins]: the search kernel reads one dimension of 64 consecutive codes per wave load
         embt.shape = {e.dim, e.bins};
-        if (!emb.data.empty()) {
-            embt.data.resize(emb.data.size());
-            for (int r = 0; r < e.bins; ++r)
-                for (int d = 0; d < e.dim; ++d) embt.data[size_t(d) * e.bins + r] = emb.data[size_t(r) * e.dim + d];
-        }
+        if (!emb.data.empty()) transpose_codebook(emb.data.data(), e.bins, e.dim, embt.data);
         e.cb[size_t(j)] = b.put_f32(embt);
         e.c2[size_t(j)] = b.put_f32(c2);
     }

@@ -75,6 +75,9 @@ void pack_conv_h1(const ConvW& c, const std::vector<float>& w, std::vector<uint1
 void pack_conv_h1_perm(const ConvW& c, const std::vector<float>& w, std::vector<uint16_t>& tiles);                      // ConvW::w1p
 void snake_params(const std::vector<float>& alpha, const std::vector<float>& beta, std::vector<float>& ea, std::vector<float>& ib);
 void snake_params_f16(const std::vector<float>& alpha, const std::vector<float>& beta, std::vector<float>& ea16, std::vector<float>& ib16);
+// An encoder codebook [bins][dim] as the residual-VQ search reads it, [dim][bins] (EncW::cb; q3tts_debug_rowop transposes a
+// caller's codebooks with it)
+void transpose_codebook(const float* emb, int bins, int dim, std::vector<float>& embt);
 
 struct CodecW {
     // RVQ (SpeechTokenizer.swift:175-227): codebooks [size][inner], output projections fused

@@ -148,6 +148,37 @@ class ConvDebug(C.Structure):  # q3tts_conv_debug
                 ("out", C.c_void_p), ("out2", C.c_void_p), ("pcm", f32p), ("nonfinite", i32p)]
 
 
+class RowopDebug(C.Structure):  # q3tts_rowop_debug
+    _fields_ = [("op", C.c_int32), ("check_only", C.c_int32), ("p", C.c_int32 * 16), ("f", C.c_float * 4),
+                ("in", C.c_void_p * 8), ("in_bytes", C.c_int64 * 8), ("io", C.c_void_p * 4), ("io_bytes", C.c_int64 * 4)]
+
+
+ROWOPS = ("rvq_gather", "rmsnorm_f32", "dwconv_ln", "silu_mul_f32", "attn_full_f32", "roll_history", "roll_history_rows",
+          "history_state_rows", "stream_take_chunk", "enc_init_conv", "layernorm_f32", "rope_qk_f32", "attn_causal_f32", "rvq_encode",
+          "log_mel", "time_stats", "scale_res", "asp_concat", "asp_pool", "mask_tail", "copy2d_f32")  # q3tts_rowop_debug.op
+
+
+def rowop(handle, op, p, f, ins, ios, check_only=False):
+    """q3tts_debug_rowop (the slot table: include/q3tts.h). op: a name of ROWOPS; p / f: the int and float parameters; ins: the
+    read-only operands and ios: the in/out buffers, numpy arrays or None, in slot order. The in/out arrays are written in place.
+    check_only: the host checks alone (handle may be None; no GPU). Returns the status."""
+    a = RowopDebug(op=ROWOPS.index(op), check_only=1 if check_only else 0)
+    for i, v in enumerate(p):
+        a.p[i] = int(v)
+    for i, v in enumerate(f):
+        a.f[i] = float(v)
+    inp = getattr(a, "in")  # (the header's name is a Python keyword)
+    for i, v in enumerate(ins):
+        if v is not None:
+            assert v.flags["C_CONTIGUOUS"]
+            inp[i], a.in_bytes[i] = v.ctypes.data, v.nbytes
+    for i, v in enumerate(ios):
+        if v is not None:
+            assert v.flags["C_CONTIGUOUS"] and v.flags["WRITEABLE"]
+            a.io[i], a.io_bytes[i] = v.ctypes.data, v.nbytes
+    return lib().q3tts_debug_rowop(handle, C.byref(a))
+
+
 _lib = None
 
 
@@ -248,6 +279,8 @@ def lib() -> C.CDLL:
         L.q3tts_debug_gemm.argtypes = [vp, C.POINTER(GemmDebug)]
     if hasattr(L, "q3tts_debug_conv"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_conv.argtypes = [vp, C.POINTER(ConvDebug)]
+    if hasattr(L, "q3tts_debug_rowop"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_debug_rowop.argtypes = [vp, C.POINTER(RowopDebug)]
     if hasattr(L, "q3tts_debug_build_decode_codes"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_build_decode_codes.argtypes = [vp, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
     L.q3tts_debug_codec_stage.argtypes = [vp, i32p, C.c_int32, C.c_char_p, f32p, C.c_int64, i32p, i32p]

@@ -951,6 +951,15 @@ class Qwen3TTSModel:
         r.update(out=out, out2=out2, pcm=pcm, nonfinite=nonfinite)
         return r
 
+    def debug_rowop(self, op, p, f=(), ins=(), ios=()):
+        """One launch of a row kernel's launcher on these host buffers (q3tts_debug_rowop; the slot table per op: q3tts.h). op: a
+        name of _lib.ROWOPS; ins: read-only numpy arrays (or None) in slot order; ios: the in/out arrays, copied, launched on and
+        returned as the launch left them."""
+        ios = [None if v is None else np.ascontiguousarray(v).copy() for v in ios]
+        ins = [None if v is None else np.ascontiguousarray(v) for v in ins]
+        self._check(L.rowop(self._h, op, p, f, ins, ios))
+        return ios
+
     def debug_codec_stage(self, codes: np.ndarray, stage: str) -> np.ndarray:
         codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
         F = codes.shape[0]

@@ -107,9 +107,15 @@ typedef struct {
                            stage carries its input's margin and one int32 per row (the last hop's offset) from chunk to chunk.
                            The causal form delays the audio by D 24 kHz samples (0 at 2x, 80 at 1.5x, 480 at 0.8x, 1200 at
                            0.5x): a waveform starts with about D * Hs / 480 samples of silence and its last D input samples are
-                           not spoken (no flush). Hs == 480 is off. Per handle, not per request: the rows of one pass share one
-                           samples-per-frame. Outside [0.5, 2.0], NaN or infinite: Q3TTS_ERR_INVALID_INPUT at load, before any
-                           GPU work */
+                           not spoken (no flush). Hs == 480 is off. This is the handle's speed: what a request without a speed
+                           of its own gets (request_speeds below). Outside [0.5, 2.0], NaN or infinite:
+                           Q3TTS_ERR_INVALID_INPUT at load, before any GPU work */
+    int32_t request_speeds; /* new: non-zero makes the handle admit q3tts_request.speed ("Speaking rate per request" below). The
+                           fade tables of every hop in [240, 960] go to the device once, at load (2.8 MB), and what holds rows of
+                           different speeds is sized for the slowest, 4 * 960 * L / M samples per frame
+                           (q3tts_model_info.max_samples_per_frame). 0 (default): the handle allocates and launches what it
+                           did, and a request with a speed is Q3TTS_ERR_INVALID_INPUT. With the option and no request speed
+                           the samples are those of the same handle without it, bit for bit */
 } q3tts_load_opts;
 
 void q3tts_default_load_opts(q3tts_load_opts* o);
@@ -139,6 +145,9 @@ typedef struct {
     int32_t max_batch;
     int64_t weight_bytes;      /* distinct bytes streamed per decode step (roofline accounting) */
     int32_t speaker_embedding_dim; /* enc_dim of the speaker encoder, 0 when absent */
+    int32_t max_samples_per_frame; /* new: samples per frame of the slowest request the handle admits: 4 * 960 * sample_rate /
+                                      24000 with q3tts_load_opts.request_speeds, samples_per_frame (the handle's own, what a
+                                      request without a speed gets) otherwise */
 } q3tts_model_info;
 q3tts_status q3tts_model_get_info(const q3tts_model* m, q3tts_model_info* out);
 
@@ -175,6 +184,11 @@ typedef struct {
     const char* speaker;  /* NULL = none */
     const char* language; /* NULL = "auto" */
     int32_t max_tokens;   /* 0 = 2048 (reference default) */
+    float speed;          /* new: this request's speaking rate ("Speaking rate per request" below). 0 (default): the handle's.
+                             Otherwise in [0.5, 2.0], on a handle loaded with request_speeds; 1.0 is "no stretch for this
+                             request", whatever the handle's own speed. The field lies in what was padding behind max_tokens:
+                             sizeof(q3tts_request) and Q3TTS_ABI_VERSION are unchanged, and a caller that zeroes the struct
+                             (as every example here does) asks for the handle's speed */
     /* Voice clone -- generateVoiceClone(text:referenceAudio:referenceText:language:...) (Qwen3.swift:1009-1020).
      * ref_audio != NULL selects it; speaker / instruct_ids are then ignored, as in the reference.
      *   ref_audio     = reference waveform, 24 kHz mono float32 (host memory, read during the call; a NaN or infinite
@@ -624,6 +638,31 @@ q3tts_status q3tts_model_get_speed(const q3tts_model* m, float* effective_speed,
 q3tts_status q3tts_time_stretch(q3tts_model* m, const float* in, int64_t n_in, float speed, int32_t causal, float* out, int64_t cap,
                                 int64_t* n_out);
 
+/* ---- Speaking rate per request (new) ---------------------------------------------------------------------------------------
+ * On a handle loaded with q3tts_load_opts.request_speeds a request may set q3tts_request.speed. It then gets, bit for bit, what
+ * a handle loaded with speed = that value (and the same output_sample_rate) gives for the request alone -- status, codes,
+ * n_frames, pcm, n_samples -- whatever the other rows of the batch speak at; the codes never depend on the speed. Hs is chosen
+ * by the rule of q3tts_load_opts.speed with the handle's L / M (the nearest admissible hop, never a refusal for
+ * admissibility); 1.0 is Hs = 480: no stretch for that request. Results count in the request's own samples per frame,
+ * 4 * Hs * L / M: n_samples follows the end trim count(code0 > 0) * samples_per_frame with it, a voice request's cut likewise.
+ * Honoured by q3tts_generate, q3tts_generate_begin / _end, q3tts_generate_queued, q3tts_generate_voices,
+ * q3tts_generate_queued_voices, q3tts_session_submit and q3tts_session_submit_open, with the audio delivered whole and with
+ * streamed audio (audio_window_frames > 0): every AUDIO_CHUNK of the request -- sample_offset = k * C * its own samples per
+ * frame, n_samples, bytes -- is what the request streamed alone on the handle of its speed delivers, whichever request held
+ * the slot before; a voice's saved prefix state is kept per hop. NOT BUILT, Q3TTS_ERR_INVALID_INPUT for a request whose hop
+ * differs from the handle's: the chunked exact decode (audio_chunk_frames > 0 with audio_window_frames == 0) and streamed audio
+ * on a handle with output_sample_rate (the resampler's input margin would need a frame size per row). A request speed whose
+ * hop is the handle's own is the handle's path and is accepted everywhere.
+ * Q3TTS_ERR_INVALID_INPUT before any GPU work, the engine and the session staying usable: a non-zero speed on a handle without
+ * request_speeds; a NaN, an infinity or a value outside [0.5, 2.0]. q3tts_session_submit / _submit_open check on the calling
+ * thread. q3tts_codec_decode*, q3tts_time_stretch and the debug entry points take no request and keep the handle's speed.
+ *
+ * q3tts_request_speed_info: what a request at `speed` gets on this handle (0: the handle's own) -- the effective speed 480 / Hs,
+ * Hs, D in 24 kHz samples and the samples per frame at the output rate; any pointer may be NULL. Host arithmetic alone: no
+ * engine entry, available while a session is open. On a handle without request_speeds every non-zero speed is refused. */
+q3tts_status q3tts_request_speed_info(const q3tts_model* m, float speed, float* effective_speed, int32_t* hs, int32_t* delay_samples,
+                                      int32_t* samples_per_frame);
+
 /* Qwen3TTSSpeechTokenizer.decode (Models/SpeechTokenizer.swift:823-836): codes
  * [batch][max_frames][num_code_groups] -> pcm [batch][max_frames*1920] (caller-allocated),
  * audio_lengths[batch] = count(code0 > 0) * 1920. n_frames[b] <= max_frames are the valid rows. Every code of a valid row is
@@ -977,6 +1016,15 @@ q3tts_status q3tts_debug_codec_stage(q3tts_model* m, const int32_t* codes, int32
 /* The voices' saved tail states (the voices comment above, "streamed voice requests"): how many are held on this handle, their
  * device bytes, and how many admissions have been served from one since the model was loaded (a test hook). */
 q3tts_status q3tts_debug_prefix_states(q3tts_model* m, int32_t* n_states, int64_t* device_bytes, int64_t* n_restored);
+
+/* The time stretch kernel on B host rows with a hop per row, in the causal form with nothing in front (a test hook for the
+ * per-row path of "Speaking rate per request"; works on any handle). x [B][x_stride] at 24 kHz with lens[b] <= x_stride valid
+ * samples, hops[b] in [240, 960] (480 aligns and crossfades like any other hop, as in q3tts_time_stretch; 0: the row is
+ * copied). y [B][y_stride] is uploaded as the caller filled it and comes back whole: row b receives floor(lens[b] / 480) *
+ * hops[b] samples (lens[b] for a copied row), a row of length 0 nothing. A row that does not fit y_stride, a hop outside the
+ * range or B outside 1..4096 is Q3TTS_ERR_INVALID_INPUT. */
+q3tts_status q3tts_debug_stretch_rows(q3tts_model* m, const float* x, const int32_t* lens, const int32_t* hops, int32_t B,
+                                      int64_t x_stride, float* y, int64_t y_stride);
 
 /* The slotted codec stream of a streamed q3tts_generate_queued, driven by the queue's schedule without the talker (a test hook:
  * the real layer widths in seconds). codes [n_reqs][max_frames][16], n_frames[n_reqs] <= max_frames. Requests take the free ones

@@ -129,6 +129,7 @@ void q3tts_default_load_opts(q3tts_load_opts* o) {
     o->codec_fp32 = 0;
     o->output_sample_rate = 0;
     o->speed = 0.0f;
+    o->request_speeds = 0;
 }
 
 void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
@@ -249,6 +250,7 @@ q3tts_status q3tts_model_get_info(const q3tts_model* m, q3tts_model_info* out) {
         out->cp_vocab_size = c.talker.cp.vocab_size;
         out->codec_eos_token_id = c.talker.codec_eos_token_id;
         out->samples_per_frame = cr ? cr->upsample() : (c.has_codec ? c.codec.total_upsample() : c.decode_upsample_rate);
+        out->max_samples_per_frame = cr ? cr->max_upsample() : out->samples_per_frame;
         out->max_batch = m->eng->opts().max_batch;
         out->weight_bytes = md.step_weight_bytes;
     }, false);
@@ -325,6 +327,25 @@ q3tts_status q3tts_model_get_speed(const q3tts_model* m, float* effective_speed,
         if (effective_speed) *effective_speed = float(double(q3::kStretchHa) / double(h));
         if (hs) *hs = h;
         if (delay_samples) *delay_samples = cr ? cr->stretch_delay_samples() : 0;
+    }, false);
+}
+
+q3tts_status q3tts_request_speed_info(const q3tts_model* m, float speed, float* effective_speed, int32_t* hs, int32_t* delay_samples,
+                                      int32_t* samples_per_frame) {
+    return guarded(const_cast<q3tts_model*>(m), [&] {
+        Q3_CHECK(m, 3, "Invalid input: null argument");
+        const q3::CodecRunner* cr = m->eng->codec_runner();
+        Q3_CHECK(cr != nullptr, 1, "Model not initialized: Speech tokenizer not loaded");
+        int h = cr->stretch_hs();
+        if (speed != 0.0f) {  // (a NaN is not 0 and fails the range)
+            Q3_CHECK(cr->request_speeds(), 3, "Invalid input: q3tts_request.speed needs a handle loaded with q3tts_load_opts.request_speeds");
+            h = cr->speed_plan().hs_of(speed);
+            Q3_CHECK(h != 0, 3, "Invalid input: q3tts_request.speed must be 0 (the handle's speed) or between 0.5 and 2.0");
+        }
+        if (effective_speed) *effective_speed = float(double(q3::kStretchHa) / double(h));
+        if (hs) *hs = h;
+        if (delay_samples) *delay_samples = h == q3::kStretchHa ? 0 : q3::stretch_delay(h);
+        if (samples_per_frame) *samples_per_frame = speed == 0.0f ? cr->upsample() : cr->upsample_of(h);
     }, false);
 }
 
@@ -691,6 +712,14 @@ q3tts_status q3tts_debug_prefix_states(q3tts_model* m, int32_t* n_states, int64_
     return guarded(m, [&] {
         Q3_CHECK(m && n_states && device_bytes && n_restored, 3, "Invalid input: null argument");
         m->eng->prefix_cache().stats(n_states, device_bytes, n_restored);
+    });
+}
+
+q3tts_status q3tts_debug_stretch_rows(q3tts_model* m, const float* x, const int32_t* lens, const int32_t* hops, int32_t B, int64_t x_stride,
+                                      float* y, int64_t y_stride) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && x && lens && hops && y, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_stretch_rows(x, lens, hops, B, x_stride, y, y_stride);
     });
 }
 

@@ -16,7 +16,8 @@ size_t kScratchBudget = size_t(24) << 30;  // activation scratch per group of ro
 }
 void CodecRunner::set_scratch_budget(size_t bytes) { kScratchBudget = bytes ? bytes : (size_t(24) << 30); }
 
-CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate, float speed) : m_(m), st_(st) {
+CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate, float speed, bool request_speeds)
+    : m_(m), st_(st) {
     native_ = mid_ = up_ = m.cfg.codec.total_upsample();
     if (speed != 0.0f && speed != 1.0f) {
         Q3_CHECK(speed >= 0.5f && speed <= 2.0f, 3, "Invalid input: speed must be 0 (off) or between 0.5 and 2.0");
@@ -55,6 +56,18 @@ CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int ou
         std::copy(out_plan_.tab.begin(), out_plan_.tab.end(), padded.begin());
         Q3_HIP(hipMemcpy(out_tab_.grow(n), padded.data(), n * 4, hipMemcpyHostToDevice));
     }
+    if (native_ % kStretchHa == 0) rs_plan_.hops_per_frame = native_ / kStretchHa;
+    if (resample_) {
+        rs_plan_.L = out_plan_.L;
+        rs_plan_.M = out_plan_.M;
+    }
+    rs_plan_.handle_hs = stretch_hs();
+    if (request_speeds) {
+        Q3_CHECK(native_ % kStretchHa == 0, 3, "Invalid input: the codec's frame is not a whole number of 480-sample hops: no request speeds");
+        const std::vector<float> all = make_fade_all();
+        Q3_HIP(hipMemcpy(fade_all_.grow(all.size()), all.data(), all.size() * 4, hipMemcpyHostToDevice));
+        rs_ = true;
+    }
     Q3_CHECK(m.cfg.codec.head_dim == 64, 6, "codec transformer head_dim must be 64");
     const char* e = std::getenv("Q3TTS_CODEC_FP32");  // tests switch per model load without touching the load options
     fp32_mfma_ = fp32_convs || (e && e[0] == '1');
@@ -91,6 +104,7 @@ size_t CodecRunner::floats_per_frame() const {
         per_frame = std::max(per_frame, size_t(ppf) * C);
     }
     if (stretch_) per_frame = std::max(per_frame, size_t(mid_));  // the stretched signal in front of the resampler
+    if (rs_) per_frame = std::max(per_frame, size_t(rs_plan_.max_mid_spf()));  // ... of the slowest row
     return per_frame;
 }
 
@@ -416,7 +430,12 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
         }
         // 7. outSnake -> outConv -> clip (:687-688, :781)
         // (a resampled decode: out_conv's own clip stays, the flags of a non-finite waveform come from it as before)
-        const bool post = resample_ || stretch_;  // stages behind out_conv: its signal goes to one more tail tensor
+        // rows with hops of their own (a one-shot decode with row_hs): the stretch runs from the rows' table and everything
+        // behind it has frames of the slowest row's size, a row's samples packed at the start of its part
+        const bool own_hops = ps.own_hops;
+        const bool stretch = stretch_ || own_hops;
+        const int up = own_hops ? rs_plan_.max_spf() : up_, midf = own_hops ? rs_plan_.max_mid_spf() : mid_;
+        const bool post = resample_ || stretch;  // stages behind out_conv: its signal goes to one more tail tensor
         float* p24 = post ? static_cast<float*>(mem.get(size_t(ppf) * sizeof(float), true)) : nullptr;
         launch([&] {
             const E* x = y + size_t(H) * ppf * w.out_C;
@@ -429,14 +448,14 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
         mem.put(y);
         // X: decode_chunked with a time stretch -- recomputed context frames in front of the new ones; the stages below run on
         // the new frames (frn) and find their input's history in the context (0 everywhere else)
-        const int X = stretch_ ? ps.ctx_frames : 0;
-        const int32_t* frn = (stretch_ && ps.fr_new) ? ps.fr_new : fr;
+        const int X = stretch ? ps.ctx_frames : 0;
+        const int32_t* frn = (stretch && ps.fr_new) ? ps.fr_new : fr;
         // the resampler's input: its first new sample, row stride, samples in memory in front of it, samples per frame
         float* rin = p24 ? p24 + size_t(H) * ppf : nullptr;
         int64_t rin_stride = int64_t(T);
         int rin_hist = H * ppf, rin_frame = ppf;
         float* mid = nullptr;
-        if (stretch_) {
+        if (stretch) {
             // 8. the time stretch (stretch_plan.h): output frame f depends on input up to the end of frame f alone, and on one
             // word of state per row. A stream keeps the word in a tensor of its own, one entry per frame: the stage reads the
             // entry of the frame in front of the chunk (the margin's last: zero behind a reset, i.e. hop 0 comes next) and
@@ -445,17 +464,17 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
             float* sy = nullptr;
             int64_t sy_stride = 0;
             if (!resample_) {
-                sy = pcm ? pcm + size_t(H + X) * up_ : nullptr;  // (no memory behind the tensors in stream_open's counting pass)
-                sy_stride = int64_t(Trows) * up_;
+                sy = pcm ? pcm + size_t(H + X) * up : nullptr;  // (no memory behind the tensors in stream_open's counting pass)
+                sy_stride = int64_t(Trows) * up;
             } else if (ps.mid_carry) {
                 sy = ps.mid_carry + mid_;
                 sy_stride = ps.mid_stride;
                 rin_hist = mid_;
             } else {
-                mid = static_cast<float*>(mem.get(size_t(mid_) * sizeof(float), true));
-                sy = mid ? mid + size_t(H) * mid_ : nullptr;
-                sy_stride = int64_t(Trows) * mid_;
-                rin_hist = H * mid_;
+                mid = static_cast<float*>(mem.get(size_t(midf) * sizeof(float), true));
+                sy = mid ? mid + size_t(H) * midf : nullptr;
+                sy_stride = int64_t(Trows) * midf;
+                rin_hist = H * midf;
             }
             launch([&] {
                 StretchArgs a{};
@@ -463,6 +482,7 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
                 a.y = sy; a.y_bstride = sy_stride;
                 a.len = frn; a.len_mul = ppf;
                 a.fade = st_fade_; a.hs = st_plan_.hs; a.delay = st_plan_.delay;
+                a.hs_rows = ps.hs_rows; a.fade_all = own_hops ? static_cast<const float*>(fade_all_) : nullptr;
                 a.hist = (H + X) * ppf; a.causal = 1; a.B = nb;
                 if (words) {
                     a.state_in = words + size_t(H - 1) * kStateWords; a.state_in_bstride = int64_t(Trows) * kStateWords;
@@ -477,7 +497,7 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
             if (words) mem.put(words);
             rin = sy;
             rin_stride = sy_stride;
-            rin_frame = mid_;
+            rin_frame = midf;
         }
         if (resample_) {
             // Output frame f depends on input up to the end of frame f alone (q = floor(n M / L) stays inside the frame), and
@@ -485,8 +505,9 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
             launch([&] {
                 ResampleArgs a{};
                 a.x = rin; a.x_bstride = rin_stride;
-                a.y = pcm + size_t(H + X) * up_; a.y_bstride = int64_t(Trows) * up_;
+                a.y = pcm + size_t(H + X) * up; a.y_bstride = int64_t(Trows) * up;
                 a.len = frn; a.len_mul = rin_frame; a.max_in = int64_t(Trows - H - X) * rin_frame;
+                a.len_mul_rows = ps.mid_rows;
                 a.tab = out_tab_; a.L = out_plan_.L; a.M = out_plan_.M; a.K = out_plan_.K;
                 a.hist = rin_hist; a.centred = 0; a.clamp = 1; a.B = nb;
                 launch_resample(a, st_);
@@ -502,7 +523,9 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
 
 int CodecRunner::decode(const int32_t* codes_dev, int code_stride_frames, const std::vector<int>& frames, float** pcm_dev,
                         const std::string& stage, std::vector<float>* stage_out, int* stage_T, int* stage_C, int32_t* nonfinite_host,
-                        bool force_fp32) {
+                        bool force_fp32, const int* row_hs) {
+    Q3_CHECK(!row_hs || rs_, 7, "internal error: per-row hops on a handle without request speeds");
+    const int up = row_hs ? rs_plan_.max_spf() : up_;  // samples per frame of the PCM's layout
     struct Fp32Scope {  // the override ends with the call, however it ends
         bool& flag;
         bool old;
@@ -516,7 +539,7 @@ int CodecRunner::decode(const int32_t* codes_dev, int code_stride_frames, const 
     for (int f : frames) Fmax = std::max(Fmax, f);
     Q3_CHECK(Fmax > 0, 3, "Invalid input: no frames to decode");
     const size_t per_frame = floats_per_frame();
-    const size_t pcm_floats = size_t(B) * Fmax * up_;
+    const size_t pcm_floats = size_t(B) * Fmax * up;
     int rows_per_chunk = int(std::max<size_t>(1, kScratchBudget / (4 * per_frame * Fmax * sizeof(float))));
     rows_per_chunk = std::min(rows_per_chunk, B);
     const size_t big = align_up(size_t(rows_per_chunk) * Fmax * per_frame * sizeof(float), 256);
@@ -524,15 +547,33 @@ int CodecRunner::decode(const int32_t* codes_dev, int code_stride_frames, const 
     float* bufs[4];
     for (int i = 0; i < 4; ++i) bufs[i] = reinterpret_cast<float*>(buf_ + align_up(pcm_floats * sizeof(float), 256) + size_t(i) * big);
     upload_lens(frames.data(), B);
+    if (row_hs) {  // (behind upload_lens' synchronisation: the staging pair is free)
+        if (size_t(2 * B) > rowhs_dev_.capacity()) Q3_HIP(hipStreamSynchronize(st_));
+        rowhs_dev_.grow(size_t(2 * B));
+        rowhs_host_.grow(size_t(2 * B));
+        for (int b = 0; b < B; ++b) {
+            const int hs = row_hs[b];
+            Q3_CHECK(hs >= kStretchHsMin && hs <= kStretchHsMax && rs_plan_.spf(hs) * int64_t(rs_plan_.M) == int64_t(rs_plan_.mid_spf(hs)) * rs_plan_.L,
+                     7, "internal error: a row's synthesis hop is not admissible");
+            rowhs_host_[b] = hs == kStretchHa ? 0 : hs;
+            rowhs_host_[B + b] = rs_plan_.mid_spf(hs);
+        }
+        Q3_HIP(hipMemcpyAsync(rowhs_dev_, rowhs_host_, size_t(2 * B) * 4, hipMemcpyHostToDevice, st_));
+    }
     for (int r0 = 0; r0 < B; r0 += rows_per_chunk) {
         Pass ps{};
         ps.nb = std::min(rows_per_chunk, B - r0);
         ps.row0 = r0;
         ps.fr = lens_dev_ + r0;
+        if (row_hs) {
+            ps.own_hops = true;
+            ps.hs_rows = rowhs_dev_ + r0;
+            ps.mid_rows = rowhs_dev_ + B + r0;
+        }
         ps.stage = &stage; ps.stage_out = stage_out; ps.stage_T = stage_T; ps.stage_C = stage_C;
         run_front(ps, codes_dev + size_t(r0) * code_stride_frames * 16, code_stride_frames, Fmax, bufs);
         Ring ring(bufs, big, size_t(ps.nb) * Fmax);
-        run_tail(ps, ring, bufs[0], Fmax, pcm + size_t(r0) * Fmax * up_);
+        run_tail(ps, ring, bufs[0], Fmax, pcm + size_t(r0) * Fmax * up);
     }
     if (nonfinite_host) Q3_HIP(hipMemcpyAsync(nonfinite_host, nf_dev_, size_t(B) * 4, hipMemcpyDeviceToHost, st_));
     *pcm_dev = pcm;
@@ -669,7 +710,7 @@ void CodecRunner::stream_prefix() {
     const size_t all = size_t(S.cfg.rows) * S.cfg.max_frames * m_.cfg.codec.latent_dim * sizeof(float);
     S.x_all = S.cfg.window < 0 ? reinterpret_cast<float*>(S.take(all)) : nullptr;
     S.lat = static_cast<float*>(S.get(size_t(m_.cfg.codec.latent_dim) * sizeof(float), false));
-    S.pcm = static_cast<float*>(S.get(size_t(up_) * sizeof(float), false));
+    S.pcm = static_cast<float*>(S.get(size_t(S.up) * sizeof(float), false));
 }
 
 void CodecRunner::stream_open(const StreamCfg& cfg) {
@@ -680,6 +721,10 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
     Q3_CHECK(cfg.rows >= 1 && cfg.max_frames >= 1 && cfg.lookahead >= 0, 3, "Invalid input: streamed decode geometry");
     Q3_CHECK(cfg.chunk_frames >= S.hist, 3, "Invalid input: audio_chunk_frames of a streamed decode must be at least " + std::to_string(S.hist));
     S.Tal = S.hist + cfg.chunk_frames;
+    S.own_hops = cfg.per_row && stream_own_hops();
+    S.up = S.own_hops ? rs_plan_.max_spf() : up_;
+    S.row_hs.assign(size_t(cfg.rows), stretch_ ? st_plan_.hs : 0);
+    if (S.own_hops) Q3_CHECK(stretch_lookback(kStretchHsMax) <= S.hist * native_, 7, "internal error: time stretch history beyond the stream's margin");
     S.next_chunk = 0;
     S.front_done = false;
     S.lens_used = 0;
@@ -704,6 +749,7 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
     Pass ps{};
     ps.nb = cfg.rows;
     ps.hist_frames = S.hist;
+    ps.own_hops = S.own_hops;
     stream_prefix();
     run_tail(ps, S, S.lat, S.Tal, S.pcm);
     const size_t need = align_up(S.off, 256);
@@ -740,10 +786,11 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
         Q3_HIP(hipStreamSynchronize(st_));  // `table` is pageable stack memory: the copy below must not outlive it
         Q3_HIP(hipMemcpy(S.roll_desc, table.data(), table.size() * sizeof(RollDesc), hipMemcpyHostToDevice));
         const size_t R = size_t(cfg.rows);
-        S.ring_pcm.grow(size_t(kRingSlots) * R * cfg.chunk_frames * up_);
+        const size_t na = S.own_hops ? 6 : 5;  // (a hop per row as the sixth)
+        S.ring_pcm.grow(size_t(kRingSlots) * R * cfg.chunk_frames * S.up);
         S.ring_nf.grow(size_t(kRingSlots) * R);
-        S.ring_args_host.grow(size_t(kRingSlots) * 5 * R);
-        S.ring_args_dev.grow(size_t(kRingSlots) * 5 * R);
+        S.ring_args_host.grow(size_t(kRingSlots) * na * R);
+        S.ring_args_dev.grow(size_t(kRingSlots) * na * R);
         while (S.ring_ev.size() < size_t(2) * kRingSlots) {
             hipEvent_t e = nullptr;
             Q3_HIP(hipEventCreate(&e));
@@ -751,8 +798,8 @@ void CodecRunner::stream_open(const StreamCfg& cfg) {
         }
         S.ring_busy.assign(size_t(kRingSlots), 0);
         S.ring_next = 0;
-        S.quiet_args_host.grow(size_t(kQuietSlots) * 5 * R);
-        S.quiet_args_dev.grow(size_t(kQuietSlots) * 5 * R);
+        S.quiet_args_host.grow(size_t(kQuietSlots) * na * R);
+        S.quiet_args_dev.grow(size_t(kQuietSlots) * na * R);
         while (S.quiet_ev.size() < size_t(kQuietSlots)) {
             hipEvent_t e = nullptr;
             Q3_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -772,6 +819,14 @@ void CodecRunner::stream_reset_row(int b, int prefix) {
     S.plan.reset_row(b, prefix);
     launch_roll_history_rows(reinterpret_cast<const RollDesc*>(static_cast<uint8_t*>(S.roll_desc)), S.n_roll, S.roll_max_ff, S.Tal, S.hist,
                              S.cfg.chunk_frames, nullptr, b, S.cfg.rows, nf_dev_, st_);
+}
+
+void CodecRunner::stream_set_row_hs(int b, int hs) {
+    Stream& S = stream_;
+    Q3_CHECK(S.open && S.cfg.per_row && b >= 0 && b < S.cfg.rows, 3, "Invalid input: row outside the slotted stream");
+    Q3_CHECK(S.own_hops || hs == stretch_hs(), 7, "internal error: a hop per row in a stream that has one frame size");
+    Q3_CHECK(hs >= kStretchHsMin && hs <= kStretchHsMax, 7, "internal error: a row's synthesis hop is not admissible");
+    if (S.own_hops) S.row_hs[size_t(b)] = hs == kStretchHa ? 0 : hs;
 }
 
 void CodecRunner::stream_save_row(int b, uint8_t* blob_dev) {
@@ -826,8 +881,9 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
         const int slot = emits ? S.ring_next : S.quiet_next;
         S.plan.plan_pass(avail, final_rows, rows);
         // ---- per-row arguments of this pass; everything that becomes an address is checked here ----
-        int32_t* h = emits ? S.ring_args_host + size_t(slot) * 5 * B : S.quiet_args_host + size_t(slot) * 5 * B;
-        int32_t* d = emits ? S.ring_args_dev + size_t(slot) * 5 * B : S.quiet_args_dev + size_t(slot) * 5 * B;
+        const size_t na = S.own_hops ? 6 : 5;
+        int32_t* h = emits ? S.ring_args_host + size_t(slot) * na * B : S.quiet_args_host + size_t(slot) * na * B;
+        int32_t* d = emits ? S.ring_args_dev + size_t(slot) * na * B : S.quiet_args_dev + size_t(slot) * na * B;
         if (!emits && S.quiet_used[size_t(slot)]) Q3_HIP(hipEventSynchronize(S.quiet_ev[size_t(slot)]));  // its last pass has read them
         int Fw = 0, max_take = 0;
         for (int b = 0; b < B; ++b) {
@@ -842,6 +898,7 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
             h[2 * B + b] = r.part ? r.w0 : 0;
             h[3 * B + b] = r.part ? r.f0 - r.w0 : 0;
             h[4 * B + b] = r.part ? 1 : 0;  // roll the participants, leave the others
+            if (S.own_hops) h[5 * B + b] = S.row_hs[size_t(b)];
             Fw = std::max(Fw, h[0 * B + b]);
             max_take = std::max(max_take, h[1 * B + b]);
         }
@@ -857,7 +914,7 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
             S.quiet_next = (slot + 1) % kQuietSlots;
         }
         // (the pinned arguments of a ring slot are rewritten only after the caller has waited for the slot's `done`)
-        Q3_HIP(hipMemcpyAsync(d, h, size_t(5) * B * 4, hipMemcpyHostToDevice, st_));
+        Q3_HIP(hipMemcpyAsync(d, h, na * B * 4, hipMemcpyHostToDevice, st_));
         Pass ps{};
         ps.nb = B;
         ps.stage = &none;
@@ -869,8 +926,12 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
         // ---- the causal tail over the chunks, state carried in the participants' margins ----
         ps.fr = d + 1 * B;
         ps.hist_frames = S.hist;
+        if (S.own_hops) {
+            ps.own_hops = true;
+            ps.hs_rows = d + 5 * B;
+        }
         stream_prefix();  // the same walk over the arena as in stream_open
-        Q3_HIP(hipMemsetAsync(S.pcm, 0, size_t(B) * S.Tal * up_ * 4, st_));
+        Q3_HIP(hipMemsetAsync(S.pcm, 0, size_t(B) * S.Tal * S.up * 4, st_));
         run_tail(ps, S, S.lat, S.Tal, S.pcm);
         Q3_CHECK(int(S.rolls.size()) == S.n_roll, 7, "internal error: the slotted stream's history table is stale");
         // (a row's take is below C at its last chunk and at the end of a reference prefix, after which more chunks follow)
@@ -880,10 +941,11 @@ bool CodecRunner::stream_push_rows(const int32_t* codes_dev, int code_stride_fra
             Q3_HIP(hipEventRecord(S.quiet_ev[size_t(slot)], st_));
             continue;
         }
-        float* pcm_slot = S.ring_pcm + size_t(slot) * B * C * up_;
+        const int up = S.up;
+        float* pcm_slot = S.ring_pcm + size_t(slot) * B * C * up;
         int32_t* nf_slot = S.ring_nf + size_t(slot) * B;
-        Q3_HIP(hipMemcpy2DAsync(pcm_slot, size_t(C) * up_ * sizeof(float), S.pcm + size_t(S.hist) * up_, size_t(S.Tal) * up_ * sizeof(float),
-                                size_t(C) * up_ * sizeof(float), size_t(B), hipMemcpyDeviceToHost, st_));
+        Q3_HIP(hipMemcpy2DAsync(pcm_slot, size_t(C) * up * sizeof(float), S.pcm + size_t(S.hist) * up, size_t(S.Tal) * up * sizeof(float),
+                                size_t(C) * up * sizeof(float), size_t(B), hipMemcpyDeviceToHost, st_));
         Q3_HIP(hipMemcpyAsync(nf_slot, nf_dev_, size_t(B) * 4, hipMemcpyDeviceToHost, st_));
         Q3_HIP(hipEventRecord(done, st_));
         SlotPass sp;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "model.h"
+#include "request_speed_plan.h"
 #include "resample_plan.h"
 #include "stream_plan.h"
 #include "stretch_plan.h"
@@ -25,7 +26,10 @@ class CodecRunner {
     // row (d of the last hop). In a stream the word lives in a tail tensor of its own, one 16-byte entry per frame, so whatever
     // rolls, zeroes, saves or restores margins carries it like any other history; decode_chunked, which recomputes its left
     // context, cannot recompute the word and carries it (and the resampler's input margin) from chunk to chunk.
-    CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false, int output_rate = 0, float speed = 0.0f);
+    // request_speeds: rows of one decode() may speak at speeds of their own (request_speed_plan.h). The fade tables of every
+    // hop go to the device here, once; a decode without a hop table is the handle's own, untouched.
+    CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false, int output_rate = 0, float speed = 0.0f,
+                bool request_speeds = false);
     // codes_dev: [B][code_stride_frames][16] int32 on the device; rows decode frames[b] frames.
     // pcm_dev receives [B][Fmax*upsample] float32 (Fmax = max(frames)); returns Fmax.
     // If `stage` is non-empty the activation after that stage is copied to stage_out ([B][T][C]).
@@ -34,9 +38,13 @@ class CodecRunner {
     // the fp32 matrix-core path (q3tts_load_opts.codec_fp32) has the reference's range.
     // force_fp32: this call contracts on the fp32 matrix cores whatever the runner's default (the engine re-decodes rows
     // that left the fp16 range this way, so that a checkpoint with large activations still gets the reference's waveform).
+    // row_hs (host [B], a handle with request_speeds; nullptr: every row at the handle's speed, the layout above): row b's
+    // synthesis hop (480: no stretch for that row). pcm_dev then receives [B][Fmax * max_upsample()], row b's
+    // frames[b] * upsample_of(row_hs[b]) samples packed at the start of its part; the arithmetic of a row is that of a handle
+    // loaded with the row's speed, bit for bit.
     int decode(const int32_t* codes_dev, int code_stride_frames, const std::vector<int>& frames, float** pcm_dev,
                const std::string& stage = std::string(), std::vector<float>* stage_out = nullptr, int* stage_T = nullptr,
-               int* stage_C = nullptr, int32_t* nonfinite_host = nullptr, bool force_fp32 = false);
+               int* stage_C = nullptr, int32_t* nonfinite_host = nullptr, bool force_fp32 = false, const int* row_hs = nullptr);
     bool fp32_convs() const { return fp32_mfma_; }
     // The same decode with the causal tail (everything behind the pre-transformer) evaluated `chunk_frames` frames at a
     // time (row f1 of SURVEY 8f): each chunk's samples land in pcm_host ([B][Fmax * upsample], pinned host memory) at
@@ -92,6 +100,16 @@ class CodecRunner {
     // tail's state into the first generated chunk; their samples are delivered nowhere (RowPlan::emit == 0) and a pass in
     // which no row emits takes no ring slot and is not appended to stream_push_rows' `out`.
     void stream_reset_row(int b, int prefix = 0);
+    // Request speeds in a slotted stream (a handle with request_speeds and no output rate: stream_own_hops()): every row has a
+    // synthesis hop of its own, the handle's until stream_set_row_hs says otherwise -- called for a new occupant in front of its
+    // reset / load; it holds for the passes issued from then on. The tensors with history in front of the stretch (out_conv's
+    // signal, the state words) have the decoder's own frame size whatever the hop, so margins roll, zero, save and restore as
+    // they did; the PCM behind the stretch carries no margin and has frames of the slowest row's size (stream_upsample()), a
+    // row's take * upsample_of(hs) samples packed at the start of its part of a ring slot. A saved state is valid for the hop it
+    // was made with (the state word is that hop's).
+    bool stream_own_hops() const { return rs_ && !resample_; }
+    int stream_upsample() const { return stream_own_hops() ? rs_plan_.max_spf() : up_; }
+    void stream_set_row_hs(int b, int hs);
     // The state a row's occupant has left in the tail -- its margins in every tensor with history -- as one blob of
     // stream_state_bytes() bytes of device memory (16-byte aligned), saved or restored with one launch on the codec stream.
     // A row whose prefix has been decoded (stream_in_prefix(b) false after the pushes that decoded it) saved into a blob, and a
@@ -118,6 +136,12 @@ class CodecRunner {
     int hist_frames() const;
     int upsample() const { return up_; }            // PCM samples per frame at the output rate
     int native_upsample() const { return native_; }  // the decoder's own samples per frame (1920)
+    // request speeds (request_speed_plan.h): whether rows may have hops of their own, the plan, a hop's samples per frame and
+    // the slowest row's, which sizes what holds rows of mixed speeds
+    bool request_speeds() const { return rs_; }
+    const RequestSpeedPlan& speed_plan() const { return rs_plan_; }
+    int upsample_of(int hs) const { return rs_plan_.spf(hs); }
+    int max_upsample() const { return rs_ ? rs_plan_.max_spf() : up_; }
     int output_rate() const { return resample_ ? out_plan_.out_rate : kResampleNative; }
     // the time stretch of this handle: synthesis hop (480: off), effective speed 480 / Hs, delay D in 24 kHz samples
     int stretch_hs() const { return stretch_ ? st_plan_.hs : kStretchHa; }
@@ -138,6 +162,11 @@ class CodecRunner {
         int32_t* carry = nullptr;         // device [nb]: the stretch's state word per row, read and written
         float* mid_carry = nullptr;       // the resampler's input: [nb][mid_stride], one frame of margin in front of the new frames
         int64_t mid_stride = 0;
+        // rows with hops of their own (decode with row_hs): device [nb] hop per row, 0 for a row without a stretch, and
+        // [nb] samples per frame in front of the resampler; every tensor behind the stretch then has max-sized frames
+        bool own_hops = false;  // (set without the tables in stream_open's counting pass)
+        const int32_t* hs_rows = nullptr;
+        const int32_t* mid_rows = nullptr;
         const std::string* stage = nullptr;
         std::vector<float>* stage_out = nullptr;
         int* stage_T = nullptr;
@@ -174,6 +203,9 @@ class CodecRunner {
         bool open = false, dry = false;  // dry: the counting pass of stream_open (no memory behind the tensors, no launches)
         StreamCfg cfg;
         int hist = 0, Tal = 0;       // margin frames, frames per allocation (hist + chunk)
+        bool own_hops = false;       // slotted stream with a hop per row
+        int up = 0;                  // samples per frame of the PCM tensor and the ring slots
+        std::vector<int32_t> row_hs; // [rows] the hop table's entries (0: the row is copied)
         int next_chunk = 0;
         bool front_done = false;     // window < 0: the pre-transformer ran over all frames
         DevBuf<uint8_t> arena;
@@ -230,6 +262,11 @@ class CodecRunner {
     bool stretch_ = false;
     StretchPlan st_plan_;
     DevBuf<float> st_fade_;   // its fade table on the device
+    bool rs_ = false;             // request speeds
+    RequestSpeedPlan rs_plan_;
+    DevBuf<float> fade_all_;      // the fade tables of every hop (request_speed_plan.h)
+    DevBuf<int32_t> rowhs_dev_;   // decode with row_hs: [2][B] hops and mid frame sizes
+    PinnedBuf<int32_t> rowhs_host_;
     static constexpr int kStateWords = 4;  // int32s per frame of the stretch's state tensor (the word and padding to 16 bytes)
     DevBuf<int32_t> ch_words_;  // decode_chunked: [B] state words carried from chunk to chunk
     DevBuf<float> ch_mid_;      // decode_chunked: [B][(1 + chunk) * mid_] stretched signal with one frame of margin

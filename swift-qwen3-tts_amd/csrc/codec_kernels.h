@@ -200,6 +200,7 @@ struct ResampleArgs {
     int64_t y_bstride;
     const int32_t* len;  // device [B]
     int len_mul;
+    const int32_t* len_mul_rows;  // device [B] or nullptr: row b's valid length is len[b] * len_mul_rows[b] instead (per-row hops)
     const float* tab;    // device [L][2K], padded to whole float4s
     int L, M, K;
     int hist;
@@ -227,6 +228,11 @@ struct StretchArgs {
     int len_mul;
     const float* fade;   // device [hs]
     int hs, delay;
+    // Per-row hops (causal form): hs_rows[b] is row b's synthesis hop and fade_all the fade tables of every hop, table Hs at
+    // fade_all + (Hs - 240) * 960; hs / delay / fade are then unused. Entry 0: the row is copied (speed 1). nullptr: every
+    // row at `hs`.
+    const int32_t* hs_rows;
+    const float* fade_all;
     int hist;
     int causal;
     int B;

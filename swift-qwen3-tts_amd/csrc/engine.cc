@@ -64,7 +64,9 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
         Q3_HIP(hipMalloc(reinterpret_cast<void**>(&stamps_), 64 * 8));
         Q3_HIP(hipMemset(stamps_, 0, 64 * 8));
     }
-    if (m_->has_codec) codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0, opts.output_sample_rate, opts.speed);
+    if (m_->has_codec)
+        codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0, opts.output_sample_rate, opts.speed,
+                                               opts.request_speeds != 0);
     if (m_->has_codec_encoder || m_->has_speaker_encoder) fe_ = std::make_unique<VoiceFrontEnd>(*m_, st_);
 }
 
@@ -563,6 +565,20 @@ ResolvedRequest Engine::resolve(const q3tts_request& r, const q3tts_sampling& sp
     const ModelConfig& cfg = m_->cfg;
     const TalkerConfig& t = cfg.talker;
     ResolvedRequest o;
+    if (r.speed != 0.0f) {  // (a NaN is not 0 and fails the range below)
+        Q3_CHECK(codec_ && codec_->request_speeds(), 3,
+                 "Invalid input: q3tts_request.speed needs a handle loaded with q3tts_load_opts.request_speeds");
+        const int hs = codec_->speed_plan().hs_of(r.speed);
+        Q3_CHECK(hs != 0, 3, "Invalid input: q3tts_request.speed must be 0 (the handle's speed) or between 0.5 and 2.0");
+        if (hs != codec_->stretch_hs()) {
+            // streamed audio: the slotted stream has a hop per row. Not built: the chunked exact decode (audio_window_frames == 0)
+            // and streams on a handle with an output rate (the resampler's input margin would have a frame size per row)
+            Q3_CHECK(sp.audio_chunk_frames == 0 || (sp.audio_window_frames > 0 && codec_->stream_own_hops()), 3,
+                     "Invalid input: a request speed other than the handle's with audio_chunk_frames > 0 needs audio_window_frames > 0 "
+                     "(streamed audio) and a handle without output_sample_rate");
+            o.hs = hs;
+        }
+    }
     Q3_CHECK(r.text_ids && r.n_text_ids >= 4, 3, "Invalid input: text_ids must hold the chat-template tokens");
     Q3_CHECK(r.route >= 0 && r.route <= 2, 3, "Invalid input: unknown q3tts_request.route");
     o.text_ids.assign(r.text_ids, r.text_ids + r.n_text_ids);
@@ -993,6 +1009,43 @@ void Engine::time_stretch(const float* in, int64_t n_in, float speed, bool causa
     Q3_HIP(hipMemcpy(out, rs_out_dev_, size_t(no) * 4, hipMemcpyDeviceToHost));
 }
 
+void Engine::debug_stretch_rows(const float* x, const int32_t* lens, const int32_t* hops, int B, int64_t x_stride, float* y,
+                                int64_t y_stride) {
+    Q3_CHECK(B >= 1 && B <= 4096 && x_stride >= 1 && y_stride >= 1 && x_stride <= (int64_t(1) << 26) && y_stride <= (int64_t(1) << 27), 3,
+             "Invalid input: debug_stretch_rows takes 1..4096 rows of at most 2^26 samples");
+    for (int b = 0; b < B; ++b) {
+        Q3_CHECK(hops[b] == 0 || (hops[b] >= kStretchHsMin && hops[b] <= kStretchHsMax), 3, "Invalid input: a hop must be 0 or lie in [240, 960]");
+        Q3_CHECK(lens[b] >= 0 && lens[b] <= x_stride, 3, "Invalid input: a row is longer than x_stride");
+        const int64_t no = hops[b] == 0 ? int64_t(lens[b]) : int64_t(lens[b] / kStretchHa) * hops[b];
+        Q3_CHECK(no <= y_stride, 3, "Invalid input: a row's output does not fit y_stride");
+    }
+    // rows start at 16-byte boundaries on the device, as the tail's tensors do
+    const int64_t xs = (x_stride + 3) & ~int64_t(3), ys = (y_stride + 3) & ~int64_t(3);
+    if (dbg_fade_all_.capacity() == 0) {
+        const std::vector<float> all = make_fade_all();
+        Q3_HIP(hipMemcpy(dbg_fade_all_.grow(all.size()), all.data(), all.size() * 4, hipMemcpyHostToDevice));
+    }
+    DevBuf<float> dx, dy;
+    DevBuf<int32_t> dl;
+    dx.grow(size_t(B) * size_t(xs));
+    dy.grow(size_t(B) * size_t(ys));
+    dl.grow(size_t(2 * B));
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy2D(dx, size_t(xs) * 4, x, size_t(x_stride) * 4, size_t(x_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy2D(dy, size_t(ys) * 4, y, size_t(y_stride) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(dl, lens, size_t(B) * 4, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(dl + B, hops, size_t(B) * 4, hipMemcpyHostToDevice));
+    StretchArgs sa{};
+    sa.x = dx; sa.x_bstride = xs;
+    sa.y = dy; sa.y_bstride = ys;
+    sa.len = dl; sa.len_mul = 1;
+    sa.hs_rows = dl + B; sa.fade_all = dbg_fade_all_;
+    sa.causal = 1; sa.B = B;
+    launch_stretch(sa, st_);
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy2D(y, size_t(y_stride) * 4, dy, size_t(ys) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyDeviceToHost));
+}
+
 std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids,
                                             int sample_rate) {
     const TalkerConfig& t = m_->cfg.talker;
@@ -1125,6 +1178,11 @@ int Engine::begin(const q3tts_request* reqs, int n, const q3tts_sampling& sp, q3
     Q3_HIP(hipEventRecord(ev_[1], st_));
     Job& J = jobs_[slot];
     J.reset(n, codec_->upsample());
+    {
+        std::vector<int> hs;
+        for (const auto& r : rr) hs.push_back(r.hs);
+        set_row_speeds(J, hs);
+    }
     J.chunk_frames = sp.audio_chunk_frames;
     J.frontend = frontend;
     J.busy = true;  // nothing below gives the slot back except end() -- or a back half that fails inside this call
@@ -1462,7 +1520,8 @@ void Engine::start_decode(Job& J, const std::vector<int>& dframes, bool overlapp
                                                 J.nf_chunk_host);
         } else {
             float* pcm_dev = nullptr;
-            codec_->decode(J.dec_codes, J.Fdec, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, J.nf_host);
+            codec_->decode(J.dec_codes, J.Fdec, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, J.nf_host, false,
+                           J.row_hs.empty() ? nullptr : J.row_hs.data());
             Q3_HIP(hipMemcpyAsync(J.pcm_host, pcm_dev, floats * 4, hipMemcpyDeviceToHost, cst));
         }
         J.decoded = true;
@@ -1515,6 +1574,8 @@ void Engine::release_job(Job& J) {
 void Engine::Job::reset(int rows, int upsample) {
     n = rows;
     up = upsample;
+    row_hs.clear();
+    row_up.assign(size_t(n), upsample);
     Fdec = 0;
     frames.assign(size_t(n), 0);
     ref_T.assign(size_t(n), 0);
@@ -1536,6 +1597,18 @@ void Engine::Job::reset(int rows, int upsample) {
 void Engine::Job::clear_chunk_flags(int frames) {
     const size_t slots = size_t(ceil_div(frames, chunk_frames) + 1) * size_t(n);
     std::memset(nf_chunk_host.grow(slots), 0, slots * 4);
+}
+
+void Engine::set_row_speeds(Job& J, const std::vector<int>& hs) {
+    bool any = false;
+    for (int h : hs) any = any || h != 0;
+    if (!any) return;
+    J.up = codec_->max_upsample();
+    J.row_hs.assign(size_t(J.n), codec_->stretch_hs());
+    for (int b = 0; b < J.n; ++b) {
+        if (hs[size_t(b)] != 0) J.row_hs[size_t(b)] = hs[size_t(b)];
+        J.row_up[size_t(b)] = codec_->upsample_of(J.row_hs[size_t(b)]);
+    }
 }
 
 void check_row_sampling(const q3tts_sampling& sp, int n) {
@@ -1609,11 +1682,11 @@ void Engine::emit_tokens(q3tts_event_cb cb, void* user, int row, int request, in
 // 0 < valid < len (SpeechTokenizer.swift:831-833, Qwen3.swift:954-959); clone rows lose the reference's share
 // (Qwen3.swift:1195-1199, Float arithmetic)
 void Engine::compute_cuts(Job& J) {
-    const int n = J.n, up = J.up;
+    const int n = J.n;
     J.row_cut.assign(size_t(n), 0);
     J.row_ns.assign(size_t(n), 0);
     for (int b = 0; b < n; ++b) {
-        const int F = J.frames[size_t(b)];
+        const int F = J.frames[size_t(b)], up = J.row_up[size_t(b)];  // (the row's own samples per frame)
         if (F == 0 || !J.decoded) continue;
         const int32_t* codes = J.codes_host.data() + size_t(b) * Fcap_ * 16;
         int valid_tok = 0;
@@ -1725,9 +1798,11 @@ void Engine::staging_loop() {
 // only) and handed out like any other. A streamed row (audio_window_frames > 0) stopped delivering chunks at its first flagged
 // one (fire_chunks): its remaining AUDIO_CHUNK events come from this decode -- the exact one-shot arithmetic -- and its AUDIO
 // is what was delivered. Returns the rows that are non-finite even in fp32 (they fail with AUDIO_DECODING_FAILED).
-Engine::ExactDecode Engine::decode_rows_fp32(const std::vector<int>& dframes, const std::function<void(int, int32_t*, hipStream_t)>& place) {
-    const int R = int(dframes.size()), up = codec_->upsample();
+Engine::ExactDecode Engine::decode_rows_fp32(const std::vector<int>& dframes, const std::function<void(int, int32_t*, hipStream_t)>& place,
+                                             const std::vector<int>* hs) {
+    const int R = int(dframes.size()), up = hs ? codec_->max_upsample() : codec_->upsample();
     ExactDecode d;
+    d.up = up;
     for (int f : dframes) d.Fd = std::max(d.Fd, f);
     hipStream_t cst = codec_stream(false);
     DevBuf<int32_t> dcodes;
@@ -1736,7 +1811,7 @@ Engine::ExactDecode Engine::decode_rows_fp32(const std::vector<int>& dframes, co
     d.pcm.grow(size_t(R) * d.Fd * up);
     for (int i = 0; i < R; ++i) place(i, dcodes + size_t(i) * d.Fd * 16, cst);
     float* pcm_dev = nullptr;
-    codec_->decode(dcodes, d.Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, d.nf, true);
+    codec_->decode(dcodes, d.Fd, dframes, &pcm_dev, std::string(), nullptr, nullptr, nullptr, d.nf, true, hs ? hs->data() : nullptr);
     Q3_HIP(hipMemcpyAsync(d.pcm, pcm_dev, size_t(R) * d.Fd * up * 4, hipMemcpyDeviceToHost, cst));
     Q3_HIP(hipStreamSynchronize(cst));
     return d;
@@ -1756,14 +1831,16 @@ std::vector<int> Engine::redo_rows_fp32(Job& J) {
         if (J.nf_host[b] && J.frames[size_t(b)] > 0 && J.st_pcm[size_t(b)]) rows.push_back(b);
     if (rows.empty()) return bad;
     if (codec_->fp32_convs()) return rows;  // already the fp32 kernels: nothing wider to fall back to
-    const int R = int(rows.size()), up = J.up;
-    std::vector<int> dframes((size_t)(R));
+    const int R = int(rows.size()), up = J.up;  // (the layout's samples per frame: the re-decode's is the job's)
+    std::vector<int> dframes((size_t)(R)), hs;
     for (int i = 0; i < R; ++i) dframes[size_t(i)] = J.frames[size_t(rows[size_t(i)])] + J.ref_T[size_t(rows[size_t(i)])];
+    if (!J.row_hs.empty())  // every row is decoded again at its own speed
+        for (int b : rows) hs.push_back(J.row_hs[size_t(b)]);
     // the codes the first decode read: the job's own device copy ([reference ++] generated; row stride J.Fdec frames)
     const ExactDecode d = decode_rows_fp32(dframes, [&J, &rows, &dframes](int i, int32_t* dst, hipStream_t cst) {
         Q3_HIP(hipMemcpyAsync(dst, J.dec_codes + size_t(rows[size_t(i)]) * J.Fdec * 16, size_t(dframes[size_t(i)]) * 64,
                               hipMemcpyDeviceToDevice, cst));
-    });
+    }, hs.empty() ? nullptr : &hs);
     const int Fd = d.Fd;
     const float* hpcm = d.pcm;
     for (int i = 0; i < R; ++i) {
@@ -1774,7 +1851,8 @@ std::vector<int> Engine::redo_rows_fp32(Job& J) {
         }
         // decoded-stream coordinates: sample p of the decode is sample p - cut of the row's audio; chunk k covers
         // [k * step, (k + 1) * step). Chunks below `held` have been delivered from the first decode and stay as they are.
-        const int64_t cut = J.row_cut[size_t(b)], ns = J.row_ns[size_t(b)], step = int64_t(std::max(J.chunk_frames, 1)) * up;
+        const int64_t cut = J.row_cut[size_t(b)], ns = J.row_ns[size_t(b)];
+        const int64_t step = int64_t(std::max(J.chunk_frames, 1)) * (J.prefixed ? J.row_up[size_t(b)] : up);
         if (J.prefixed) {  // chunks count from the row's own first frame: chunk k is samples [k * step, (k + 1) * step) of its audio
             refire_held(J.st_pcm[size_t(b)].get(), hpcm + size_t(i) * Fd * up + cut, std::min(ns, int64_t(std::max(0, J.held_from[size_t(b)])) * step),
                         ns, step, J.cb, J.user, J.request_base + b);

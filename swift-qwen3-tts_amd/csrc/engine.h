@@ -68,6 +68,9 @@ struct ResolvedRequest {
     // A session's open-text request (q3tts_session_submit_open): text_ids = role + the content so far, without the 5 tail tokens
     // (n_tail = 0). text_open: the text may still grow; max_frames is then the open cap (max_tokens) and open_max_tokens /
     // open_force_frames give final_text_cap() what it needs at the close.
+    // q3tts_request.speed on a handle with request_speeds: the request's own synthesis hop (480: no stretch); 0: the handle's
+    // (also when the request's hop is the handle's own)
+    int hs = 0;
     int n_tail = 5;
     bool text_open = false;
     int open_max_tokens = 0, open_force_frames = 0;
@@ -101,8 +104,9 @@ struct PrefixCache {
         const Voice* voice = nullptr;
         int chunk = 0, window = 0, lookahead = 0, path = 0;
         size_t bytes = 0;
+        int hs = 0;  // the synthesis hop the state was made with (its state word is that hop's); 0: the handle's
         bool operator==(const Key& o) const {
-            return voice == o.voice && chunk == o.chunk && window == o.window && lookahead == o.lookahead && path == o.path && bytes == o.bytes;
+            return hs == o.hs && voice == o.voice && chunk == o.chunk && window == o.window && lookahead == o.lookahead && path == o.path && bytes == o.bytes;
         }
     };
     struct Entry : Key {
@@ -278,6 +282,8 @@ class Engine {
     void resample(const float* in, int64_t n_in, int in_rate, int out_rate, bool centred, float* out, int64_t cap, int64_t* n_out);
     // q3tts_time_stretch: a 24 kHz host buffer through kernels/stretch.hip (stretch_plan.h); causal: the decoder stage's form
     void time_stretch(const float* in, int64_t n_in, float speed, bool causal, float* out, int64_t cap, int64_t* n_out);
+    // q3tts_debug_stretch_rows: the kernel's per-row path (a hop per row, the fade tables of every hop) on host rows, causal form
+    void debug_stretch_rows(const float* x, const int32_t* lens, const int32_t* hops, int B, int64_t x_stride, float* y, int64_t y_stride);
     void debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C);
 
     std::vector<std::string> speakers;  // sorted (Qwen3.swift:965-971)
@@ -355,7 +361,9 @@ class Engine {
         int back = 0;         // 1: queued for or running on the worker thread (work_mu_)
         int back_status = 0;  // q3::Error status the back half ended with (0: it finished)
         std::string back_err;
-        int n = 0, Fdec = 0, up = 0;
+        int n = 0, Fdec = 0, up = 0;  // up: samples per frame of the PCM buffers' layout (the slowest row's when rows have hops of their own)
+        std::vector<int> row_hs;      // rows with speeds of their own: row b's synthesis hop; empty: every row at the handle's
+        std::vector<int> row_up;      // [n] row b's samples per frame (== up unless row_hs)
         std::vector<int> frames, ref_T, target_tokens, n_prompt;
         std::vector<int> req_index;   // queued decode batch: row b is request req_index[b] (results / events); empty: row b
         std::vector<q3tts_result*> row_out;  // queued decode batch: where row b's result goes (end() is given no array)
@@ -417,11 +425,15 @@ class Engine {
     // its mechanical part, shared with a streamed queue's held requests: rows of dframes[i] frames, whose codes place(i, dst,
     // cst) puts on the device, through the exact decode on codec_stream(false); returns with the PCM on the host
     struct ExactDecode {
-        PinnedBuf<float> pcm;   // [rows][Fd * upsample]
+        PinnedBuf<float> pcm;   // [rows][Fd * up]
         PinnedBuf<int32_t> nf;  // [rows]: non-finite even so
-        int Fd = 0;
+        int Fd = 0, up = 0;     // up: samples per frame of pcm's layout
     };
-    ExactDecode decode_rows_fp32(const std::vector<int>& dframes, const std::function<void(int, int32_t*, hipStream_t)>& place);
+    // hs (optional): the rows' own synthesis hops (Job::row_hs)
+    ExactDecode decode_rows_fp32(const std::vector<int>& dframes, const std::function<void(int, int32_t*, hipStream_t)>& place,
+                                 const std::vector<int>* hs = nullptr);
+    // the rows' own hops (ResolvedRequest::hs, 0: the handle's) into a job that has just been reset
+    void set_row_speeds(Job& J, const std::vector<int>& hs);
     // a streamed request held back at the chunk that starts at sample `at`: samples [at, ns) of its audio from the exact decode
     // (src: its sample 0 there), then the AUDIO_CHUNK events it is still owed, in steps of `step` samples
     void refire_held(float* own, const float* src, int64_t at, int64_t ns, int64_t step, q3tts_event_cb cb, void* user, int index);
@@ -475,6 +487,7 @@ class Engine {
         DevBuf<float> fade;
     };
     std::vector<std::unique_ptr<StretchDev>> stretchers_;
+    DevBuf<float> dbg_fade_all_;  // debug_stretch_rows: the fade tables of every hop, uploaded at its first call
     const ResamplerDev& resampler(int in_rate, int out_rate);
     // `audio` (host, n samples at in_rate, finite) -> device buffer of *n_out samples at out_rate, queued on st_
     const float* resample_upload(const float* audio, int64_t n, int in_rate, int out_rate, bool centred, int64_t* n_out);

@@ -239,7 +239,8 @@ struct Engine::QueueRun {
     void* const user;
     const double t_call;
     const bool open_text;  // (a session) rows may starve: the frame end reads text_open_ and raises starved_
-    const int up, burst_frames;
+    const int up, burst_frames;  // up: the handle's samples per frame
+    int up_of(const ResolvedRequest& rq) const { return rq.hs ? e.codec_->upsample_of(rq.hs) : up; }  // the request's own
     // ---- destruction order: members go in reverse, so whatever ends the call
     //   audio     first: its SlotStream closes the runner's stream and drains the codec stream before the buffers its passes
     //             read and write are freed (the same order inside Audio);
@@ -422,14 +423,15 @@ void Engine::QueueRun::Audio::admit_rows(const std::vector<int>& fresh) {
         const int req = r.sl[size_t(s)].req, R = n_ref[size_t(s)];
         const ResolvedRequest& rq = r.live.at(req).rr;
         key.voice = rq.voice;
+        key.hs = rq.hs;  // (a state is valid for the hop it was made with: keyed, so a voice has one per hop in use)
         std::shared_ptr<PrefixCache::Entry> hit = R > 0 && r.q.prefix_cache ? r.q.prefix_cache->find(key) : nullptr;
         if (hit) {
             Q3_HIP(hipStreamWaitEvent(ss->cst, hit->ready, 0));
-            ss->admit(s, req, rq.max_frames, R, hit->blob);
+            ss->admit(s, req, rq.max_frames, R, hit->blob, rq.hs);
             ++r.q.prefix_cache->restored;
             in_use.push_back(std::move(hit));
         } else {
-            ss->admit(s, req, rq.max_frames, R);
+            ss->admit(s, req, rq.max_frames, R, nullptr, rq.hs);
             if (R > 0) primed.push_back(s);
         }
     }
@@ -449,6 +451,7 @@ void Engine::QueueRun::Audio::save_states(const std::vector<int>& primed, Prefix
         if (!r.q.prefix_cache || key.bytes == 0) continue;
         auto n = std::make_shared<PrefixCache::Entry>();
         key.voice = r.live.at(r.sl[size_t(s)].req).rr.voice;
+        key.hs = r.live.at(r.sl[size_t(s)].req).rr.hs;
         static_cast<PrefixCache::Key&>(*n) = key;
         n->blob.grow(key.bytes);
         Q3_HIP(hipEventCreateWithFlags(&n->ready, hipEventDisableTiming));
@@ -490,13 +493,19 @@ void Engine::QueueRun::Audio::redo_held(std::unordered_map<int, SlotStream::Out>
             dframes[size_t(i)] = refs[size_t(i)] + w[size_t(i)]->frames;
         }
         const bool widest = e.codec_->fp32_convs();  // already the fp32 kernels: nothing wider to fall back to
+        std::vector<int> hs;  // every request is decoded again at its own speed
+        bool own = false;
+        for (int i = 0; i < R; ++i) {
+            own = own || w[size_t(i)]->rr.hs != 0;
+            hs.push_back(w[size_t(i)]->rr.hs ? w[size_t(i)]->rr.hs : e.codec_->stretch_hs());
+        }
         ExactDecode d;
         if (!widest)
             d = e.decode_rows_fp32(dframes, [&w, &refs, &dframes](int i, int32_t* dst, hipStream_t) {
                 const int ref = refs[size_t(i)];
                 if (ref > 0) Q3_HIP(hipMemcpy(dst, w[size_t(i)]->rr.voice->codes_host.data(), size_t(ref) * 64, hipMemcpyHostToDevice));
                 Q3_HIP(hipMemcpy(dst + size_t(ref) * 16, w[size_t(i)]->codes.data(), size_t(dframes[size_t(i)] - ref) * 64, hipMemcpyHostToDevice));
-            });
+            }, own ? &hs : nullptr);
         for (int i = 0; i < R; ++i) {
             const int req = held[h0 + i];
             SlotStream::Out& o = outs.at(req);
@@ -505,8 +514,9 @@ void Engine::QueueRun::Audio::redo_held(std::unordered_map<int, SlotStream::Out>
                 e.last_error = kCodecRangeMsg;
                 continue;
             }
-            const int64_t step = int64_t(r.sp.audio_chunk_frames) * r.up, ns = int64_t(w[size_t(i)]->frames) * r.up;
-            e.refire_held(o.pcm.get(), d.pcm + (size_t(i) * d.Fd + refs[size_t(i)]) * r.up, std::min(ns, int64_t(o.held_from) * step), ns, step,
+            const int64_t rup = r.up_of(w[size_t(i)]->rr);  // (the request's own samples per frame; d.up is the decode's layout)
+            const int64_t step = int64_t(r.sp.audio_chunk_frames) * rup, ns = int64_t(w[size_t(i)]->frames) * rup;
+            e.refire_held(o.pcm.get(), d.pcm + size_t(i) * d.Fd * d.up + size_t(refs[size_t(i)]) * rup, std::min(ns, int64_t(o.held_from) * step), ns, step,
                           r.cb, r.user, req);
             r.fill_result(req, Q3TTS_OK, o.pcm.release());
         }
@@ -559,7 +569,7 @@ void Engine::QueueRun::fill_result(int req, q3tts_status status, float* pcm) {
     if (!rp->codes) throw Error(5, "out of host memory for the results");
     std::memcpy(rp->codes, w.codes.data(), size_t(w.frames) * 16 * 4);
     rp->n_frames = w.frames;
-    rp->n_samples = int64_t(w.frames) * up;  // all generated frames: what has left cannot be trimmed (include/q3tts.h)
+    rp->n_samples = int64_t(w.frames) * up_of(w.rr);  // all generated frames: what has left cannot be trimmed (include/q3tts.h)
     rp->pcm = own.release();
     if (!cb) return;
     std::unique_lock<std::mutex> lk = e.cb_lock();
@@ -588,6 +598,11 @@ void Engine::QueueRun::decode(bool overlapped) {
     Job& J = e.jobs_[0];
     const int R = std::min(int(waiting.size()), e.Bm_), Fcap = e.Fcap_;
     J.reset(R, up);
+    {
+        std::vector<int> hs;
+        for (int b = 0; b < R; ++b) hs.push_back(live.at(waiting[size_t(b)]).rr.hs);
+        e.set_row_speeds(J, hs);
+    }
     J.req_index.assign(size_t(R), 0);
     J.row_out.assign(size_t(R), nullptr);
     J.row_span.assign(size_t(R), 0);

@@ -78,10 +78,12 @@ inline void emit_info_audio(q3tts_event_cb cb, void* user, int index, const q3tt
 struct Engine::SlotStream {
     Engine& e;
     hipStream_t cst = nullptr;
-    const int C, up;
+    const int C, up;      // up: samples per frame of a ring slot's rows (the slowest row's where rows have hops of their own)
+    const int handle_up;  // what a request without a speed of its own gets
     bool hold = true;  // a request stops taking chunks at its first one flagged non-finite (the engine re-decodes it in fp32)
     struct Out {       // one request
         MallocPtr<float> pcm;  // [cap frames * up]
+        int up = 0;            // the request's own samples per frame
         int frames = -1;       // its length, once retired
         int landed = 0;        // chunks taken from the ring
         int held_from = -1;    // first chunk held back
@@ -111,7 +113,7 @@ struct Engine::SlotStream {
     std::function<void(int)> on_complete;
 
     SlotStream(Engine& eng, int rows, int chunk, int window, int lookahead, int max_frames, bool overlapped, int max_prefix = 0)
-        : e(eng), C(chunk), up(eng.codec_->upsample()), req_of_row(size_t(rows), -1), copied(size_t(rows), 0),
+        : e(eng), C(chunk), up(eng.codec_->stream_upsample()), handle_up(eng.codec_->upsample()), req_of_row(size_t(rows), -1), copied(size_t(rows), 0),
           prefix(size_t(rows), 0), reused(size_t(rows), 0) {
         for (hipEvent_t* ev : {&ev_codes, &ev_pushed}) Q3_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
         cst = e.codec_stream(overlapped);
@@ -128,15 +130,18 @@ struct Engine::SlotStream {
             if (ev) (void)hipEventDestroy(ev);
     }
     // prefix: the reference frames in front of the row's codes (a streamed clone row); state: that prefix's saved tail state
-    void admit(int row, int req, int cap_frames, int n_prefix = 0, const uint8_t* state = nullptr) {
+    // hs: the request's own synthesis hop (ResolvedRequest::hs), 0: the handle's
+    void admit(int row, int req, int cap_frames, int n_prefix = 0, const uint8_t* state = nullptr, int hs = 0) {
         // on cst: behind the previous occupant's last chunk, in front of this one's first
+        if (e.codec_->stream_own_hops()) e.codec_->stream_set_row_hs(row, hs ? hs : e.codec_->stretch_hs());
         if (state) e.codec_->stream_load_row(row, n_prefix, state);
         else e.codec_->stream_reset_row(row, n_prefix);
         req_of_row[size_t(row)] = req;
         copied[size_t(row)] = 0;
         prefix[size_t(row)] = n_prefix;
         Out& o = out[req];
-        o.pcm.reset(static_cast<float*>(std::malloc(std::max<size_t>(size_t(cap_frames) * up * 4, 4))));
+        o.up = hs ? e.codec_->upsample_of(hs) : handle_up;
+        o.pcm.reset(static_cast<float*>(std::malloc(std::max<size_t>(size_t(cap_frames) * o.up * 4, 4))));
         Q3_CHECK(o.pcm != nullptr, 5, "out of host memory for the results");
     }
     void check_complete(int req) {
@@ -172,7 +177,7 @@ struct Engine::SlotStream {
             if (o.dropped) continue;
             if (hold && o.held_from < 0 && f.pass.nf[b]) o.held_from = r.k;
             if (o.held_from < 0) {
-                const int64_t off = int64_t(r.k) * C * up, n = int64_t(r.take) * up;
+                const int64_t off = int64_t(r.k) * C * o.up, n = int64_t(r.take) * o.up;  // (the row's samples lie at the start of its part)
                 std::memcpy(o.pcm.get() + off, f.pass.pcm + b * size_t(C) * up, size_t(n) * 4);
                 if (on_chunk) on_chunk(req, r.k, o.pcm.get() + off, n, off);
             }
@@ -290,7 +295,7 @@ struct Engine::StreamedDecode {
             any_clone = any_clone || r.clone;
             if (r.clone) ref_max = std::max(ref_max, r.ref_T);
         }
-        if (any_clone) {
+        if (any_clone || !J.row_hs.empty()) {  // (rows with hops of their own: the slotted stream has a hop per row)
             open_prefixed(sp, cb, user, rr, ref_max, t_start);
             return;
         }
@@ -335,8 +340,8 @@ struct Engine::StreamedDecode {
                 ref[size_t(b)] = e.ref_codes_dev_ + rr[size_t(b)].ref_off;
                 n_ref[size_t(b)] = rr[size_t(b)].ref_T;
             }
-        ss->stage_prefixes(ref.data(), n_ref.data(), e.codes_, e.Fcap_, J.dec_codes, stride, e.st_);
-        for (int b = 0; b < J.n; ++b) ss->admit(b, b, e.Fcap_, n_ref[size_t(b)]);
+        if (ref_max > 0) ss->stage_prefixes(ref.data(), n_ref.data(), e.codes_, e.Fcap_, J.dec_codes, stride, e.st_);
+        for (int b = 0; b < J.n; ++b) ss->admit(b, b, e.Fcap_, n_ref[size_t(b)], nullptr, rr[size_t(b)].hs);
         ss->push(J.dec_codes, stride, avail.data(), fin.data());  // the prefixes need no generated frame: they start at once
         J.streamed = J.prefixed = true;
     }
@@ -382,7 +387,9 @@ struct Engine::StreamedDecode {
         for (int b = 0; b < J.n; ++b) {
             const SlotStream::Out& o = ss->out[b];
             Q3_CHECK(o.complete, 7, "internal error: a row of the streamed job was left incomplete");
-            std::memcpy(J.pcm_host + (size_t(b) * stride + ss->prefix[size_t(b)]) * J.up, o.pcm.get(), size_t(J.frames[size_t(b)]) * J.up * 4);
+            const size_t rup = size_t(J.row_up[size_t(b)]);  // (the row's own samples per frame; J.up is the layout's)
+            std::memcpy(J.pcm_host + size_t(b) * stride * J.up + size_t(ss->prefix[size_t(b)]) * rup, o.pcm.get(),
+                        size_t(J.frames[size_t(b)]) * rup * 4);
             J.held_from[size_t(b)] = o.held_from;
             J.nf_host[b] = o.held_from >= 0 ? 1 : 0;
         }

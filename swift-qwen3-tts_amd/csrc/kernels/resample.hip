@@ -16,7 +16,7 @@ constexpr int kTile = 256;  // outputs per workgroup == threads
 __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int b = blockIdx.y;
-    const int64_t n_in = int64_t(a.len[b]) * a.len_mul;
+    const int64_t n_in = int64_t(a.len[b]) * (a.len_mul_rows ? a.len_mul_rows[b] : a.len_mul);  // (a row's own frame size behind per-row hops)
     if (n_in <= 0) return;  // a row of length 0 touches nothing
     const int64_t n_out = (n_in * a.L + a.M - 1) / a.M;
     const int64_t n0 = int64_t(blockIdx.x) * kTile;

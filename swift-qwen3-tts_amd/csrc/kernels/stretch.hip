@@ -34,14 +34,30 @@ __global__ __launch_bounds__(kThreads) void stretch_kernel(StretchArgs a) {
     const int64_t n_in = int64_t(a.len[b]) * a.len_mul;
     if (n_in <= 0) return;  // a row of length 0 touches nothing, its state included
     constexpr int Ha = kStretchHa, Dl = kStretchDelta;
-    const int Hs = a.hs;
-    const int64_t D = a.causal ? a.delay : 0;
+    // The hop is the row's own when the launch carries a table (uniform over the workgroup: one workgroup owns a row, so
+    // its hop count, window length and loop bounds are scalars as before). Entry 0: the row speaks at speed 1 -- a copy.
+    int Hs = a.hs, delay = a.delay;
+    const float* fd = a.fade;
+    if (a.hs_rows) {
+        Hs = __builtin_amdgcn_readfirstlane(a.hs_rows[b]);
+        if (Hs == 0) {
+            const float* xc = a.x + int64_t(b) * a.x_bstride;
+            float* yc = a.y + int64_t(b) * a.y_bstride;
+            for (int64_t n = t; n < n_in; n += kThreads) yc[n] = xc[n];
+            return;
+        }
+        if (Hs < kStretchHsMin || Hs > kStretchHsMax) return;  // (never: the host chose it; the LDS arrays end at 960)
+        const int d1 = Dl + Hs - Ha, d2 = Dl + 2 * Hs - 2 * Ha;  // stretch_delay(Hs)
+        delay = d1 > d2 ? (d1 > 0 ? d1 : 0) : (d2 > 0 ? d2 : 0);
+        fd = a.fade_all + size_t(Hs - kStretchHsMin) * kStretchHsMax;
+    }
+    const int64_t D = a.causal ? delay : 0;
     const int64_t lo = a.causal ? -int64_t(a.hist) : 0;
     const int64_t hops = a.causal ? n_in / Ha : (n_in + Ha - 1) / Ha;
     const int64_t n_out = a.causal ? hops * Hs : (n_in * Hs + Ha - 1) / Ha;
     const float* x = a.x + int64_t(b) * a.x_bstride;
     float* y = a.y + int64_t(b) * a.y_bstride;
-    for (int n = t; n < Hs; n += kThreads) fade[n] = a.fade[n];
+    for (int n = t; n < Hs; n += kThreads) fade[n] = fd[n];
     int word = a.state_in ? a.state_in[int64_t(b) * a.state_in_bstride] : 0;
     const int wlen = Hs + 2 * Dl;
     for (int64_t m = 0; m < hops; ++m) {
@@ -103,9 +119,13 @@ __global__ __launch_bounds__(kThreads) void stretch_kernel(StretchArgs a) {
 
 void launch_stretch(const StretchArgs& a, hipStream_t st) {
     if (a.B <= 0) return;
-    Q3_CHECK(a.hs >= kStretchHsMin && a.hs <= kStretchHsMax && a.len_mul >= 1 && a.hist >= 0 && a.delay >= 0, 7,
-             "internal error: time stretch geometry");
-    Q3_CHECK(!a.causal || a.delay == stretch_delay(a.hs), 7, "internal error: time stretch delay");
+    if (a.hs_rows) {
+        Q3_CHECK(a.fade_all && a.causal && a.len_mul >= 1 && a.hist >= 0, 7, "internal error: time stretch geometry (per-row hops)");
+    } else {
+        Q3_CHECK(a.hs >= kStretchHsMin && a.hs <= kStretchHsMax && a.len_mul >= 1 && a.hist >= 0 && a.delay >= 0, 7,
+                 "internal error: time stretch geometry");
+        Q3_CHECK(!a.causal || a.delay == stretch_delay(a.hs), 7, "internal error: time stretch delay");
+    }
     Q3_CHECK(!a.state_frames || (a.frame_hops >= 1 && a.state_frame_words >= 1), 7, "internal error: time stretch state layout");
     Q3_CHECK(a.B <= 0x7fffffff, 3, "Invalid input: too many rows in one time stretch");
     (void)hipGetLastError();  // the runtime's last-error slot is sticky: an earlier, handled failure must not be read as this launch's

@@ -20,7 +20,7 @@ class LoadOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_batch", C.c_int32), ("max_frames", C.c_int32),
                 ("max_prompt", C.c_int32), ("use_graph", C.c_int32), ("weights_from_broadcast", C.c_int32),
                 ("n_streams", C.c_int32), ("codec_overlap_cus", C.c_int32), ("codec_fp32", C.c_int32),
-                ("output_sample_rate", C.c_int32), ("speed", C.c_float)]
+                ("output_sample_rate", C.c_int32), ("speed", C.c_float), ("request_speeds", C.c_int32)]
 
 
 class CommId(C.Structure):  # q3tts_comm_id == ncclUniqueId
@@ -34,13 +34,13 @@ class ModelInfo(C.Structure):
                 ("text_vocab_size", C.c_int32), ("num_code_groups", C.c_int32),
                 ("cp_hidden_size", C.c_int32), ("cp_num_layers", C.c_int32), ("cp_vocab_size", C.c_int32),
                 ("codec_eos_token_id", C.c_int32), ("samples_per_frame", C.c_int32), ("max_batch", C.c_int32),
-                ("weight_bytes", C.c_int64), ("speaker_embedding_dim", C.c_int32)]
+                ("weight_bytes", C.c_int64), ("speaker_embedding_dim", C.c_int32), ("max_samples_per_frame", C.c_int32)]
 
 
 class Request(C.Structure):
     _fields_ = [("text_ids", i32p), ("n_text_ids", C.c_int32), ("instruct_ids", i32p),
                 ("n_instruct_ids", C.c_int32), ("target_token_count", C.c_int32), ("speaker", C.c_char_p),
-                ("language", C.c_char_p), ("max_tokens", C.c_int32),
+                ("language", C.c_char_p), ("max_tokens", C.c_int32), ("speed", C.c_float),
                 ("ref_audio", f32p), ("n_ref_samples", C.c_int64), ("ref_text_ids", i32p),
                 ("n_ref_text_ids", C.c_int32), ("route", C.c_int32)]
 
@@ -249,6 +249,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "q3tts_codec_decode_streamed_prefixed"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_codec_decode_streamed_prefixed.argtypes = [vp, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                            f32p]
+    if hasattr(L, "q3tts_request_speed_info"):
+        L.q3tts_request_speed_info.argtypes = [vp, C.c_float, C.POINTER(C.c_float), i32p, i32p, i32p]
+        L.q3tts_debug_stretch_rows.argtypes = [vp, f32p, i32p, i32p, C.c_int32, C.c_int64, f32p, C.c_int64]
     if hasattr(L, "q3tts_debug_prefix_states"):
         L.q3tts_debug_prefix_states.argtypes = [vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "q3tts_debug_codec_stream_slots"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)

@@ -77,6 +77,9 @@ class GenerationRequest:
     # a reusable voice prompt (Qwen3TTSModel.create_voice): the request is then a voice-clone request whose reference is that
     # voice -- no ref_audio / ref_text_ids beside it; speaker, instruct_ids and route are ignored
     voice: Optional["Voice"] = None
+    # this request's speaking rate (q3tts_request.speed): 0 = the handle's; 0.5 .. 2.0 on a model loaded with
+    # request_speeds=True, 1.0 meaning "no stretch for this request"
+    speed: float = 0.0
 
 
 @dataclass
@@ -162,12 +165,14 @@ class Qwen3TTSModel:
                         max_prompt: int = 512, use_graph: bool = True,
                         weights_from_broadcast: bool = False, n_streams: int = 0,
                         codec_overlap_cus: int = 0, codec_fp32: bool = False,
-                        output_sample_rate: int = 0, speed: float = 0.0) -> "Qwen3TTSModel":
+                        output_sample_rate: int = 0, speed: float = 0.0, request_speeds: bool = False) -> "Qwen3TTSModel":
         """output_sample_rate (q3tts_load_opts.output_sample_rate): 0 = 24000; 8000, 12000, 16000, 22050, 32000, 44100 or
         48000 make every waveform of this handle leave at that rate (sample_rate and info.samples_per_frame report it).
         speed (q3tts_load_opts.speed): 0 or 1.0 = off; 0.5 .. 2.0 make this handle speak that much faster, pitch preserved,
         through the time stretch in the decoder's tail (`speed`, `stretch_hs` and `stretch_delay_samples` report what was
-        chosen, info.samples_per_frame follows)."""
+        chosen, info.samples_per_frame follows).
+        request_speeds (q3tts_load_opts.request_speeds): the handle admits GenerationRequest.speed, a speaking rate per
+        request (`request_speed_info` tells what one becomes; info.max_samples_per_frame is the slowest request's)."""
         lib = L.lib()
         o = L.LoadOpts()
         lib.q3tts_default_load_opts(C.byref(o))
@@ -179,6 +184,7 @@ class Qwen3TTSModel:
         o.codec_fp32 = 1 if codec_fp32 else 0
         o.output_sample_rate = int(output_sample_rate)
         o.speed = float(speed)
+        o.request_speeds = 1 if request_speeds else 0
         h = C.c_void_p()
         st = lib.q3tts_model_load(model_path.encode(), C.byref(o), C.byref(h))
         if st != 0:
@@ -228,6 +234,24 @@ class Qwen3TTSModel:
     def stretch_delay_samples(self) -> int:
         """The delay D of the causal time stretch in 24 kHz samples (q3tts.h, "Speaking rate")."""
         return self._speed()[2]
+
+    def request_speed_info(self, speed: float) -> Tuple[float, int, int, int]:
+        """q3tts_request_speed_info: what a request at `speed` gets on this handle (0: the handle's own) -- the effective
+        speed 480 / Hs, Hs, the delay D in 24 kHz samples and its samples per frame at the output rate. Host arithmetic alone."""
+        s, hs, d, spf = C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.q3tts_request_speed_info(self._h, float(speed), C.byref(s), C.byref(hs), C.byref(d), C.byref(spf)))
+        return float(s.value), int(hs.value), int(d.value), int(spf.value)
+
+    def debug_stretch_rows(self, x: np.ndarray, lens: Sequence[int], hops: Sequence[int], y: np.ndarray) -> np.ndarray:
+        """q3tts_debug_stretch_rows: the stretch kernel's per-row path on host rows x [B][x_stride]; y [B][y_stride] comes back
+        with what each row wrote."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.ascontiguousarray(y, np.float32).copy()
+        ln = np.ascontiguousarray(lens, np.int32)
+        hp = np.ascontiguousarray(hops, np.int32)
+        self._check(self._lib.q3tts_debug_stretch_rows(self._h, x.ctypes.data_as(L.f32p), ln.ctypes.data_as(L.i32p), hp.ctypes.data_as(L.i32p),
+                                                       x.shape[0], x.shape[1], y.ctypes.data_as(L.f32p), y.shape[1]))
+        return y
 
     @property
     def tts_model_type(self) -> str:
@@ -343,6 +367,7 @@ class Qwen3TTSModel:
             arr[i].speaker = r.speaker.encode() if r.speaker is not None else None
             arr[i].language = (r.language or "auto").encode()
             arr[i].max_tokens = int(r.max_tokens)
+            arr[i].speed = float(getattr(r, "speed", 0.0) or 0.0)
             arr[i].route = int(getattr(r, "route", 0))
             if r.ref_audio is not None:
                 ra = np.ascontiguousarray(np.asarray(r.ref_audio, np.float32).reshape(-1))

@@ -19,6 +19,10 @@ its last TOKEN's arrival (the burst boundary that retired it) minus its generate
 --mixed-sampling gives the ragged workload's requests parameters of their own (q3tts_sampling.per_request), four sets in turn:
 the call's, greedy, top-k 20 / top-p 0.9 / T 0.7 with a seed, and repetition penalty 1.5; static and queued must still agree bit
 for bit, and the queue's rows now include top-p rows beside the others in every frame step.
+--request-speeds S1,S2,... loads the handle with q3tts_load_opts.request_speeds and deals the speeds round robin over the requests
+(q3tts_request.speed): static and queued must still agree bit for bit. With --stream the
+streamed queue serves them too (every ring slot then holds rows of the slowest request's frame size, printed in bytes); on a handle
+with --output-sample-rate only speeds whose hop is the handle's are streamed, and the streamed run is skipped otherwise.
 --voices N (a Base checkpoint) runs the ragged workload as voice-clone requests with N reference clips (3 s each) shared round-robin:
   static   pipelined batches whose requests carry their clip as ref_audio (every batch encodes its clips again)
   queued   one q3tts_generate_queued call whose requests name one of N voices made once by create_voice
@@ -394,12 +398,18 @@ def main():
                     help="load the model with q3tts_load_opts.output_sample_rate = R (0: the decoder's own 24000)")
     ap.add_argument("--speed", type=float, default=0.0, metavar="S",
                     help="load the model with q3tts_load_opts.speed = S (0: off; 0.5 .. 2.0: the time stretch in the decoder's tail)")
+    ap.add_argument("--request-speeds", default=None, metavar="S1,S2,...",
+                    help="load the model with q3tts_load_opts.request_speeds and deal these speeds round robin over the requests "
+                         "(q3tts_request.speed; 0: the handle's)")
     ap.add_argument("--only-stream", action="store_true", help="with --stream: skip the static / queued comparison in front of it")
     args = ap.parse_args()
     from qwen3tts import Qwen3TTSModel, RequestSampling
     rate_kw = dict(output_sample_rate=args.output_sample_rate) if args.output_sample_rate else {}
     if args.speed:
         rate_kw["speed"] = args.speed
+    req_speeds = [float(s) for s in args.request_speeds.split(",")] if args.request_speeds else []
+    if req_speeds:
+        rate_kw["request_speeds"] = True
 
     ckpt = bench.ensure_checkpoint(args.preset, 0, None)
     if args.voices > 0:  # (an ICL prompt carries the reference text and one row per reference frame: 3 s are 38 frames)
@@ -421,11 +431,19 @@ def main():
                 RequestSampling(repetition_penalty=1.5)]
         for i, r in enumerate(ragged):
             r.sampling = sets[i % 4]
+    if req_speeds:
+        for reqs in (ragged, base):
+            for i, r in enumerate(reqs):
+                r.speed = req_speeds[i % len(req_speeds)]
+        hops = sorted({model.request_speed_info(s)[1] for s in req_speeds})
+        extra = (model.info.max_samples_per_frame - model.info.samples_per_frame) * 4
+        print(f"# request speeds {req_speeds} -> synthesis hops {hops} (the handle's: {model.stretch_hs}); PCM buffers of mixed jobs hold "
+              f"{model.info.max_samples_per_frame} samples per frame, {extra} bytes per row and frame more than the handle's own", flush=True)
     sampling = dict(temperature=0.9, top_k=50, top_p=1.0, repetition_penalty=1.05, seed=1234)
     workloads = [("ragged", ragged, dict(sampling)), ("uniform", base, dict(sampling, force_frames=200))]
 
     # warm-up: both frame graphs captured, projected tables built, codec scratch grown
-    warm = [type(r)(r.text_ids, r.target_token_count, r.instruct_ids, r.speaker, r.language, 8) for r in base[:2 * args.slots]]
+    warm = [type(r)(r.text_ids, r.target_token_count, r.instruct_ids, r.speaker, r.language, 8, speed=r.speed) for r in base[:2 * args.slots]]
     run_static(model, warm, args.slots, sampling)
     run_queued(model, warm, args.slots, sampling)
 
@@ -457,9 +475,18 @@ def main():
     if args.stream:
         c, w, l = (int(x) for x in args.stream.split(","))
         skw = dict(audio_chunk_frames=c, audio_window_frames=w, audio_lookahead_frames=l)
-        run_queued_timed(model, warm, args.slots, dict(sampling, **skw))  # stream arena, pinned ring
+        # (on a handle with an output rate a request speed at another hop than the handle's is served with whole audio only)
+        streamable = not args.output_sample_rate or all(model.request_speed_info(s)[1] == model.stretch_hs for s in req_speeds)
+        if req_speeds and streamable:
+            ring = 8 * args.slots * c * 4  # CodecRunner::kRingSlots pinned slots of [slots][chunk * samples per frame] floats
+            print(f"# pinned ring: {ring * model.info.max_samples_per_frame} bytes ({ring * model.info.samples_per_frame} without "
+                  f"request_speeds)", flush=True)
+        if streamable:
+            run_queued_timed(model, warm, args.slots, dict(sampling, **skw))  # stream arena, pinned ring
+        else:
+            print("# --request-speeds with a hop other than the handle's at an output rate: the streamed run is skipped", flush=True)
         rows = {}
-        for name, kw in (("queued", dict(sampling)), ("streamed", dict(sampling, **skw))):
+        for name, kw in (("queued", dict(sampling)), ("streamed", dict(sampling, **skw)))[:2 if streamable else 1]:
             out, dt, tm, lat = run_queued_timed(model, ragged, args.slots, kw)
             frames = sum(int(r.codes.shape[0]) for r in out)
             rows[name] = (out, frames / dt)
@@ -467,6 +494,9 @@ def main():
             print(f"ragged   {name:8s} (callback) frames {frames:7d}  wall {dt:8.3f} s  frames/s {frames / dt:9.1f}  frame_steps {tm.frame_steps:6d}  "
                   f"codec {tm.codec_ms:8.1f} ms  first_audio {tm.first_audio_ms:7.1f} ms  {what}: median {np.median(lat) * 1e3:7.1f} ms  "
                   f"worst {lat.max() * 1e3:7.1f} ms  failed {sum(1 for r in out if r.status != 0)}", flush=True)
+        if not streamable:
+            model.close()
+            return
         same = all(np.array_equal(x.codes, y.codes) for x, y in zip(rows["queued"][0], rows["streamed"][0]))
         print(f"ragged   streamed --stream {args.stream}: same codes as the queue without it: {same}   frames/s streamed / queued: "
               f"{rows['streamed'][1] / rows['queued'][1]:.3f}", flush=True)

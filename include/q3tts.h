@@ -120,9 +120,33 @@ typedef struct {
 
 void q3tts_default_load_opts(q3tts_load_opts* o);
 
+/* new: the load options with what has been added since q3tts_load_opts was last pinned. q3tts_load_opts keeps its layout and
+ * its last field (existing callers and tests pin both), so a later option lives here, behind the options it extends, and is
+ * given to q3tts_model_load_ex. q3tts_model_load(dir, opts, out) is q3tts_model_load_ex with `base` = *opts and every
+ * extension at its default. */
+typedef struct {
+    q3tts_load_opts base; /* every option above, with its meaning and checks */
+    float pitch;        /* this handle's pitch in semitones at an unchanged duration
+                           ("Pitch" below). 0 (default): off -- nothing is added, launched or allocated, the samples are what a
+                           handle loaded without this field gives, bit for bit. Otherwise in [-12, 12]: with Ho the hop the
+                           handle would have had (480, or the Hs of `speed`) and rho = 2^(pitch / 12), Hp is the integer nearest
+                           to Ho * rho, ties toward Ho; Hp == Ho is off as well. The time stretch then runs at Hs = Hp and one
+                           resampler behind it takes Hp * M samples to Ho * L (L / M: output_sample_rate / 24000), so
+                           samples_per_frame, n_samples and every count in samples are those of the same handle without a
+                           pitch, every frequency is multiplied by Hp / Ho (q3tts_model_get_pitch reports the effective
+                           12 log2(Hp / Ho)), and every guarantee of `speed` with `output_sample_rate` holds, bit for bit.
+                           Q3TTS_ERR_INVALID_INPUT at load: a pitch outside [-12, 12], NaN or infinite, or together with
+                           request_speeds (both before any GPU work); no Hp in [240, 960] for this speed (never clamped:
+                           speed 0.5 leaves no room upward, speed 2 none downward); a codec frame that is not a whole number
+                           of 480-sample hops. Formants move with the pitch: beyond a few semitones the voice changes */
+} q3tts_load_opts_ex;
+
+void q3tts_default_load_opts_ex(q3tts_load_opts_ex* o); /* q3tts_default_load_opts for `base`, pitch 0 */
+
 /* Qwen3TTSModel.fromPretrained(_:) (Models/Qwen3.swift:1382-1452) + postLoadHook (:1455-1495,
  * minus the text tokenizer, which stays with the caller). */
 q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts, q3tts_model** out);
+q3tts_status q3tts_model_load_ex(const char* model_dir, const q3tts_load_opts_ex* opts, q3tts_model** out);
 void q3tts_model_free(q3tts_model* m);
 
 /* Message of the last failure on this handle (NULL handle: last load failure on this thread).
@@ -638,6 +662,24 @@ q3tts_status q3tts_model_get_speed(const q3tts_model* m, float* effective_speed,
 q3tts_status q3tts_time_stretch(q3tts_model* m, const float* in, int64_t n_in, float speed, int32_t causal, float* out, int64_t cap,
                                 int64_t* n_out);
 
+/* ---- Pitch (new) -----------------------------------------------------------------------------------------------------------
+ * q3tts_load_opts_ex.pitch, q3tts_pitch_shift: the time stretch above at Hs = Hp followed by the polyphase FIR of "Sample rates"
+ * for the ratio L' / M' = (Ho * L) / (Hp * M) reduced -- the same filter definition for any pair of integers: cutoff
+ * 0.945 * min(1, L' / M') of the input Nyquist, K' = ceil(16 / that factor) (at most 204), 2K' taps per phase. The decoder uses the
+ * causal forms of both; Hp == 480 (for example speed 1.25 with pitch +3.86) runs no stretch stage at all.
+ * q3tts_model_get_pitch: the effective shift 12 log2(Hp / Ho) in semitones (0: off), Hp, Ho (equal: off) and the delay of the two
+ * stages in output samples, ceil((D(Hp) * Hp / 480 + K') * L' / M') with D of "Speaking rate" (0 when Hp == 480 or off) -- the
+ * stretch's D 24 kHz samples are D * Hp / 480 samples in front of the FIR, which adds its K'. Any pointer may be NULL. On a
+ * pitched handle q3tts_model_get_speed keeps reporting the speaking rate, 480 / Ho and Ho.
+ * q3tts_pitch_shift: `in` (host, n_in >= 1 samples at 24 kHz) through the whole, undelayed forms -- the whole stretch at Hp
+ * (Ho = 480), then the centred FIR Hp -> 480, not clipped -- to `out` (host, `cap` samples of room); *n_out =
+ * ceil(ceil(n_in * Hp / 480) * L' / M') is always set. Hp == 480 (semitones 0): a copy. Q3TTS_ERR_INVALID_INPUT, the engine
+ * staying usable: semitones outside [-12, 12], NaN or infinite; n_in < 1 or > 2^26; non-finite samples; cap too small. One
+ * engine entry point like q3tts_time_stretch: one caller per handle, refused while a session is open. A pitch per request, a
+ * pitch per q3tts_codec_decode* call and formant preservation are not offered. */
+q3tts_status q3tts_model_get_pitch(const q3tts_model* m, float* effective_semitones, int32_t* hp, int32_t* ho, int32_t* delay_samples);
+q3tts_status q3tts_pitch_shift(q3tts_model* m, const float* in, int64_t n_in, float semitones, float* out, int64_t cap, int64_t* n_out);
+
 /* ---- Speaking rate per request (new) ---------------------------------------------------------------------------------------
  * On a handle loaded with q3tts_load_opts.request_speeds a request may set q3tts_request.speed. It then gets, bit for bit, what
  * a handle loaded with speed = that value (and the same output_sample_rate) gives for the request alone -- status, codes,
@@ -1025,6 +1067,16 @@ q3tts_status q3tts_debug_prefix_states(q3tts_model* m, int32_t* n_states, int64_
  * range or B outside 1..4096 is Q3TTS_ERR_INVALID_INPUT. */
 q3tts_status q3tts_debug_stretch_rows(q3tts_model* m, const float* x, const int32_t* lens, const int32_t* hops, int32_t B,
                                       int64_t x_stride, float* y, int64_t y_stride);
+
+/* The general-ratio resampler (kernels/resample_ratio.hip) on B host rows, for any pair of positive integers in_units ->
+ * out_units (a test hook; works on any handle): the filter of "Pitch" for L' / M' = out_units / in_units reduced. x
+ * [B][row_stride]: row b holds `hist` samples in front (read where the filter reaches back beyond the row's first sample; 0:
+ * none) and then lens[b] valid samples, hist + lens[b] <= row_stride. centred != 0: the centred form, otherwise the causal one;
+ * clamp != 0: the result is clipped to [-1, 1]. y [B][y_stride] is uploaded as the caller filled it and comes back whole: row b
+ * receives ceil(lens[b] * L' / M') samples, a row of length 0 nothing. Q3TTS_ERR_INVALID_INPUT: a row that does not fit, B
+ * outside 1..4096, a pair whose table exceeds 16 MiB or whose 256-output input span exceeds 64 KiB. */
+q3tts_status q3tts_debug_resample_ratio(q3tts_model* m, const float* x, const int32_t* lens, int32_t B, int64_t row_stride, int64_t in_units,
+                                        int64_t out_units, int32_t centred, int32_t clamp, int32_t hist, float* y, int64_t y_stride);
 
 /* The slotted codec stream of a streamed q3tts_generate_queued, driven by the queue's schedule without the talker (a test hook:
  * the real layer widths in seconds). codes [n_reqs][max_frames][16], n_frames[n_reqs] <= max_frames. Requests take the free ones

@@ -132,6 +132,12 @@ void q3tts_default_load_opts(q3tts_load_opts* o) {
     o->request_speeds = 0;
 }
 
+void q3tts_default_load_opts_ex(q3tts_load_opts_ex* o) {
+    std::memset(o, 0, sizeof(*o));
+    q3tts_default_load_opts(&o->base);
+    o->pitch = 0.0f;
+}
+
 void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
     s->temperature = 0.9f;
     s->top_k = 50;
@@ -148,17 +154,39 @@ void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
 }
 
 q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts, q3tts_model** out) {
+    q3tts_load_opts_ex ex;
+    q3tts_default_load_opts_ex(&ex);
+    if (opts) ex.base = *opts;
+    return q3tts_model_load_ex(model_dir, &ex, out);
+}
+
+q3tts_status q3tts_model_load_ex(const char* model_dir, const q3tts_load_opts_ex* opts, q3tts_model** out) {
     if (out) *out = nullptr;
     return guarded(nullptr, [&] {
         Q3_CHECK(model_dir && out, 3, "Invalid input: null argument");
         q3::debug_env_reload();  // the launchers' diagnostic switches are read here, once per load (kernels.h DebugEnv)
-        q3tts_load_opts o;
-        if (opts) o = *opts;
-        else q3tts_default_load_opts(&o);
+        q3tts_load_opts_ex ex;
+        if (opts) ex = *opts;
+        else q3tts_default_load_opts_ex(&ex);
+        const q3tts_load_opts& o = ex.base;
+        const float pitch = ex.pitch;
         Q3_CHECK(o.max_batch >= 1 && o.max_batch <= 64, 3, "Invalid input: max_batch must be in 1..64");
         Q3_CHECK(o.max_frames >= 1 && o.max_prompt >= 16, 3, "Invalid input: max_frames / max_prompt too small");
         // (a NaN fails every comparison: refused like a value out of range, and before the first call into the GPU runtime)
         Q3_CHECK(o.speed == 0.0f || (o.speed >= 0.5f && o.speed <= 2.0f), 3, "Invalid input: speed must be 0 (off) or between 0.5 and 2.0");
+        Q3_CHECK(q3::pitch_semitones_valid(pitch), 3, "Invalid input: pitch must be 0 (off) or between -12 and 12 semitones");
+        Q3_CHECK(pitch == 0.0f || o.request_speeds == 0, 3,
+                 "Invalid input: pitch and request_speeds cannot be combined (a table per pair of hops)");
+        if (pitch != 0.0f && (o.output_sample_rate == 0 || o.output_sample_rate == q3::kResampleNative ||
+                                q3::resample_rate_supported(o.output_sample_rate))) {
+            // no Hp in [240, 960]: refused here when no frame of 1 to 8 hops admits the combination (the codec's own frame is
+            // known only once the checkpoint is read; the runner checks again with it)
+            const int rate = o.output_sample_rate ? o.output_sample_rate : q3::kResampleNative;
+            const int g = q3::resample_detail::gcd(q3::kResampleNative, rate);
+            bool some = false;
+            for (int hops = 1; hops <= 8; ++hops) some = some || q3::pitch_choose(pitch, o.speed, hops, rate / g, q3::kResampleNative / g).status == 0;
+            Q3_CHECK(some, 3, "Invalid input: no hop in [240, 960] for this pitch and speed");
+        }
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
         Q3_CHECK(e == hipSuccess && ndev > 0, 7, "no HIP device available: this engine has no CPU fallback");
@@ -171,7 +199,7 @@ q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts
         lo.skip_tensor_data = o.weights_from_broadcast != 0;
         auto model = q3::load_model(model_dir, lo);
         auto h = std::make_unique<q3tts_model>();
-        h->eng = std::make_unique<EngineGroup>(std::move(model), o);
+        h->eng = std::make_unique<EngineGroup>(std::move(model), o, pitch);
         *out = h.release();
     });
 }
@@ -328,6 +356,25 @@ q3tts_status q3tts_model_get_speed(const q3tts_model* m, float* effective_speed,
         if (hs) *hs = h;
         if (delay_samples) *delay_samples = cr ? cr->stretch_delay_samples() : 0;
     }, false);
+}
+
+q3tts_status q3tts_model_get_pitch(const q3tts_model* m, float* effective_semitones, int32_t* hp, int32_t* ho, int32_t* delay_samples) {
+    return guarded(const_cast<q3tts_model*>(m), [&] {
+        Q3_CHECK(m, 3, "Invalid input: null argument");
+        const q3::CodecRunner* cr = m->eng->codec_runner();
+        const int o = cr ? cr->stretch_hs() : q3::kStretchHa, p = cr ? cr->pitch_hp() : o;
+        if (effective_semitones) *effective_semitones = p == o ? 0.0f : float(q3::pitch_effective_semitones(p, o));
+        if (hp) *hp = p;
+        if (ho) *ho = o;
+        if (delay_samples) *delay_samples = cr ? cr->pitch_delay_out_samples() : 0;
+    }, false);
+}
+
+q3tts_status q3tts_pitch_shift(q3tts_model* m, const float* in, int64_t n_in, float semitones, float* out, int64_t cap, int64_t* n_out) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && in && out && n_out, 3, "Invalid input: null argument");
+        m->eng->lane0().pitch_shift(in, n_in, semitones, out, cap, n_out);
+    });
 }
 
 q3tts_status q3tts_request_speed_info(const q3tts_model* m, float speed, float* effective_speed, int32_t* hs, int32_t* delay_samples,
@@ -720,6 +767,14 @@ q3tts_status q3tts_debug_stretch_rows(q3tts_model* m, const float* x, const int3
     return guarded(m, [&] {
         Q3_CHECK(m && x && lens && hops && y, 3, "Invalid input: null argument");
         m->eng->lane0().debug_stretch_rows(x, lens, hops, B, x_stride, y, y_stride);
+    });
+}
+
+q3tts_status q3tts_debug_resample_ratio(q3tts_model* m, const float* x, const int32_t* lens, int32_t B, int64_t row_stride, int64_t in_units,
+                                        int64_t out_units, int32_t centred, int32_t clamp, int32_t hist, float* y, int64_t y_stride) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && x && lens && y, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_resample_ratio(x, lens, B, row_stride, in_units, out_units, centred != 0, clamp != 0, hist, y, y_stride);
     });
 }
 

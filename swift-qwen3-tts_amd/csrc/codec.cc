@@ -16,10 +16,54 @@ size_t kScratchBudget = size_t(24) << 30;  // activation scratch per group of ro
 }
 void CodecRunner::set_scratch_budget(size_t bytes) { kScratchBudget = bytes ? bytes : (size_t(24) << 30); }
 
-CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate, float speed, bool request_speeds)
+CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate, float speed, bool request_speeds,
+                         float pitch)
     : m_(m), st_(st) {
     native_ = mid_ = up_ = m.cfg.codec.total_upsample();
-    if (speed != 0.0f && speed != 1.0f) {
+    const bool other_rate = output_rate != 0 && output_rate != kResampleNative;
+    int hL = 1, hM = 1;  // the handle's output rate over 24000, reduced
+    if (other_rate && resample_rate_supported(output_rate)) {
+        const int g = resample_detail::gcd(kResampleNative, output_rate);
+        hL = output_rate / g;
+        hM = kResampleNative / g;
+    }
+    if (pitch != 0.0f && (!other_rate || resample_rate_supported(output_rate))) {  // (an unsupported rate is refused below)
+        Q3_CHECK(!request_speeds, 3, "Invalid input: pitch and request_speeds cannot be combined (a table per pair of hops)");
+        Q3_CHECK(native_ % kStretchHa == 0, 3, "Invalid input: the codec's frame is not a whole number of 480-sample hops: no pitch other than 0");
+        const int hops = native_ / kStretchHa;
+        const PitchChoice pc = pitch_choose(pitch, speed, hops, hL, hM);
+        Q3_CHECK(pc.status != 1, 3, "Invalid input: pitch must be 0 (off) or between -12 and 12 semitones");
+        Q3_CHECK(pc.status != 2, 3, "Invalid input: speed must be 0 (off) or between 0.5 and 2.0");
+        Q3_CHECK(pc.status == 0, 3, "Invalid input: no hop in [240, 960] for this pitch and speed");
+        if (pc.on()) {
+            pitched_ = true;
+            ho_ = pc.ho;
+            pitch_hp_ = pc.hp;
+            out_rate_ = other_rate ? output_rate : kResampleNative;
+            mid_ = hops * pc.hp;
+            if (pc.hp != kStretchHa) {  // (Hp == 480: the resampler reads out_conv's signal, no stretch stage and no delay of one)
+                st_plan_ = make_stretch_plan(pc.hp);
+                Q3_CHECK(stretch_lookback(pc.hp) <= hist_frames() * native_, 7, "internal error: time stretch history beyond the stream's margin");
+                stretch_ = true;
+                Q3_HIP(hipMemcpy(st_fade_.grow(size_t(pc.hp)), st_plan_.fade.data(), size_t(pc.hp) * 4, hipMemcpyHostToDevice));
+            }
+            const PitchRatio pr = pitch_ratio(pc.hp, pc.ho, hL, hM);
+            out_plan_ = make_resample_plan(int(pr.in_units), int(pr.out_units));
+            Q3_CHECK(out_plan_.L == pr.L && out_plan_.M == pr.M && out_plan_.K == pr.K, 7, "internal error: pitch ratio and resampling plan disagree");
+            up_ = int(int64_t(hops) * pc.ho * hL / hM);
+            // phase 0 recurs at every frame and q stays inside it; the FIR's look-back lies inside the margins the streams and
+            // decode_chunked (one frame of the stretched signal) carry
+            Q3_CHECK(int64_t(up_) * out_plan_.M == int64_t(mid_) * out_plan_.L, 7, "internal error: a pitched frame is not whole samples");
+            Q3_CHECK(out_plan_.taps() - 1 <= hist_frames() * mid_ && out_plan_.taps() - 1 <= mid_, 7,
+                     "internal error: resampler history beyond the stream's margin");
+            Q3_CHECK(resample_ratio_lds_bytes(out_plan_.L, out_plan_.M, out_plan_.K) <= 64 * 1024, 7, "internal error: resampler span beyond its LDS budget");
+            resample_ = true;
+            pitch_delay_ = q3::pitch_delay_out_samples(pc.hp, pr);
+            const std::vector<float> tab = resample_table_output_order(out_plan_);
+            Q3_HIP(hipMemcpy(out_tab_.grow(tab.size()), tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        }
+    }
+    if (!pitched_ && speed != 0.0f && speed != 1.0f) {
         Q3_CHECK(speed >= 0.5f && speed <= 2.0f, 3, "Invalid input: speed must be 0 (off) or between 0.5 and 2.0");
         Q3_CHECK(native_ % kStretchHa == 0, 3, "Invalid input: the codec's frame is not a whole number of 480-sample hops: no speed other than 1");
         const int hops = native_ / kStretchHa;
@@ -37,10 +81,11 @@ CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int ou
             Q3_CHECK(stretch_lookback(hs) <= hist_frames() * native_, 7, "internal error: time stretch history beyond the stream's margin");
             mid_ = up_ = hops * hs;
             stretch_ = true;
+            ho_ = hs;
             Q3_HIP(hipMemcpy(st_fade_.grow(size_t(hs)), st_plan_.fade.data(), size_t(hs) * 4, hipMemcpyHostToDevice));
         }
     }
-    if (output_rate != 0 && output_rate != kResampleNative) {
+    if (!pitched_ && other_rate) {
         Q3_CHECK(resample_rate_supported(output_rate), 3,
                  "Invalid input: output_sample_rate must be 0, 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000");
         out_plan_ = make_resample_plan(kResampleNative, output_rate);
@@ -51,16 +96,15 @@ CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int ou
         Q3_CHECK(out_plan_.taps() - 1 <= hist_frames() * mid_, 7, "internal error: resampler history beyond the stream's margin");
         up_ = int(int64_t(mid_) * out_plan_.L / out_plan_.M);
         resample_ = true;
+        out_rate_ = output_rate;
         const size_t n = align_up(out_plan_.tab.size(), 4);
         std::vector<float> padded(n, 0.0f);
         std::copy(out_plan_.tab.begin(), out_plan_.tab.end(), padded.begin());
         Q3_HIP(hipMemcpy(out_tab_.grow(n), padded.data(), n * 4, hipMemcpyHostToDevice));
     }
     if (native_ % kStretchHa == 0) rs_plan_.hops_per_frame = native_ / kStretchHa;
-    if (resample_) {
-        rs_plan_.L = out_plan_.L;
-        rs_plan_.M = out_plan_.M;
-    }
+    rs_plan_.L = hL;
+    rs_plan_.M = hM;
     rs_plan_.handle_hs = stretch_hs();
     if (request_speeds) {
         Q3_CHECK(native_ % kStretchHa == 0, 3, "Invalid input: the codec's frame is not a whole number of 480-sample hops: no request speeds");
@@ -510,7 +554,8 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
                 a.len_mul_rows = ps.mid_rows;
                 a.tab = out_tab_; a.L = out_plan_.L; a.M = out_plan_.M; a.K = out_plan_.K;
                 a.hist = rin_hist; a.centred = 0; a.clamp = 1; a.B = nb;
-                launch_resample(a, st_);
+                if (pitched_) launch_resample_ratio(a, st_);
+                else launch_resample(a, st_);
             });
         }
         if (mid) mem.put(mid);

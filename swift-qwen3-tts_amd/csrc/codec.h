@@ -1,11 +1,12 @@
 // codec.h -- neural codec decoder runner (codes -> PCM at 24 kHz or at the handle's output rate) on the HIP kernels in
-// kernels/codec_conv.hip, kernels/codec_misc.hip, kernels/stretch.hip and kernels/resample.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
+// kernels/codec_conv.hip, kernels/codec_misc.hip, kernels/stretch.hip, kernels/resample.hip and kernels/resample_ratio.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
 // (/root/reference/Sources/Qwen3TTS/Models/SpeechTokenizer.swift:754-784).
 #pragma once
 #include <string>
 #include <vector>
 
 #include "model.h"
+#include "pitch_plan.h"
 #include "request_speed_plan.h"
 #include "resample_plan.h"
 #include "stream_plan.h"
@@ -28,8 +29,13 @@ class CodecRunner {
     // context, cannot recompute the word and carries it (and the resampler's input margin) from chunk to chunk.
     // request_speeds: rows of one decode() may speak at speeds of their own (request_speed_plan.h). The fade tables of every
     // hop go to the device here, once; a decode without a hop table is the handle's own, untouched.
+    // pitch: 0 -- off, nothing is added. Otherwise semitones in [-12, 12] (pitch_plan.h): with Ho the hop the handle would have
+    // had (480, or the speed's) and Hp the integer nearest to Ho * 2^(pitch / 12), the stretch runs at Hs = Hp (no stretch stage
+    // when Hp == 480) and ONE resampler behind it, Hp * M -> Ho * L on kernels/resample_ratio.hip, does pitch and output rate
+    // together: the same pair of stages as a speed with an output rate, so every statement above holds with mid samples per
+    // frame 4 Hp and upsample() that of the handle without a pitch. Hp == Ho is off. Not together with request_speeds.
     CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false, int output_rate = 0, float speed = 0.0f,
-                bool request_speeds = false);
+                bool request_speeds = false, float pitch = 0.0f);
     // codes_dev: [B][code_stride_frames][16] int32 on the device; rows decode frames[b] frames.
     // pcm_dev receives [B][Fmax*upsample] float32 (Fmax = max(frames)); returns Fmax.
     // If `stage` is non-empty the activation after that stage is copied to stage_out ([B][T][C]).
@@ -142,10 +148,15 @@ class CodecRunner {
     const RequestSpeedPlan& speed_plan() const { return rs_plan_; }
     int upsample_of(int hs) const { return rs_plan_.spf(hs); }
     int max_upsample() const { return rs_ ? rs_plan_.max_spf() : up_; }
-    int output_rate() const { return resample_ ? out_plan_.out_rate : kResampleNative; }
-    // the time stretch of this handle: synthesis hop (480: off), effective speed 480 / Hs, delay D in 24 kHz samples
-    int stretch_hs() const { return stretch_ ? st_plan_.hs : kStretchHa; }
+    int output_rate() const { return out_rate_; }  // (a pitched handle resamples whatever its rate: resample_ does not tell)
+    // the speaking rate of this handle: its hop Ho (480: off; on a pitched handle the stretch itself runs at pitch_hp()),
+    // effective speed 480 / Ho, the stretch stage's delay D in 24 kHz samples
+    int stretch_hs() const { return ho_; }
     int stretch_delay_samples() const { return stretch_ ? st_plan_.delay : 0; }
+    // the pitch of this handle (pitch_plan.h): the hop in front of the resampler (== stretch_hs(): off), the delay of the
+    // stretch and the FIR together in output samples
+    int pitch_hp() const { return pitched_ ? pitch_hp_ : ho_; }
+    int pitch_delay_out_samples() const { return pitch_delay_; }
     hipStream_t stream() const { return st_; }
     void set_stream(hipStream_t st) { st_ = st; }  // the caller drains the old stream first (shared scratch)
 
@@ -256,8 +267,12 @@ class CodecRunner {
     int up_ = 1920;      // samples per frame of the PCM handed out (== native_ unless an output rate was asked for)
     int native_ = 1920;  // samples per frame behind out_conv
     bool resample_ = false;
-    ResamplePlan out_plan_;   // 24000 -> output rate
-    DevBuf<float> out_tab_;   // its phase table on the device
+    int out_rate_ = kResampleNative;  // the rate of the PCM handed out
+    ResamplePlan out_plan_;   // 24000 -> output rate (a pitched handle: Hp * M -> Ho * L)
+    DevBuf<float> out_tab_;   // its phase table on the device (a pitched handle: in output order, for resample_ratio.hip)
+    int ho_ = kStretchHa;     // the speaking rate's hop
+    bool pitched_ = false;    // the resampler is the general-ratio one and the stretch, if any, runs at pitch_hp_
+    int pitch_hp_ = kStretchHa, pitch_delay_ = 0;
     int mid_ = 1920;          // samples per frame behind the time stretch == in front of the resampler (4 Hs, or native_)
     bool stretch_ = false;
     StretchPlan st_plan_;

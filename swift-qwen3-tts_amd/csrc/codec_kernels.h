@@ -210,6 +210,12 @@ struct ResampleArgs {
 };
 void launch_resample(const ResampleArgs& a, hipStream_t st);
 size_t resample_lds_bytes(int L, int M, int K);
+// The same stage for any reduced ratio (kernels/resample_ratio.hip): `tab` is the plan's table in output order, [2K][L] with
+// column c holding phase (c * M) % L (pitch_plan.h resample_table_output_order), and stays in global memory; everything else
+// in ResampleArgs means what it means above. Chosen by its callers -- a pitched handle, q3tts_pitch_shift,
+// q3tts_debug_resample_ratio -- never by a table size.
+void launch_resample_ratio(const ResampleArgs& a, hipStream_t st);
+size_t resample_ratio_lds_bytes(int L, int M, int K);
 
 // ---- time stretch (kernels/stretch.hip; the definition: stretch_plan.h) ----
 // Row b's input starts at x + b * x_bstride and has len[b] * len_mul valid samples at 24 kHz; its outputs (causal:

@@ -13,7 +13,7 @@ std::string lower(const std::string& s) {
 }
 }  // namespace
 
-Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opts) {
+Engine::Engine(Model* model, const q3tts_load_opts& opts, float pitch) : m_(model), opts_(opts) {
     Q3_HIP(hipSetDevice(m_->device));
     {
         // The AR loop is a chain of short dependent launches (latency), the codec decode a few hundred large ones
@@ -66,7 +66,7 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts) : m_(model), opts_(opt
     }
     if (m_->has_codec)
         codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0, opts.output_sample_rate, opts.speed,
-                                               opts.request_speeds != 0);
+                                               opts.request_speeds != 0, pitch);
     if (m_->has_codec_encoder || m_->has_speaker_encoder) fe_ = std::make_unique<VoiceFrontEnd>(*m_, st_);
 }
 
@@ -1042,6 +1042,113 @@ void Engine::debug_stretch_rows(const float* x, const int32_t* lens, const int32
     sa.hs_rows = dl + B; sa.fade_all = dbg_fade_all_;
     sa.causal = 1; sa.B = B;
     launch_stretch(sa, st_);
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy2D(y, size_t(y_stride) * 4, dy, size_t(ys) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyDeviceToHost));
+}
+
+const Engine::ResamplerDev& Engine::ratio_resampler(int64_t in_units, int64_t out_units) {
+    Q3_CHECK(in_units >= 1 && out_units >= 1 && in_units <= (int64_t(1) << 30) && out_units <= (int64_t(1) << 30), 3,
+             "Invalid input: a resampling ratio takes two integers between 1 and 2^30");
+    for (const auto& r : ratios_)
+        if (r->plan.in_rate == int(in_units) && r->plan.out_rate == int(out_units)) return *r;
+    // (sized before it is built: the table's L * 2K entries cost a Bessel series each)
+    const PitchRatio pr = pitch_ratio(int(in_units), int(out_units), 1, 1);
+    Q3_CHECK(int64_t(pr.L) * 2 * pr.K <= (int64_t(1) << 22), 3, "Invalid input: the ratio's phase table is larger than 16 MiB");
+    Q3_CHECK(resample_ratio_lds_bytes(pr.L, pr.M, pr.K) <= 64 * 1024, 3, "Invalid input: the ratio's input span is larger than its LDS budget");
+    auto r = std::make_unique<ResamplerDev>();
+    r->plan = make_resample_plan(int(in_units), int(out_units));
+    const std::vector<float> tab = resample_table_output_order(r->plan);
+    Q3_HIP(hipMemcpy(r->tab.grow(tab.size()), tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    ratios_.push_back(std::move(r));
+    return *ratios_.back();
+}
+
+void Engine::pitch_shift(const float* in, int64_t n_in, float semitones, float* out, int64_t cap, int64_t* n_out) {
+    // (the pitch is refused first, whatever else is wrong, and before any GPU work)
+    const int hp = pitch_choose_hp(kStretchHa, semitones);
+    Q3_CHECK(hp != 0, 3, "Invalid input: pitch must lie between -12 and 12 semitones");
+    Q3_CHECK(in && out && n_out && n_in > 0, 3, "Invalid input: empty audio");
+    Q3_CHECK(n_in <= (int64_t(1) << 26), 3, "Invalid input: pitch shift takes between 1 and 2^26 samples");
+    const int64_t n_mid = (n_in * hp + kStretchHa - 1) / kStretchHa;  // the whole form's length at Hp
+    const PitchRatio pr = pitch_ratio(hp, kStretchHa, 1, 1);
+    const int64_t no = hp == kStretchHa ? n_in : (n_mid * pr.L + pr.M - 1) / pr.M;
+    *n_out = no;
+    Q3_CHECK(cap >= no, 3, "Invalid input: output buffer too small for the shifted audio");
+    bool finite = true;
+    for (int64_t i = 0; i < n_in; ++i) finite = finite && (std::fabs(in[i]) <= 3.0e38f);
+    Q3_CHECK(finite, 3, "Invalid input: audio holds non-finite samples");
+    if (hp == kStretchHa) {  // off: the samples as they are
+        std::memcpy(out, in, size_t(n_in) * 4);
+        return;
+    }
+    StretchDev* sd = nullptr;
+    for (const auto& s : stretchers_)
+        if (s->plan.hs == hp) sd = s.get();
+    if (!sd) {
+        auto s = std::make_unique<StretchDev>();
+        s->plan = make_stretch_plan(hp);
+        Q3_HIP(hipMemcpy(s->fade.grow(size_t(hp)), s->plan.fade.data(), size_t(hp) * 4, hipMemcpyHostToDevice));
+        stretchers_.push_back(std::move(s));
+        sd = stretchers_.back().get();
+    }
+    const ResamplerDev& r = ratio_resampler(hp, kStretchHa);
+    const float* a = upload_audio(in, n_in);
+    if (size_t(no) > rs_out_dev_.capacity() || size_t(n_mid) > ps_mid_dev_.capacity()) Q3_HIP(hipStreamSynchronize(st_));  // the old buffers may still be read
+    rs_out_dev_.grow(size_t(no));
+    ps_mid_dev_.grow(size_t(n_mid));
+    rs_len_dev_.grow(2);
+    const int32_t len[2] = {int32_t(n_in), int32_t(n_mid)};
+    Q3_HIP(hipStreamSynchronize(st_));  // `len` is pageable stack memory, and the device words may still feed an earlier launch
+    Q3_HIP(hipMemcpy(rs_len_dev_, len, 8, hipMemcpyHostToDevice));
+    StretchArgs sa{};
+    sa.x = a; sa.y = ps_mid_dev_;
+    sa.len = rs_len_dev_; sa.len_mul = 1;
+    sa.fade = sd->fade; sa.hs = hp; sa.delay = 0;
+    sa.causal = 0; sa.B = 1;
+    launch_stretch(sa, st_);
+    ResampleArgs ra{};
+    ra.x = ps_mid_dev_; ra.x_bstride = 0;
+    ra.y = rs_out_dev_; ra.y_bstride = 0;
+    ra.len = rs_len_dev_ + 1; ra.len_mul = 1; ra.max_in = n_mid;
+    ra.tab = r.tab; ra.L = r.plan.L; ra.M = r.plan.M; ra.K = r.plan.K;
+    ra.hist = 0; ra.centred = 1; ra.clamp = 0; ra.B = 1;
+    launch_resample_ratio(ra, st_);
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy(out, rs_out_dev_, size_t(no) * 4, hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_resample_ratio(const float* x, const int32_t* lens, int B, int64_t row_stride, int64_t in_units, int64_t out_units,
+                                  bool centred, bool clamp, int hist, float* y, int64_t y_stride) {
+    Q3_CHECK(B >= 1 && B <= 4096 && row_stride >= 1 && y_stride >= 1 && row_stride <= (int64_t(1) << 26) && y_stride <= (int64_t(1) << 27) &&
+                 hist >= 0 && hist <= row_stride, 3,
+             "Invalid input: debug_resample_ratio takes 1..4096 rows of at most 2^26 samples");
+    const ResamplerDev& r = ratio_resampler(in_units, out_units);
+    int64_t max_in = 0;
+    for (int b = 0; b < B; ++b) {
+        Q3_CHECK(lens[b] >= 0 && int64_t(hist) + lens[b] <= row_stride, 3, "Invalid input: a row is longer than row_stride");
+        Q3_CHECK(r.plan.out_len(lens[b]) <= y_stride, 3, "Invalid input: a row's output does not fit y_stride");
+        max_in = std::max<int64_t>(max_in, lens[b]);
+    }
+    // a row's first sample (behind its margin) starts at a 16-byte boundary on the device, as the tail's tensors do
+    const int64_t hpad = (int64_t(hist) + 3) & ~int64_t(3);
+    const int64_t xs = (hpad - hist + row_stride + 3) & ~int64_t(3), ys = (y_stride + 3) & ~int64_t(3);
+    DevBuf<float> dx, dy;
+    DevBuf<int32_t> dl;
+    dx.grow(size_t(B) * size_t(xs));
+    dy.grow(size_t(B) * size_t(ys));
+    dl.grow(size_t(B));
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemset(dx, 0, size_t(B) * size_t(xs) * 4));
+    Q3_HIP(hipMemcpy2D(dx + (hpad - hist), size_t(xs) * 4, x, size_t(row_stride) * 4, size_t(row_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy2D(dy, size_t(ys) * 4, y, size_t(y_stride) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(dl, lens, size_t(B) * 4, hipMemcpyHostToDevice));
+    ResampleArgs ra{};
+    ra.x = dx + hpad; ra.x_bstride = xs;
+    ra.y = dy; ra.y_bstride = ys;
+    ra.len = dl; ra.len_mul = 1; ra.max_in = max_in;
+    ra.tab = r.tab; ra.L = r.plan.L; ra.M = r.plan.M; ra.K = r.plan.K;
+    ra.hist = hist; ra.centred = centred ? 1 : 0; ra.clamp = clamp ? 1 : 0; ra.B = B;
+    launch_resample_ratio(ra, st_);
     Q3_HIP(hipStreamSynchronize(st_));
     Q3_HIP(hipMemcpy2D(y, size_t(y_stride) * 4, dy, size_t(ys) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyDeviceToHost));
 }

@@ -20,6 +20,7 @@
 #include "../../include/q3tts.h"
 #include "kernels.h"
 #include "model.h"
+#include "pitch_plan.h"
 #include "queue_slots.h"
 #include "resample_plan.h"
 #include "session_queue.h"
@@ -201,7 +202,7 @@ struct QueueShared {
 class Engine {
   public:
     // One lane: a slice of the batch with its own stream, workspace, KV pool and frame graph.
-    Engine(Model* model, const q3tts_load_opts& opts);
+    Engine(Model* model, const q3tts_load_opts& opts, float pitch = 0.0f);  // pitch: q3tts_load_opts_ex.pitch
     ~Engine();
 
     Model& model() { return *m_; }
@@ -284,6 +285,12 @@ class Engine {
     void time_stretch(const float* in, int64_t n_in, float speed, bool causal, float* out, int64_t cap, int64_t* n_out);
     // q3tts_debug_stretch_rows: the kernel's per-row path (a hop per row, the fade tables of every hop) on host rows, causal form
     void debug_stretch_rows(const float* x, const int32_t* lens, const int32_t* hops, int B, int64_t x_stride, float* y, int64_t y_stride);
+    // q3tts_pitch_shift: a 24 kHz host buffer through the whole, undelayed form of a pitched handle's two stages -- the time
+    // stretch whole at Hp (pitch_plan.h, Ho = 480), then the centred general-ratio resampler Hp -> 480
+    void pitch_shift(const float* in, int64_t n_in, float semitones, float* out, int64_t cap, int64_t* n_out);
+    // q3tts_debug_resample_ratio: kernels/resample_ratio.hip on host rows, any positive integer pair
+    void debug_resample_ratio(const float* x, const int32_t* lens, int B, int64_t row_stride, int64_t in_units, int64_t out_units, bool centred,
+                              bool clamp, int hist, float* y, int64_t y_stride);
     void debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C);
 
     std::vector<std::string> speakers;  // sorted (Qwen3.swift:965-971)
@@ -489,6 +496,11 @@ class Engine {
     std::vector<std::unique_ptr<StretchDev>> stretchers_;
     DevBuf<float> dbg_fade_all_;  // debug_stretch_rows: the fade tables of every hop, uploaded at its first call
     const ResamplerDev& resampler(int in_rate, int out_rate);
+    // the general-ratio filters (kernels/resample_ratio.hip) q3tts_pitch_shift and q3tts_debug_resample_ratio have been asked
+    // for: the plan of the pair as given, the table in output order on the device
+    std::vector<std::unique_ptr<ResamplerDev>> ratios_;
+    const ResamplerDev& ratio_resampler(int64_t in_units, int64_t out_units);
+    DevBuf<float> ps_mid_dev_;  // pitch_shift: the stretched signal between its two stages
     // `audio` (host, n samples at in_rate, finite) -> device buffer of *n_out samples at out_rate, queued on st_
     const float* resample_upload(const float* audio, int64_t n, int in_rate, int out_rate, bool centred, int64_t* n_out);
     bool prepare_clone_rows(std::vector<ResolvedRequest>& reqs);  // true: the front end ran (some row carried a waveform)
@@ -582,7 +594,7 @@ class Session;
 // batches, each on a context of its own, are what the two-deep pipeline runs side by side (Engine::begin).
 class EngineGroup {
   public:
-    EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts);
+    EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts, float pitch = 0.0f);
     Model& model() { return *model_; }
     ~EngineGroup();
     Engine& lane0() {  // the engine behind the single-engine entry points; a back half still running on it finishes first

@@ -23,6 +23,10 @@ class LoadOpts(C.Structure):
                 ("output_sample_rate", C.c_int32), ("speed", C.c_float), ("request_speeds", C.c_int32)]
 
 
+class LoadOptsEx(C.Structure):  # q3tts_load_opts_ex: the options above and what has been added behind them
+    _fields_ = [("base", LoadOpts), ("pitch", C.c_float)]
+
+
 class CommId(C.Structure):  # q3tts_comm_id == ncclUniqueId
     _fields_ = [("bytes", C.c_char * 128)]
 
@@ -252,6 +256,14 @@ def lib() -> C.CDLL:
     if hasattr(L, "q3tts_request_speed_info"):
         L.q3tts_request_speed_info.argtypes = [vp, C.c_float, C.POINTER(C.c_float), i32p, i32p, i32p]
         L.q3tts_debug_stretch_rows.argtypes = [vp, f32p, i32p, i32p, C.c_int32, C.c_int64, f32p, C.c_int64]
+    if hasattr(L, "q3tts_pitch_shift"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_default_load_opts_ex.argtypes = [C.POINTER(LoadOptsEx)]
+        L.q3tts_default_load_opts_ex.restype = None
+        L.q3tts_model_load_ex.argtypes = [C.c_char_p, C.POINTER(LoadOptsEx), C.POINTER(vp)]
+        L.q3tts_model_get_pitch.argtypes = [vp, C.POINTER(C.c_float), i32p, i32p, i32p]
+        L.q3tts_pitch_shift.argtypes = [vp, f32p, C.c_int64, C.c_float, f32p, C.c_int64, C.POINTER(C.c_int64)]
+        L.q3tts_debug_resample_ratio.argtypes = [vp, f32p, i32p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                 f32p, C.c_int64]
     if hasattr(L, "q3tts_debug_prefix_states"):
         L.q3tts_debug_prefix_states.argtypes = [vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "q3tts_debug_codec_stream_slots"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)

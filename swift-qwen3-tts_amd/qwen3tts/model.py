@@ -165,14 +165,17 @@ class Qwen3TTSModel:
                         max_prompt: int = 512, use_graph: bool = True,
                         weights_from_broadcast: bool = False, n_streams: int = 0,
                         codec_overlap_cus: int = 0, codec_fp32: bool = False,
-                        output_sample_rate: int = 0, speed: float = 0.0, request_speeds: bool = False) -> "Qwen3TTSModel":
+                        output_sample_rate: int = 0, speed: float = 0.0, request_speeds: bool = False,
+                        pitch: float = 0.0) -> "Qwen3TTSModel":
         """output_sample_rate (q3tts_load_opts.output_sample_rate): 0 = 24000; 8000, 12000, 16000, 22050, 32000, 44100 or
         48000 make every waveform of this handle leave at that rate (sample_rate and info.samples_per_frame report it).
         speed (q3tts_load_opts.speed): 0 or 1.0 = off; 0.5 .. 2.0 make this handle speak that much faster, pitch preserved,
         through the time stretch in the decoder's tail (`speed`, `stretch_hs` and `stretch_delay_samples` report what was
         chosen, info.samples_per_frame follows).
         request_speeds (q3tts_load_opts.request_speeds): the handle admits GenerationRequest.speed, a speaking rate per
-        request (`request_speed_info` tells what one becomes; info.max_samples_per_frame is the slowest request's)."""
+        request (`request_speed_info` tells what one becomes; info.max_samples_per_frame is the slowest request's).
+        pitch (q3tts_load_opts_ex.pitch): 0 = off; -12 .. 12 semitones shift this handle's pitch at an unchanged duration
+        (`pitch_info` reports what was chosen; sample counts are those of the handle without it). Not with request_speeds."""
         lib = L.lib()
         o = L.LoadOpts()
         lib.q3tts_default_load_opts(C.byref(o))
@@ -186,7 +189,15 @@ class Qwen3TTSModel:
         o.speed = float(speed)
         o.request_speeds = 1 if request_speeds else 0
         h = C.c_void_p()
-        st = lib.q3tts_model_load(model_path.encode(), C.byref(o), C.byref(h))
+        if pitch == 0.0:  # (a float comparison: a NaN goes on to be refused below)
+            st = lib.q3tts_model_load(model_path.encode(), C.byref(o), C.byref(h))
+        else:
+            if not hasattr(lib, "q3tts_model_load_ex"):
+                raise Qwen3TTSError(3, "Invalid input: this build of the library has no pitch option")
+            ex = L.LoadOptsEx()
+            lib.q3tts_default_load_opts_ex(C.byref(ex))
+            ex.base, ex.pitch = o, float(pitch)
+            st = lib.q3tts_model_load_ex(model_path.encode(), C.byref(ex), C.byref(h))
         if st != 0:
             raise Qwen3TTSError(st, (lib.q3tts_last_error(None) or b"").decode())
         m = cls(h, lib)
@@ -241,6 +252,25 @@ class Qwen3TTSModel:
         s, hs, d, spf = C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
         self._check(self._lib.q3tts_request_speed_info(self._h, float(speed), C.byref(s), C.byref(hs), C.byref(d), C.byref(spf)))
         return float(s.value), int(hs.value), int(d.value), int(spf.value)
+
+    def pitch_info(self) -> Tuple[float, int, int, int]:
+        """q3tts_model_get_pitch: the effective shift 12 log2(Hp / Ho) in semitones (0: off), the hop Hp in front of the
+        resampler, the handle's hop Ho (equal: off) and the delay of the two stages in output samples."""
+        s, hp, ho, d = C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.q3tts_model_get_pitch(self._h, C.byref(s), C.byref(hp), C.byref(ho), C.byref(d)))
+        return float(s.value), int(hp.value), int(ho.value), int(d.value)
+
+    def debug_resample_ratio(self, x: np.ndarray, lens: Sequence[int], in_units: int, out_units: int, y: np.ndarray,
+                             centred: bool = False, clamp: bool = False, hist: int = 0) -> np.ndarray:
+        """q3tts_debug_resample_ratio: the general-ratio resampler on host rows x [B][row_stride], each `hist` samples of
+        margin followed by lens[b] samples; y [B][y_stride] comes back with what each row wrote."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.ascontiguousarray(y, np.float32).copy()
+        ln = np.ascontiguousarray(lens, np.int32)
+        self._check(self._lib.q3tts_debug_resample_ratio(self._h, x.ctypes.data_as(L.f32p), ln.ctypes.data_as(L.i32p), x.shape[0], x.shape[1],
+                                                         int(in_units), int(out_units), 1 if centred else 0, 1 if clamp else 0, int(hist),
+                                                         y.ctypes.data_as(L.f32p), y.shape[1]))
+        return y
 
     def debug_stretch_rows(self, x: np.ndarray, lens: Sequence[int], hops: Sequence[int], y: np.ndarray) -> np.ndarray:
         """q3tts_debug_stretch_rows: the stretch kernel's per-row path on host rows x [B][x_stride]; y [B][y_stride] comes back
@@ -327,6 +357,16 @@ class Qwen3TTSModel:
         n = C.c_int64(0)
         self._check(self._lib.q3tts_time_stretch(self._h, a.ctypes.data_as(L.f32p), a.size, float(speed), 1 if causal else 0,
                                                  out.ctypes.data_as(L.f32p), out.size, C.byref(n)))
+        return out[: n.value]
+
+    def pitch_shift(self, audio: np.ndarray, semitones: float) -> np.ndarray:
+        """q3tts_pitch_shift: 24 kHz audio shifted by `semitones` at (nearly) its duration, on the device: the whole time
+        stretch at Hp = round(480 * 2^(semitones / 12)), then the centred resampler Hp -> 480 (include/q3tts.h, "Pitch")."""
+        a = np.ascontiguousarray(np.asarray(audio, np.float32).reshape(-1))
+        out = np.zeros(a.size + 8, np.float32)  # (two roundings up, at most 2 + 480 / Hp samples over n_in)
+        n = C.c_int64(0)
+        self._check(self._lib.q3tts_pitch_shift(self._h, a.ctypes.data_as(L.f32p), a.size, float(semitones), out.ctypes.data_as(L.f32p),
+                                                out.size, C.byref(n)))
         return out[: n.value]
 
     @staticmethod

@@ -23,6 +23,8 @@ for bit, and the queue's rows now include top-p rows beside the others in every 
 (q3tts_request.speed): static and queued must still agree bit for bit. With --stream the
 streamed queue serves them too (every ring slot then holds rows of the slowest request's frame size, printed in bytes); on a handle
 with --output-sample-rate only speeds whose hop is the handle's are streamed, and the streamed run is skipped otherwise.
+--output-sample-rate R, --speed S and --pitch P load the handle with those options (q3tts_load_opts): every path then runs with the
+stages they add to the codec tail.
 --voices N (a Base checkpoint) runs the ragged workload as voice-clone requests with N reference clips (3 s each) shared round-robin:
   static   pipelined batches whose requests carry their clip as ref_audio (every batch encodes its clips again)
   queued   one q3tts_generate_queued call whose requests name one of N voices made once by create_voice
@@ -398,6 +400,8 @@ def main():
                     help="load the model with q3tts_load_opts.output_sample_rate = R (0: the decoder's own 24000)")
     ap.add_argument("--speed", type=float, default=0.0, metavar="S",
                     help="load the model with q3tts_load_opts.speed = S (0: off; 0.5 .. 2.0: the time stretch in the decoder's tail)")
+    ap.add_argument("--pitch", type=float, default=0.0, metavar="SEMITONES",
+                    help="load the model with q3tts_load_opts_ex.pitch (0: off; -12 .. 12: the stretch at Hp and the general-ratio resampler)")
     ap.add_argument("--request-speeds", default=None, metavar="S1,S2,...",
                     help="load the model with q3tts_load_opts.request_speeds and deal these speeds round robin over the requests "
                          "(q3tts_request.speed; 0: the handle's)")
@@ -407,6 +411,8 @@ def main():
     rate_kw = dict(output_sample_rate=args.output_sample_rate) if args.output_sample_rate else {}
     if args.speed:
         rate_kw["speed"] = args.speed
+    if args.pitch:
+        rate_kw["pitch"] = args.pitch
     req_speeds = [float(s) for s in args.request_speeds.split(",")] if args.request_speeds else []
     if req_speeds:
         rate_kw["request_speeds"] = True

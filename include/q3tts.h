@@ -898,6 +898,7 @@ typedef struct {
     int32_t tall;                    /* the tall form takes it: tall_shape 2 (128 x 64) or 3 (64 x 64); the rest is 0 */
     int32_t tall_shape;
     int32_t split, mbw, nw, ch, np, gx, ntw;  /* SkinnyGeom (csrc/kernels.h) */
+    int32_t tm;                      /* SkinnyGeom::tm: a gate/up workgroup takes its tiles one by one (fills what was padding) */
     /* inputs */
     const uint16_t* x;
     const void* W;                   /* bf16 [N][K], or uint32 [N][K / 8] with quant; epi 2: the gate matrix */

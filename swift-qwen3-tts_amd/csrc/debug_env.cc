@@ -21,6 +21,7 @@ const DebugEnv* read_env() {
     DebugEnv* d = new DebugEnv{};  // never freed: a reader on another thread may still hold the previous one
     d->gemm_no_row_split = flag("Q3TTS_GEMM_NO_ROW_SPLIT");
     d->gemm_one_pair = flag("Q3TTS_GEMM_ONE_PAIR");
+    d->gemm_parent_forms = number("Q3TTS_GEMM_PARENT_FORMS", 0) != 0;
     d->no_tall_gemm = flag("Q3TTS_NO_TALL_GEMM");
     d->tall_shape = number("Q3TTS_TALL_SHAPE", 0);
     d->chunk_qsplit = number("Q3TTS_CHUNK_QSPLIT", 0);

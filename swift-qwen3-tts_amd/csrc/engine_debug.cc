@@ -315,7 +315,7 @@ void Engine::debug_attention(const q3tts_attn_debug& d) {
 void Engine::debug_gemm_check(q3tts_gemm_debug& d, GemmArgs& ga, NormRowsArgs& na) {
     static const uint16_t dummy16 = 0;  // geometry_only: "this operand takes part" without a buffer
     static const uint32_t dummy32 = 0;
-    d.rode = d.tall = d.tall_shape = d.split = d.mbw = d.nw = d.ch = d.np = d.gx = d.ntw = 0;
+    d.rode = d.tall = d.tall_shape = d.split = d.mbw = d.nw = d.ch = d.np = d.gx = d.ntw = d.tm = 0;
     Q3_CHECK(d.mode == 0 || d.mode == 1, 3, "debug_gemm: unknown mode");
     const bool rider = d.mode == 1 || d.rider_M > 0;
     if (rider) {
@@ -362,7 +362,7 @@ void Engine::debug_gemm_check(q3tts_gemm_debug& d, GemmArgs& ga, NormRowsArgs& n
         d.tall_shape = gemm_tall_shape(ga);
     } else {
         Q3_CHECK(g.mbw >= 1 && g.mbw <= 4, 3, "debug_gemm: more than 4 row blocks per workgroup");
-        d.split = g.split; d.mbw = g.mbw; d.nw = g.nw; d.ch = g.ch; d.np = g.np; d.gx = g.gx; d.ntw = g.ntw ? 1 : 0;
+        d.split = g.split; d.mbw = g.mbw; d.nw = g.nw; d.ch = g.ch; d.np = g.np; d.gx = g.gx; d.ntw = g.ntw ? 1 : 0; d.tm = g.tm ? 1 : 0;
     }
     if (rider) d.rode = gemm_norm_rows_rides(ga, na) ? 1 : 0;
 }

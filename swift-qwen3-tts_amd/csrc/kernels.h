@@ -14,6 +14,8 @@ namespace q3 {
 struct DebugEnv {
     bool gemm_no_row_split;  // Q3TTS_GEMM_NO_ROW_SPLIT: row blocks of narrow layers stay in one workgroup
     bool gemm_one_pair;      // Q3TTS_GEMM_ONE_PAIR: one weight tile per workgroup everywhere
+    bool gemm_parent_forms;  // Q3TTS_GEMM_PARENT_FORMS: gate/up workgroups of several tiles in chunk-major order with the epilogues
+                             // behind the last MFMA (the forms before the tile-major ones; A/B and equality tests)
     bool no_tall_gemm;       // Q3TTS_NO_TALL_GEMM: prefill chunks through the skinny kernels
     int tall_shape;          // Q3TTS_TALL_SHAPE = 2 | 3: force one tile shape of the tall GEMM (0: automatic)
     int chunk_qsplit;        // Q3TTS_CHUNK_QSPLIT: workgroups sharing a chunk's queries (0: automatic)
@@ -83,6 +85,7 @@ struct SkinnyGeom {
     int nw, ch, np;    // waves, k chunks per wave (0: streamed), weight tiles per workgroup
     int gx;            // grid.x
     bool ntw;          // non-temporal weight loads
+    bool tm;           // several gate/up tiles per workgroup taken tile by tile (gemm_body.inc TM)
 };
 SkinnyGeom skinny_geometry(const GemmArgs& a);
 // The same launch with riders (kernels/row_jobs.h): n.M extra workgroups, each the RMSNorm of one row -- a job that reads what

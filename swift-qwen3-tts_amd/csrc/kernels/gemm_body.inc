@@ -1,5 +1,42 @@
 // gemm_body.inc -- device-side body of the skinny decode GEMM (see gemm_decode.hip for the design notes). Included inside
 // namespace q3 { namespace { ... } } by gemm_decode.hip.
+// Diagnostic build only (make TIMELINE=1 defines Q3TTS_GEMM_TIMELINE; the shipped library holds none of this): clock stamps
+// (100 MHz wall clock, the same on every CU) of each wave of the first and the last workgroup of the talker's 32-row gate/up,
+// down_proj and qkv launches, kept in registers and written by lane 0 with plain stores behind the last output store into a buffer
+// nothing else reads. tools/gemm_timeline.py prints the last launch's table. Stamps: 0 wave start, 1 prologue done (rstd known),
+// 2 first MFMAs issued (first weight fragments and their x landed), 3 last MFMA issued (last weight fragment landed),
+// 4 every wave's partials of the last tile in LDS, 5 last tile reduced, 6 last store issued, 7 first tile reduced.
+#ifdef Q3TTS_GEMM_TIMELINE
+__device__ unsigned long long g_gemm_tl[4][2][8][8];  // [gate/up chunk-major | gate/up tile-major | down_proj | qkv][first | last workgroup][wave][stamp]
+#define Q3_TL_BEGIN()                                                                                                       \
+    constexpr int kTlForm = (EPI == 2 && MB == 2 && NW == 8 && CH == 2 && NP == 3 && NTW) ? (TM ? 1 : 0)                    \
+                            : ((EPI == 3 && MB == 1 && NW == 8 && CH == 6 && !NORM && NTW) ? 2                              \
+                               : ((EPI == 0 && MB == 2 && NW == 8 && CH == 2 && NORM && NP == 1 && NTW) ? 3 : -1));         \
+    unsigned long long tl_[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                                                   \
+    Q3_TL(0)
+#define Q3_TL(k)                                   \
+    do {                                           \
+        if constexpr (kTlForm >= 0) {              \
+            __builtin_amdgcn_sched_barrier(0);     \
+            tl_[k] = wall_clock64();               \
+            __builtin_amdgcn_sched_barrier(0);     \
+        }                                          \
+    } while (0)
+#define Q3_TL_END()                                                                                                         \
+    do {                                                                                                                    \
+        if constexpr (kTlForm >= 0) {                                                                                       \
+            const bool tl_last = blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1;                                \
+            if ((tl_last || (blockIdx.x == 0 && blockIdx.y == 0)) && lane == 0) {                                           \
+                _Pragma("unroll") for (int k = 0; k < 8; ++k) g_gemm_tl[kTlForm][tl_last ? 1 : 0][wave][k] = tl_[k];        \
+            }                                                                                                               \
+        }                                                                                                                   \
+    } while (0)
+#else
+#define Q3_TL_BEGIN() ((void)0)
+#define Q3_TL(k) ((void)0)
+#define Q3_TL_END() ((void)0)
+#endif
+
 __device__ __forceinline__ f32x4 mfma16(const uint4& a, const uint4& b, f32x4 c) {
     bf16x8 av, bv;
     __builtin_memcpy(&av, &a, 16);
@@ -51,20 +88,34 @@ __device__ __forceinline__ void dequant_chunk(const uint4& qw, uint32_t sb, uint
 // its 64 rows of x, so at one tile each the x operand is 0.1-0.8 GB of L2 traffic per launch (3072 workgroups x 256 KB for
 // gate/up); four tiles per workgroup quarter it. Per-output arithmetic does not depend on NP.
 // NTW: weight tiles are loaded non-temporally (common.h ld16).
-template <int MB, int EPI, int NW, int CH, bool NORM, bool QUANT, int NP = 1, bool NTW = false>
+// TM: tile-major order for a workgroup of several gate/up tiles (EPI 2, NORM, every chunk's x prefetched). A wave that
+// requests everything up front (64 wave-wide loads at NP 3) stands at the issue of its loads until the memory system has
+// taken the last one -- 7.8 of the 12.5 us a wave of the 1.7B talker's gate/up launch lives (profiles/talker_gemm_timeline.txt)
+// -- and only then starts the prologue's VALU work (rstd, then normalising x: 1.3 us, 2.7 us for the second wave of a SIMD),
+// with every MFMA and all NP epilogues behind that. Here only tile 0's weights are requested with the sums of squares and
+// x; the prologue and the normalisation of x (once, into the registers it arrived in) run while those are in flight, the
+// other tiles' weights are requested behind them, tile by tile (loads return in issue order), and each tile's MFMAs are
+// followed at once by its reduction and store, so tile t's epilogue runs while tiles t + 1.. are still arriving. Every tile
+// has LDS buffers of its own, so no barrier guards their reuse. Per output the arithmetic is the same: wave w's chunks in
+// order, four MFMAs per chunk, wave partials added in wave order.
+template <int MB, int EPI, int NW, int CH, bool NORM, bool QUANT, int NP = 1, bool NTW = false, bool TM = false>
 __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int tile, const int mb0) {
     constexpr int NT = NP;                   // weight tiles per workgroup
     constexpr int NR = 1;                    // tiles reduced per pass of the epilogue
+    constexpr int NB = TM ? NT : 1;          // LDS reduction buffers
+    constexpr int kDefer = TM ? NT - 1 : 0;  // tiles whose weights are requested behind the prologue
+    static_assert(!TM || (EPI == 2 && NORM && !QUANT && CH > 0 && NP > 1), "tile-major order is a gate/up form");
     // EPI 2: a.N counts output columns, eight per tile; the last workgroup of a ragged width re-reads the last tile for its
     // missing ones and does not store them
     const int n_tiles = (EPI == 2) ? (a.N >> 3) : (a.N >> 4);
-    __shared__ float red[NW][NR][MB][4][64];
-    __shared__ __attribute__((aligned(16))) uint16_t ys[MB][16][16];
+    __shared__ float red[NB][NW][NR][MB][4][64];
+    __shared__ __attribute__((aligned(16))) uint16_t ys[NB][MB][16][16];
     __shared__ float rstd_s[NORM ? 16 * MB : 1];
     __shared__ float ssp_s[NORM ? 8 : 1][NORM ? 16 * MB : 1];
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
+    Q3_TL_BEGIN();
     // mb0: first 16-row block of this workgroup (launch_q splits the rows of narrow layers)
     const int KC = a.K >> 7;  // 128-wide k chunks
 
@@ -108,9 +159,9 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
     constexpr int WL = QUANT ? 1 : 4;  // dwordx4 loads per (chunk, tile): packed int4 needs one
     uint4 wf[CHR][NT][WL];
     uint32_t wsb[CHR][NT];
-    auto load_w = [&](int c, int kc) {
+    auto load_w = [&](int c, int kc, int t0, int t1) {  // chunk c of tiles t0 .. t1 - 1
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
+        for (int t = t0; t < t1; ++t) {
             const int tt = tile * NT + t;
             const size_t blk = (size_t)(tt < n_tiles ? tt : n_tiles - 1) * KC + kc;
             if constexpr (QUANT) {
@@ -138,6 +189,7 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
     // frame step); beside a codec decode, which leaves the frame loop half of the CUs, the launch's 256 workgroups then run
     // together instead of in two rounds (steady pipelined step 795.0 -> 791.4 ms).
     constexpr int XG = (MB == 2 && NORM && CH == 2 && NT == 1 && EPI == 0) ? 1 : XG0;
+    static_assert(!TM || XG == CH, "tile-major order keeps every chunk's x fragments in registers");
     uint4 xr[XG > 0 ? XG : 1][MB][4];
     uint4 nwr[(NORM && XG > 0) ? XG : 1][4];
     // issue order: weights then x, or (NORM) x then weights so that normalising x overlaps the weights' arrival.
@@ -146,11 +198,19 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
     for (int ph = 0; ph < 2; ++ph) {
         if (ph == 1) __builtin_amdgcn_sched_barrier(0);  // issue order between the two groups as written
         if ((ph == 0) != NORM) {
-    if constexpr (CH > 0) {
+    if constexpr (TM) {
+#pragma unroll
+            for (int t = 0; t < NT - kDefer; ++t)
+#pragma unroll
+                for (int c = 0; c < CH; ++c) {
+                    const int kl = wave + c * NW;
+                    load_w(c, kl < KC ? kl : 0, t, t + 1);
+                }
+    } else if constexpr (CH > 0) {
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 const int kl = wave + c * NW;
-                load_w(c, kl < KC ? kl : 0);
+                load_w(c, kl < KC ? kl : 0, 0, NT);
             }
         }
         } else {
@@ -211,6 +271,26 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) rstd[mb] = rstd_s[16 * mb + (lane & 15)];
     }
+    Q3_TL(1);
+    if constexpr (TM) {  // x normalised once, in place: every tile multiplies with the same fragments
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) xr[c][mb][i] = norm8(xr[c][mb][i], nwr[c][i], rstd[mb]);
+        }
+        // only now the other tiles' weights (the barriers keep hipcc from hoisting the requests in front of the VALU work)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = NT - kDefer; t < NT; ++t)
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                const int kl = wave + c * NW;
+                load_w(c, kl < KC ? kl : 0, t, t + 1);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    }
 
     // 3. x fragments (+ norm) and MFMAs
     auto chunk = [&](int kc, int c, const uint4 (*xpre)[4], const uint4* nwpre) {
@@ -256,7 +336,9 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
                 for (int i = 0; i < 4; ++i) acc[t][mb] = mfma16(w[t][i], xf[i], acc[t][mb]);
         }
     };
-    if constexpr (CH > 0) {
+    if constexpr (TM) {
+        // the MFMAs stand in front of each tile's epilogue below
+    } else if constexpr (CH > 0) {
         // chunks in groups of XG: the first group's fragments are already in flight; each later group is requested as a
         // whole (one round trip per group) into the same registers
 #pragma unroll
@@ -287,26 +369,45 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
                     const int kl = wave + (g0 + c) * NW;
                     if (kl < KC) chunk(kl, g0 + c, xr[c], NORM ? nwr[c] : nullptr);  // wave-uniform
                 }
+                if (g0 + c == 0) Q3_TL(2);
             }
         }
     } else {
         for (int kl = wave; kl < KC; kl += NW) {
-            load_w(0, kl);
+            load_w(0, kl, 0, NT);
             chunk(kl, 0, nullptr, nullptr);
         }
     }
 
+    if constexpr (!TM) Q3_TL(3);
     // 4. cross-wave K reduction through LDS, fixed wave order; one tile (EPI 2: one gate/up pair) per pass
 #pragma unroll
     for (int pr = 0; pr < NT / NR; ++pr) {
-    if (pr > 0) __syncthreads();  // the previous pair's red / ys reads
+    const int rb = TM ? pr : 0;  // this pass's LDS buffers
+    if constexpr (TM) {
+        // tile pr's fragments are complete before those of the tiles behind it: its MFMAs, chunks in the wave's order
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            if (wave + c * NW < KC) {  // wave-uniform
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[pr][mb] = mfma16(wf[c][pr][i], xr[c][mb][i], acc[pr][mb]);
+            }
+        }
+        if (pr == 0) Q3_TL(2);
+        if (pr == NT - 1) Q3_TL(3);
+    } else {
+        if (pr > 0) __syncthreads();  // the previous pair's red / ys reads
+    }
 #pragma unroll
     for (int t = 0; t < NR; ++t)
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) red[wave][t][mb][q][lane] = acc[pr * NR + t][mb][q];
+            for (int q = 0; q < 4; ++q) red[rb][wave][t][mb][q][lane] = acc[pr * NR + t][mb][q];
     __syncthreads();
+    if (pr == NT / NR - 1) Q3_TL(4);
     const int otile = tile * (NT / NR) + pr;  // 16-column output tile
 
     if constexpr (EPI == 2) {
@@ -318,10 +419,10 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
             float g = 0.f, u = 0.f;
 #pragma unroll
             for (int w = 0; w < NW; ++w) {
-                g += red[w][0][mb][q][lg];
-                u += red[w][0][mb][q][lu];
+                g += red[rb][w][0][mb][q][lg];
+                u += red[rb][w][0][mb][q][lu];
             }
-            ys[mb][b][f] = f2bf(rbf(silu_f(rbf(g))) * rbf(u));
+            ys[rb][mb][b][f] = f2bf(rbf(silu_f(rbf(g))) * rbf(u));
         }
     } else {
     // 256*MB outputs per tile: thread -> (mb, batch row b, feature f)
@@ -331,29 +432,31 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
         const int src_lane = (f >> 2) * 16 + b, q = f & 3;
         float sum = 0.f;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) sum += red[w][0][mb][q][src_lane];
+        for (int w = 0; w < NW; ++w) sum += red[rb][w][0][mb][q][src_lane];
         const int n = otile * 16 + f;
         float y = sum;
         if (a.bias && otile < n_tiles) y += bf2f(a.bias[n]);
         uint16_t yb = f2bf(y);
         if (EPI == 0 && a.act_silu) yb = f2bf(silu_f(bf2f(yb)));
-        ys[mb][b][f] = yb;
+        ys[rb][mb][b][f] = yb;
     }
     }
     __syncthreads();
+    if (pr == 0) Q3_TL(7);
+    if (pr == NT / NR - 1) Q3_TL(5);
     if constexpr (EPI == 2) {  // one 16-byte store per (mb, row b): the tile's eight columns
         for (int o = threadIdx.x; o < 16 * MB; o += NW * 64) {
             const int mb = o >> 4, b = o & 15;
             const int m = 16 * (mb0 + mb) + b;
             if (m < a.M && otile < n_tiles)
-                *reinterpret_cast<uint4*>(a.y + act_tiled_offset(m, otile * 8, a.yMB)) = *reinterpret_cast<const uint4*>(&ys[mb][b][0]);
+                *reinterpret_cast<uint4*>(a.y + act_tiled_offset(m, otile * 8, a.yMB)) = *reinterpret_cast<const uint4*>(&ys[rb][mb][b][0]);
         }
     } else
     // 16-byte stores: thread -> (mb, row b, 8-feature piece p)
     for (int o = threadIdx.x; o < 32 * MB; o += NW * 64) {
         const int mb = o >> 5, b = (o >> 1) & 15, p = o & 1;
         const int m = 16 * (mb0 + mb) + b;
-        uint4 v = *reinterpret_cast<const uint4*>(&ys[mb][b][8 * p]);
+        uint4 v = *reinterpret_cast<const uint4*>(&ys[rb][mb][b][8 * p]);
         const int n = otile * 16 + 8 * p;
         if constexpr (EPI == 3) {
             uint16_t* hp = a.y + act_tiled_offset(m, n, a.yMB);
@@ -390,4 +493,6 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmArgs& a, const int ti
         }
     }
     }
+    Q3_TL(6);
+    Q3_TL_END();
 }

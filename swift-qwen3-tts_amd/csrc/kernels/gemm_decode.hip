@@ -36,10 +36,10 @@ namespace {
 
 #include "gemm_body.inc"
 
-template <int MB, int EPI, int NW, int CH, bool NORM, bool QUANT, int NP = 1, bool NTW = false>
+template <int MB, int EPI, int NW, int CH, bool NORM, bool QUANT, int NP = 1, bool NTW = false, bool TM = false>
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmArgs a) {
     __builtin_amdgcn_s_setprio(3);  // the AR chain's waves go first where they share a CU with a codec decode (engine.cc)
-    gemm_skinny_body<MB, EPI, NW, CH, NORM, QUANT, NP, NTW>(a, blockIdx.x, blockIdx.y * MB);
+    gemm_skinny_body<MB, EPI, NW, CH, NORM, QUANT, NP, NTW, TM>(a, blockIdx.x, blockIdx.y * MB);
 }
 
 // gemm_skinny_kernel<MB, 0, 8, CH, true, QUANT> plus riders: workgroups tiles .. tiles + n.M - 1 of grid.x normalise one row each
@@ -76,6 +76,15 @@ void launch_mb(const GemmArgs& a, const SkinnyGeom& g, hipStream_t st) {
         // gate/up tiles are self-contained, so a workgroup takes as many as it needs for the launch to be ONE round of at
         // most 256 workgroups: 768 tiles (6144 columns) -> 3 each, 384 (3072) -> 2 each
         if (g.np > 1) {
+            if constexpr (MB == 2 && NORM && !QUANT) {
+                // tile by tile (gemm_body.inc TM): the two forms the 32-row frame step launches, the 1.7B talker's and the predictor's
+                // (skinny_geometry sets tm for exactly these two)
+                if constexpr (NTW) {
+                    if (g.tm) { hipLaunchKernelGGL((gemm_skinny_kernel<2, 2, 8, 2, true, false, 3, true, true>), grid, dim3(512), 0, st, a); return; }
+                } else {
+                    if (g.tm) { hipLaunchKernelGGL((gemm_skinny_kernel<2, 2, 8, 1, true, false, 2, false, true>), grid, dim3(512), 0, st, a); return; }
+                }
+            }
 #define Q3_GEMM_NP(CHv, NPv) hipLaunchKernelGGL((gemm_skinny_kernel<MB, 2, 8, CHv, NORM, QUANT, NPv, NTW>), grid, dim3(512), 0, st, a)
             if (g.ch == 1) { if (g.np == 2) Q3_GEMM_NP(1, 2); else Q3_GEMM_NP(1, 3); }
             else { if (g.np == 2) Q3_GEMM_NP(2, 2); else Q3_GEMM_NP(2, 3); }
@@ -175,6 +184,8 @@ SkinnyGeom skinny_geometry(const GemmArgs& a) {
             g.np = np;
             g.gx = (t + np - 1) / np;
             shaped = true;
+            // the instantiated tile-major forms (launch_mb): two row blocks, bf16 weights, norm prologue
+            g.tm = !env.gemm_parent_forms && g.mbw == 2 && norm && !a.Wsb && ((g.ntw && g.ch == 2 && np == 3) || (!g.ntw && g.ch == 1 && np == 2));
         }
     }
     if (!shaped) {
@@ -229,3 +240,11 @@ void launch_gemm_skinny(const GemmArgs& a, hipStream_t st) {
 }
 
 }  // namespace q3
+
+#ifdef Q3TTS_GEMM_TIMELINE
+// diagnostic build only: the stamps of the last instrumented launches (gemm_body.inc), [4][2][8][8] ticks of 10 ns
+extern "C" int q3tts_debug_gemm_timeline(unsigned long long* out) {
+    if (hipDeviceSynchronize() != hipSuccess) return 7;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(q3::g_gemm_tl), sizeof(q3::g_gemm_tl)) == hipSuccess ? 0 : 7;
+}
+#endif

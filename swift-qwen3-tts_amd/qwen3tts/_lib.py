@@ -129,7 +129,7 @@ class GemmDebug(C.Structure):  # q3tts_gemm_debug
                 ("rider_eps", C.c_float),
                 ("rode", C.c_int32), ("tall", C.c_int32), ("tall_shape", C.c_int32),
                 ("split", C.c_int32), ("mbw", C.c_int32), ("nw", C.c_int32), ("ch", C.c_int32), ("np", C.c_int32), ("gx", C.c_int32),
-                ("ntw", C.c_int32),
+                ("ntw", C.c_int32), ("tm", C.c_int32),
                 ("x", u16p), ("W", C.c_void_p), ("scales", u16p), ("biases", u16p), ("W_up", C.c_void_p), ("scales_up", u16p),
                 ("biases_up", u16p), ("bias", u16p), ("norm_w", u16p), ("ss_in", f32p), ("rider_h", u16p), ("rider_w", u16p),
                 ("rider_ss_in", f32p),
@@ -303,7 +303,7 @@ def lib() -> C.CDLL:
     return L
 
 
-GEOM_FIELDS = ("rode", "tall", "tall_shape", "split", "mbw", "nw", "ch", "np", "gx", "ntw")
+GEOM_FIELDS = ("rode", "tall", "tall_shape", "split", "mbw", "nw", "ch", "np", "gx", "ntw", "tm")
 
 
 def gemm_geometry(**kw) -> dict:

@@ -1050,6 +1050,111 @@ typedef struct {
 } q3tts_rowop_debug;
 q3tts_status q3tts_debug_rowop(q3tts_model* m, q3tts_rowop_debug* a);
 
+/* One launch of a row kernel of the LM side of the frame step (csrc/kernels/sampler.hip, csrc/kernels/lm_misc.hip with the jobs of
+ * csrc/kernels/row_jobs.h) on caller-supplied host buffers, through the product's own launch_* function; op 1 with `split` makes
+ * two launches. The contract of q3tts_debug_rowop: the call allocates and frees its own device buffers and touches neither weights
+ * nor caches nor the engine's loop state; in[] is uploaded whole; every io[] buffer is uploaded as the caller filled it and
+ * returned whole, so that a sentinel shows what was and was not written; device tables of pointers (cp_emb[15]) are built from
+ * offsets into one caller pool; a slot an op does not name must be NULL; a named slot holds exactly the bytes its shape states
+ * ("pool": any whole number of bf16) unless marked optional ("?"). The three record types below are the kernels' own
+ * (csrc/kernels.h SamplingParams, AdmitDesc, TextAppendDesc), handed over as they lie in device memory.
+ * Per op: p[] by index, then the in[] and io[] slots by index. Sizes in elements; bf16 = raw bits in uint16_t; i32 / u32 / i64 / u8
+ * / f32 as named; "tiled MB" = the fragment-major activation layout of csrc/common.h act_tiled_offset with MB row blocks,
+ * [MB * 16 * H] elements.
+ *    0 sampler             p: 0 B, 1 V, 2 ldl, 3 is_talker, 4 suppress_lo, 5 suppress_hi, 6 eos_id, 7 cb, 8 advance, 9 Fmax,
+ *                             10 forced_frames (ff), 11 emb_rows, 12 emb_ld, 13 H (0: no gather), 14 next_MB, 15 next_row0, 16 nss,
+ *                             17 next_ss_ld, 18 dump_ld, 19 dump_off
+ *                          in: 0 logits bf16 [B][ldl], 1 sp q3tts_lm_sampling_params [B], 2 max_frames? i32 [B], 3 advance_gate? u8 [B],
+ *                             4 forced? i32 [B][ff][16], 5 emb bf16 [emb_rows][emb_ld] (H > 0), 6 emb_ss? f32 [emb_rows][nss],
+ *                             7 row_key? u32 [B]
+ *                          io: 0 n_frames i32 [B], 1 finished u8 [B], 2 active u8 [B], 3 kv_len i32 [B], 4 cur_codes i32 [B][16],
+ *                             5 codes i32 [B][Fmax][16] (Fmax > 0), 6 seen? u8 [B][V], 7 sampled? i32 [B][ff][16],
+ *                             8 logits_dump? bf16 [B][ff][dump_ld], 9 next_x bf16 tiled next_MB (H > 0),
+ *                             10 next_ss: f32 [nss][next_ss_ld] with emb_ss, else next_ss? f32 [B]
+ *    1 sampler + frame end the slots of op 0 (a code-predictor draw: is_talker 0, V <= 2048, cb = groups - 1) and those of op 2;
+ *                          p: 26 split (0: launch_sampler_with_frame_end; 1: launch_sampler, then launch_frame_end on the same
+ *                             arguments), 27 cp_len_is_kv_len (1: io 14 is NULL and the frame end's cp_len is the sampler's
+ *                             kv_len, as in the frame step)
+ *    2 frame_end           p: 0 B, 20 H, 21 groups, 22 Tmax, 23 hMB, 24 Vt (rows of codec_emb), 25 Vcp (rows of a cp_emb table)
+ *                          in: 2 max_frames i32 [B], 8 tables bf16 pool, 9 offsets i64 [groups + 1] (codec_emb [Vt][H], cp_emb[0 ..
+ *                             groups - 2] [Vcp][H], tts_pad [H]), 10 trailing bf16 [B][Tmax][H], 11 n_trailing i32 [B],
+ *                             12 text_open? u8 [B]
+ *                          io: 0 n_frames, 1 finished, 2 active, 4 cur_codes (read only), 11 trailing_idx i32 [B],
+ *                             12 h bf16 tiled hMB, 13 ss_out f32 [B], 14 cp_len i32 [B], 15 starved? u8 [B] (with text_open)
+ *    3 gather_rows         p: 0 n, 1 rows, 2 ld, 3 dim, 4 ldo, 5 out_MB (0: row-major), 6 map_n
+ *                          in: 0 table bf16 [rows][ld], 1 ids i32 [n], 2 token_map? i32 [map_n]; io: 0 out bf16 [n][ldo] or tiled out_MB
+ *    4 tile_rows           p: 0 rows, 1 dim, 2 lds, 3 dstMB; in: 0 src bf16 [rows][lds]; io: 0 dst bf16 tiled dstMB
+ *    5 untile_rows         p: 0 rows, 1 dim, 2 srcMB, 3 ldd; in: 0 src bf16 tiled srcMB; io: 0 dst bf16 [rows][ldd]
+ *    6 add_rows            p: 0 rows, 1 dim, 2 lda, 3 ldb (0: one row for all), 4 ldo
+ *                          in: 0 a bf16 [rows][lda], 1 b bf16 [rows][ldb] or [dim]; io: 0 out bf16 [rows][ldo]
+ *    7 compose_rows        p: 0 n, 1 dim, 2 proj_rows, 3 ldp, 4 table_rows, 5 ldt, 6 extra_rows, 7 lde, 8 dst_rows, 9 ldd
+ *                          in: 0 proj bf16 [proj_rows][ldp], 1 table bf16 [table_rows][ldt], 2 extra? bf16 [extra_rows][lde],
+ *                             3 a i32 [n], 4 b i32 [n], 5 dst_row i32 [n]; io: 0 dst bf16 [dst_rows][ldd]
+ *    8 ref_embed_rows      p: 0 T, 1 groups, 2 H, 3 ldo, 4 Vt, 5 Vcp
+ *                          in: 0 codes i32 [groups][T], 1 tables bf16 pool, 2 offsets i64 [groups]; io: 0 out bf16 [T][ldo]
+ *    9 f32_to_bf16         p: 0 n; in: 0 x f32 [n]; io: 0 out bf16 [n]
+ *   10 ss_to_table         p: 0 rows, 1 nss, 2 ss_ld; in: 0 ss f32 [nss][ss_ld]; io: 0 dst f32 [rows][nss]
+ *   11 copy_rows           p: 0 rows, 1 dim, 2 lds, 3 ldd; in: 0 src bf16 [(rows - 1) lds + dim]; io: 0 dst bf16 [(rows - 1) ldd + dim]
+ *   12 prefill_load        p: 0 B, 1 Pmax, 2 step, 3 H, 4 hMB
+ *                          in: 0 prompt bf16 [B][Pmax][H], 1 n_prompt i32 [B]; io: 0 h bf16 tiled hMB, 1 ss_out f32 [B], 2 active u8 [B]
+ *   13 prefill_chunk_load  p: 0 B, 1 Pmax, 2 r_base, 3 H, 4 hMB, 5 C; in: as op 12; io: 0 h bf16 tiled hMB, 1 ss_out f32 [C B]
+ *   14 advance_len         p: 0 B; in: 0 active? u8 [B]; io: 0 kv_len i32 [B]
+ *   15 advance_len_chunk   p: 0 B, 1 r_base, 2 C; in: 0 n_prompt i32 [B]; io: 0 kv_len i32 [B]
+ *   16 admit_rows          p: 0 k, 1 slots, 2 H, 3 V, 4 Fmax, 5 srcMB, 6 hMB
+ *                          in: 0 desc q3tts_lm_admit_desc [k], 1 src_h bf16 tiled srcMB, 2 src_ss f32 [k], 3 src_kv_len i32 [k],
+ *                             4 src_n_prompt i32 [k]
+ *                          io: 0 h bf16 tiled hMB, 1 ss f32 [slots], 2 kv_len, 3 n_prompt, 4 n_trailing, 5 max_frames, 6 n_frames,
+ *                             7 cp_len, 8 trailing_idx (i32 [slots] each), 9 cur_codes i32 [slots][16], 10 codes i32 [slots][Fmax][16],
+ *                             11 row_key u32 [slots], 12 sp q3tts_lm_sampling_params [slots], 13 finished u8 [slots], 14 active u8
+ *                             [slots], 15 seen u8 [slots][V], 16 text_open? u8 [slots], 17 starved? u8 [slots]
+ *   17 text_append_rows    p: 0 k, 1 slots, 2 H, 3 Tmax, 4 groups, 5 hMB, 6 Vt, 7 Vcp, 8 src_rows
+ *                          in: 0 desc q3tts_lm_text_desc [k], 1 src bf16 [src_rows][H], 2 eos_row bf16 [H], 3 tables bf16 pool,
+ *                             4 offsets i64 [groups + 1] (as op 2), 5 cur_codes i32 [slots][16]
+ *                          io: 0 trailing bf16 [slots][Tmax][H], 1 n_trailing i32 [slots], 2 text_open u8 [slots], 3 max_frames i32
+ *                             [slots], 4 trailing_idx i32 [slots], 5 h bf16 tiled hMB, 6 ss_out f32 [slots], 7 cp_len i32 [slots],
+ *                             8 starved u8 [slots], 9 finished u8 [slots], 10 active u8 [slots]
+ *   18 cancel_rows         p: 0 slots, 1 mask bits 0..31, 2 mask bits 32..63, 3 n (length of the two arrays, slots <= n <= 64)
+ *                          io: 0 finished u8 [n], 1 active u8 [n]
+ * Every argument that becomes an address, a grid size or an index is checked on the host before anything is launched
+ * (Q3TTS_ERR_INVALID_INPUT): the slot sizes against the strides and counts given; B, slots and k within 1..64; V <= 4096; H % 8 for
+ * what a kernel moves in 16-byte pieces (H, dim, ld*, emb_ld, table offsets) and H % 128 for every tiled buffer; rows of a tiled
+ * buffer (B, n, C B, k, slots, next_row0 + B) inside its MB * 16; every value a kernel uses as an index: n_frames >= 0, forced
+ * entries and the codes of cur_codes inside the tables they select (op 0 with a gather: emb_rows >= V, any token may be drawn;
+ * op 1: V within the last group's table), eos_id in -1 .. V - 1, ids / token_map / a / b / dst_row / codes inside their tables,
+ * n_trailing within 0..Tmax and trailing_idx >= 0, n_prompt within 0..Pmax and the prompt position a launch loads below Pmax,
+ * slot numbers inside 0..slots and distinct (admit_rows also takes -1: the row is skipped), src_row + n_new <= src_rows and
+ * n_new + close <= Tmax (a descriptor that fits on its own but not behind the slot's n_trailing goes through: the kernel skips it),
+ * dump_off + V <= dump_ld, next_ss_ld >= next_row0 + B, ss_ld >= rows; table ranges inside their pools.
+ * check_only != 0 runs only these checks: no GPU is needed and m may be NULL. */
+typedef struct {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    float rep_penalty;
+    uint64_t seed;
+    uint32_t row0;
+    int32_t mask_eos;
+} q3tts_lm_sampling_params;
+typedef struct {
+    int32_t slot, n_trailing, max_frames;
+    uint32_t row_key;
+    int32_t text_open;
+    int32_t pad_;
+    q3tts_lm_sampling_params sp;
+} q3tts_lm_admit_desc;
+typedef struct {
+    int32_t slot, src_row, n_new, close, max_frames, pad_;
+} q3tts_lm_text_desc;
+typedef struct {
+    int32_t op, check_only;
+    int32_t p[32];
+    const void* in[14];
+    int64_t in_bytes[14];
+    void* io[18];
+    int64_t io_bytes[18];
+} q3tts_lmop_debug;
+q3tts_status q3tts_debug_lmop(q3tts_model* m, q3tts_lmop_debug* a);
+
 /* Codec decoder with intermediate activations (SpeechTokenizer.swift:754-784) for one utterance:
  * stage names: "quantizer","pre_conv","pre_transformer","upsample0","upsample1","init_conv",
  * "block0".."block3". Output is channels-last [T][C] float32; *T,*C receive the shape. */

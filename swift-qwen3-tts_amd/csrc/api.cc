@@ -738,6 +738,16 @@ q3tts_status q3tts_debug_rowop(q3tts_model* m, q3tts_rowop_debug* a) {
     });
 }
 
+q3tts_status q3tts_debug_lmop(q3tts_model* m, q3tts_lmop_debug* a) {
+    if (a && a->check_only) {  // host code only: no model, no GPU
+        return guarded(nullptr, [&] { q3::Engine::debug_lmop_check(*a); });
+    }
+    return guarded(m, [&] {
+        Q3_CHECK(m && a, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_lmop(*a);
+    });
+}
+
 q3tts_status q3tts_codec_decode_streamed(q3tts_model* m, const int32_t* codes, const int32_t* n_frames, int32_t batch, int32_t max_frames,
                                          int32_t chunk_frames, int32_t window, int32_t lookahead, float* pcm) {
     return guarded(m, [&] {

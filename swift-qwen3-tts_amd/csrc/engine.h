@@ -258,6 +258,9 @@ class Engine {
     // q3tts_debug_rowop (rowop_debug.cc): one launch of a codec_misc.hip / voice_frontend.hip launcher; the check is host code
     static void debug_rowop_check(const q3tts_rowop_debug& d);
     void debug_rowop(q3tts_rowop_debug& d);
+    // q3tts_debug_lmop (lmop_debug.cc): one launch of a sampler.hip / lm_misc.hip launcher; the check is host code
+    static void debug_lmop_check(const q3tts_lmop_debug& d);
+    void debug_lmop(q3tts_lmop_debug& d);
     void debug_build_decode_codes(const int32_t* refs, const int32_t* ref_T, const int32_t* gen, const int32_t* n_frames, int R,
                                   int gen_stride, int Fdec, bool misalign, int32_t* out);
     void codec_decode(const int32_t* codes, const int32_t* n_frames, int batch, int max_frames, float* pcm,

@@ -206,6 +206,9 @@ __device__ __forceinline__ void sampler_body(const SamplerArgs& a, const FrameEn
     if (tid == 0) n_surv = 0;
     if (row_done) {
         if (tid == 0 && a.advance && gate && !a.advance_gate) a.kv_len[b] += 1;  // predictor rows keep in step
+        // (behind the advance above, whose kv_len is this array in the frame step: what frame_end_kernel leaves of a finished row)
+        if constexpr (FEND)
+            if (tid == 0) fe->cp_len[b] = 0;
         return;
     }
     if (a.logits_dump && frame < a.forced_frames)
@@ -245,8 +248,12 @@ __device__ __forceinline__ void sampler_body(const SamplerArgs& a, const FrameEn
             const int i = k * kThreads + tid;
             if (i < V) x = better(x, Best{l[k], i});
         }
-        tok = block_argmax<kThreads>(x, scratch).i;
-        if (tok == 0x7fffffff) tok = 0;  // every logit NaN (a damaged checkpoint): no maximum exists; the token is a table row next step
+        const Best g = block_argmax<kThreads>(x, scratch);
+        tok = g.i;
+        // every logit NaN (a damaged checkpoint): no maximum exists; the token is a table row next step. The talker's suppressed
+        // range is -inf beside the NaNs and would win with its first index, a token that must never come out; a row without a
+        // NaN whose maximum is -inf is -inf everywhere and has picked index 0 already.
+        if (tok == 0x7fffffff || g.v == -INFINITY) tok = 0;
     } else {
         const bool have_eos = TALKER && a.eos_id >= 0 && a.eos_id < V;
         const float eos_logit = have_eos ? vals[a.eos_id] : 0.f;

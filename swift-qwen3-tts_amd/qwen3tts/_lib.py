@@ -183,6 +183,50 @@ def rowop(handle, op, p, f, ins, ios, check_only=False):
     return lib().q3tts_debug_rowop(handle, C.byref(a))
 
 
+class LmSamplingParams(C.Structure):  # q3tts_lm_sampling_params (csrc/kernels.h SamplingParams)
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("rep_penalty", C.c_float),
+                ("seed", C.c_uint64), ("row0", C.c_uint32), ("mask_eos", C.c_int32)]
+
+
+class LmAdmitDesc(C.Structure):  # q3tts_lm_admit_desc (csrc/kernels.h AdmitDesc)
+    _fields_ = [("slot", C.c_int32), ("n_trailing", C.c_int32), ("max_frames", C.c_int32), ("row_key", C.c_uint32),
+                ("text_open", C.c_int32), ("pad_", C.c_int32), ("sp", LmSamplingParams)]
+
+
+class LmTextDesc(C.Structure):  # q3tts_lm_text_desc (csrc/kernels.h TextAppendDesc)
+    _fields_ = [("slot", C.c_int32), ("src_row", C.c_int32), ("n_new", C.c_int32), ("close", C.c_int32),
+                ("max_frames", C.c_int32), ("pad_", C.c_int32)]
+
+
+class LmopDebug(C.Structure):  # q3tts_lmop_debug
+    _fields_ = [("op", C.c_int32), ("check_only", C.c_int32), ("p", C.c_int32 * 32),
+                ("in", C.c_void_p * 14), ("in_bytes", C.c_int64 * 14), ("io", C.c_void_p * 18), ("io_bytes", C.c_int64 * 18)]
+
+
+LMOPS = ("sampler", "sampler_frame_end", "frame_end", "gather_rows", "tile_rows", "untile_rows", "add_rows", "compose_rows",
+         "ref_embed_rows", "f32_to_bf16", "ss_to_table", "copy_rows", "prefill_load", "prefill_chunk_load", "advance_len",
+         "advance_len_chunk", "admit_rows", "text_append_rows", "cancel_rows")  # q3tts_lmop_debug.op
+
+
+def lmop(handle, op, p, ins, ios, check_only=False):
+    """q3tts_debug_lmop (the slot table: include/q3tts.h). op: a name of LMOPS; p: {index: value} of the int parameters; ins / ios:
+    {slot: numpy array} of the read-only operands and of the in/out buffers. The in/out arrays are written in place.
+    check_only: the host checks alone (handle may be None; no GPU). Returns the status."""
+    a = LmopDebug(op=LMOPS.index(op), check_only=1 if check_only else 0)
+    for i, v in p.items():
+        a.p[i] = int(v)
+    inp = getattr(a, "in")  # (the header's name is a Python keyword)
+    for i, v in ins.items():
+        if v is not None:
+            assert v.flags["C_CONTIGUOUS"]
+            inp[i], a.in_bytes[i] = v.ctypes.data, v.nbytes
+    for i, v in ios.items():
+        if v is not None:
+            assert v.flags["C_CONTIGUOUS"] and v.flags["WRITEABLE"]
+            a.io[i], a.io_bytes[i] = v.ctypes.data, v.nbytes
+    return lib().q3tts_debug_lmop(handle, C.byref(a))
+
+
 _lib = None
 
 
@@ -296,6 +340,8 @@ def lib() -> C.CDLL:
         L.q3tts_debug_conv.argtypes = [vp, C.POINTER(ConvDebug)]
     if hasattr(L, "q3tts_debug_rowop"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_rowop.argtypes = [vp, C.POINTER(RowopDebug)]
+    if hasattr(L, "q3tts_debug_lmop"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_debug_lmop.argtypes = [vp, C.POINTER(LmopDebug)]
     if hasattr(L, "q3tts_debug_build_decode_codes"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_debug_build_decode_codes.argtypes = [vp, i32p, i32p, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
     L.q3tts_debug_codec_stage.argtypes = [vp, i32p, C.c_int32, C.c_char_p, f32p, C.c_int64, i32p, i32p]

@@ -1025,6 +1025,15 @@ class Qwen3TTSModel:
         self._check(L.rowop(self._h, op, p, f, ins, ios))
         return ios
 
+    def debug_lmop(self, op, p, ins=None, ios=None):
+        """One launch of a frame-step row kernel's launcher on these host buffers (q3tts_debug_lmop; the slot table per op:
+        q3tts.h). op: a name of _lib.LMOPS; p: {index: value}; ins: {slot: read-only numpy array}; ios: {slot: in/out array},
+        copied, launched on and returned (a dict by slot) as the launch left them."""
+        ios = {i: np.ascontiguousarray(v).copy() for i, v in (ios or {}).items() if v is not None}
+        ins = {i: np.ascontiguousarray(v) for i, v in (ins or {}).items() if v is not None}
+        self._check(L.lmop(self._h, op, p, ins, ios))
+        return ios
+
     def debug_codec_stage(self, codes: np.ndarray, stage: str) -> np.ndarray:
         codes = np.ascontiguousarray(codes, np.int32).reshape(-1, 16)
         F = codes.shape[0]

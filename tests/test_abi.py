@@ -78,7 +78,9 @@ def test_ctypes_mirror_has_the_headers_layout(tmp_path):
              ("q3tts_request", _lib.Request), ("q3tts_sampling", _lib.Sampling), ("q3tts_gen_info", _lib.GenInfo),
              ("q3tts_event", _lib.Event), ("q3tts_result", _lib.Result), ("q3tts_timing", _lib.Timing),
              ("q3tts_attn_debug", _lib.AttnDebug), ("q3tts_gemm_debug", _lib.GemmDebug), ("q3tts_conv_debug", _lib.ConvDebug),
-             ("q3tts_rowop_debug", _lib.RowopDebug)]
+             ("q3tts_rowop_debug", _lib.RowopDebug), ("q3tts_lmop_debug", _lib.LmopDebug),
+             ("q3tts_lm_sampling_params", _lib.LmSamplingParams), ("q3tts_lm_admit_desc", _lib.LmAdmitDesc),
+             ("q3tts_lm_text_desc", _lib.LmTextDesc)]
     lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "q3tts.h"', 'int main(void) {']
     for cname, cls in pairs:
         lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

@@ -138,7 +138,8 @@ typedef struct {
                            Q3TTS_ERR_INVALID_INPUT at load: a pitch outside [-12, 12], NaN or infinite, or together with
                            request_speeds (both before any GPU work); no Hp in [240, 960] for this speed (never clamped:
                            speed 0.5 leaves no room upward, speed 2 none downward); a codec frame that is not a whole number
-                           of 480-sample hops. Formants move with the pitch: beyond a few semitones the voice changes */
+                           of 480-sample hops. Formants move with the pitch: beyond a few semitones the voice changes
+                           (q3tts_load_opts_ex2.keep_formants keeps them) */
 } q3tts_load_opts_ex;
 
 void q3tts_default_load_opts_ex(q3tts_load_opts_ex* o); /* q3tts_default_load_opts for `base`, pitch 0 */
@@ -147,6 +148,26 @@ void q3tts_default_load_opts_ex(q3tts_load_opts_ex* o); /* q3tts_default_load_op
  * minus the text tokenizer, which stays with the caller). */
 q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts, q3tts_model** out);
 q3tts_status q3tts_model_load_ex(const char* model_dir, const q3tts_load_opts_ex* opts, q3tts_model** out);
+
+/* new: q3tts_load_opts_ex is pinned in its turn (its last field is `pitch`); what comes later lives behind the whole of it and is
+ * given to q3tts_model_load_ex2. q3tts_model_load_ex(dir, opts, out) is q3tts_model_load_ex2 with `ex` = *opts and
+ * keep_formants = 0. */
+typedef struct {
+    q3tts_load_opts_ex ex; /* every option above, with its meaning and checks */
+    int32_t keep_formants; /* 0 (default): off. 1: a pitch of this handle keeps the formants ("Formant preservation" below): the
+                              spectral envelope is estimated per hop by linear prediction, taken off in front of the pitch
+                              resampler and put back behind it, so the excitation moves and the voice stays. With pitch 0, or a
+                              pitch whose Hp == Ho, nothing is added, launched or allocated and the samples are those of the
+                              handle without the option, bit for bit. Sample counts never change. Q3TTS_ERR_INVALID_INPUT at load,
+                              before any GPU work: a value other than 0 / 1; 1 with an output_sample_rate other than 0 / 24000
+                              (the synthesis filter runs at 24 kHz spacing; a second rate stage behind it is not offered). On
+                              such a handle a q3tts_generate with audio_chunk_frames > 0 that would not be streamed -- no
+                              audio_window_frames, or a voice-clone row without audio_stream_reference: the chunked exact decode
+                              -- is Q3TTS_ERR_INVALID_INPUT, before any GPU work: stream it, or decode in one piece */
+} q3tts_load_opts_ex2;
+
+void q3tts_default_load_opts_ex2(q3tts_load_opts_ex2* o); /* q3tts_default_load_opts_ex for `ex`, keep_formants 0 */
+q3tts_status q3tts_model_load_ex2(const char* model_dir, const q3tts_load_opts_ex2* opts, q3tts_model** out);
 void q3tts_model_free(q3tts_model* m);
 
 /* Message of the last failure on this handle (NULL handle: last load failure on this thread).
@@ -675,10 +696,28 @@ q3tts_status q3tts_time_stretch(q3tts_model* m, const float* in, int64_t n_in, f
  * (Ho = 480), then the centred FIR Hp -> 480, not clipped -- to `out` (host, `cap` samples of room); *n_out =
  * ceil(ceil(n_in * Hp / 480) * L' / M') is always set. Hp == 480 (semitones 0): a copy. Q3TTS_ERR_INVALID_INPUT, the engine
  * staying usable: semitones outside [-12, 12], NaN or infinite; n_in < 1 or > 2^26; non-finite samples; cap too small. One
- * engine entry point like q3tts_time_stretch: one caller per handle, refused while a session is open. A pitch per request, a
- * pitch per q3tts_codec_decode* call and formant preservation are not offered. */
+ * engine entry point like q3tts_time_stretch: one caller per handle, refused while a session is open. A pitch per request and a
+ * pitch per q3tts_codec_decode* call are not offered; formant preservation is the option below. */
 q3tts_status q3tts_model_get_pitch(const q3tts_model* m, float* effective_semitones, int32_t* hp, int32_t* ho, int32_t* delay_samples);
 q3tts_status q3tts_pitch_shift(q3tts_model* m, const float* in, int64_t n_in, float semitones, float* out, int64_t cap, int64_t* n_out);
+
+/* ---- Formant preservation (new) ---------------------------------------------------------------------------------------------
+ * q3tts_load_opts_ex2.keep_formants on a handle whose pitch is on (Hp != Ho, output rate 24000). The mid signal y is the
+ * resampler's input, Hp samples per hop; hop h covers mid samples [h Hp, (h+1) Hp) and output samples [h Ho, (h+1) Ho). Per hop:
+ * a periodic Hann window of 2 Hp samples over y[(h-1) Hp, (h+1) Hp), the fp32 autocorrelation r[0..24], a Gaussian lag window of
+ * 60 Hz, r[0] *= 1 + 1e-4, Levinson-Durbin of order 24 in fp32 -> a_h[1..24] (all 0, the hop passing through, when r[0] < 1e-9,
+ * a reflection coefficient reaches 1 or the error leaves (0, inf)); e[n] = y[n] + sum_k a_h[k] y[n-k] goes through the
+ * resampler (unclipped); z[n] = e'[n] - sum_k a_h[k] z[n-k] over output hop h, pcm = clip(z). The tail is out_conv -> stretch
+ * (if Hp != 480) -> analyse / whiten -> resampler -> synthesise + clip; one-shot decodes, lock-step and slotted streams, voices'
+ * saved prefix states (which grow by hist * (align16(16 Hp) + align16(96)) bytes: the margins of e and of the filter's state) and
+ * the held-request re-decode carry it bit for bit, as they carry the stretch. csrc/formant_plan.h is the definition, summation
+ * orders included; kernels/formant.hip equals it bit for bit.
+ * q3tts_model_get_keep_formants: *on = 1 when the stage runs on this handle (the option with a pitch that is on), else 0.
+ * q3tts_pitch_shift_formants: q3tts_pitch_shift with the stage -- the whole stretch at Hp, analyse + whiten, the centred FIR
+ * Hp -> 480, synthesise, not clipped; same arguments, lengths and refusals. Hp == 480: a copy. */
+q3tts_status q3tts_model_get_keep_formants(const q3tts_model* m, int32_t* on);
+q3tts_status q3tts_pitch_shift_formants(q3tts_model* m, const float* in, int64_t n_in, float semitones, float* out, int64_t cap,
+                                        int64_t* n_out);
 
 /* ---- Speaking rate per request (new) ---------------------------------------------------------------------------------------
  * On a handle loaded with q3tts_load_opts.request_speeds a request may set q3tts_request.speed. It then gets, bit for bit, what
@@ -1183,6 +1222,19 @@ q3tts_status q3tts_debug_stretch_rows(q3tts_model* m, const float* x, const int3
  * outside 1..4096, a pair whose table exceeds 16 MiB or whose 256-output input span exceeds 64 KiB. */
 q3tts_status q3tts_debug_resample_ratio(q3tts_model* m, const float* x, const int32_t* lens, int32_t B, int64_t row_stride, int64_t in_units,
                                         int64_t out_units, int32_t centred, int32_t clamp, int32_t hist, float* y, int64_t y_stride);
+
+/* The two kernels of "Formant preservation" (kernels/formant.hip) on B host rows (a test hook; works on any handle), hops hp and
+ * ho in [240, 960]. mode 0: analyse + whiten -- x [B][x_stride], row b holding `hist` samples in front and then lens[b] mid
+ * samples; coef [B][coef_stride] receives 24 floats per hop (ceil(lens[b] / hp) hops), y [B][y_stride] the whitened lens[b]
+ * samples. mode 1: synthesise with given coefficients -- x rows hold lens[b] samples of e' (hist must be 0), coef is read
+ * (ceil(lens[b] / ho) hops), state_in [B][24] (NULL: zeros) is the rows' last 24 values of z in front, state_out [B][24] (NULL:
+ * not wanted) those behind, y receives z, clipped to [-1, 1] when clamp != 0. mode 2: both with the identity in between, only
+ * when hp == ho -- x as in mode 0, coef written, states as in mode 1, y receives z. coef and y are uploaded as the caller
+ * filled them and come back whole; a row of length 0 touches nothing. Q3TTS_ERR_INVALID_INPUT: a mode, hop or B (1..4096) out
+ * of range, mode 2 with hp != ho, a row that does not fit its strides, a state given to mode 0, a margin given to mode 1. */
+q3tts_status q3tts_debug_formant_rows(q3tts_model* m, int32_t mode, int32_t hp, int32_t ho, const int32_t* lens, int32_t B, const float* x,
+                                      int64_t x_stride, int32_t hist, float* coef, int64_t coef_stride, const float* state_in, float* state_out,
+                                      float* y, int64_t y_stride, int32_t clamp);
 
 /* The slotted codec stream of a streamed q3tts_generate_queued, driven by the queue's schedule without the talker (a test hook:
  * the real layer widths in seconds). codes [n_reqs][max_frames][16], n_frames[n_reqs] <= max_frames. Requests take the free ones

@@ -138,6 +138,12 @@ void q3tts_default_load_opts_ex(q3tts_load_opts_ex* o) {
     o->pitch = 0.0f;
 }
 
+void q3tts_default_load_opts_ex2(q3tts_load_opts_ex2* o) {
+    std::memset(o, 0, sizeof(*o));
+    q3tts_default_load_opts_ex(&o->ex);
+    o->keep_formants = 0;
+}
+
 void q3tts_default_sampling(q3tts_sampling* s) {  // Qwen3.swift:1296-1299
     s->temperature = 0.9f;
     s->top_k = 50;
@@ -161,13 +167,22 @@ q3tts_status q3tts_model_load(const char* model_dir, const q3tts_load_opts* opts
 }
 
 q3tts_status q3tts_model_load_ex(const char* model_dir, const q3tts_load_opts_ex* opts, q3tts_model** out) {
+    q3tts_load_opts_ex2 ex2;
+    q3tts_default_load_opts_ex2(&ex2);
+    if (opts) ex2.ex = *opts;
+    return q3tts_model_load_ex2(model_dir, &ex2, out);
+}
+
+q3tts_status q3tts_model_load_ex2(const char* model_dir, const q3tts_load_opts_ex2* opts, q3tts_model** out) {
     if (out) *out = nullptr;
     return guarded(nullptr, [&] {
         Q3_CHECK(model_dir && out, 3, "Invalid input: null argument");
         q3::debug_env_reload();  // the launchers' diagnostic switches are read here, once per load (kernels.h DebugEnv)
-        q3tts_load_opts_ex ex;
-        if (opts) ex = *opts;
-        else q3tts_default_load_opts_ex(&ex);
+        q3tts_load_opts_ex2 ex2;
+        if (opts) ex2 = *opts;
+        else q3tts_default_load_opts_ex2(&ex2);
+        const q3tts_load_opts_ex& ex = ex2.ex;
+        const int32_t keep_formants = ex2.keep_formants;
         const q3tts_load_opts& o = ex.base;
         const float pitch = ex.pitch;
         Q3_CHECK(o.max_batch >= 1 && o.max_batch <= 64, 3, "Invalid input: max_batch must be in 1..64");
@@ -177,6 +192,9 @@ q3tts_status q3tts_model_load_ex(const char* model_dir, const q3tts_load_opts_ex
         Q3_CHECK(q3::pitch_semitones_valid(pitch), 3, "Invalid input: pitch must be 0 (off) or between -12 and 12 semitones");
         Q3_CHECK(pitch == 0.0f || o.request_speeds == 0, 3,
                  "Invalid input: pitch and request_speeds cannot be combined (a table per pair of hops)");
+        Q3_CHECK(keep_formants == 0 || keep_formants == 1, 3, "Invalid input: keep_formants must be 0 or 1");
+        Q3_CHECK(keep_formants == 0 || o.output_sample_rate == 0 || o.output_sample_rate == q3::kResampleNative, 3,
+                 "Invalid input: keep_formants needs output_sample_rate 0 or 24000 (the synthesis filter runs at 24 kHz spacing)");
         if (pitch != 0.0f && (o.output_sample_rate == 0 || o.output_sample_rate == q3::kResampleNative ||
                                 q3::resample_rate_supported(o.output_sample_rate))) {
             // no Hp in [240, 960]: refused here when no frame of 1 to 8 hops admits the combination (the codec's own frame is
@@ -199,7 +217,7 @@ q3tts_status q3tts_model_load_ex(const char* model_dir, const q3tts_load_opts_ex
         lo.skip_tensor_data = o.weights_from_broadcast != 0;
         auto model = q3::load_model(model_dir, lo);
         auto h = std::make_unique<q3tts_model>();
-        h->eng = std::make_unique<EngineGroup>(std::move(model), o, pitch);
+        h->eng = std::make_unique<EngineGroup>(std::move(model), o, pitch, keep_formants != 0);
         *out = h.release();
     });
 }
@@ -374,6 +392,22 @@ q3tts_status q3tts_pitch_shift(q3tts_model* m, const float* in, int64_t n_in, fl
     return guarded(m, [&] {
         Q3_CHECK(m && in && out && n_out, 3, "Invalid input: null argument");
         m->eng->lane0().pitch_shift(in, n_in, semitones, out, cap, n_out);
+    });
+}
+
+q3tts_status q3tts_model_get_keep_formants(const q3tts_model* m, int32_t* on) {
+    return guarded(const_cast<q3tts_model*>(m), [&] {
+        Q3_CHECK(m, 3, "Invalid input: null argument");
+        const q3::CodecRunner* cr = m->eng->codec_runner();
+        if (on) *on = (cr && cr->keep_formants()) ? 1 : 0;
+    }, false);
+}
+
+q3tts_status q3tts_pitch_shift_formants(q3tts_model* m, const float* in, int64_t n_in, float semitones, float* out, int64_t cap,
+                                        int64_t* n_out) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && in && out && n_out, 3, "Invalid input: null argument");
+        m->eng->lane0().pitch_shift_formants(in, n_in, semitones, out, cap, n_out);
     });
 }
 
@@ -785,6 +819,15 @@ q3tts_status q3tts_debug_resample_ratio(q3tts_model* m, const float* x, const in
     return guarded(m, [&] {
         Q3_CHECK(m && x && lens && y, 3, "Invalid input: null argument");
         m->eng->lane0().debug_resample_ratio(x, lens, B, row_stride, in_units, out_units, centred != 0, clamp != 0, hist, y, y_stride);
+    });
+}
+
+q3tts_status q3tts_debug_formant_rows(q3tts_model* m, int32_t mode, int32_t hp, int32_t ho, const int32_t* lens, int32_t B, const float* x,
+                                      int64_t x_stride, int32_t hist, float* coef, int64_t coef_stride, const float* state_in, float* state_out,
+                                      float* y, int64_t y_stride, int32_t clamp) {
+    return guarded(m, [&] {
+        Q3_CHECK(m && lens && x && coef && y, 3, "Invalid input: null argument");
+        m->eng->lane0().debug_formant_rows(mode, hp, ho, lens, B, x, x_stride, hist, coef, coef_stride, state_in, state_out, y, y_stride, clamp != 0);
     });
 }
 

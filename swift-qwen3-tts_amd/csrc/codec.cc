@@ -17,7 +17,7 @@ size_t kScratchBudget = size_t(24) << 30;  // activation scratch per group of ro
 void CodecRunner::set_scratch_budget(size_t bytes) { kScratchBudget = bytes ? bytes : (size_t(24) << 30); }
 
 CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int output_rate, float speed, bool request_speeds,
-                         float pitch)
+                         float pitch, bool keep_formants)
     : m_(m), st_(st) {
     native_ = mid_ = up_ = m.cfg.codec.total_upsample();
     const bool other_rate = output_rate != 0 && output_rate != kResampleNative;
@@ -61,6 +61,16 @@ CodecRunner::CodecRunner(const Model& m, hipStream_t st, bool fp32_convs, int ou
             pitch_delay_ = q3::pitch_delay_out_samples(pc.hp, pr);
             const std::vector<float> tab = resample_table_output_order(out_plan_);
             Q3_HIP(hipMemcpy(out_tab_.grow(tab.size()), tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+            if (keep_formants) {
+                Q3_CHECK(!other_rate, 3, "Invalid input: keep_formants needs output_sample_rate 0 or 24000 (the synthesis filter runs at 24 kHz spacing)");
+                // the analysis reads Hp + P samples in front of a frame's first one: inside the mid tensor's margin
+                Q3_CHECK(pc.hp + kFormantOrder <= hist_frames() * mid_ && up_ % hops == 0, 7, "internal error: formant history beyond the stream's margin");
+                const FormantPlan fp = make_formant_plan(pc.hp);
+                std::vector<float> t(fp.win);
+                t.insert(t.end(), fp.lag, fp.lag + kFormantOrder + 1);
+                Q3_HIP(hipMemcpy(fm_win_.grow(t.size()), t.data(), t.size() * 4, hipMemcpyHostToDevice));
+                formant_ = true;
+            }
         }
     }
     if (!pitched_ && speed != 0.0f && speed != 1.0f) {
@@ -543,23 +553,76 @@ void CodecRunner::run_tail(const Pass& ps, Mem& mem, float* in, int Trows, float
             rin_stride = sy_stride;
             rin_frame = midf;
         }
+        // 8b. keep_formants (formant_plan.h): analyse + whiten the resampler's input hop by hop; the resampler then reads the
+        // whitened signal e (one more tail tensor with a margin: the FIR reads 2K' - 1 samples back) and writes the unclipped
+        // e' to a tail tensor instead of the PCM; the synthesis filter behind it writes the PCM. Hop h depends on the mid
+        // signal up to the end of hop h alone, and the filter's state, P floats per row, lives in a tensor of its own, one
+        // entry per frame, exactly as the stretch's word does.
+        const int fhops = ppf / kStretchHa;  // hops per frame
+        float *fe = nullptr, *fcoef = nullptr, *fep = nullptr, *fstate = nullptr;
+        bool tail_in_held = post;  // p24 (and mid) are still held
+        if (formant_) {
+            Q3_CHECK(resample_ && !own_hops && !ps.mid_carry && X == 0, 7, "internal error: formant stage on a path that cannot carry it");
+            fe = static_cast<float*>(mem.get(size_t(midf) * sizeof(float), true));
+            fcoef = static_cast<float*>(mem.get(size_t(fhops) * kFormantOrder * sizeof(float), false));
+            launch([&] {
+                FormantAnalyseArgs a{};
+                a.y = rin; a.y_bstride = rin_stride;
+                a.len = frn; a.len_mul = rin_frame; a.hist = rin_hist; a.hp = pitch_hp_;
+                a.win = fm_win_; a.lag = fm_win_ + 2 * size_t(pitch_hp_);
+                a.coef = fcoef + size_t(H) * fhops * kFormantOrder; a.coef_bstride = int64_t(Trows) * fhops * kFormantOrder;
+                a.e = fe + size_t(H) * midf; a.e_bstride = int64_t(Trows) * midf;
+                a.B = nb; a.max_len = int64_t(Trows - H) * rin_frame;
+                launch_formant_analyse(a, st_);
+            });
+            // (the Ring holds four tensors at most: the stage's input is done with)
+            if (mid) mem.put(mid);
+            mid = nullptr;
+            mem.put(p24);
+            tail_in_held = false;
+            fep = static_cast<float*>(mem.get(size_t(up) * sizeof(float), false));
+        }
         if (resample_) {
             // Output frame f depends on input up to the end of frame f alone (q = floor(n M / L) stays inside the frame), and
             // the phase of a chunk's first sample is 0: the rows are addressed frame by frame like every other tensor.
             launch([&] {
                 ResampleArgs a{};
                 a.x = rin; a.x_bstride = rin_stride;
-                a.y = pcm + size_t(H + X) * up; a.y_bstride = int64_t(Trows) * up;
+                if (formant_) {
+                    a.x = fe + size_t(H) * midf; a.x_bstride = int64_t(Trows) * midf;
+                }
+                a.y = (formant_ ? fep : pcm) + size_t(H + X) * up; a.y_bstride = int64_t(Trows) * up;
                 a.len = frn; a.len_mul = rin_frame; a.max_in = int64_t(Trows - H - X) * rin_frame;
                 a.len_mul_rows = ps.mid_rows;
                 a.tab = out_tab_; a.L = out_plan_.L; a.M = out_plan_.M; a.K = out_plan_.K;
-                a.hist = rin_hist; a.centred = 0; a.clamp = 1; a.B = nb;
+                a.hist = formant_ ? H * midf : rin_hist; a.centred = 0; a.clamp = formant_ ? 0 : 1; a.B = nb;
                 if (pitched_) launch_resample_ratio(a, st_);
                 else launch_resample(a, st_);
             });
         }
+        if (formant_) {
+            mem.put(fe);
+            fstate = H > 0 ? static_cast<float*>(mem.get(size_t(kFormantOrder) * sizeof(float), true)) : nullptr;
+            launch([&] {
+                FormantSynthArgs a{};
+                a.ep = fep + size_t(H) * up; a.ep_bstride = int64_t(Trows) * up;
+                a.out = pcm + size_t(H) * up; a.out_bstride = int64_t(Trows) * up;
+                a.len = frn; a.len_mul = up; a.ho = up / fhops;
+                a.coef = fcoef + size_t(H) * fhops * kFormantOrder; a.coef_bstride = int64_t(Trows) * fhops * kFormantOrder;
+                a.clamp = 1; a.B = nb; a.max_len = int64_t(Trows - H) * up;
+                if (fstate) {
+                    a.state_in = fstate + size_t(H - 1) * kFormantOrder; a.state_in_bstride = int64_t(Trows) * kFormantOrder;
+                    a.state_frames = fstate + size_t(H) * kFormantOrder; a.state_frames_bstride = int64_t(Trows) * kFormantOrder;
+                    a.frame_hops = fhops; a.state_frame_words = kFormantOrder;
+                }
+                launch_formant_synth(a, st_);
+            });
+            if (fstate) mem.put(fstate);
+            mem.put(fep);
+            mem.put(fcoef);
+        }
         if (mid) mem.put(mid);
-        if (post) mem.put(p24);
+        if (tail_in_held) mem.put(p24);
     };
     if (w.f16_main && !fp32_mfma_ && !no_h1_) main_decoder(uint16_t{});
     else main_decoder(float{});
@@ -639,6 +702,8 @@ int CodecRunner::decode_chunked(const int32_t* codes_dev, int code_stride_frames
     for (int f : frames) Fmax = std::max(Fmax, f);
     Q3_CHECK(Fmax > 0 && chunk_frames > 0, 3, "Invalid input: no frames to decode");
     Q3_CHECK(B <= kMaxRows, 3, "Invalid input: too many rows in one codec decode");
+    // (the recomputed left context cannot recompute the synthesis filter's state, nor the analysis window in front of a chunk)
+    Q3_CHECK(!formant_, 3, "Invalid input: the chunked exact decode is not offered on a handle with keep_formants");
     Q3_HIP(hipMemsetAsync(nf_dev_, 0, size_t(B) * 4, st_));
     const int H = tail_context_frames();
     const int n_chunks = ceil_div(Fmax, chunk_frames);

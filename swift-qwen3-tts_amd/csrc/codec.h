@@ -1,10 +1,12 @@
 // codec.h -- neural codec decoder runner (codes -> PCM at 24 kHz or at the handle's output rate) on the HIP kernels in
-// kernels/codec_conv.hip, kernels/codec_misc.hip, kernels/stretch.hip, kernels/resample.hip and kernels/resample_ratio.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
+// kernels/codec_conv.hip, kernels/codec_misc.hip, kernels/stretch.hip, kernels/resample.hip, kernels/resample_ratio.hip and
+// kernels/formant.hip. Mirrors Qwen3TTSSpeechTokenizerDecoder
 // (/root/reference/Sources/Qwen3TTS/Models/SpeechTokenizer.swift:754-784).
 #pragma once
 #include <string>
 #include <vector>
 
+#include "formant_plan.h"
 #include "model.h"
 #include "pitch_plan.h"
 #include "request_speed_plan.h"
@@ -34,8 +36,15 @@ class CodecRunner {
     // when Hp == 480) and ONE resampler behind it, Hp * M -> Ho * L on kernels/resample_ratio.hip, does pitch and output rate
     // together: the same pair of stages as a speed with an output rate, so every statement above holds with mid samples per
     // frame 4 Hp and upsample() that of the handle without a pitch. Hp == Ho is off. Not together with request_speeds.
+    // keep_formants (formant_plan.h; kernels/formant.hip): on a pitched handle at 24 kHz the tail becomes out_conv -> stretch
+    // (if Hp != 480) -> analyse / whiten -> the resampler, unclamped, into a tail tensor -> synthesise + clip -> PCM. Four more
+    // tail tensors: the whitened signal e (4 Hp floats per frame, with a margin: the FIR reads back into it), the coefficients
+    // (hops * P floats per frame), the unclipped e' (a frame of output samples) and the synthesis filter's state, one entry
+    // of P floats per frame with a margin, carried like the stretch's word. A saved prefix state grows by the two margins:
+    // hist_frames() * (align16(4 Hp * 4) + align16(P * 4)) bytes. Without a pitch (or Hp == Ho) the option adds nothing.
+    // decode_chunked is refused on such a handle: its recomputed context cannot recompute the filter's state.
     CodecRunner(const Model& m, hipStream_t st, bool fp32_convs = false, int output_rate = 0, float speed = 0.0f,
-                bool request_speeds = false, float pitch = 0.0f);
+                bool request_speeds = false, float pitch = 0.0f, bool keep_formants = false);
     // codes_dev: [B][code_stride_frames][16] int32 on the device; rows decode frames[b] frames.
     // pcm_dev receives [B][Fmax*upsample] float32 (Fmax = max(frames)); returns Fmax.
     // If `stage` is non-empty the activation after that stage is copied to stage_out ([B][T][C]).
@@ -157,6 +166,7 @@ class CodecRunner {
     // stretch and the FIR together in output samples
     int pitch_hp() const { return pitched_ ? pitch_hp_ : ho_; }
     int pitch_delay_out_samples() const { return pitch_delay_; }
+    bool keep_formants() const { return formant_; }  // the formant stage runs (the option on a handle whose pitch is on)
     hipStream_t stream() const { return st_; }
     void set_stream(hipStream_t st) { st_ = st; }  // the caller drains the old stream first (shared scratch)
 
@@ -273,6 +283,8 @@ class CodecRunner {
     int ho_ = kStretchHa;     // the speaking rate's hop
     bool pitched_ = false;    // the resampler is the general-ratio one and the stretch, if any, runs at pitch_hp_
     int pitch_hp_ = kStretchHa, pitch_delay_ = 0;
+    bool formant_ = false;    // keep_formants on a pitched handle: analyse / whiten in front of the resampler, synthesise behind it
+    DevBuf<float> fm_win_;    // FormantPlan's tables on the device: win [2 Hp], then lag [P + 1]
     int mid_ = 1920;          // samples per frame behind the time stretch == in front of the resampler (4 Hs, or native_)
     bool stretch_ = false;
     StretchPlan st_plan_;

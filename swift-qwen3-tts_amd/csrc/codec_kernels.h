@@ -252,6 +252,58 @@ struct StretchArgs {
 };
 void launch_stretch(const StretchArgs& a, hipStream_t st);
 
+// ---- formant preservation of a pitched handle (kernels/formant.hip; the definition: formant_plan.h) ----
+// Analyse + whiten, in front of the pitch resampler. Row b's mid signal starts at y + b * y_bstride and has len[b] * len_mul
+// valid samples at `hp` per hop; `hist` samples exist in memory in front of every row's first one (0: they are taken as zero).
+// Hop h's P coefficients a[1..P] go to coef + b * coef_bstride + h * P, its whitened samples to e + b * e_bstride + h * hp.
+// A row of length 0 touches nothing; samples at and behind a row's length are never read. win [2 hp] and lag [P + 1] are
+// FormantPlan's tables on the device.
+struct FormantAnalyseArgs {
+    const float* y;
+    int64_t y_bstride;
+    const int32_t* len;  // device [B]
+    int len_mul;
+    int hist;
+    int hp;
+    const float* win;
+    const float* lag;
+    float* coef;
+    int64_t coef_bstride;
+    float* e;
+    int64_t e_bstride;
+    int B;
+    int64_t max_len;     // the longest row's samples: sizes the grid
+};
+void launch_formant_analyse(const FormantAnalyseArgs& a, hipStream_t st);
+// Synthesise (+ clip when clamp != 0), behind the resampler. Row b's e' starts at ep + b * ep_bstride and has len[b] * len_mul
+// samples at `ho` per hop; hop h reads the coefficients at coef + b * coef_bstride + h * P; the result goes to
+// out + b * out_bstride. The row's state, P floats (its last P values of the unclipped z, oldest first), all optional:
+// state_in[b * state_in_bstride ..] is read on entry (nullptr: zeros), the state as it stands behind every frame_hops-th hop
+// goes to state_frames[b * state_frames_bstride + frame * state_frame_words ..], the state behind the last hop to
+// state_out[b * state_out_bstride ..] (which may be state_in: one wave owns the row). A row of length 0 touches nothing.
+struct FormantSynthArgs {
+    const float* ep;
+    int64_t ep_bstride;
+    float* out;
+    int64_t out_bstride;
+    const int32_t* len;  // device [B]
+    int len_mul;
+    int ho;
+    const float* coef;
+    int64_t coef_bstride;
+    int clamp;
+    int B;
+    int64_t max_len;     // the longest row's samples
+    const float* state_in;
+    int64_t state_in_bstride;
+    float* state_frames;
+    int64_t state_frames_bstride;
+    int frame_hops, state_frame_words;
+    float* state_out;
+    int64_t state_out_bstride;
+};
+void launch_formant_synth(const FormantSynthArgs& a, hipStream_t st);
+
 // ---- voice-clone front end (kernels/voice_frontend.hip) ------------------------------------------
 // first SEANet conv: 1 -> C channels, causal k taps (SpeechTokenizerEncoder.swift:404-414). w [C][K], out [S][C]
 void launch_enc_init_conv(const float* audio, int64_t S, int B, const float* w, const float* bias, int C, int K, float* out,

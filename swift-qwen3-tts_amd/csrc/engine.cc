@@ -13,7 +13,7 @@ std::string lower(const std::string& s) {
 }
 }  // namespace
 
-Engine::Engine(Model* model, const q3tts_load_opts& opts, float pitch) : m_(model), opts_(opts) {
+Engine::Engine(Model* model, const q3tts_load_opts& opts, float pitch, bool keep_formants) : m_(model), opts_(opts) {
     Q3_HIP(hipSetDevice(m_->device));
     {
         // The AR loop is a chain of short dependent launches (latency), the codec decode a few hundred large ones
@@ -66,7 +66,7 @@ Engine::Engine(Model* model, const q3tts_load_opts& opts, float pitch) : m_(mode
     }
     if (m_->has_codec)
         codec_ = std::make_unique<CodecRunner>(*m_, st_codec_, opts.codec_fp32 != 0, opts.output_sample_rate, opts.speed,
-                                               opts.request_speeds != 0, pitch);
+                                               opts.request_speeds != 0, pitch, keep_formants);
     if (m_->has_codec_encoder || m_->has_speaker_encoder) fe_ = std::make_unique<VoiceFrontEnd>(*m_, st_);
 }
 
@@ -1153,6 +1153,149 @@ void Engine::debug_resample_ratio(const float* x, const int32_t* lens, int B, in
     Q3_HIP(hipMemcpy2D(y, size_t(y_stride) * 4, dy, size_t(ys) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyDeviceToHost));
 }
 
+void Engine::pitch_shift_formants(const float* in, int64_t n_in, float semitones, float* out, int64_t cap, int64_t* n_out) {
+    // (the pitch is refused first, whatever else is wrong, and before any GPU work)
+    const int hp = pitch_choose_hp(kStretchHa, semitones);
+    Q3_CHECK(hp != 0, 3, "Invalid input: pitch must lie between -12 and 12 semitones");
+    if (hp == kStretchHa) {  // off: pitch_shift's copy, with its checks
+        pitch_shift(in, n_in, semitones, out, cap, n_out);
+        return;
+    }
+    Q3_CHECK(in && out && n_out && n_in > 0, 3, "Invalid input: empty audio");
+    Q3_CHECK(n_in <= (int64_t(1) << 26), 3, "Invalid input: pitch shift takes between 1 and 2^26 samples");
+    const int64_t n_mid = (n_in * hp + kStretchHa - 1) / kStretchHa;  // the whole form's length at Hp
+    const PitchRatio pr = pitch_ratio(hp, kStretchHa, 1, 1);
+    const int64_t no = (n_mid * pr.L + pr.M - 1) / pr.M;
+    *n_out = no;
+    Q3_CHECK(cap >= no, 3, "Invalid input: output buffer too small for the shifted audio");
+    bool finite = true;
+    for (int64_t i = 0; i < n_in; ++i) finite = finite && (std::fabs(in[i]) <= 3.0e38f);
+    Q3_CHECK(finite, 3, "Invalid input: audio holds non-finite samples");
+    StretchDev* sd = nullptr;
+    for (const auto& s : stretchers_)
+        if (s->plan.hs == hp) sd = s.get();
+    if (!sd) {
+        auto s = std::make_unique<StretchDev>();
+        s->plan = make_stretch_plan(hp);
+        Q3_HIP(hipMemcpy(s->fade.grow(size_t(hp)), s->plan.fade.data(), size_t(hp) * 4, hipMemcpyHostToDevice));
+        stretchers_.push_back(std::move(s));
+        sd = stretchers_.back().get();
+    }
+    const ResamplerDev& r = ratio_resampler(hp, kStretchHa);
+    const FormantPlan fp = make_formant_plan(hp);
+    std::vector<float> tabs(fp.win);
+    tabs.insert(tabs.end(), fp.lag, fp.lag + kFormantOrder + 1);
+    const int64_t hops = (n_mid + hp - 1) / hp;
+    DevBuf<float> dtab, de, dcoef, dep;  // (freed behind the synchronisation below)
+    dtab.grow(tabs.size());
+    de.grow(size_t(n_mid));
+    dcoef.grow(size_t(hops) * kFormantOrder);
+    dep.grow(size_t(no));
+    const float* a = upload_audio(in, n_in);
+    if (size_t(no) > rs_out_dev_.capacity() || size_t(n_mid) > ps_mid_dev_.capacity()) Q3_HIP(hipStreamSynchronize(st_));  // the old buffers may still be read
+    rs_out_dev_.grow(size_t(no));
+    ps_mid_dev_.grow(size_t(n_mid));
+    rs_len_dev_.grow(4);
+    const int32_t len[3] = {int32_t(n_in), int32_t(n_mid), int32_t(no)};
+    Q3_HIP(hipStreamSynchronize(st_));  // `len` is pageable stack memory, and the device words may still feed an earlier launch
+    Q3_HIP(hipMemcpy(rs_len_dev_, len, 12, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy(dtab, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
+    StretchArgs sa{};
+    sa.x = a; sa.y = ps_mid_dev_;
+    sa.len = rs_len_dev_; sa.len_mul = 1;
+    sa.fade = sd->fade; sa.hs = hp; sa.delay = 0;
+    sa.causal = 0; sa.B = 1;
+    launch_stretch(sa, st_);
+    FormantAnalyseArgs fa{};
+    fa.y = ps_mid_dev_; fa.len = rs_len_dev_ + 1; fa.len_mul = 1; fa.hist = 0; fa.hp = hp;
+    fa.win = dtab; fa.lag = dtab + 2 * size_t(hp);
+    fa.coef = dcoef; fa.e = de; fa.B = 1; fa.max_len = n_mid;
+    launch_formant_analyse(fa, st_);
+    ResampleArgs ra{};
+    ra.x = de; ra.x_bstride = 0;
+    ra.y = dep; ra.y_bstride = 0;
+    ra.len = rs_len_dev_ + 1; ra.len_mul = 1; ra.max_in = n_mid;
+    ra.tab = r.tab; ra.L = r.plan.L; ra.M = r.plan.M; ra.K = r.plan.K;
+    ra.hist = 0; ra.centred = 1; ra.clamp = 0; ra.B = 1;
+    launch_resample_ratio(ra, st_);
+    FormantSynthArgs fs{};
+    fs.ep = dep; fs.out = rs_out_dev_; fs.len = rs_len_dev_ + 2; fs.len_mul = 1; fs.ho = kStretchHa;
+    fs.coef = dcoef; fs.clamp = 0; fs.B = 1; fs.max_len = no;
+    launch_formant_synth(fs, st_);
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy(out, rs_out_dev_, size_t(no) * 4, hipMemcpyDeviceToHost));
+}
+
+void Engine::debug_formant_rows(int mode, int hp, int ho, const int32_t* lens, int B, const float* x, int64_t x_stride, int hist, float* coef,
+                                int64_t coef_stride, const float* state_in, float* state_out, float* y, int64_t y_stride, bool clamp) {
+    constexpr int P = kFormantOrder;
+    Q3_CHECK(mode >= 0 && mode <= 2, 3, "Invalid input: debug_formant_rows mode must be 0 (analyse + whiten), 1 (synthesise) or 2 (both)");
+    Q3_CHECK(hp >= kStretchHsMin && hp <= kStretchHsMax && ho >= kStretchHsMin && ho <= kStretchHsMax, 3,
+             "Invalid input: debug_formant_rows takes hops between 240 and 960");
+    Q3_CHECK(mode != 2 || hp == ho, 3, "Invalid input: debug_formant_rows runs both kernels with the identity in between only when Hp == Ho");
+    Q3_CHECK(B >= 1 && B <= 4096 && x_stride >= 1 && y_stride >= 1 && coef_stride >= P && x_stride <= (int64_t(1) << 26) &&
+                 y_stride <= (int64_t(1) << 26) && coef_stride <= (int64_t(1) << 26) && hist >= 0 && hist <= x_stride,
+             3, "Invalid input: debug_formant_rows takes 1..4096 rows of at most 2^26 samples");
+    Q3_CHECK(mode != 1 || hist == 0, 3, "Invalid input: debug_formant_rows synthesises rows without a margin (their history is the state)");
+    Q3_CHECK(mode != 0 || (!state_in && !state_out), 3, "Invalid input: debug_formant_rows analyses without a state");
+    const int hop = mode == 1 ? ho : hp;  // the hop the rows' lengths count in
+    int64_t max_len = 0;
+    for (int b = 0; b < B; ++b) {
+        Q3_CHECK(lens[b] >= 0 && int64_t(hist) + lens[b] <= x_stride && lens[b] <= y_stride, 3, "Invalid input: a row is longer than its stride");
+        Q3_CHECK((int64_t(lens[b]) + hop - 1) / hop * P <= coef_stride, 3, "Invalid input: a row's coefficients do not fit coef_stride");
+        max_len = std::max<int64_t>(max_len, lens[b]);
+    }
+    const int64_t hpad = (int64_t(hist) + 3) & ~int64_t(3);
+    const int64_t xs = (hpad - hist + x_stride + 3) & ~int64_t(3), ys = (y_stride + 3) & ~int64_t(3), cs = (coef_stride + 3) & ~int64_t(3);
+    DevBuf<float> dx, dy, dc, dm, ds, dtab;
+    DevBuf<int32_t> dl;
+    dx.grow(size_t(B) * size_t(xs));
+    dy.grow(size_t(B) * size_t(ys));
+    dc.grow(size_t(B) * size_t(cs));
+    dm.grow(size_t(B) * size_t(ys));  // mode 2: the whitened signal between the kernels
+    ds.grow(size_t(B) * P);
+    dl.grow(size_t(B));
+    const FormantPlan fp = make_formant_plan(hp);
+    std::vector<float> tabs(fp.win);
+    tabs.insert(tabs.end(), fp.lag, fp.lag + P + 1);
+    dtab.grow(tabs.size());
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy(dtab, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
+    Q3_HIP(hipMemset(dx, 0, size_t(B) * size_t(xs) * 4));
+    Q3_HIP(hipMemcpy2D(dx + (hpad - hist), size_t(xs) * 4, x, size_t(x_stride) * 4, size_t(x_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy2D(dy, size_t(ys) * 4, y, size_t(y_stride) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy2D(dm, size_t(ys) * 4, y, size_t(y_stride) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    Q3_HIP(hipMemcpy2D(dc, size_t(cs) * 4, coef, size_t(coef_stride) * 4, size_t(coef_stride) * 4, size_t(B), hipMemcpyHostToDevice));
+    if (state_in) Q3_HIP(hipMemcpy(ds, state_in, size_t(B) * P * 4, hipMemcpyHostToDevice));
+    else Q3_HIP(hipMemset(ds, 0, size_t(B) * P * 4));
+    Q3_HIP(hipMemcpy(dl, lens, size_t(B) * 4, hipMemcpyHostToDevice));
+    if (mode != 1) {
+        FormantAnalyseArgs fa{};
+        fa.y = dx + hpad; fa.y_bstride = xs;
+        fa.len = dl; fa.len_mul = 1; fa.hist = hist; fa.hp = hp;
+        fa.win = dtab; fa.lag = dtab + 2 * size_t(hp);
+        fa.coef = dc; fa.coef_bstride = cs;
+        fa.e = mode == 0 ? dy : dm; fa.e_bstride = ys;
+        fa.B = B; fa.max_len = max_len;
+        launch_formant_analyse(fa, st_);
+    }
+    if (mode != 0) {
+        FormantSynthArgs fs{};
+        fs.ep = mode == 1 ? dx + hpad : dm; fs.ep_bstride = mode == 1 ? xs : ys;
+        fs.out = dy; fs.out_bstride = ys;
+        fs.len = dl; fs.len_mul = 1; fs.ho = ho;
+        fs.coef = dc; fs.coef_bstride = cs;
+        fs.clamp = clamp ? 1 : 0; fs.B = B; fs.max_len = max_len;
+        fs.state_in = ds; fs.state_in_bstride = P;
+        fs.state_out = ds; fs.state_out_bstride = P;
+        launch_formant_synth(fs, st_);
+    }
+    Q3_HIP(hipStreamSynchronize(st_));
+    Q3_HIP(hipMemcpy2D(y, size_t(y_stride) * 4, dy, size_t(ys) * 4, size_t(y_stride) * 4, size_t(B), hipMemcpyDeviceToHost));
+    Q3_HIP(hipMemcpy2D(coef, size_t(coef_stride) * 4, dc, size_t(cs) * 4, size_t(coef_stride) * 4, size_t(B), hipMemcpyDeviceToHost));
+    if (state_out) Q3_HIP(hipMemcpy(state_out, ds, size_t(B) * P * 4, hipMemcpyDeviceToHost));
+}
+
 std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids,
                                             int sample_rate) {
     const TalkerConfig& t = m_->cfg.talker;
@@ -1380,6 +1523,17 @@ int Engine::open_job(const q3tts_request* reqs, int n, const q3tts_sampling& sp,
     Q3_CHECK(n >= 1 && n <= Bm_, 3, "Invalid input: batch size must be between 1 and max_batch");
     Q3_CHECK(m_->cfg.talker.num_code_groups == 16, 3, "Invalid input: num_code_groups must be 16");
     Q3_CHECK(sp.audio_chunk_frames >= 0, 3, "Invalid input: audio_chunk_frames must not be negative");
+    if (sp.audio_chunk_frames > 0 && codec_ && codec_->keep_formants()) {
+        // (before any GPU work) a job with chunks that will not be streamed -- no window, a clone row without
+        // audio_stream_reference, a debug job: begin()'s own condition -- goes to the chunked exact decode, which recomputes its
+        // left context and cannot recompute the synthesis filter's state
+        bool any_clone = false;
+        for (int i = 0; reqs && i < n; ++i) any_clone = any_clone || reqs[i].ref_audio != nullptr || (voices && voices[i]);
+        const bool streamed = sp.audio_window_frames > 0 && (!any_clone || sp.audio_stream_reference != 0) && !dbg;
+        Q3_CHECK(streamed, 3,
+                 "Invalid input: audio_chunk_frames on a handle with keep_formants needs streamed audio: audio_window_frames > 0, and "
+                 "audio_stream_reference for voice-clone rows (the chunked exact decode is not offered; or decode in one piece)");
+    }
     if (sp.audio_chunk_frames > 0 && sp.audio_window_frames > 0 && m_->has_codec)  // before any GPU work (the stream would refuse it later)
         Q3_CHECK(sp.audio_chunk_frames >= codec_->hist_frames(), 3,
                  "Invalid input: audio_chunk_frames of a streamed decode must be at least " + std::to_string(codec_->hist_frames()));

@@ -202,7 +202,8 @@ struct QueueShared {
 class Engine {
   public:
     // One lane: a slice of the batch with its own stream, workspace, KV pool and frame graph.
-    Engine(Model* model, const q3tts_load_opts& opts, float pitch = 0.0f);  // pitch: q3tts_load_opts_ex.pitch
+    // pitch: q3tts_load_opts_ex.pitch; keep_formants: q3tts_load_opts_ex2.keep_formants
+    Engine(Model* model, const q3tts_load_opts& opts, float pitch = 0.0f, bool keep_formants = false);
     ~Engine();
 
     Model& model() { return *m_; }
@@ -294,6 +295,12 @@ class Engine {
     // q3tts_debug_resample_ratio: kernels/resample_ratio.hip on host rows, any positive integer pair
     void debug_resample_ratio(const float* x, const int32_t* lens, int B, int64_t row_stride, int64_t in_units, int64_t out_units, bool centred,
                               bool clamp, int hist, float* y, int64_t y_stride);
+    // q3tts_pitch_shift_formants: pitch_shift with the formant stage (formant_plan.h formant_shift_reference): the whole stretch
+    // at Hp, analyse + whiten, the centred resampler Hp -> 480, synthesise; not clipped
+    void pitch_shift_formants(const float* in, int64_t n_in, float semitones, float* out, int64_t cap, int64_t* n_out);
+    // q3tts_debug_formant_rows: kernels/formant.hip on host rows (include/q3tts.h states the modes)
+    void debug_formant_rows(int mode, int hp, int ho, const int32_t* lens, int B, const float* x, int64_t x_stride, int hist, float* coef,
+                            int64_t coef_stride, const float* state_in, float* state_out, float* y, int64_t y_stride, bool clamp);
     void debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C);
 
     std::vector<std::string> speakers;  // sorted (Qwen3.swift:965-971)
@@ -597,7 +604,7 @@ class Session;
 // batches, each on a context of its own, are what the two-deep pipeline runs side by side (Engine::begin).
 class EngineGroup {
   public:
-    EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts, float pitch = 0.0f);
+    EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts, float pitch = 0.0f, bool keep_formants = false);
     Model& model() { return *model_; }
     ~EngineGroup();
     Engine& lane0() {  // the engine behind the single-engine entry points; a back half still running on it finishes first

@@ -10,7 +10,7 @@ namespace q3 {
 // ------------------------------------------------------------------------------------------------
 // EngineGroup
 // ------------------------------------------------------------------------------------------------
-EngineGroup::EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts, float pitch) : model_(std::move(model)), opts_(opts) {
+EngineGroup::EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& opts, float pitch, bool keep_formants) : model_(std::move(model)), opts_(opts) {
     int lanes = opts.n_streams;
     // Measured: a lane's frame step takes ~4-5 ms whatever its batch size (latency-bound chain), and
     // n concurrent chains overlap by 1.6x (n=2) / 2.2x (n=4). Splitting ONE batch into lanes therefore never pays -- each
@@ -20,7 +20,7 @@ EngineGroup::EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& op
     q3tts_load_opts lo = opts;
     lo.max_batch = ceil_div(opts.max_batch, lanes);
     for (int i = 0; i < lanes; ++i) {
-        lanes_.push_back(std::make_unique<Engine>(model_.get(), lo, pitch));
+        lanes_.push_back(std::make_unique<Engine>(model_.get(), lo, pitch, keep_formants));
         lanes_.back()->cb_mutex = &cb_mutex_;
         // keep the sum of queued kernel packets of all lanes well under the 16k-entry AQL queue (~650 nodes per frame)
         lanes_.back()->max_inflight_frames = std::max(2, 12000 / 650 / lanes);
@@ -29,7 +29,7 @@ EngineGroup::EngineGroup(std::unique_ptr<Model> model, const q3tts_load_opts& op
     if (lanes == 1) {
         // The second job context: a full engine of its own (stream, workspace, KV pool, frame graphs, codec runner) on the
         // shared model. Allocated here, at load, so that no steady-state step allocates; include/q3tts.h states the memory.
-        ctx1_ = std::make_unique<Engine>(model_.get(), lo, pitch);
+        ctx1_ = std::make_unique<Engine>(model_.get(), lo, pitch, keep_formants);
         ctx1_->cb_mutex = &cb_mutex_;
         background_ = !debug_env().serial_jobs;  // (the serial switch: both contexts exist and alternate, on the parent's schedule)
         if (background_)

@@ -37,6 +37,8 @@ def main(argv=None) -> int:
                     help="new: speaking rate, pitch preserved (0 or 1 = off, 0.5 .. 2.0); stretched on the device behind the decoder")
     ap.add_argument("--pitch", type=float, default=0.0,
                     help="new: pitch in semitones at an unchanged duration (0 = off, -12 .. 12); shifted on the device behind the decoder")
+    ap.add_argument("--keep-formants", action="store_true",
+                    help="new: with --pitch, keep the voice's formants (a linear-prediction envelope per hop around the resampler); 24 kHz only")
     ap.add_argument("--resample-reference", action="store_true",
                     help="new: resample a reference clip that is not 24 kHz on the device instead of feeding it in as it is")
     a = ap.parse_args(argv)
@@ -61,13 +63,14 @@ def main(argv=None) -> int:
     t0 = time.time()
     model = Qwen3TTSModel.from_pretrained(a.model, device=a.device, max_batch=1, max_frames=min(a.max_tokens, 2048) + 8,
                                           max_prompt=1024, output_sample_rate=a.output_sample_rate,
-                                          speed=a.speed, pitch=a.pitch)
+                                          speed=a.speed, pitch=a.pitch, **(dict(keep_formants=True) if a.keep_formants else {}))
     print(f"Model loaded in {time.time() - t0:.2f}s")
     if a.speed not in (0.0, 1.0):
         print(f"Speed: {model.speed:.4f}x (synthesis hop {model.stretch_hs}, delay {model.stretch_delay_samples} samples)")
     if a.pitch != 0.0:
         ps, hp, ho, pd = model.pitch_info()
-        print(f"Pitch: {ps:+.4f} semitones (hop {hp} resampled to {ho}, delay {pd} samples)")
+        print(f"Pitch: {ps:+.4f} semitones (hop {hp} resampled to {ho}, delay {pd} samples)"
+              + (", formants kept" if a.keep_formants and model.keep_formants_info() else ""))
     print()
     print("Generating audio...")
     t1 = time.time()

@@ -27,6 +27,10 @@ class LoadOptsEx(C.Structure):  # q3tts_load_opts_ex: the options above and what
     _fields_ = [("base", LoadOpts), ("pitch", C.c_float)]
 
 
+class LoadOptsEx2(C.Structure):  # q3tts_load_opts_ex2: q3tts_load_opts_ex whole, and what has been added behind it
+    _fields_ = [("ex", LoadOptsEx), ("keep_formants", C.c_int32)]
+
+
 class CommId(C.Structure):  # q3tts_comm_id == ncclUniqueId
     _fields_ = [("bytes", C.c_char * 128)]
 
@@ -308,6 +312,14 @@ def lib() -> C.CDLL:
         L.q3tts_pitch_shift.argtypes = [vp, f32p, C.c_int64, C.c_float, f32p, C.c_int64, C.POINTER(C.c_int64)]
         L.q3tts_debug_resample_ratio.argtypes = [vp, f32p, i32p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                                  f32p, C.c_int64]
+    if hasattr(L, "q3tts_pitch_shift_formants"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_default_load_opts_ex2.argtypes = [C.POINTER(LoadOptsEx2)]
+        L.q3tts_default_load_opts_ex2.restype = None
+        L.q3tts_model_load_ex2.argtypes = [C.c_char_p, C.POINTER(LoadOptsEx2), C.POINTER(vp)]
+        L.q3tts_model_get_keep_formants.argtypes = [vp, i32p]
+        L.q3tts_pitch_shift_formants.argtypes = [vp, f32p, C.c_int64, C.c_float, f32p, C.c_int64, C.POINTER(C.c_int64)]
+        L.q3tts_debug_formant_rows.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int32, f32p, C.c_int64, C.c_int32, f32p, C.c_int64,
+                                               f32p, f32p, f32p, C.c_int64, C.c_int32]
     if hasattr(L, "q3tts_debug_prefix_states"):
         L.q3tts_debug_prefix_states.argtypes = [vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "q3tts_debug_codec_stream_slots"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)

@@ -166,7 +166,7 @@ class Qwen3TTSModel:
                         weights_from_broadcast: bool = False, n_streams: int = 0,
                         codec_overlap_cus: int = 0, codec_fp32: bool = False,
                         output_sample_rate: int = 0, speed: float = 0.0, request_speeds: bool = False,
-                        pitch: float = 0.0) -> "Qwen3TTSModel":
+                        pitch: float = 0.0, keep_formants: bool = False) -> "Qwen3TTSModel":
         """output_sample_rate (q3tts_load_opts.output_sample_rate): 0 = 24000; 8000, 12000, 16000, 22050, 32000, 44100 or
         48000 make every waveform of this handle leave at that rate (sample_rate and info.samples_per_frame report it).
         speed (q3tts_load_opts.speed): 0 or 1.0 = off; 0.5 .. 2.0 make this handle speak that much faster, pitch preserved,
@@ -175,7 +175,10 @@ class Qwen3TTSModel:
         request_speeds (q3tts_load_opts.request_speeds): the handle admits GenerationRequest.speed, a speaking rate per
         request (`request_speed_info` tells what one becomes; info.max_samples_per_frame is the slowest request's).
         pitch (q3tts_load_opts_ex.pitch): 0 = off; -12 .. 12 semitones shift this handle's pitch at an unchanged duration
-        (`pitch_info` reports what was chosen; sample counts are those of the handle without it). Not with request_speeds."""
+        (`pitch_info` reports what was chosen; sample counts are those of the handle without it). Not with request_speeds.
+        keep_formants (q3tts_load_opts_ex2.keep_formants): the pitch keeps the voice's formants -- a linear-prediction envelope
+        per hop, taken off in front of the pitch resampler and put back behind it (`keep_formants_info` tells whether the stage
+        runs: it needs a pitch that is on). 24 kHz output only."""
         lib = L.lib()
         o = L.LoadOpts()
         lib.q3tts_default_load_opts(C.byref(o))
@@ -189,7 +192,14 @@ class Qwen3TTSModel:
         o.speed = float(speed)
         o.request_speeds = 1 if request_speeds else 0
         h = C.c_void_p()
-        if pitch == 0.0:  # (a float comparison: a NaN goes on to be refused below)
+        if keep_formants is not False:  # (anything but the default goes to the library, which refuses what is not 0 / 1)
+            if not hasattr(lib, "q3tts_model_load_ex2"):
+                raise Qwen3TTSError(3, "Invalid input: this build of the library has no keep_formants option")
+            ex2 = L.LoadOptsEx2()
+            lib.q3tts_default_load_opts_ex2(C.byref(ex2))
+            ex2.ex.base, ex2.ex.pitch, ex2.keep_formants = o, float(pitch), int(keep_formants)
+            st = lib.q3tts_model_load_ex2(model_path.encode(), C.byref(ex2), C.byref(h))
+        elif pitch == 0.0:  # (a float comparison: a NaN goes on to be refused below)
             st = lib.q3tts_model_load(model_path.encode(), C.byref(o), C.byref(h))
         else:
             if not hasattr(lib, "q3tts_model_load_ex"):
@@ -259,6 +269,29 @@ class Qwen3TTSModel:
         s, hp, ho, d = C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
         self._check(self._lib.q3tts_model_get_pitch(self._h, C.byref(s), C.byref(hp), C.byref(ho), C.byref(d)))
         return float(s.value), int(hp.value), int(ho.value), int(d.value)
+
+    def keep_formants_info(self) -> bool:
+        """q3tts_model_get_keep_formants: whether the formant-preserving stage runs on this handle (the option with a pitch that is
+        on)."""
+        on = C.c_int32(0)
+        self._check(self._lib.q3tts_model_get_keep_formants(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def debug_formant_rows(self, mode: int, hp: int, ho: int, x: np.ndarray, lens: Sequence[int], coef: np.ndarray, y: np.ndarray,
+                           hist: int = 0, state_in: Optional[np.ndarray] = None, want_state: bool = False, clamp: bool = False):
+        """q3tts_debug_formant_rows: kernels/formant.hip on host rows x [B][x_stride] (mode 0: analyse + whiten, 1: synthesise
+        with `coef`, 2: both, Hp == Ho). Returns (y, coef, state behind or None) as the kernels left them."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.ascontiguousarray(y, np.float32).copy()
+        coef = np.ascontiguousarray(coef, np.float32).copy()
+        ln = np.ascontiguousarray(lens, np.int32)
+        si = None if state_in is None else np.ascontiguousarray(state_in, np.float32)
+        so = np.zeros((x.shape[0], 24), np.float32) if want_state else None
+        self._check(self._lib.q3tts_debug_formant_rows(
+            self._h, int(mode), int(hp), int(ho), ln.ctypes.data_as(L.i32p), x.shape[0], x.ctypes.data_as(L.f32p), x.shape[1], int(hist),
+            coef.ctypes.data_as(L.f32p), coef.shape[1], None if si is None else si.ctypes.data_as(L.f32p),
+            None if so is None else so.ctypes.data_as(L.f32p), y.ctypes.data_as(L.f32p), y.shape[1], 1 if clamp else 0))
+        return y, coef, so
 
     def debug_resample_ratio(self, x: np.ndarray, lens: Sequence[int], in_units: int, out_units: int, y: np.ndarray,
                              centred: bool = False, clamp: bool = False, hist: int = 0) -> np.ndarray:
@@ -359,13 +392,15 @@ class Qwen3TTSModel:
                                                  out.ctypes.data_as(L.f32p), out.size, C.byref(n)))
         return out[: n.value]
 
-    def pitch_shift(self, audio: np.ndarray, semitones: float) -> np.ndarray:
+    def pitch_shift(self, audio: np.ndarray, semitones: float, keep_formants: bool = False) -> np.ndarray:
         """q3tts_pitch_shift: 24 kHz audio shifted by `semitones` at (nearly) its duration, on the device: the whole time
-        stretch at Hp = round(480 * 2^(semitones / 12)), then the centred resampler Hp -> 480 (include/q3tts.h, "Pitch")."""
+        stretch at Hp = round(480 * 2^(semitones / 12)), then the centred resampler Hp -> 480 (include/q3tts.h, "Pitch").
+        keep_formants: q3tts_pitch_shift_formants, the same with the formant-preserving stage around the resampler."""
         a = np.ascontiguousarray(np.asarray(audio, np.float32).reshape(-1))
         out = np.zeros(a.size + 8, np.float32)  # (two roundings up, at most 2 + 480 / Hp samples over n_in)
         n = C.c_int64(0)
-        self._check(self._lib.q3tts_pitch_shift(self._h, a.ctypes.data_as(L.f32p), a.size, float(semitones), out.ctypes.data_as(L.f32p),
+        fn = self._lib.q3tts_pitch_shift_formants if keep_formants else self._lib.q3tts_pitch_shift
+        self._check(fn(self._h, a.ctypes.data_as(L.f32p), a.size, float(semitones), out.ctypes.data_as(L.f32p),
                                                 out.size, C.byref(n)))
         return out[: n.value]
 

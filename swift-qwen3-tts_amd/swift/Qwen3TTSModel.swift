@@ -132,20 +132,25 @@ public final class Qwen3TTSModel {
     /// 48000 make every waveform of this model leave at that rate, resampled on the device behind the decoder
     /// (q3tts_load_opts.output_sample_rate); `sampleRate` reports it. `speed` (new; 0 or 1 = off): 0.5 ... 2.0 make the model
     /// speak that much faster, pitch preserved, through the time stretch in the decoder's tail (q3tts_load_opts.speed);
-    /// `speed` / `stretchDelaySamples` report what was chosen.
+    /// `speed` / `stretchDelaySamples` report what was chosen. `pitch` (new; 0 = off): -12 ... 12 semitones at an unchanged
+    /// duration (q3tts_load_opts_ex.pitch); `keepFormants` (new): the pitch keeps the voice's formants
+    /// (q3tts_load_opts_ex2.keep_formants; 24 kHz output only); `keepsFormants` reports whether the stage runs.
     public static func fromPretrained(_ modelPath: String, device: Int32 = 0, maxBatch: Int32 = 1,
-                                      outputSampleRate: Int32 = 0, speed: Float = 0) async throws -> Qwen3TTSModel {
+                                      outputSampleRate: Int32 = 0, speed: Float = 0, pitch: Float = 0,
+                                      keepFormants: Bool = false) async throws -> Qwen3TTSModel {
         // Qwen3.swift:1386-1388: the same decode of the same file (a malformed config fails here, before the engine sees it)
         let configData = try Data(contentsOf: URL(fileURLWithPath: modelPath).appendingPathComponent("config.json"))
         let config = try JSONDecoder().decode(Qwen3TTSModelConfig.self, from: configData)
-        var opts = q3tts_load_opts()
-        q3tts_default_load_opts(&opts)
-        opts.device = device
-        opts.max_batch = maxBatch
-        opts.output_sample_rate = outputSampleRate
-        opts.speed = speed
+        var opts = q3tts_load_opts_ex2()
+        q3tts_default_load_opts_ex2(&opts)
+        opts.ex.base.device = device
+        opts.ex.base.max_batch = maxBatch
+        opts.ex.base.output_sample_rate = outputSampleRate
+        opts.ex.base.speed = speed
+        opts.ex.pitch = pitch
+        opts.keep_formants = keepFormants ? 1 : 0
         var h: OpaquePointer?
-        let st = q3tts_model_load(modelPath, &opts, &h)
+        let st = q3tts_model_load_ex2(modelPath, &opts, &h)
         guard st == Q3TTS_OK, let h else { throw AudioGenerationError.from(st, String(cString: q3tts_last_error(nil))) }
         var mi = q3tts_model_info()
         q3tts_model_get_info(h, &mi)
@@ -159,6 +164,8 @@ public final class Qwen3TTSModel {
     public var speed: Float { var s: Float = 1; q3tts_model_get_speed(handle, &s, nil, nil); return s }
     /// The delay of the causal time stretch in 24 kHz samples (0: off)
     public var stretchDelaySamples: Int { var d: Int32 = 0; q3tts_model_get_speed(handle, nil, nil, &d); return Int(d) }
+    /// Whether the formant-preserving stage runs on this model (keepFormants with a pitch that is on) -- q3tts_model_get_keep_formants
+    public var keepsFormants: Bool { var on: Int32 = 0; q3tts_model_get_keep_formants(handle, &on); return on != 0 }
     public var ttsModelType: String { withUnsafeBytes(of: info.tts_model_type) { String(cString: $0.bindMemory(to: CChar.self).baseAddress!) } }
     public var supportsVoiceCloning: Bool { info.supports_voice_cloning != 0 }                // Qwen3.swift:1210
     public var hasVoiceCloning: Bool { info.has_voice_cloning != 0 }                          // Qwen3.swift:61

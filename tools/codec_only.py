@@ -13,6 +13,7 @@ from qwen3tts import Qwen3TTSModel, synth  # noqa: E402
 B, F, reps = int(sys.argv[1]) if len(sys.argv) > 1 else 16, int(sys.argv[2]) if len(sys.argv) > 2 else 200, 3
 speed = float(os.environ.get("Q3TTS_CODEC_ONLY_SPEED", "0"))  # q3tts_load_opts.speed: the time stretch behind out_conv (stretch.hip)
 pitch = float(os.environ.get("Q3TTS_CODEC_ONLY_PITCH", "0"))  # q3tts_load_opts_ex.pitch: the stretch at Hp and resample_ratio.hip behind it
+keep = os.environ.get("Q3TTS_CODEC_ONLY_KEEP_FORMANTS") == "1"  # q3tts_load_opts_ex2.keep_formants: formant.hip around the resampler
 rate = int(os.environ.get("Q3TTS_CODEC_ONLY_RATE", "0"))      # q3tts_load_opts.output_sample_rate (resample.hip without a pitch)
 f16 = os.environ.get("Q3TTS_CODEC_ONLY_F16") == "1"   # the speech tokenizer stored in float16 ("lite" checkpoints): codec_conv_h1.hip
 d = "/tmp/q3tts_codec_only" + ("_f16" if f16 else "")
@@ -38,11 +39,12 @@ modes = ("0", "1") if os.environ.get("Q3TTS_CODEC_COMPARE") else (os.environ.get
 for mode in modes:   # "1": fp32 matrix-core path, "0": fp16x2 (default)
     os.environ["Q3TTS_CODEC_FP32"] = mode
     m = Qwen3TTSModel.from_pretrained(d, max_batch=1, max_frames=8, max_prompt=64, **(dict(speed=speed) if speed else {}),
-                                      **(dict(pitch=pitch) if pitch else {}), **(dict(output_sample_rate=rate) if rate else {}))
+                                      **(dict(pitch=pitch) if pitch else {}), **(dict(output_sample_rate=rate) if rate else {}),
+                                      **(dict(keep_formants=True) if keep else {}))
     for i in range(reps):
         t0 = time.time()
         out = m.codec_decode(codes)
-        print(f"codec_decode fp32_mfma={mode} speed={speed} pitch={pitch} rate={rate or 24000} B={B} F={F}: wall {1e3 * (time.time() - t0):.1f} ms, "
+        print(f"codec_decode fp32_mfma={mode} speed={speed} pitch={pitch}{' keep_formants' if keep else ''} rate={rate or 24000} B={B} F={F}: wall {1e3 * (time.time() - t0):.1f} ms, "
               f"device {m.last_timing().codec_ms:.1f} ms", flush=True)
     pcm[mode] = np.asarray(out[0] if isinstance(out, (tuple, list)) else out)
     m.close()

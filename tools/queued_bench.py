@@ -402,6 +402,8 @@ def main():
                     help="load the model with q3tts_load_opts.speed = S (0: off; 0.5 .. 2.0: the time stretch in the decoder's tail)")
     ap.add_argument("--pitch", type=float, default=0.0, metavar="SEMITONES",
                     help="load the model with q3tts_load_opts_ex.pitch (0: off; -12 .. 12: the stretch at Hp and the general-ratio resampler)")
+    ap.add_argument("--keep-formants", action="store_true",
+                    help="load the model with q3tts_load_opts_ex2.keep_formants (with --pitch: analyse / whiten and synthesise around the resampler)")
     ap.add_argument("--request-speeds", default=None, metavar="S1,S2,...",
                     help="load the model with q3tts_load_opts.request_speeds and deal these speeds round robin over the requests "
                          "(q3tts_request.speed; 0: the handle's)")
@@ -413,6 +415,8 @@ def main():
         rate_kw["speed"] = args.speed
     if args.pitch:
         rate_kw["pitch"] = args.pitch
+    if args.keep_formants:
+        rate_kw["keep_formants"] = True
     req_speeds = [float(s) for s in args.request_speeds.split(",")] if args.request_speeds else []
     if req_speeds:
         rate_kw["request_speeds"] = True

@@ -565,7 +565,8 @@ q3tts_status q3tts_generate_queued_voices(q3tts_model* m, const q3tts_request* r
  *     is not answered with INVALID_INPUT). A server stops its submitting threads before it frees the model.
  * While a session is open every other entry point that uses the engine (q3tts_generate*, q3tts_generate_begin, q3tts_codec_*,
  * q3tts_voice_create / _free, q3tts_speaker_embedding, q3tts_debug_*, the arena calls) returns INVALID_INPUT ("a session is open")
- * without touching the GPU, and the session goes on: voices are created before open. q3tts_model_get_info, q3tts_last_error,
+ * without touching the GPU, and the session goes on: voices are created before open (or by the session itself: "Live voices"
+ * below). q3tts_model_get_info, q3tts_last_error,
  * q3tts_voice_get_info, the tokenizer and q3tts_last_timing stay available.
  * q3tts_last_error and the session calls: a submit, cancel, wait or get_stats that is refused keeps its message for the thread
  * that made the call. q3tts_last_error(model) on that thread returns it until the thread's next call on the handle or session
@@ -634,6 +635,71 @@ q3tts_status q3tts_session_submit_open(q3tts_session* s, const q3tts_request* re
                                        int64_t* ticket);
 q3tts_status q3tts_session_append_text(q3tts_session* s, int64_t ticket, const int32_t* ids, int32_t n, int32_t final);
 q3tts_status q3tts_session_get_text_stats(const q3tts_session* s, q3tts_session_text_stats* out);
+
+/* Live voices (new): a session that makes voices, and takes ref_audio requests, while it runs -- a voice-clone server adds a
+ * speaker without stopping every other speaker's audio. The front end of a clip (upload, the centred resample for a clip at
+ * another rate, codec encoder, speaker encoder, prompt rows: what q3tts_voice_create[_rate] runs) is enqueued by the loop thread
+ * on one of `live_voices` streams of its own, beside the frame steps, and polled at the burst boundaries; the loop never waits
+ * for it while a row is running, and a boundary neither synchronises the device nor allocates or frees device memory for it:
+ * the lanes' scratch, their pinned staging and a pool of `max_voices` voice slots are made at open, and in a streamed session
+ * (audio_stream_reference) one saved prefix state per slot when the loop starts. A session-made voice keeps at most one saved
+ * state -- the first (geometry, speed) it is streamed with; a further one is decoded at every admission -- in its slot's place,
+ * which goes to the next voice with the slot: a session's state memory is bounded by max_voices and nothing is allocated or freed
+ * for it while the session runs. An anonymous voice (a ref_audio submit) saves none: no other ticket could use it. (A voice made
+ * by q3tts_voice_create before open keeps its states in memory of their own, allocated at its first streamed admission, as
+ * before.)
+ * Contract: a session-made voice holds the very bits q3tts_voice_create[_rate] gives for the same clip, text and rate on this
+ * handle, whatever ran beside its front end. So ticket t stays bit-identical to the request generated alone at row_base + t,
+ * whether it names a session-made voice (reference: q3tts_generate_voices with an ordinary voice of the clip) or brought its
+ * clip as ref_audio (reference: q3tts_generate of that request), streamed forms included. A ticket whose voice is not ready is
+ * not admitted and does not hold back the tickets behind it; without such tickets, admission order stays ticket order.
+ *   q3tts_session_open_ex: q3tts_session_open with `live_voices` front-end jobs in flight at most (0..4; 0: exactly the session
+ *     q3tts_session_open gives, which passes 0) and `max_voices` session-made voices alive at once, anonymous ones included
+ *     (0: 4 * slots). base.max_ref_frames bounds a clip as it bounds a voice and must be > 0 with live_voices > 0. live_voices > 0
+ *     on a model without the speech-tokenizer encoder: MODEL_NOT_INITIALIZED. Otherwise INVALID_INPUT as q3tts_session_open.
+ *   q3tts_session_voice_create: any thread, also from inside an event callback; it never waits for the loop. Every host check
+ *     of q3tts_voice_create[_rate] runs on the calling thread, and encoded_frames(samples at 24 kHz) <= max_ref_frames. The
+ *     clip and the text ids are copied, and the handle returned at once is a voice from that moment: q3tts_voice_get_info
+ *     answers (ref_frames, n_ref_samples and device_bytes are known on the host) and q3tts_session_submit may name it.
+ *     Q3TTS_ERR_BUSY: live_voices jobs are waiting or running, or max_voices voices are alive. INVALID_INPUT on a session opened
+ *     without live_voices. A refused call leaves the session running.
+ *   q3tts_session_voice_wait: blocks until the voice's front end is done; *ready = 0 on timeout (timeout_ms < 0: for ever).
+ *     Refused inside a callback, like q3tts_session_wait. Q3TTS_ERR_CANCELLED: the job was abandoned by a close without drain.
+ *   q3tts_session_voice_free: any thread. The voice can be named no more; its slot and its saved prefix states are released
+ *     at the first boundary at which no pending or running ticket names it, and the tickets already accepted complete unchanged.
+ *   q3tts_session_submit with ref_audio / ref_text_ids on a session with live_voices > 0: accepted (24 kHz, as q3tts_request says).
+ *     The session makes an anonymous voice for the ticket -- it counts against both limits -- and frees it when the ticket
+ *     retires, is cancelled, or the session closes. Streamed: the rules of voice rows (audio_stream_reference). With
+ *     live_voices == 0 the refusal stands as it was.
+ *   q3tts_session_get_voice_stats: created = voices accepted since open (anonymous ones included), ready = front ends finished,
+ *     in_flight = jobs waiting or running now, alive = voices holding a slot now, deferred_frees = q3tts_session_voice_free calls
+ *     that could not release at once, anonymous = voices made for ref_audio submits, frontend_ms_sum = the jobs' device time by
+ *     their lanes' events, frame_steps_beside = frame steps of the bursts during which at least one job was in flight (in flight
+ *     when the burst was launched, or launched while it ran), burst_ms_beside / burst_ms_alone = the loop thread's time from
+ *     launching a burst to seeing it finished, summed over those bursts / over all the others.
+ * Lifetime: a ready session-made voice is an ordinary voice of the handle. After q3tts_session_close it may be passed to
+ * q3tts_generate_voices, q3tts_generate_queued_voices, a later session and q3tts_voice_free; q3tts_model_free releases what is
+ * left. Close with drain finishes the accepted jobs. Close without drain lets launched jobs finish (they are short) and abandons
+ * the others: such a voice is refused wherever a voice is named (INVALID_INPUT) and still has to be freed. q3tts_voice_create /
+ * _free stay refused while a session is open. */
+typedef struct {
+    q3tts_session_opts base;
+    int32_t live_voices; /* front-end jobs in flight, 0..4; 0 = no live voices */
+    int32_t max_voices;  /* session-made voices alive at once; 0 = 4 * slots */
+} q3tts_session_opts_ex;
+typedef struct {
+    int64_t created, ready, in_flight, alive, deferred_frees, anonymous;
+    double frontend_ms_sum;
+    int64_t frame_steps_beside;
+    double burst_ms_beside, burst_ms_alone; /* host time of the bursts counted in frame_steps_beside / of all the others */
+} q3tts_session_voice_stats;
+q3tts_status q3tts_session_open_ex(q3tts_model* m, const q3tts_session_opts_ex* opts, const q3tts_sampling* sampling, q3tts_event_cb cb,
+                                   void* user, q3tts_session** out);
+q3tts_status q3tts_session_voice_create(q3tts_session* s, const float* ref_audio, int64_t n_ref_samples, int32_t sample_rate,
+                                        const int32_t* ref_text_ids, int32_t n_ref_text_ids, q3tts_voice** out);
+q3tts_status q3tts_session_voice_wait(q3tts_session* s, const q3tts_voice* v, int32_t timeout_ms /* <0: for ever */, int32_t* ready);
+q3tts_status q3tts_session_voice_free(q3tts_session* s, q3tts_voice* v);
+q3tts_status q3tts_session_get_voice_stats(const q3tts_session* s, q3tts_session_voice_stats* out);
 
 /* ---- Sample rates (new: the reference speaks and hears 24 kHz only) -----------------------------------------------------
  * One polyphase FIR serves the output side (q3tts_load_opts.output_sample_rate) and the input side (q3tts_voice_create_rate,

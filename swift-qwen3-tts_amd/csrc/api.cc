@@ -500,6 +500,16 @@ q3tts_status q3tts_generate_end(q3tts_model* m, q3tts_job* job, q3tts_result* re
 q3tts_status q3tts_session_open(q3tts_model* m, const q3tts_session_opts* opts, const q3tts_sampling* sampling, q3tts_event_cb cb,
                                 void* user, q3tts_session** out) {
     if (out) *out = nullptr;
+    if (!opts) return guarded(m, [&] { Q3_CHECK(false, 3, "Invalid input: null argument"); }, false);
+    q3tts_session_opts_ex ex;
+    std::memset(&ex, 0, sizeof(ex));
+    ex.base = *opts;  // live_voices 0: exactly the session without live voices
+    return q3tts_session_open_ex(m, &ex, sampling, cb, user, out);
+}
+
+q3tts_status q3tts_session_open_ex(q3tts_model* m, const q3tts_session_opts_ex* opts, const q3tts_sampling* sampling, q3tts_event_cb cb,
+                                   void* user, q3tts_session** out) {
+    if (out) *out = nullptr;
     return guarded(m, [&] {
         Q3_CHECK(m && opts && out, 3, "Invalid input: null argument");
         q3tts_sampling sp;
@@ -510,6 +520,34 @@ q3tts_status q3tts_session_open(q3tts_model* m, const q3tts_session_opts* opts, 
         m->session->m = m;
         *out = m->session.get();
     }, false);
+}
+
+q3tts_status q3tts_session_voice_create(q3tts_session* s, const float* ref_audio, int64_t n_ref_samples, int32_t sample_rate,
+                                        const int32_t* ref_text_ids, int32_t n_ref_text_ids, q3tts_voice** out) {
+    if (out) *out = nullptr;
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(out, 3, "Invalid input: null argument");
+        *out = reinterpret_cast<q3tts_voice*>(x.create_voice(ref_audio, n_ref_samples, sample_rate, ref_text_ids, n_ref_text_ids));
+    });
+}
+
+q3tts_status q3tts_session_voice_wait(q3tts_session* s, const q3tts_voice* v, int32_t timeout_ms, int32_t* ready) {
+    if (ready) *ready = 0;
+    return session_call(s, [&](q3::Session& x) { x.voice_wait(voice_of(v), timeout_ms, ready); });
+}
+
+q3tts_status q3tts_session_voice_free(q3tts_session* s, q3tts_voice* v) {
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(v, 3, "Invalid input: null argument");
+        x.free_voice(voice_of(v));
+    });
+}
+
+q3tts_status q3tts_session_get_voice_stats(const q3tts_session* s, q3tts_session_voice_stats* out) {
+    return session_call(s, [&](q3::Session& x) {
+        Q3_CHECK(out, 3, "Invalid input: null argument");
+        x.voice_stats(out);
+    });
 }
 
 q3tts_status q3tts_session_submit(q3tts_session* s, const q3tts_request* req, const q3tts_voice* voice, const q3tts_row_sampling* rs,

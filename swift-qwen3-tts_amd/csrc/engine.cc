@@ -121,6 +121,7 @@ Engine::~Engine() {
     if (qws_) (void)hipFree(qws_);
     codec_.reset();
     fe_.reset();
+    live_close();
     for (auto& L : fe_lanes_) {
         L.fe.reset();
         if (L.done) (void)hipEventDestroy(L.done);
@@ -1317,8 +1318,8 @@ std::unique_ptr<Voice> Engine::create_voice(const float* audio, int64_t n_sample
     v->ref_T = T;
     v->n_ref_samples = n_samples;
     v->ref_text_ids.assign(ref_text_ids, ref_text_ids + n_ref_text_ids);
-    v->codes_dev.grow(size_t(16) * T);
-    v->rows_dev.grow(size_t(1 + T) * H);
+    v->codes_dev = v->codes_own.grow(size_t(16) * T);
+    v->rows_dev = v->rows_own.grow(size_t(1 + T) * H);
     v->device_bytes = int64_t(size_t(16) * T * 4 + size_t(1 + T) * H * 2);
     Q3_HIP(hipEventRecord(ev_fe_[0], st_));
     fe_->encode(a, n_samples, v->codes_dev);

@@ -36,16 +36,66 @@ struct DebugOpts {
     int32_t* sampled = nullptr;         // host [n][frames][16]
 };
 
-// A reusable voice prompt (q3tts_voice): one reference clip and its transcript, encoded once (Engine::create_voice) and then
-// read-only, so that every job context and every lane may read it. The device buffers hold what prepare_clone_rows produces
-// for a waveform row; the host copies spare the requests that name the voice any device-to-host copy.
+// The device memory of the voices a session makes while it runs (q3tts_session_voice_create): `slots` places of `slot_bytes`
+// each, allocated when the session opens so that no boundary allocates or frees. A voice holds its place, and through the shared
+// pointer the pool, until the voice goes: voices outlive the session that made them.
+// `states`: one saved prefix state (PrefixCache) per slot for a streamed session, allocated once by the session's stream when the
+// loop starts (state_bytes is the codec stream's to say) and recycled with the slot: a session-made voice keeps at most one
+// state, in its slot's place, so the state memory of a session is bounded and nothing is allocated or freed for it at a boundary.
+struct VoicePool {
+    DevBuf<uint8_t> mem;
+    size_t slot_bytes = 0;
+    const int n_slots;
+    DevBuf<uint8_t> states;  // [n_slots][state_bytes], or empty
+    size_t state_bytes = 0;
+    std::mutex mu;
+    std::vector<int> free_slots;
+    VoicePool(int slots, size_t bytes) : slot_bytes(align_up(bytes, 256)), n_slots(slots) {
+        mem.grow(size_t(slots) * slot_bytes);
+        for (int i = slots; i-- > 0;) free_slots.push_back(i);
+    }
+    int take() {  // -1: none free
+        std::lock_guard<std::mutex> lk(mu);
+        if (free_slots.empty()) return -1;
+        const int s = free_slots.back();
+        free_slots.pop_back();
+        return s;
+    }
+    void give(int s) {
+        std::lock_guard<std::mutex> lk(mu);
+        free_slots.push_back(s);
+    }
+};
+
+// A reusable voice prompt (q3tts_voice): one reference clip and its transcript, encoded once (Engine::create_voice, or a
+// session's live lane) and then read-only, so that every job context and every lane may read it. The device buffers hold what
+// prepare_clone_rows produces for a waveform row; the host copies spare the requests that name the voice any device-to-host copy.
 struct Voice {
+    enum State { kReady = 0, kPending = 1, kAbandoned = 2 };
     const void* owner = nullptr;        // the EngineGroup it was created on
+    // Counts up over every voice of the process: what identifies a voice in PrefixCache beside its address, which a later voice
+    // may get again (the allocator's choice) as it may get the same pool slot.
+    uint64_t serial = next_serial();
+    // a session-made voice is a voice from its creation on; its device rows and host code copies are valid once kReady
+    std::atomic<int> state{kReady};
     int ref_T = 0;                      // reference frames
     int64_t n_ref_samples = 0;
     std::vector<int32_t> ref_text_ids;
-    DevBuf<int32_t> codes_dev;          // [16][ref_T]
-    DevBuf<uint16_t> rows_dev;          // [1 + ref_T][H] bf16: x-vector row (zeros without a speaker encoder), then the frames' embedding sums
+    int32_t* codes_dev = nullptr;       // [16][ref_T]
+    uint16_t* rows_dev = nullptr;       // [1 + ref_T][H] bf16: x-vector row (zeros without a speaker encoder), then the frames' embedding sums
+    DevBuf<int32_t> codes_own;          // what the two point into: buffers of its own (q3tts_voice_create) ...
+    DevBuf<uint16_t> rows_own;
+    std::shared_ptr<VoicePool> pool;    // ... or a place in a session's pool
+    int pool_slot = -1;
+    bool anonymous = false;             // made for one ref_audio ticket: no other ticket can restore a state of it, so none is saved
+    bool state_taken = false;           // (the session's loop thread) its slot's place in pool->states holds a state of it
+    ~Voice() {
+        if (pool && pool_slot >= 0) pool->give(pool_slot);
+    }
+    static uint64_t next_serial() {
+        static std::atomic<uint64_t> n{0};
+        return ++n;
+    }
     std::vector<int32_t> codes_host;    // [ref_T][16] frame-major, as the decoder reads them
     std::vector<int32_t> code0;         // [ref_T] first code row (valid-length count of the end trim)
     int64_t device_bytes = 0;
@@ -103,15 +153,22 @@ using MallocPtr = std::unique_ptr<T, FreeDeleter>;  // std::malloc'd host memory
 struct PrefixCache {
     struct Key {
         const Voice* voice = nullptr;
+        uint64_t serial = 0;  // Voice::serial (of() sets both)
         int chunk = 0, window = 0, lookahead = 0, path = 0;
         size_t bytes = 0;
         int hs = 0;  // the synthesis hop the state was made with (its state word is that hop's); 0: the handle's
+        void of(const Voice* v) {
+            voice = v;
+            serial = v ? v->serial : 0;
+        }
         bool operator==(const Key& o) const {
-            return hs == o.hs && voice == o.voice && chunk == o.chunk && window == o.window && lookahead == o.lookahead && path == o.path && bytes == o.bytes;
+            return hs == o.hs && voice == o.voice && serial == o.serial && chunk == o.chunk && window == o.window && lookahead == o.lookahead && path == o.path && bytes == o.bytes;
         }
     };
     struct Entry : Key {
-        DevBuf<uint8_t> blob;
+        DevBuf<uint8_t> own;               // the state's memory: its own ...
+        std::shared_ptr<VoicePool> pool;   // ... or its voice's place in a session's pool (kept alive with the entry)
+        uint8_t* blob = nullptr;
         hipEvent_t ready = nullptr;  // behind the save: a restore on another stream waits for it
         ~Entry() {
             if (ready) (void)hipEventDestroy(ready);
@@ -182,8 +239,25 @@ struct RequestSource {
     virtual bool has_appends() { return false; }
     virtual void take_appends(std::vector<TextAppend>& out) { out.clear(); }  // for running tickets, in arrival order
     // every running row waits for text: sleeps until a boundary has something to do (an append, a cancel, a request while can_admit, close)
-    virtual void wait_for_text(bool /*can_admit*/) {}
+    // timeout_ms >= 0: at the latest after that long (a voice job is in flight: its lane has to be polled)
+    virtual void wait_for_text(bool /*can_admit*/, int /*timeout_ms*/ = -1) {}
     virtual void text_progress(int /*starved_now*/, int /*starve_events*/) {}
+    // ---- live voices (a session opened with live_voices > 0) ----
+    struct VoiceJob {  // one clip's front end, as q3tts_session_voice_create copied it
+        int64_t id = -1;
+        Voice* voice = nullptr;    // its place is taken: ref_T, n_ref_samples (24 kHz) and the device pointers are set
+        std::vector<float> clip;   // at `rate`
+        int rate = 24000;
+    };
+    virtual bool live_voices() const { return false; }
+    virtual bool has_voice_work() { return false; }                               // jobs to launch or voices to release
+    virtual int take_voice_jobs(std::vector<VoiceJob>& out, int /*max*/) { out.clear(); return 0; }
+    virtual void voice_done(int64_t /*id*/, double /*frontend_ms*/) {}           // (the voice's host copies are filled)
+    // voices nothing uses any more: released here, on the loop thread; before(v) runs first for each (the stream disowns the
+    // states of v it has not published yet)
+    virtual VoicePool* voice_pool() { return nullptr; }  // where session-made voices and their saved states live
+    virtual void release_voices(const std::function<void(const Voice*)>& /*before*/) {}
+    virtual void burst_done(int /*frame_steps*/, double /*ms*/, bool /*beside a voice job*/) {}
 };
 
 // What the lanes of one slot loop share: the request source and what was fixed before the loop started.
@@ -302,6 +376,15 @@ class Engine {
     void debug_formant_rows(int mode, int hp, int ho, const int32_t* lens, int B, const float* x, int64_t x_stride, int hist, float* coef,
                             int64_t coef_stride, const float* state_in, float* state_out, float* y, int64_t y_stride, bool clamp);
     void debug_frontend_stage(const float* audio, int64_t n_samples, const char* stage, float* out, int64_t cap, int* T, int* C);
+
+    // ---- live voices (a session opened with live_voices > 0; engine_queue.cc) ----
+    // the host checks of create_voice (status 1 / 3), callable from any thread: nothing of the engine's state is written.
+    // Returns the clip's samples at 24 kHz
+    int64_t check_voice_clip(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids, int sample_rate) const;
+    // `lanes` front ends on non-blocking streams of their own, each with scratch, device buffers and pinned staging for a clip of
+    // max_ref_frames frames at any supported rate; the resamplers' tables. Before the session's loop starts / behind its end
+    void live_open(int lanes, int max_ref_frames);
+    void live_close();
 
     std::vector<std::string> speakers;  // sorted (Qwen3.swift:965-971)
     const CodecRunner* codec_runner() const { return codec_.get(); }  // nullptr: the checkpoint has no codec decoder
@@ -490,6 +573,23 @@ class Engine {
         DevBuf<float> spk;
     };
     std::vector<FeLane> fe_lanes_;
+    // A live-voice lane: FeLane plus what lets create_voice's sequence run on it without an allocation or a wait
+    struct LiveLane {
+        FeLane fe;
+        hipEvent_t t0 = nullptr, t1 = nullptr;  // around the front end's kernels (timed)
+        DevBuf<float> in, a24;                  // the clip at its own rate / at 24 kHz
+        DevBuf<int32_t> len;
+        PinnedBuf<uint8_t> stage;               // the clip, its length word, the codes read back
+        size_t stage_codes = 0, stage_len = 0;  // byte offsets in stage
+        int64_t id = -1;                        // the job in flight (-1: free)
+        Voice* voice = nullptr;
+    };
+    std::vector<LiveLane> live_lanes_;
+    int64_t live_max_in_ = 0, live_max_24_ = 0;
+    int live_in_flight() const;
+    void live_launch(LiveLane& L, RequestSource::VoiceJob& job);
+    // lanes whose job has finished: the voice's host copies filled, src told; wait: every lane in flight, whatever it takes
+    void live_poll(RequestSource& src, bool wait);
     const float* upload_audio(const float* audio, int64_t n);
     // the polyphase filters this engine has been asked for, tables on the device (built on first use)
     struct ResamplerDev {
@@ -620,6 +720,7 @@ class EngineGroup {
     // or one already freed, is not `mine`
     Voice* create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids, int sample_rate = 24000);
     void free_voice(Voice* v);
+    Voice* adopt_voice(std::unique_ptr<Voice> v);  // a voice made elsewhere (a session's) joins the group's
     bool mine(const Voice* v) const;
     PrefixCache& prefix_cache() { return prefix_cache_; }
     // Two-deep pipeline (Engine::begin / end); the job id names the context and its slot. With more than one lane a job runs
@@ -631,7 +732,7 @@ class EngineGroup {
                          q3tts_result* results, const Voice* const* voices = nullptr);
     // q3tts_session_*: one session at a time; while it is open its loop thread owns the first context (api.cc refuses the
     // entry points that would use an engine). close_session joins the thread and returns the status the loop failed with (0: none)
-    Session* open_session(const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
+    Session* open_session(const q3tts_session_opts_ex& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
     Session* session() const { return session_.get(); }
     int close_session(bool drain);
     std::string last_error;
@@ -654,6 +755,7 @@ class EngineGroup {
     q3tts_load_opts opts_;
     std::mutex cb_mutex_;
     std::vector<std::unique_ptr<Engine>> lanes_;
+    mutable std::mutex voices_mu_;  // (a session's threads create, name and free voices side by side)
     std::vector<std::unique_ptr<Voice>> voices_;
     PrefixCache prefix_cache_;  // the voices' tail states for streamed requests; a voice's entries go with it (free_voice)
     void check_voices(const q3tts_request* reqs, int n, const Voice* const* voices) const;  // status 3 before any GPU work
@@ -674,7 +776,11 @@ class Session final : public RequestSource {
         ResolvedRequest rr;
         SamplingParams params{};
     };
-    Session(EngineGroup& g, Engine& lane, const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
+    struct ClipJob {  // a live voice's front-end job as the queue holds it
+        std::vector<float> clip;
+        int rate = 24000;
+    };
+    Session(EngineGroup& g, Engine& lane, const q3tts_session_opts_ex& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user);
     ~Session() override;  // closes without drain
     // every check of a queued request on the calling thread; throws Error (3: refused, 9: max_pending waiting, or what the loop failed with)
     void submit(const q3tts_request& r, const Voice* voice, const q3tts_row_sampling* rs, int64_t* ticket);
@@ -683,6 +789,12 @@ class Session final : public RequestSource {
     void append_text(int64_t ticket, const int32_t* ids, int32_t n, bool final);
     void text_stats(q3tts_session_text_stats* s) const { queue_.text_stats(s); }
     int cancel(int64_t ticket) { return queue_.cancel(ticket); }
+    // live voices (include/q3tts.h "Live voices"): any thread; each throws Error on a refusal, which changes nothing
+    Voice* create_voice(const float* audio, int64_t n_samples, int sample_rate, const int32_t* ref_text_ids, int n_ref_text_ids,
+                        bool anonymous = false);
+    void voice_wait(const Voice* v, int32_t timeout_ms, int32_t* ready);
+    void free_voice(const Voice* v, bool count = true);
+    void voice_stats(q3tts_session_voice_stats* s) const { queue_.voice_stats(s); }
     void wait(int64_t ticket, int32_t timeout_ms, q3tts_result* out, int32_t* ready);
     void stats(q3tts_session_stats* s) const { queue_.stats(s); }
     int close(bool drain);  // joins the loop thread; the status it failed with, or 0
@@ -701,18 +813,31 @@ class Session final : public RequestSource {
     bool open_text() const override { return true; }
     bool has_appends() override { return queue_.has_appends(); }
     void take_appends(std::vector<TextAppend>& out) override;
-    void wait_for_text(bool can_admit) override { queue_.wait_for_text(can_admit); }
+    void wait_for_text(bool can_admit, int timeout_ms = -1) override { queue_.wait_for_text(can_admit, timeout_ms); }
     void text_progress(int starved_now, int starve_events) override { queue_.text_progress(starved_now, starve_events); }
+    bool live_voices() const override { return live_voices_ > 0; }
+    VoicePool* voice_pool() override { return pool_.get(); }
+    bool has_voice_work() override { return queue_.has_voice_work(); }
+    int take_voice_jobs(std::vector<VoiceJob>& out, int max) override;
+    void voice_done(int64_t id, double frontend_ms) override { queue_.voice_done(id, frontend_ms); }
+    void release_voices(const std::function<void(const Voice*)>& before) override;
+    void burst_done(int frame_steps, double ms, bool beside) override { queue_.burst_done(frame_steps, ms, beside); }
 
   private:
     void loop();
+    int64_t voice_id(const Voice* v) const;  // -1: not a voice this session made (or released already)
+    void submit_checked(const q3tts_request& r, const Voice* voice, const q3tts_row_sampling* rs, int64_t* ticket);
     EngineGroup& g_;
     Engine& lane_;
-    const int slots_, max_ref_frames_;
+    const int slots_, max_ref_frames_, live_voices_, max_voices_;
+    std::shared_ptr<VoicePool> pool_;  // max_voices_ places; the voices keep it alive behind the session
+    mutable std::mutex vmu_;
+    std::unordered_map<const Voice*, int64_t> vids_;  // the voices this session made and has not released
+
     q3tts_sampling sp_;
     q3tts_event_cb cb_;
     void* user_;
-    SessionQueue<Item> queue_;
+    SessionQueue<Item, ClipJob> queue_;
     mutable std::mutex err_mu_;
     std::string error_;  // what the loop thread failed with
     std::thread thread_;

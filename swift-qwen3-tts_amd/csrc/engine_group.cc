@@ -118,24 +118,37 @@ void EngineGroup::run_lanes(int L, bool serial, F&& fn) {
 Voice* EngineGroup::create_voice(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids, int sample_rate) {
     std::unique_ptr<Voice> v = lane0().create_voice(audio, n_samples, ref_text_ids, n_ref_text_ids, sample_rate);
     timing = lanes_[0]->timing;
+    return adopt_voice(std::move(v));
+}
+
+Voice* EngineGroup::adopt_voice(std::unique_ptr<Voice> v) {
+    std::lock_guard<std::mutex> lk(voices_mu_);
     v->owner = this;
     voices_.push_back(std::move(v));
     return voices_.back().get();
 }
 
 bool EngineGroup::mine(const Voice* v) const {
+    std::lock_guard<std::mutex> lk(voices_mu_);
     for (const auto& p : voices_)
         if (p.get() == v) return true;
     return false;
 }
 
 void EngineGroup::free_voice(Voice* v) {
-    for (size_t i = 0; i < voices_.size(); ++i)
-        if (voices_[i].get() == v) {
-            prefix_cache_.drop(v);  // (no call is running: a saved state is read only inside a queued call)
-            voices_.erase(voices_.begin() + ptrdiff_t(i));
-            return;
-        }
+    std::unique_ptr<Voice> gone;
+    {
+        std::lock_guard<std::mutex> lk(voices_mu_);
+        for (size_t i = 0; i < voices_.size(); ++i)
+            if (voices_[i].get() == v) {
+                // (no call that reads the voice is running: a saved state is read only inside a queued call; a session releases a
+                // voice only when no ticket names it)
+                prefix_cache_.drop(v);
+                gone = std::move(voices_[i]);
+                voices_.erase(voices_.begin() + ptrdiff_t(i));
+                break;
+            }
+    }
 }
 
 void EngineGroup::check_voices(const q3tts_request* reqs, int n, const Voice* const* voices) const {
@@ -144,6 +157,8 @@ void EngineGroup::check_voices(const q3tts_request* reqs, int n, const Voice* co
         if (!voices[i]) continue;
         Q3_CHECK(mine(voices[i]), 3,
                  "Invalid input: the voice of request " + std::to_string(i) + " was not created on this model handle (or has been freed)");
+        Q3_CHECK(voices[i]->state.load(std::memory_order_acquire) == Voice::kReady, 3,
+                 "Invalid input: the voice of request " + std::to_string(i) + " was abandoned by a session closed without drain");
         Q3_CHECK(reqs[i].ref_audio == nullptr && reqs[i].ref_text_ids == nullptr, 3,
                  "Invalid input: request " + std::to_string(i) + " names a voice and carries ref_audio / ref_text_ids as well");
     }
@@ -307,10 +322,17 @@ static void free_one_result(q3tts_result* r) {
     r->codes = nullptr;
 }
 
-Session::Session(EngineGroup& g, Engine& lane, const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user)
-    : g_(g), lane_(lane), slots_(so.slots), max_ref_frames_(std::max(0, so.max_ref_frames)), sp_(sp), cb_(cb), user_(user),
-      queue_(so.max_pending, &free_one_result) {
+Session::Session(EngineGroup& g, Engine& lane, const q3tts_session_opts_ex& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user)
+    : g_(g), lane_(lane), slots_(so.base.slots), max_ref_frames_(std::max(0, so.base.max_ref_frames)), live_voices_(so.live_voices),
+      max_voices_(so.live_voices > 0 ? (so.max_voices > 0 ? so.max_voices : 4 * so.base.slots) : 0), sp_(sp), cb_(cb), user_(user),
+      queue_(so.base.max_pending, &free_one_result) {
     sp_.per_request = nullptr;  // (a submit brings its own overrides)
+    if (live_voices_ > 0) {  // everything a live voice needs on the device, now: no boundary allocates
+        const size_t H = size_t(g_.model().cfg.talker.hidden_size);
+        pool_ = std::make_shared<VoicePool>(max_voices_, align_up(size_t(64) * max_ref_frames_, 256) + 2 * H * (size_t(1) + max_ref_frames_));
+        lane_.live_open(live_voices_, max_ref_frames_);
+        queue_.enable_voices(live_voices_, max_voices_);
+    }
     thread_ = std::thread([this] { loop(); });
 }
 
@@ -357,9 +379,128 @@ void Session::loop() {
     }
 }
 
+int64_t Session::voice_id(const Voice* v) const {
+    std::lock_guard<std::mutex> lk(vmu_);
+    auto it = vids_.find(v);
+    return it == vids_.end() ? -1 : it->second;
+}
+
+Voice* Session::create_voice(const float* audio, int64_t n_samples, int sample_rate, const int32_t* ref_text_ids, int n_ref_text_ids,
+                             bool anonymous) {
+    Q3_CHECK(live_voices_ > 0, 3, "Invalid input: the session was opened without live_voices (q3tts_session_open_ex)");
+    const int64_t n24 = lane_.check_voice_clip(audio, n_samples, ref_text_ids, n_ref_text_ids, sample_rate);
+    const int T = lane_.encoded_frames(n24);
+    Q3_CHECK(T >= 1 && T <= max_ref_frames_, 3, "Invalid input: the clip is longer than the session's max_ref_frames");
+    const size_t H = size_t(g_.model().cfg.talker.hidden_size);
+    auto v = std::make_unique<Voice>();
+    v->state.store(Voice::kPending);
+    v->ref_T = T;
+    v->n_ref_samples = n24;
+    v->ref_text_ids.assign(ref_text_ids, ref_text_ids + n_ref_text_ids);
+    v->device_bytes = int64_t(size_t(16) * T * 4 + size_t(1 + T) * H * 2);
+    v->anonymous = anonymous;
+    ClipJob job;
+    job.clip.assign(audio, audio + n_samples);
+    job.rate = sample_rate;
+    // one creator at a time from here on: a call that is about to be refused for live_voices holds its slot where no other
+    // creator can miss it
+    std::unique_lock<std::mutex> lk(vmu_);
+    const int slot = pool_->take();
+    if (slot < 0) throw Error(Q3TTS_ERR_BUSY, "Session busy: max_voices voices are alive");
+    v->pool = pool_;
+    v->pool_slot = slot;
+    uint8_t* base = pool_->mem + size_t(slot) * pool_->slot_bytes;
+    v->codes_dev = reinterpret_cast<int32_t*>(base);
+    v->rows_dev = reinterpret_cast<uint16_t*>(base + align_up(size_t(64) * max_ref_frames_, 256));
+    int64_t id = -1;
+    const int st = queue_.submit_voice(std::move(job), v.get(), &id, anonymous);
+    if (st == Q3TTS_OK) {  // (vmu_ is held: a release on the loop thread finds the voice in vids_ and among the group's)
+        Voice* p = g_.adopt_voice(std::move(v));
+        vids_[p] = id;
+        return p;
+    }
+    v.reset();  // (never launched: its place goes back, still under vmu_)
+    lk.unlock();
+    if (st == Q3TTS_ERR_BUSY) throw Error(st, "Session busy: live_voices front-end jobs are in flight, or max_voices voices are alive");
+    const std::string why = error();
+    throw Error(st, why.empty() ? std::string("Invalid input: the session is closing") : why);
+}
+
+void Session::voice_wait(const Voice* v, int32_t timeout_ms, int32_t* ready) {
+    Q3_CHECK(!on_loop_thread(), 3, "Invalid input: q3tts_session_voice_wait inside an event callback would wait for the thread it runs on");
+    Q3_CHECK(v && ready, 3, "Invalid input: null argument");
+    const int64_t id = voice_id(v);
+    Q3_CHECK(id >= 0, 3, "Invalid input: not a voice of this session (or it has been released)");
+    const int st = queue_.voice_wait(id, timeout_ms, ready);
+    if (st == Q3TTS_ERR_CANCELLED) throw Error(st, "Cancelled: the voice's front end was abandoned");
+    Q3_CHECK(st == Q3TTS_OK, st, "Invalid input: the voice has been freed");
+}
+
+void Session::free_voice(const Voice* v, bool count) {
+    const int64_t id = voice_id(v);
+    Q3_CHECK(id >= 0, 3, "Invalid input: not a voice of this session (or it has been released)");
+    Q3_CHECK(queue_.free_voice(id, count) == Q3TTS_OK, 3, "Invalid input: the voice has been freed already");
+}
+
+int Session::take_voice_jobs(std::vector<VoiceJob>& out, int max) {
+    std::vector<SessionQueue<Item, ClipJob>::VoiceTake> jobs;
+    queue_.take_voice_jobs(jobs, max);
+    out.clear();
+    for (auto& j : jobs) {
+        out.emplace_back();
+        out.back().id = j.id;
+        out.back().voice = static_cast<Voice*>(j.tag);
+        out.back().clip = std::move(j.job.clip);
+        out.back().rate = j.job.rate;
+    }
+    return int(out.size());
+}
+
+// on the loop thread, at a boundary: host memory and the pool's free list alone (a session-made voice's saved state lies in its
+// pool slot's place and is recycled with it)
+void Session::release_voices(const std::function<void(const Voice*)>& before) {
+    std::vector<std::pair<int64_t, void*>> rel;
+    queue_.take_voice_releases(rel);
+    for (auto& kv : rel) {
+        Voice* v = static_cast<Voice*>(kv.second);
+        if (before) before(v);
+        {
+            std::lock_guard<std::mutex> lk(vmu_);
+            vids_.erase(v);
+        }
+        g_.free_voice(v);
+        queue_.voice_released(kv.first);
+    }
+}
+
 void Session::submit(const q3tts_request& r, const Voice* voice, const q3tts_row_sampling* rs, int64_t* ticket) {
+    if (r.ref_audio != nullptr && live_voices_ > 0) {  // an anonymous voice, this ticket's alone: freed when the ticket is done
+        Q3_CHECK(!voice, 3, "Invalid input: the request names a voice and carries ref_audio / ref_text_ids as well");
+        const Voice* av = create_voice(r.ref_audio, r.n_ref_samples, kResampleNative, r.ref_text_ids, r.n_ref_text_ids, true);
+        q3tts_request named = r;
+        named.ref_audio = nullptr;
+        named.n_ref_samples = 0;
+        named.ref_text_ids = nullptr;
+        named.n_ref_text_ids = 0;
+        try {
+            submit_checked(named, av, rs, ticket);
+        } catch (...) {
+            free_voice(av, false);
+            throw;
+        }
+        free_voice(av, false);
+        return;
+    }
+    submit_checked(r, voice, rs, ticket);
+}
+
+void Session::submit_checked(const q3tts_request& r, const Voice* voice, const q3tts_row_sampling* rs, int64_t* ticket) {
+    int64_t vid = -1;
     if (voice) {
         Q3_CHECK(g_.mine(voice), 3, "Invalid input: the voice was not created on this model handle (or has been freed)");
+        vid = voice_id(voice);
+        Q3_CHECK(vid >= 0 || voice->state.load(std::memory_order_acquire) == Voice::kReady, 3,
+                 "Invalid input: the voice was abandoned by a session closed without drain");
         Q3_CHECK(r.ref_audio == nullptr && r.ref_text_ids == nullptr, 3,
                  "Invalid input: the request names a voice and carries ref_audio / ref_text_ids as well");
         Q3_CHECK(voice->ref_T <= max_ref_frames_, 3,
@@ -374,10 +515,11 @@ void Session::submit(const q3tts_request& r, const Voice* voice, const q3tts_row
     Item it;
     it.rr = lane_.check_queued(r, sp_, voice);
     it.params = fold_sampling(one, 0, 0u);  // (a queued slot keys on its ticket, not on row0)
-    const int st = queue_.submit(std::move(it), ticket);
+    const int st = queue_.submit(std::move(it), ticket, false, 0, 0, vid);
     if (st == Q3TTS_ERR_BUSY) throw Error(st, "Session busy: max_pending requests are already waiting");
     if (st == Q3TTS_OK) return;
     const std::string why = error();
+    if (vid >= 0 && why.empty()) throw Error(st, "Invalid input: the voice has been freed or abandoned (or the session is closing)");
     throw Error(st, why.empty() ? std::string("Invalid input: the session is closing or has run out of tickets") : why);
 }
 
@@ -412,7 +554,7 @@ void Session::append_text(int64_t ticket, const int32_t* ids, int32_t n, bool fi
 }
 
 void Session::take_appends(std::vector<TextAppend>& out) {
-    std::vector<SessionQueue<Item>::TextMsg> msgs;
+    std::vector<SessionQueue<Item, ClipJob>::TextMsg> msgs;
     queue_.take_appends(msgs);
     out.clear();
     for (auto& m : msgs) {
@@ -434,13 +576,25 @@ int Session::close(bool drain) {
     Q3_CHECK(!on_loop_thread(), 3, "Invalid input: q3tts_session_close inside an event callback would join the thread it runs on");
     queue_.close(drain);
     if (thread_.joinable()) thread_.join();
+    if (live_voices_ > 0) {  // behind the loop: the lanes go, and what the queue still knows of the voices is settled
+        lane_.live_close();
+        std::vector<SessionQueue<Item, ClipJob>::VoiceLeft> left;
+        queue_.retire_voices(left);
+        for (auto& l : left) {
+            Voice* v = static_cast<Voice*>(l.tag);
+            if (l.freed) g_.free_voice(v);
+            else v->state.store(l.state == int(SessionQueue<Item, ClipJob>::VoiceReady) ? Voice::kReady : Voice::kAbandoned);
+        }
+        std::lock_guard<std::mutex> lk(vmu_);
+        vids_.clear();
+    }
     return queue_.failed();
 }
 
 bool Session::take(QueueItem& out) {
     int64_t t = -1;
     Item it;
-    SessionQueue<Item>::TextTake text;
+    SessionQueue<Item, ClipJob>::TextTake text;
     if (!queue_.take(&t, &it, &text)) return false;
     if (text.open) {  // what was appended while it waited is part of its text; closed already: the ordinary request it now is
         it.rr.text_ids.insert(it.rr.text_ids.end(), text.early.begin(), text.early.end());
@@ -462,14 +616,22 @@ void Session::take_cancels(std::vector<int>& out) {
     out.assign(t.begin(), t.end());
 }
 
-Session* EngineGroup::open_session(const q3tts_session_opts& so, const q3tts_sampling& sp, q3tts_event_cb cb, void* user) {
+Session* EngineGroup::open_session(const q3tts_session_opts_ex& sx, const q3tts_sampling& sp, q3tts_event_cb cb, void* user) {
+    const q3tts_session_opts& so = sx.base;
     Q3_CHECK(!session_, 3, "Invalid input: a session is already open on this model handle");
     Q3_CHECK(lanes_.size() == 1, 3, "Invalid input: q3tts_session_open is not supported with n_streams > 1");
     Q3_CHECK(so.max_pending >= 0 && so.max_ref_frames >= 0, 3, "Invalid input: max_pending / max_ref_frames must not be negative");
+    Q3_CHECK(sx.live_voices >= 0 && sx.live_voices <= 4, 3, "Invalid input: live_voices must be between 0 and 4");
+    Q3_CHECK(sx.max_voices >= 0 && sx.max_voices <= 65536, 3, "Invalid input: max_voices must be between 0 and 65536");
+    if (sx.live_voices > 0) {
+        Q3_CHECK(so.max_ref_frames > 0, 3, "Invalid input: live_voices needs max_ref_frames > 0 (it bounds a clip)");
+        Q3_CHECK(model_->has_codec_encoder, 1,
+                 "Model not initialized: live voices require the speech tokenizer encoder. Make sure to load a model with encoder weights.");
+    }
     check_queue_open(so.slots, sp);
     if (sp.audio_chunk_frames > 0) lanes_[0]->check_stream_chunk(sp.audio_chunk_frames);
     lanes_[0]->drain();
-    session_ = std::make_unique<Session>(*this, *lanes_[0], so, sp, cb, user);
+    session_ = std::make_unique<Session>(*this, *lanes_[0], sx, sp, cb, user);
     return session_.get();
 }
 

@@ -1,5 +1,6 @@
 // engine_queue.cc -- continuous batching (q3tts_generate_queued, q3tts_session_*): the slot loop. See engine.h.
 #include "engine_stream.h"
+#include "frontend.h"
 
 namespace q3 {
 
@@ -280,6 +281,13 @@ struct Engine::QueueRun {
     void loop();
     q3tts_timing finish();
 
+    const bool live_voices;  // (a session with live voices) front ends run on the engine's live lanes beside the slot loop
+    std::vector<RequestSource::VoiceJob> vjobs;
+    int burst_steps = 0;  // the burst in flight: its frame steps, its launch time, whether a voice job ran beside it
+    bool burst_beside = false;
+    double burst_t0 = 0;
+    void voices_boundary();
+    void launch_voice_jobs();
     void forget_settled();
     void apply_cancels();
     int admit_boundary();
@@ -334,6 +342,12 @@ struct Engine::QueueRun::Audio {
         scodes.grow(size_t(S) * stride * 16);
         if (r.q.prefix_cache) add_flags();
         open();
+        // a session with live voices: the place of every pool slot's saved state, once, before the loop's first boundary
+        VoicePool* pool = r.q.prefix_cache ? r.q.src->voice_pool() : nullptr;
+        if (pool && pool->state_bytes == 0 && e.codec_->stream_state_bytes() > 0) {
+            pool->state_bytes = align_up(e.codec_->stream_state_bytes(), 256);
+            pool->states.grow(size_t(pool->n_slots) * pool->state_bytes);
+        }
     }
     void open() {
         ss.reset();
@@ -370,6 +384,12 @@ struct Engine::QueueRun::Audio {
     }
     void redo_held(std::unordered_map<int, SlotStream::Out>& outs);
     void redo_held_and_reopen();
+    // a voice is being released: a state of it whose save has not settled yet must never be published -- the next voice may get
+    // this one's address
+    void drop_voice(const Voice* v) {
+        for (PendingState& p : pending)
+            if (p.entry->voice == v) p.entry->of(nullptr);
+    }
 };
 
 // saved states whose save has run: into the cache, unless the prefix left the fp16 range
@@ -385,7 +405,7 @@ void Engine::QueueRun::Audio::settle(bool wait) {
             }
             Q3_HIP(pq);
         }
-        if (*pending[i].flag == 0) r.q.prefix_cache->publish(pending[i].entry);
+        if (*pending[i].flag == 0 && pending[i].entry->voice) r.q.prefix_cache->publish(pending[i].entry);  // (voice gone: drop_voice)
         free_flags.push_back(pending[i].flag);
         pending.erase(pending.begin() + ptrdiff_t(i));
     }
@@ -416,13 +436,13 @@ void Engine::QueueRun::Audio::admit_rows(const std::vector<int>& fresh) {
     }
     // the voices' reference frames to the front of their slots' code rows: behind ev_pushed where the row had an occupant
     if (any_ref) ss->stage_prefixes(ref.data(), n_ref.data(), e.codes_, e.Fcap_, scodes, stride, e.st_);
-    PrefixCache::Key key{nullptr, r.sp.audio_chunk_frames, r.sp.audio_window_frames, std::max(0, r.sp.audio_lookahead_frames),
+    PrefixCache::Key key{nullptr, 0, r.sp.audio_chunk_frames, r.sp.audio_window_frames, std::max(0, r.sp.audio_lookahead_frames),
                          e.codec_->stream_path(), e.codec_->stream_state_bytes()};
     std::vector<int> primed;
     for (int s : fresh) {
         const int req = r.sl[size_t(s)].req, R = n_ref[size_t(s)];
         const ResolvedRequest& rq = r.live.at(req).rr;
-        key.voice = rq.voice;
+        key.of(rq.voice);
         key.hs = rq.hs;  // (a state is valid for the hop it was made with: keyed, so a voice has one per hop in use)
         std::shared_ptr<PrefixCache::Entry> hit = R > 0 && r.q.prefix_cache ? r.q.prefix_cache->find(key) : nullptr;
         if (hit) {
@@ -449,11 +469,22 @@ void Engine::QueueRun::Audio::save_states(const std::vector<int>& primed, Prefix
     for (int s : primed) {
         Q3_CHECK(!e.codec_->stream_in_prefix(s), 7, "internal error: a reference prefix was left undecoded at its admission");
         if (!r.q.prefix_cache || key.bytes == 0) continue;
+        const Voice* vc = r.live.at(r.sl[size_t(s)].req).rr.voice;
+        // A session-made voice keeps one state, in its pool slot's place (no allocation here, and none to free when the voice
+        // goes); an anonymous one none, since no other ticket can name it. Every further admission of such a voice primes again.
+        const bool pooled = vc->pool && vc->pool_slot >= 0 && vc->pool.get() == r.q.src->voice_pool();
+        if (pooled && (vc->anonymous || vc->state_taken || key.bytes > vc->pool->state_bytes)) continue;
         auto n = std::make_shared<PrefixCache::Entry>();
-        key.voice = r.live.at(r.sl[size_t(s)].req).rr.voice;
+        key.of(vc);
         key.hs = r.live.at(r.sl[size_t(s)].req).rr.hs;
         static_cast<PrefixCache::Key&>(*n) = key;
-        n->blob.grow(key.bytes);
+        if (pooled) {
+            const_cast<Voice*>(vc)->state_taken = true;  // (this thread alone reads and writes it)
+            n->pool = vc->pool;
+            n->blob = vc->pool->states + size_t(vc->pool_slot) * vc->pool->state_bytes;
+        } else {
+            n->blob = n->own.grow(key.bytes);
+        }
         Q3_HIP(hipEventCreateWithFlags(&n->ready, hipEventDisableTiming));
         if (free_flags.empty()) add_flags();  // (settle(false) returned what it could)
         int32_t* flag = free_flags.back();
@@ -538,7 +569,7 @@ Engine::QueueRun::QueueRun(Engine& eng, QueueShared& shared, int slots, const q3
                            double t0)
     : e(eng), q(shared), S(slots), sp(sampling), cb(cb_), user(user_), t_call(t0), open_text(shared.src->open_text()),
       up(eng.codec_->upsample()), burst_frames(std::max(1, eng.max_inflight_frames / 2)), keys(eng, open_text), sl(size_t(slots)),
-      h_nframes(size_t(slots), 0), h_fin(size_t(slots), 0), h_starved(size_t(slots), 0) {
+      h_nframes(size_t(slots), 0), h_fin(size_t(slots), 0), h_starved(size_t(slots), 0), live_voices(shared.src->live_voices()) {
     if (open_text) {
         Q3_HIP(hipMemsetAsync(e.text_open_, 0, size_t(S), e.st_));
         Q3_HIP(hipMemsetAsync(e.starved_, 0, size_t(S), e.st_));
@@ -692,6 +723,24 @@ int Engine::QueueRun::admit_boundary() {
 // nothing runs: the stream cannot be closed around rows that are still in it. false: the call is over.
 bool Engine::QueueRun::idle(bool all_starved) {
     if (!all_starved && !q.src->open_ended()) return false;
+    if (live_voices) {  // no row takes a frame step: waiting jobs start at once, and a job in flight is simply waited for
+        launch_voice_jobs();
+        if (e.live_in_flight() > 0) {
+            if (!all_starved) {
+                e.live_poll(*q.src, true);
+                return true;
+            }
+            // rows are waiting for text: their appends, cancels and landed chunks must not wait for a lane, so the lanes are
+            // polled at boundaries a millisecond apart while a job is in flight (no frame step is taken for it)
+            drain_decodes();
+            if (audio) audio->take_all();
+            if (!settled.empty()) return true;
+            bool room = false;
+            for (const QSlot& x : sl) room = room || x.req < 0;
+            q.src->wait_for_text(room, 1);
+            return true;
+        }
+    }
     drain_decodes();
     if (audio) {
         audio->take_all();
@@ -712,6 +761,11 @@ void Engine::QueueRun::launch_burst(int burst, int admitted) {
     }
     launched += burst;
     q.src->progress(burst, admitted);
+    if (live_voices) {  // (its end is seen in while_burst_runs)
+        burst_steps = burst;
+        burst_beside = e.live_in_flight() > 0;
+        burst_t0 = now_s();
+    }
     Q3_HIP(hipMemcpyAsync(h_nframes.data(), e.n_frames_, size_t(S) * 4, hipMemcpyDeviceToHost, e.st_));
     Q3_HIP(hipMemcpyAsync(h_fin.data(), e.finished_, size_t(S), hipMemcpyDeviceToHost, e.st_));
     if (open_text) Q3_HIP(hipMemcpyAsync(h_starved.data(), e.starved_, size_t(S), hipMemcpyDeviceToHost, e.st_));
@@ -720,6 +774,10 @@ void Engine::QueueRun::launch_burst(int burst, int admitted) {
 
 // while the burst runs: deliver the decode batch that has landed, start the next one
 void Engine::QueueRun::while_burst_runs() {
+    if (live_voices) {
+        launch_voice_jobs();
+        burst_beside = burst_beside || e.live_in_flight() > 0;  // (a job launched now runs beside this burst)
+    }
     if (dec >= 0) deliver(false);
     if (dec < 0 && !waiting.empty()) decode(true);
     if (audio) {  // chunks that have landed leave while the burst runs, without waiting for them
@@ -733,12 +791,36 @@ void Engine::QueueRun::while_burst_runs() {
         }
     }
     Q3_HIP(hipEventSynchronize(e.burst_ev_[0]));
+    if (live_voices) q.src->burst_done(burst_steps, (now_s() - burst_t0) * 1e3, burst_beside);
 }
 
 // the burst's flags on the host: rows that wait for text are no finished ones, and have taken fewer steps than were launched
 void Engine::QueueRun::read_back(int burst) {
     const StarveCount c = after_burst(sl, burst, h_nframes.data(), h_fin.data(), h_starved.data(), open_text);
     if (open_text) q.src->text_progress(c.starved_now, c.starve_events);
+}
+
+// Live voices at a boundary: the lanes' events are polled (never waited for), and the voices nothing uses any more give their
+// places back. Neither touches the device: no synchronisation, no allocation, no free.
+void Engine::QueueRun::voices_boundary() {
+    if (e.live_in_flight() > 0) e.live_poll(*q.src, false);
+    q.src->release_voices([this](const Voice* v) {
+        if (audio) audio->drop_voice(v);
+    });
+}
+
+// waiting front-end jobs onto the free lanes (while a burst runs, or at once when no row runs)
+void Engine::QueueRun::launch_voice_jobs() {
+    const int free_lanes = int(e.live_lanes_.size()) - e.live_in_flight();
+    if (free_lanes <= 0 || !q.src->has_voice_work()) return;
+    q.src->take_voice_jobs(vjobs, free_lanes);
+    for (RequestSource::VoiceJob& j : vjobs)
+        for (LiveLane& L : e.live_lanes_)
+            if (L.id < 0) {
+                e.live_launch(L, j);
+                break;
+            }
+    vjobs.clear();
 }
 
 // TOKEN events (generation order), retirement
@@ -774,6 +856,7 @@ void Engine::QueueRun::loop() {
     for (;;) {
         forget_settled();
         if (q.src->has_cancels()) apply_cancels();
+        if (live_voices) voices_boundary();  // in front of the admission: it sees the voices that have just become ready
         const int admitted = admit_boundary();
         // open-text requests: what has been appended since the last boundary, in front of the burst, in stream order on st_
         if (open_text && q.src->has_appends()) e.apply_text_appends(q, sl, live);
@@ -847,7 +930,155 @@ void Engine::run_queued(QueueShared& q, int S, const q3tts_sampling& sp, q3tts_e
     build_cp_proj_tables();
     QueueRun run(*this, q, S, sp, cb, user, t_call);  // keys set, frame graph, the upload above waited for, streamed: the stream opened
     run.loop();
+    if (run.live_voices) live_poll(*q.src, true);  // (a close without drain: the launched jobs finish)
     timing = run.finish();
+}
+
+// ------------------------------------------------------------------------------------------------
+// live voices: Engine::create_voice's sequence on a lane of its own, enqueued and polled by the slot loop
+// ------------------------------------------------------------------------------------------------
+int64_t Engine::check_voice_clip(const float* audio, int64_t n_samples, const int32_t* ref_text_ids, int n_ref_text_ids, int sample_rate) const {
+    const TalkerConfig& t = m_->cfg.talker;
+    if (sample_rate != kResampleNative)
+        Q3_CHECK(resample_pair_supported(sample_rate, kResampleNative), 3,
+                 "Invalid input: a voice's sample_rate must be 8000, 12000, 16000, 22050, 24000, 32000, 44100 or 48000");
+    check_reference(audio, n_samples, ref_text_ids, n_ref_text_ids);
+    Q3_CHECK(fe_ != nullptr, 1, "Model not initialized: Speech tokenizer encoder not available");
+    Q3_CHECK(m_->codec_enc.bins <= t.vocab_size && m_->codec_enc.bins <= t.cp.vocab_size, 3,
+             "Invalid input: encoder codebook larger than the codec embedding tables");
+    for (int i = 0; i < n_ref_text_ids; ++i)
+        Q3_CHECK(ref_text_ids[i] >= 0 && ref_text_ids[i] < t.text_vocab_size, 3, "Invalid input: reference text token id out of range");
+    int64_t n24 = n_samples;
+    if (sample_rate != kResampleNative) {
+        Q3_CHECK(n_samples <= (int64_t(1) << 28), 3, "Invalid input: resampling takes between 1 and 2^28 samples");
+        const int g = resample_detail::gcd(sample_rate, kResampleNative);
+        const int64_t L = kResampleNative / g, M = sample_rate / g;
+        n24 = (n_samples * L + M - 1) / M;
+    }
+    fe_->check_clip(n24);
+    return n24;
+}
+
+void Engine::live_open(int lanes, int max_ref_frames) {
+    Q3_HIP(hipSetDevice(m_->device));
+    Q3_CHECK(fe_ != nullptr && m_->has_codec_encoder, 1, "Model not initialized: Speech tokenizer encoder not available");
+    const int H = m_->cfg.talker.hidden_size;
+    // the longest clip whose encoding has max_ref_frames frames, and the longest one at another rate that resamples to it
+    int64_t n24 = 0;
+    for (int64_t step = int64_t(1) << 23; step > 0; step >>= 1)
+        if (n24 + step <= (int64_t(1) << 24) && fe_->encoded_frames(n24 + step) <= max_ref_frames) n24 += step;
+    Q3_CHECK(n24 >= 1, 3, "Invalid input: max_ref_frames admits no clip");
+    live_max_24_ = n24;
+    live_max_in_ = 2 * n24 + 8;  // (48 kHz: two input samples per 24 kHz sample)
+    for (int rate : {8000, 12000, 16000, 22050, 32000, 44100, 48000}) (void)resampler(rate, kResampleNative);  // tables on the device now
+    live_close();  // (lanes a failed open left behind)
+    live_lanes_.resize(size_t(lanes));
+    for (LiveLane& L : live_lanes_) {
+        Q3_HIP(hipStreamCreateWithFlags(&L.fe.st, hipStreamNonBlocking));
+        Q3_HIP(hipEventCreateWithFlags(&L.fe.done, hipEventDisableTiming));
+        Q3_HIP(hipEventCreate(&L.t0));
+        Q3_HIP(hipEventCreate(&L.t1));
+        L.fe.fe = std::make_unique<VoiceFrontEnd>(*m_, L.fe.st);
+        L.fe.fe->reserve(live_max_24_);
+        L.fe.spk.grow(size_t(H));
+        L.in.grow(size_t(live_max_in_));
+        L.a24.grow(size_t(live_max_24_));
+        L.len.grow(4);
+        L.stage_len = align_up(size_t(live_max_in_) * 4, 256);
+        L.stage_codes = L.stage_len + 256;
+        L.stage.grow(L.stage_codes + size_t(max_ref_frames) * 64);
+    }
+}
+
+void Engine::live_close() {
+    if (live_lanes_.empty()) return;
+    (void)hipSetDevice(m_->device);
+    for (LiveLane& L : live_lanes_) {
+        if (L.fe.st) (void)hipStreamSynchronize(L.fe.st);
+        if (L.fe.done) (void)hipEventDestroy(L.fe.done);
+        if (L.t0) (void)hipEventDestroy(L.t0);
+        if (L.t1) (void)hipEventDestroy(L.t1);
+        L.fe.fe.reset();
+        if (L.fe.st) (void)hipStreamDestroy(L.fe.st);
+    }
+    live_lanes_.clear();
+}
+
+int Engine::live_in_flight() const {
+    int n = 0;
+    for (const LiveLane& L : live_lanes_) n += L.id >= 0;
+    return n;
+}
+
+// Upload, the centred resample for a clip at another rate, encode, speaker embedding, f32 -> bf16, the reference frames'
+// embedding sums, the codes back to pinned memory, an event: everything enqueued on the lane's stream, nothing waited for.
+void Engine::live_launch(LiveLane& L, RequestSource::VoiceJob& job) {
+    const int H = m_->cfg.talker.hidden_size;
+    Voice& v = *job.voice;
+    const int64_t n_in = int64_t(job.clip.size()), n24 = v.n_ref_samples;
+    const int T = v.ref_T;
+    Q3_CHECK(n_in <= live_max_in_ && n24 <= live_max_24_ && size_t(T) * 64 <= L.stage.capacity() - L.stage_codes, 7,
+             "internal error: a live voice's clip beyond the lanes' reservation");
+    hipStream_t st = L.fe.st;
+    std::memcpy(L.stage, job.clip.data(), size_t(n_in) * 4);
+    job.clip = std::vector<float>();
+    Q3_HIP(hipMemcpyAsync(L.in, L.stage, size_t(n_in) * 4, hipMemcpyHostToDevice, st));
+    const float* a = L.in;
+    if (job.rate != kResampleNative) {
+        const ResamplerDev& r = resampler(job.rate, kResampleNative);  // (built by live_open)
+        int32_t* hl = reinterpret_cast<int32_t*>(L.stage + L.stage_len);
+        *hl = int32_t(n_in);
+        Q3_HIP(hipMemcpyAsync(L.len, hl, 4, hipMemcpyHostToDevice, st));
+        ResampleArgs ra{};
+        ra.x = L.in; ra.x_bstride = 0;
+        ra.y = L.a24; ra.y_bstride = 0;
+        ra.len = L.len; ra.len_mul = 1; ra.max_in = n_in;
+        ra.tab = r.tab; ra.L = r.plan.L; ra.M = r.plan.M; ra.K = r.plan.K;
+        ra.hist = 0; ra.centred = 1; ra.clamp = 0; ra.B = 1;
+        launch_resample(ra, st);
+        a = L.a24;
+    }
+    Q3_HIP(hipEventRecord(L.t0, st));
+    L.fe.fe->encode(a, n24, v.codes_dev);
+    if (m_->has_speaker_encoder) {
+        L.fe.fe->speaker_embedding(a, n24, L.fe.spk);
+        launch_f32_to_bf16(L.fe.spk, v.rows_dev, H, st);
+    } else {
+        Q3_HIP(hipMemsetAsync(v.rows_dev, 0, size_t(H) * 2, st));
+    }
+    launch_ref_embed_rows(v.codes_dev, T, 16, m_->codec_emb, m_->cp_emb_dev, H, v.rows_dev + size_t(H), H, st);
+    Q3_HIP(hipEventRecord(L.t1, st));
+    Q3_HIP(hipMemcpyAsync(L.stage + L.stage_codes, v.codes_dev, size_t(16) * T * 4, hipMemcpyDeviceToHost, st));
+    Q3_HIP(hipEventRecord(L.fe.done, st));
+    L.id = job.id;
+    L.voice = job.voice;
+}
+
+void Engine::live_poll(RequestSource& src, bool wait) {
+    for (LiveLane& L : live_lanes_) {
+        if (L.id < 0) continue;
+        if (wait) {
+            Q3_HIP(hipEventSynchronize(L.fe.done));
+        } else {
+            const hipError_t pq = hipEventQuery(L.fe.done);
+            if (pq == hipErrorNotReady) continue;
+            Q3_HIP(pq);
+        }
+        Voice& v = *L.voice;
+        const int T = v.ref_T;
+        const int32_t* rows = reinterpret_cast<const int32_t*>(L.stage + L.stage_codes);  // [16][T]
+        v.code0.assign(rows, rows + T);
+        v.codes_host.resize(size_t(T) * 16);
+        for (int f = 0; f < T; ++f)
+            for (int g = 0; g < 16; ++g) v.codes_host[size_t(f) * 16 + g] = rows[size_t(g) * T + f];
+        float ms = 0;
+        Q3_HIP(hipEventElapsedTime(&ms, L.t0, L.t1));
+        v.state.store(Voice::kReady, std::memory_order_release);  // from here on the voice is read-only: any context, any lane
+        const int64_t id = L.id;
+        L.id = -1;
+        L.voice = nullptr;
+        src.voice_done(id, double(ms));
+    }
 }
 
 }  // namespace q3

@@ -41,10 +41,12 @@ VoiceFrontEnd::VoiceFrontEnd(const Model& m, hipStream_t st) : m_(m), st_(st) {
 VoiceFrontEnd::~VoiceFrontEnd() {
     if (buf_) (void)hipFree(buf_);
     if (ones_dev_) (void)hipFree(ones_dev_);
+    if (stage_host_) (void)hipHostFree(stage_host_);
 }
 
 void VoiceFrontEnd::ensure(size_t bytes) {
     if (bytes <= buf_bytes_) return;
+    Q3_CHECK(!reserved_, 7, "internal error: a front-end pass beyond the reserved scratch");
     if (buf_) Q3_HIP(hipFree(buf_));
     buf_ = nullptr;
     buf_bytes_ = 0;
@@ -84,6 +86,86 @@ static void conv1(const ConvW& w, const float* x, int ldx, int T, float* out, in
                   int act = 0, int pre_act = 0, const float* res = nullptr, int ldr = 0, int shift = 0, int reflect = 0,
                   const float* x2 = nullptr, int ldx2 = 0) {
     convB(w, x, ldx, 0, T, 1, out, ldo, 0, st, one, act, pre_act, res, ldr, 0, shift, reflect, x2, ldx2);
+}
+
+// what encode_batch carves for B clips padded to n_samples (kept beside it: a pass that needs more than this fails in ensure())
+size_t VoiceFrontEnd::encode_bytes(int B, int64_t n_samples) const {
+    const CodecEncW& e = m_.codec_enc;
+    std::vector<int> Ts{int(n_samples)};
+    for (auto& L : e.layers) Ts.push_back(streamable_out_len(Ts.back(), 2 * L.ratio, L.ratio, 1));
+    const int Te = Ts.back(), Tq = streamable_out_len(Te, 2 * e.ds, e.ds, 1);
+    const int H = e.hidden, I = e.tlayers.empty() ? H : e.tlayers[0].fc1.N;
+    size_t pp = 0;
+    int C = e.init_C;
+    for (size_t i = 0; i < e.layers.size(); ++i) {
+        pp = std::max(pp, (size_t(Ts[i]) + e.layers[i].ratio) * C);
+        C = e.layers[i].down.N;
+    }
+    pp = std::max(pp, (size_t(Te) + e.ds) * std::max(C, H));
+    Carver cv;
+    cv.f32(pp * B);
+    cv.f32(pp * B);
+    cv.f32(size_t(Te) * H * B);
+    cv.f32(size_t(Te) * 3 * H * B);
+    cv.f32(size_t(Te) * H * B);
+    cv.f32(size_t(Te) * I * B);
+    cv.f32(size_t(Tq) * 2 * e.dim * B);
+    cv.f32(size_t(B) * (e.layers.size() + 2));
+    cv.f32(size_t(2) * B);
+    return cv.off;
+}
+
+size_t VoiceFrontEnd::speaker_bytes(int64_t n_samples) const {
+    const SpeakerEncW& s = m_.speaker;
+    const int P = int(n_samples) + s.n_fft, T = (P - s.n_fft) / s.hop + 1;
+    const int C = s.blocks[0].C, C4 = s.mfa.N, A = s.asp_tdnn.N, SE = s.blocks[0].se1.N;
+    Carver cv;
+    cv.f32(size_t(P));
+    cv.f32(size_t(T) * s.dft.N);
+    cv.f32(size_t(T) * s.n_mels);
+    cv.f32(size_t(T) * C);
+    cv.f32(size_t(T) * 3 * C);
+    cv.f32(size_t(T) * C);
+    cv.f32(size_t(T) * C);
+    cv.f32(size_t(4) * std::max({C, C4, SE}) + 64);
+    cv.f32(size_t(T) * C4);
+    cv.f32(size_t(T) * 3 * C4);
+    cv.f32(size_t(T) * A);
+    cv.f32(size_t(T) * C4);
+    cv.f32(size_t(2) * C4);
+    return cv.off;
+}
+
+void VoiceFrontEnd::reserve(int64_t n_samples) {
+    Q3_CHECK(n_samples >= 1 && n_samples <= (int64_t(1) << 24), 3, "Invalid input: reference audio must hold 1 .. 2^24 samples");
+    size_t bytes = 0;
+    if (m_.has_codec_encoder) bytes = std::max(bytes, encode_bytes(1, n_samples));
+    if (m_.has_speaker_encoder) bytes = std::max(bytes, speaker_bytes(n_samples));
+    reserved_ = false;
+    ensure(bytes);
+    if (!stage_host_) {
+        void* p = nullptr;
+        Q3_HIP(hipHostMalloc(&p, (m_.codec_enc.layers.size() + 2) * 4 + 16, hipHostMallocDefault));
+        stage_host_ = static_cast<uint8_t*>(p);
+    }
+    reserved_ = true;
+}
+
+void VoiceFrontEnd::check_clip(int64_t n_samples) const {
+    Q3_CHECK(n_samples >= 1 && n_samples <= (int64_t(1) << 24), 3, "Invalid input: reference audio must hold 1 .. 2^24 samples");
+    if (m_.has_codec_encoder) {
+        const CodecEncW& e = m_.codec_enc;
+        int T = int(n_samples);
+        for (auto& L : e.layers) T = streamable_out_len(T, 2 * L.ratio, L.ratio, 1);
+        Q3_CHECK(T <= e.max_T, 3, "Invalid input: reference audio longer than the encoder's max_position_embeddings");
+    }
+    if (m_.has_speaker_encoder) {
+        const SpeakerEncW& s = m_.speaker;
+        const int T = int(n_samples) / s.hop + 1;
+        int max_pad = (s.b0.K - 1) * s.b0.dil / 2;
+        for (auto& B : s.blocks) max_pad = std::max(max_pad, (B.res[0].K - 1) * B.res[0].dil / 2);
+        Q3_CHECK(T > max_pad, 3, "Invalid input: reference audio too short for the speaker encoder");
+    }
 }
 
 int VoiceFrontEnd::encode(const float* audio_dev, int64_t n_samples, int32_t* codes_dev, StageCapture* cap) {
@@ -157,9 +239,18 @@ void VoiceFrontEnd::encode_batch(const float* audio_dev, int B, int64_t n_sample
         }
         valid[size_t(NS - 1) * B + b] = streamable_out_len(v, 2 * e.ds, e.ds, 1);
     }
-    Q3_HIP(hipMemcpyAsync(valid_dev, valid.data(), valid.size() * 4, hipMemcpyHostToDevice, st_));
-    Q3_HIP(hipMemcpyAsync(off_dev, code_off, size_t(B) * 8, hipMemcpyHostToDevice, st_));
-    Q3_HIP(hipStreamSynchronize(st_));  // caller memory
+    if (reserved_ && B == 1) {  // through this object's pinned words: nothing of the caller's is read behind the return
+        int32_t* hv = reinterpret_cast<int32_t*>(stage_host_);
+        int64_t* ho = reinterpret_cast<int64_t*>(stage_host_ + align_up(size_t(NS) * 4, 8));
+        std::copy(valid.begin(), valid.end(), hv);
+        *ho = code_off[0];
+        Q3_HIP(hipMemcpyAsync(valid_dev, hv, valid.size() * 4, hipMemcpyHostToDevice, st_));
+        Q3_HIP(hipMemcpyAsync(off_dev, ho, 8, hipMemcpyHostToDevice, st_));
+    } else {
+        Q3_HIP(hipMemcpyAsync(valid_dev, valid.data(), valid.size() * 4, hipMemcpyHostToDevice, st_));
+        Q3_HIP(hipMemcpyAsync(off_dev, code_off, size_t(B) * 8, hipMemcpyHostToDevice, st_));
+        Q3_HIP(hipStreamSynchronize(st_));  // caller memory
+    }
     const int64_t bs = int64_t(pp);     // clip stride of the two big buffers, in floats
     // rows behind each clip's own end, up to the whole stride group the next strided conv reads
     auto zero_tail = [&](float* base, int stage, int Tpad, int C) { launch_mask_tail(base, bs, valid_dev + size_t(stage) * B, Tpad, C, B, st_); };

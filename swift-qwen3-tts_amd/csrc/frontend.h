@@ -32,6 +32,14 @@ class VoiceFrontEnd {
                       int32_t* codes_dev, StageCapture* cap = nullptr);
     // audio_dev -> emb_dev [enc_dim] fp32
     void speaker_embedding(const float* audio_dev, int64_t n_samples, float* emb_dev, StageCapture* cap = nullptr);
+    // The host checks encode() and speaker_embedding() make for a clip of n_samples (they throw what those would), without a launch:
+    // a caller that enqueues the front end on another thread refuses the clip on its own.
+    void check_clip(int64_t n_samples) const;
+    // A front end that runs beside other work (a session's live voices): the scratch for one clip of up to n_samples is allocated
+    // now, and from here on a one-clip encode() or a speaker_embedding() of such a clip neither reallocates (a larger clip is an
+    // internal error, not a reallocation) nor waits for the stream: the per-call arrays go through pinned memory this object
+    // owns, so the caller must not start a second pass before the first one has finished on the device.
+    void reserve(int64_t n_samples);
 
   private:
     const Model& m_;
@@ -39,6 +47,10 @@ class VoiceFrontEnd {
     uint8_t* buf_ = nullptr;
     size_t buf_bytes_ = 0;
     int32_t* ones_dev_ = nullptr;  // frames[b] = 1: conv_gemm addresses rows as frames[b] * ppf
+    bool reserved_ = false;
+    uint8_t* stage_host_ = nullptr;  // reserve(): pinned [stages + 2] int32 lengths, then one int64 offset
+    size_t encode_bytes(int B, int64_t n_samples) const;
+    size_t speaker_bytes(int64_t n_samples) const;
     void ensure(size_t bytes);
     void capture(StageCapture* cap, const char* name, const float* t, int T, int C, int ld);
 };

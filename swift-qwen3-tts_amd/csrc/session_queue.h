@@ -11,6 +11,12 @@
 // one goes into the append mailbox, which the consumer empties at its boundaries (take_appends); text for a Done or claimed one is
 // dropped. The consumer sleeps in wait_for_text() while every row it runs waits for text; an append, a cancel, a submit it
 // could admit, or close wakes it.
+//
+// Live voices (enable_voices, q3tts_session_voice_*): a voice is Queued (its front-end job waits in the mailbox), Running (the
+// consumer has launched it), Ready or Abandoned (a close without drain, or a failure, came first). A ticket may name a voice in
+// any state but Abandoned; take() hands out only tickets whose voice is Ready and passes over the others, so they hold nobody
+// back. A voice counts the tickets that name it, pending and running; free_voice() only marks it, and the consumer is given it
+// for release (take_voice_releases) once nothing uses it and its job is neither waiting behind a use nor running.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -43,7 +49,7 @@
 
 namespace q3 {
 
-template <class Req>
+template <class Req, class VoiceJob = int>
 class SessionQueue {
   public:
     using FreeFn = void (*)(q3tts_result*);  // frees what a result points at (q3tts_result_free of one result)
@@ -60,16 +66,25 @@ class SessionQueue {
     // ---- producers ----
     // The t-th accepted submit gets ticket t. A refused one (BUSY, closing, failed) consumes no ticket.
     // open: an open-text ticket holding n_content content tokens so far, at most text_cap in all.
-    int submit(Req&& r, int64_t* ticket, bool open = false, int n_content = 0, int text_cap = 0) {
+    // voice >= 0: the ticket names that voice (submit_voice), which must be alive, not freed and not abandoned.
+    int submit(Req&& r, int64_t* ticket, bool open = false, int n_content = 0, int text_cap = 0, int64_t voice = -1) {
         {
             std::lock_guard<std::mutex> lk(mu_);
             if (failed_) return failed_;
             if (closing_) return Q3TTS_ERR_INVALID_INPUT;
             if (next_ > int64_t(INT32_MAX)) return Q3TTS_ERR_INVALID_INPUT;  // events carry the ticket as an int32
+            VoiceEntry* ve = nullptr;
+            if (voice >= 0) {
+                auto vi = voices_.find(voice);
+                if (vi == voices_.end() || vi->second.freed || vi->second.state == VoiceAbandoned) return Q3TTS_ERR_INVALID_INPUT;
+                ve = &vi->second;
+            }
             if (int(pending_.size()) >= max_pending_) return Q3TTS_ERR_BUSY;
             const int64_t t = next_++;
             Entry& e = entries_[t];
             e.req = std::move(r);
+            e.voice = voice;
+            if (ve) ++ve->use;
             e.open = open;
             e.n_content = n_content;
             e.text_cap = text_cap;
@@ -101,7 +116,7 @@ class SessionQueue {
                 marked = true;
             }
         }
-        if (marked) work_cv_.notify_all();  // (a consumer whose rows all wait for text sleeps on it)
+        if (marked || done) work_cv_.notify_all();  // (a consumer whose rows all wait for text sleeps on it; done: a voice may have lost its last use)
         if (done) done_cv_.notify_all();
         return Q3TTS_OK;
     }
@@ -210,10 +225,12 @@ class SessionQueue {
                         kv.second.cancel = true;
                         cancels_.push_back(kv.first);
                     }
+                abandon_voices_locked(false);  // jobs not launched yet; the launched ones finish (they are short)
             }
         }
         work_cv_.notify_all();
         done_cv_.notify_all();
+        voice_cv_.notify_all();
     }
     int failed() const {
         std::lock_guard<std::mutex> lk(mu_);
@@ -231,8 +248,10 @@ class SessionQueue {
     bool take(int64_t* ticket, Req* out, TextTake* text = nullptr) {
         std::lock_guard<std::mutex> lk(mu_);
         if (pending_.empty() || failed_) return false;
-        const int64_t t = pending_.front();
-        pending_.pop_front();
+        auto first = first_admissible_locked();  // (without voices: the front)
+        if (first == pending_.end()) return false;
+        const int64_t t = *first;
+        pending_.erase(first);
         Entry& e = entries_[t];
         e.state = Running;
         *out = std::move(e.req);
@@ -248,19 +267,25 @@ class SessionQueue {
         return true;
     }
     // nothing is running: sleeps until a request is pending (true) or the queue is closing with none left (false)
+    // (with live voices: a request that can be admitted, a voice job to launch or a voice to release)
     bool wait_for_work() {
         std::unique_lock<std::mutex> lk(mu_);
-        work_cv_.wait(lk, [&] { return !pending_.empty() || closing_ || failed_; });
-        return !pending_.empty() && !failed_;
+        auto work = [&] { return first_admissible_locked() != pending_.end() || !vjobs_.empty() || !vreleases_.empty(); };
+        work_cv_.wait(lk, [&] { return work() || closing_ || failed_; });
+        return work() && !failed_;
     }
     // Every running row waits for text: sleeps until there is something to do at a boundary -- an append or a cancel in the
     // mailboxes, a pending request while `can_admit`, or the first look after close() -- and never spins: each of these is consumed by
     // the boundary that follows.
-    void wait_for_text(bool can_admit) {
+    // timeout_ms >= 0: returns after that long at the latest (the consumer has something of its own to poll)
+    void wait_for_text(bool can_admit, int timeout_ms = -1) {
         std::unique_lock<std::mutex> lk(mu_);
-        work_cv_.wait(lk, [&] {
-            return !appends_.empty() || !cancels_.empty() || (can_admit && !pending_.empty()) || (closing_ && !close_seen_) || failed_;
-        });
+        auto due = [&] {
+            return !appends_.empty() || !cancels_.empty() || (can_admit && first_admissible_locked() != pending_.end()) ||
+                   !vjobs_.empty() || !vreleases_.empty() || (closing_ && !close_seen_) || failed_;
+        };
+        if (timeout_ms < 0) work_cv_.wait(lk, due);
+        else if (!work_cv_.wait_until(lk, Q3_SESSION_WAIT_CLOCK::now() + std::chrono::milliseconds(timeout_ms), due)) return;
         if (closing_) close_seen_ = true;
     }
     bool has_appends() const {
@@ -325,14 +350,191 @@ class SessionQueue {
                 if (e.state == Running) --running_;
                 finish_locked(e, status, true);
             }
+            abandon_voices_locked(true);
         }
         work_cv_.notify_all();
         done_cv_.notify_all();
+        voice_cv_.notify_all();
     }
     void progress(int frame_steps, int admissions) {
         std::lock_guard<std::mutex> lk(mu_);
         frame_steps_ += frame_steps;
         admissions_ += admissions;
+    }
+
+    // ---- live voices ----
+    enum VoiceState { VoiceQueued, VoiceRunning, VoiceReady, VoiceAbandoned };
+    struct VoiceTake {  // a job as the consumer takes it; tag: what submit_voice was given (the consumer's handle of the voice)
+        int64_t id = -1;
+        void* tag = nullptr;
+        VoiceJob job{};
+    };
+    // live: front-end jobs waiting or running at most; max_alive: voices not yet released at most. Before the first submit_voice.
+    void enable_voices(int live, int max_alive) {
+        std::lock_guard<std::mutex> lk(mu_);
+        live_voices_ = live;
+        max_voices_ = max_alive;
+    }
+    // A new voice and its front-end job. BUSY: live jobs are waiting or running, or max_alive voices are alive. anonymous: made
+    // for one ticket (counted apart).
+    int submit_voice(VoiceJob&& job, void* tag, int64_t* id, bool anonymous = false) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            if (failed_) return failed_;
+            if (closing_ || live_voices_ <= 0) return Q3TTS_ERR_INVALID_INPUT;
+            if (int(vjobs_.size()) + v_running_ >= live_voices_ || int(voices_.size()) >= max_voices_) return Q3TTS_ERR_BUSY;
+            const int64_t v = v_next_++;
+            VoiceEntry& e = voices_[v];
+            e.job = std::move(job);
+            e.tag = tag;
+            vjobs_.push_back(v);
+            ++v_created_;
+            if (anonymous) ++v_anonymous_;
+            if (id) *id = v;
+        }
+        work_cv_.notify_all();
+        return Q3TTS_OK;
+    }
+    // The voice can be named no more. It is released at once when nothing uses it (a job still waiting is dropped: the voice is
+    // Abandoned), otherwise when its last ticket completes and its job has finished; count: such a free is a deferred one.
+    int free_voice(int64_t id, bool count = true) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            auto it = voices_.find(id);
+            if (it == voices_.end() || it->second.freed) return Q3TTS_ERR_INVALID_INPUT;
+            VoiceEntry& e = it->second;
+            e.freed = true;
+            if (e.state == VoiceQueued && e.use == 0) {
+                vjobs_.erase(std::find(vjobs_.begin(), vjobs_.end(), id));
+                e.state = VoiceAbandoned;
+                e.job = VoiceJob();
+            }
+            if (!release_if_unused_locked(id, e) && count) ++v_deferred_;
+        }
+        work_cv_.notify_all();
+        voice_cv_.notify_all();
+        return Q3TTS_OK;
+    }
+    // *ready = 1: Ready. CANCELLED: Abandoned. *ready = 0 and OK: timeout. INVALID_INPUT: no such voice, or freed.
+    int voice_wait(int64_t id, int32_t timeout_ms, int32_t* ready) {
+        if (ready) *ready = 0;
+        std::unique_lock<std::mutex> lk(mu_);
+        auto settled = [&] {
+            auto it = voices_.find(id);
+            return it == voices_.end() || it->second.freed || it->second.state == VoiceReady || it->second.state == VoiceAbandoned;
+        };
+        if (voices_.find(id) == voices_.end()) return Q3TTS_ERR_INVALID_INPUT;
+        if (timeout_ms < 0) voice_cv_.wait(lk, settled);
+        else voice_cv_.wait_until(lk, Q3_SESSION_WAIT_CLOCK::now() + std::chrono::milliseconds(timeout_ms), settled);
+        auto it = voices_.find(id);
+        if (it == voices_.end() || it->second.freed) return Q3TTS_ERR_INVALID_INPUT;
+        if (it->second.state == VoiceAbandoned) return Q3TTS_ERR_CANCELLED;
+        if (it->second.state == VoiceReady && ready) *ready = 1;
+        return Q3TTS_OK;
+    }
+    int voice_state(int64_t id) const {  // -1: no such voice
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = voices_.find(id);
+        return it == voices_.end() ? -1 : int(it->second.state);
+    }
+    void voice_stats(q3tts_session_voice_stats* s) const {
+        std::lock_guard<std::mutex> lk(mu_);
+        std::memset(s, 0, sizeof(*s));
+        s->created = v_created_;
+        s->ready = v_ready_;
+        s->in_flight = int64_t(vjobs_.size()) + v_running_;
+        s->alive = int64_t(voices_.size());  // (a voice on its way out holds its place until the consumer's next boundary)
+        s->deferred_frees = v_deferred_;
+        s->anonymous = v_anonymous_;
+        s->frontend_ms_sum = fe_ms_sum_;
+        s->frame_steps_beside = steps_beside_;
+        s->burst_ms_beside = burst_ms_beside_;
+        s->burst_ms_alone = burst_ms_alone_;
+    }
+    // the consumer: up to `max` waiting jobs in arrival order (Running from here on)
+    int take_voice_jobs(std::vector<VoiceTake>& out, int max) {
+        std::lock_guard<std::mutex> lk(mu_);
+        out.clear();
+        while (int(out.size()) < max && !vjobs_.empty() && !failed_) {
+            const int64_t v = vjobs_.front();
+            vjobs_.pop_front();
+            VoiceEntry& e = voices_[v];
+            e.state = VoiceRunning;
+            ++v_running_;
+            out.emplace_back();
+            out.back().id = v;
+            out.back().tag = e.tag;
+            out.back().job = std::move(e.job);
+            e.job = VoiceJob();
+        }
+        return int(out.size());
+    }
+    bool has_voice_work() const {
+        std::lock_guard<std::mutex> lk(mu_);
+        return !vjobs_.empty() || !vreleases_.empty();
+    }
+    void voice_done(int64_t id, double frontend_ms) {  // the consumer: the job has finished, the voice is Ready
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            auto it = voices_.find(id);
+            if (it == voices_.end() || it->second.state != VoiceRunning) return;
+            it->second.state = VoiceReady;
+            --v_running_;
+            ++v_ready_;
+            fe_ms_sum_ += frontend_ms;
+            (void)release_if_unused_locked(id, it->second);
+        }
+        voice_cv_.notify_all();
+        work_cv_.notify_all();
+    }
+    // the consumer: voices to release now (each is handed out once); voice_released() forgets one and frees its place
+    void take_voice_releases(std::vector<std::pair<int64_t, void*>>& out) {
+        std::lock_guard<std::mutex> lk(mu_);
+        out.clear();
+        for (int64_t v : vreleases_) out.emplace_back(v, voices_[v].tag);
+        vreleases_.clear();
+    }
+    void voice_released(int64_t id) {
+        std::lock_guard<std::mutex> lk(mu_);
+        voices_.erase(id);
+    }
+    // a burst of n frame steps took the consumer `ms` from its launch to its end; beside: a voice job was in flight meanwhile
+    void burst_done(int n, double ms, bool beside) {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (beside) {
+            steps_beside_ += n;
+            burst_ms_beside_ += ms;
+        } else {
+            burst_ms_alone_ += ms;
+        }
+    }
+    // Behind the consumer's end: what the queue still knows of -- voices freed but not released (first) and voices never freed
+    // (state: their VoiceState) -- is the caller's from here on; pending tickets that could not run any more are cancelled.
+    struct VoiceLeft {
+        int64_t id = -1;
+        void* tag = nullptr;
+        int state = 0;
+        bool freed = false;
+    };
+    void retire_voices(std::vector<VoiceLeft>& out) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            for (int64_t t : pending_) finish_locked(entries_[t], Q3TTS_ERR_CANCELLED, true);
+            pending_.clear();
+            abandon_voices_locked(true);
+            out.clear();
+            for (auto& kv : voices_) {
+                out.emplace_back();
+                out.back().id = kv.first;
+                out.back().tag = kv.second.tag;
+                out.back().state = int(kv.second.state);
+                out.back().freed = kv.second.freed;
+            }
+            voices_.clear();
+            vreleases_.clear();
+        }
+        done_cv_.notify_all();
+        voice_cv_.notify_all();
     }
 
   private:
@@ -344,13 +546,59 @@ class SessionQueue {
         bool open = false;           // submitted as an open-text request
         int n_content = 0, text_cap = 0;
         std::vector<int32_t> early;  // content appended while Pending
+        int64_t voice = -1;          // the voice it names (counted in that voice's use until the ticket is Done)
         Req req{};
         q3tts_result res{};
     };
+    struct VoiceEntry {
+        VoiceState state = VoiceQueued;
+        bool freed = false, releasing = false;
+        int64_t use = 0;  // tickets that name it, Pending or Running
+        void* tag = nullptr;
+        VoiceJob job{};
+    };
+    // the first pending ticket whose voice, if it names one, is Ready
+    typename std::deque<int64_t>::iterator first_admissible_locked() {
+        if (voices_.empty()) return pending_.begin();
+        for (auto it = pending_.begin(); it != pending_.end(); ++it) {
+            const int64_t v = entries_[*it].voice;
+            if (v < 0) return it;
+            auto vi = voices_.find(v);
+            if (vi != voices_.end() && vi->second.state == VoiceReady) return it;
+        }
+        return pending_.end();
+    }
+    bool release_if_unused_locked(int64_t id, VoiceEntry& e) {
+        if (!e.freed || e.use > 0 || e.releasing || (e.state != VoiceReady && e.state != VoiceAbandoned)) return false;
+        e.releasing = true;
+        vreleases_.push_back(id);
+        return true;
+    }
+    // every waiting job is dropped; all: the launched ones count as lost too (the consumer has failed or ended)
+    void abandon_voices_locked(bool all) {
+        for (auto& kv : voices_) {
+            VoiceEntry& e = kv.second;
+            if (e.state == VoiceQueued || (all && e.state == VoiceRunning)) {
+                if (e.state == VoiceRunning) --v_running_;
+                e.state = VoiceAbandoned;
+                e.job = VoiceJob();
+                (void)release_if_unused_locked(kv.first, e);
+            }
+        }
+        vjobs_.clear();
+    }
     void finish_locked(Entry& e, int status, bool wipe) {  // wipe: the result carries nothing but the status
         e.state = Done;
         e.req = Req();
         e.early = std::vector<int32_t>();
+        if (e.voice >= 0) {  // (notified by the caller, with done_cv_: the consumer looks at its next boundary anyway)
+            auto vi = voices_.find(e.voice);
+            if (vi != voices_.end()) {
+                --vi->second.use;
+                (void)release_if_unused_locked(e.voice, vi->second);
+            }
+            e.voice = -1;
+        }
         if (wipe) {
             free_(&e.res);
             std::memset(&e.res, 0, sizeof(e.res));
@@ -361,7 +609,7 @@ class SessionQueue {
     }
 
     mutable std::mutex mu_;
-    std::condition_variable work_cv_, done_cv_;
+    std::condition_variable work_cv_, done_cv_, voice_cv_;
     const int max_pending_;
     const FreeFn free_;
     std::map<int64_t, Entry> entries_;  // every ticket that is not claimed yet
@@ -375,6 +623,13 @@ class SessionQueue {
     int64_t submitted_ = 0, running_ = 0, completed_ = 0, cancelled_ = 0, frame_steps_ = 0, admissions_ = 0;
     bool closing_ = false;
     int failed_ = 0;
+    // live voices
+    int live_voices_ = 0, max_voices_ = 0, v_running_ = 0;
+    std::map<int64_t, VoiceEntry> voices_;  // every voice that has not been released
+    std::deque<int64_t> vjobs_;             // Queued, in arrival order
+    std::deque<int64_t> vreleases_;
+    int64_t v_next_ = 0, v_created_ = 0, v_ready_ = 0, v_deferred_ = 0, v_anonymous_ = 0, steps_beside_ = 0;
+    double fe_ms_sum_ = 0, burst_ms_beside_ = 0, burst_ms_alone_ = 0;
 };
 
 }  // namespace q3

@@ -107,6 +107,16 @@ class SessionStats(C.Structure):  # q3tts_session_stats
                 ("cancelled", C.c_int64), ("frame_steps", C.c_int64), ("admissions", C.c_int64)]
 
 
+class SessionOptsEx(C.Structure):  # q3tts_session_opts_ex
+    _fields_ = [("base", SessionOpts), ("live_voices", C.c_int32), ("max_voices", C.c_int32)]
+
+
+class SessionVoiceStats(C.Structure):  # q3tts_session_voice_stats
+    _fields_ = [("created", C.c_int64), ("ready", C.c_int64), ("in_flight", C.c_int64), ("alive", C.c_int64),
+                ("deferred_frees", C.c_int64), ("anonymous", C.c_int64), ("frontend_ms_sum", C.c_double),
+                ("frame_steps_beside", C.c_int64), ("burst_ms_beside", C.c_double), ("burst_ms_alone", C.c_double)]
+
+
 class SessionTextStats(C.Structure):  # q3tts_session_text_stats
     _fields_ = [("open", C.c_int64), ("starved", C.c_int64), ("appended_tokens", C.c_int64), ("starve_events", C.c_int64)]
 
@@ -284,6 +294,12 @@ def lib() -> C.CDLL:
         L.q3tts_session_wait.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(Result), i32p]
         L.q3tts_session_get_stats.argtypes = [vp, C.POINTER(SessionStats)]
         L.q3tts_session_close.argtypes = [vp, C.c_int32]
+    if hasattr(L, "q3tts_session_open_ex"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
+        L.q3tts_session_open_ex.argtypes = [vp, C.POINTER(SessionOptsEx), C.POINTER(Sampling), EVENT_CB, vp, C.POINTER(vp)]
+        L.q3tts_session_voice_create.argtypes = [vp, f32p, C.c_int64, C.c_int32, i32p, C.c_int32, C.POINTER(vp)]
+        L.q3tts_session_voice_wait.argtypes = [vp, vp, C.c_int32, i32p]
+        L.q3tts_session_voice_free.argtypes = [vp, vp]
+        L.q3tts_session_get_voice_stats.argtypes = [vp, C.POINTER(SessionVoiceStats)]
     if hasattr(L, "q3tts_session_submit_open"):  # (absent from an older build loaded through Q3TTS_LIB for an A/B run)
         L.q3tts_session_submit_open.argtypes = [vp, C.POINTER(Request), C.POINTER(RowSampling), C.POINTER(C.c_int64)]
         L.q3tts_session_append_text.argtypes = [vp, C.c_int64, i32p, C.c_int32, C.c_int32]

@@ -95,14 +95,37 @@ class Voice:
     GenerationRequest.voice; it stays usable until close() (or the end of a `with` block), or until its model is closed.
     Closing a voice while a call that names it is running is an error of the caller."""
 
-    def __init__(self, model: "Qwen3TTSModel", handle: C.c_void_p):
+    def __init__(self, model: "Qwen3TTSModel", handle: C.c_void_p, session: Optional["Session"] = None):
         self._model, self._h = model, handle
+        self._session = session  # the session that made it (Session.create_voice): its free and its wait while it is open
         vi = L.VoiceInfo()
         model._check(model._lib.q3tts_voice_get_info(handle, C.byref(vi)))
         self.info = vi  # ref_frames, ref_text_tokens, n_ref_samples, device_bytes
 
+    def wait(self, timeout: Optional[float] = None) -> "Voice":
+        """A session-made voice: waits until its front end is done (q3tts_session_voice_wait). TimeoutError when `timeout`
+        seconds pass first; status 8 (Qwen3TTSError) when a close without drain abandoned it; status 3 once the session has
+        closed (there is nothing to wait on: every job it had accepted has finished or been abandoned). A voice of
+        Qwen3TTSModel.create_voice is ready from the start."""
+        sess = self._session
+        if not self._h:
+            raise Qwen3TTSError(3, "Invalid input: the voice has been closed")
+        if sess is None:
+            return self
+        if not sess._h:
+            raise Qwen3TTSError(3, "Invalid input: the session that made the voice has been closed")
+        ready = C.c_int32(0)
+        ms = -1 if timeout is None else max(0, int(round(timeout * 1000)))
+        self._model._check(self._model._lib.q3tts_session_voice_wait(sess._handle(), self._h, ms, C.byref(ready)))
+        if not ready.value:
+            raise TimeoutError("the voice was not ready after %s s" % (timeout,))
+        return self
+
     def close(self):
-        if self._h and self._model._h:  # (a closed model has released its voices already)
+        sess = self._session
+        if self._h and sess is not None and sess._h and self._model._h:  # while its session is open: the session's free
+            self._model._lib.q3tts_session_voice_free(sess._h, self._h)
+        elif self._h and self._model._h:  # (a closed model has released its voices already)
             self._model._lib.q3tts_voice_free(self._model._h, self._h)
         self._h = None
 
@@ -595,19 +618,25 @@ class Qwen3TTSModel:
                      on_event: Optional[Callable[[int, str, object], None]] = None, temperature: float = 0.9, top_k: int = 50,
                      top_p: float = 1.0, repetition_penalty: float = 1.05, seed: int = 0, force_frames: int = 0,
                      audio_chunk_frames: int = 0, audio_window_frames: int = 0, audio_lookahead_frames: int = 4, row_base: int = 0,
-                     audio_stream_reference: int = 0) -> "Session":
-        """q3tts_session_open: the slot loop of generate_queued on a thread of its own, with an open end. Requests are
+                     audio_stream_reference: int = 0, live_voices: int = 0, max_voices: int = 0) -> "Session":
+        """q3tts_session_open[_ex]: the slot loop of generate_queued on a thread of its own, with an open end. Requests are
         submitted, cancelled and collected one by one while it runs; ticket t's result is bit-identical to
         generate_batch([request], row_base=row_base + t) with the session's keywords and the request's own `sampling`.
         `on_event(ticket, kind, payload)` fires on the session's thread. While the session is open the model's other
         generating calls are refused (status 3); voices are created before it is opened, and `max_ref_frames` bounds the
-        references a submit may name."""
+        references a submit may name. With `live_voices` > 0 (front-end jobs in flight, at most 4) the session also makes
+        voices while it runs (Session.create_voice) and takes requests that carry `ref_audio`; `max_voices` bounds the
+        session-made voices alive at once (0: 4 * slots)."""
         s = self._sampling(temperature, top_k, top_p, repetition_penalty, seed, force_frames, audio_chunk_frames,
                            audio_window_frames, audio_lookahead_frames, row_base, audio_stream_reference=audio_stream_reference)
         o = L.SessionOpts(int(self.info.max_batch) if slots is None else int(slots), int(max_pending), int(max_ref_frames))
         cb = self._event_cb(on_event)
         h = C.c_void_p()
-        self._check(self._lib.q3tts_session_open(self._h, C.byref(o), C.byref(s), cb, None, C.byref(h)))
+        if int(live_voices) == 0 and int(max_voices) == 0:
+            self._check(self._lib.q3tts_session_open(self._h, C.byref(o), C.byref(s), cb, None, C.byref(h)))
+        else:
+            ox = L.SessionOptsEx(o, int(live_voices), int(max_voices))
+            self._check(self._lib.q3tts_session_open_ex(self._h, C.byref(ox), C.byref(s), cb, None, C.byref(h)))
         return Session(self, h, cb)
 
     def generate_batch_begin(self, reqs: Sequence[GenerationRequest], temperature: float = 0.9, top_k: int = 50,
@@ -1162,6 +1191,25 @@ class Session:
     def stats(self) -> L.SessionStats:
         s = L.SessionStats()
         self._model._check(self._model._lib.q3tts_session_get_stats(self._handle(), C.byref(s)))
+        return s
+
+    def create_voice(self, ref_audio: np.ndarray, ref_text_ids: Sequence[int], sample_rate: int = 24000) -> Voice:
+        """q3tts_session_voice_create on a session opened with live_voices > 0: the clip's front end runs beside the rows in
+        flight. Returns at once; the voice may be named by submit before it is ready (the request is admitted once it is),
+        Voice.wait() blocks until then. Any thread, also from inside `on_event`. Status 9 (Qwen3TTSError) when live_voices
+        jobs are in flight or max_voices voices are alive. After the session has closed the voice is an ordinary voice of
+        the model."""
+        m = self._model
+        ra = np.ascontiguousarray(np.asarray(ref_audio, np.float32).reshape(-1))
+        rt = np.ascontiguousarray(ref_text_ids, np.int32)
+        h = C.c_void_p()
+        m._check(m._lib.q3tts_session_voice_create(self._handle(), ra.ctypes.data_as(L.f32p), ra.size, int(sample_rate),
+                                                   rt.ctypes.data_as(L.i32p), rt.size, C.byref(h)))
+        return Voice(m, h, self)
+
+    def voice_stats(self) -> L.SessionVoiceStats:
+        s = L.SessionVoiceStats()
+        self._model._check(self._model._lib.q3tts_session_get_voice_stats(self._handle(), C.byref(s)))
         return s
 
     def close(self, drain: bool = True) -> None:

@@ -46,6 +46,18 @@ request arrives j / TOK_PER_S seconds after its first one, from a feeder thread.
   whole   q3tts_session_submit of the whole request once its last token has arrived -- what a caller can do without open text
 Printed per run: the time from a request's first token to its first AUDIO_CHUNK (--stream; its AUDIO otherwise), median, p95 and max,
 to its completion, the session's starve events, and whether the two ways agree bit for bit (they must: same tickets).
+--session --live-voices K --new-voice-every N (a Base checkpoint, e.g. --preset 1.7b-base; with --arrivals and --stream) serves the
+ragged workload as voice requests over 4 known clips, where every N-th arrival brings a clip nobody has seen. Two ways, alternating
+--repeat times:
+  live     a session opened with live_voices = K: the new clip goes to Session.create_voice at its arrival and its request names
+           the voice at once; the front end runs beside the rows in flight
+  before   what a session without live voices allows: the voices of ALL clips are created before the session opens, and that time
+           is counted in front (of the wall time, and of every new-clip request's time to first audio)
+Printed per run: frames/s, the time from a new clip's arrival to the first AUDIO_CHUNK of its request (its AUDIO without --stream),
+the session's frontend_ms_sum, the frame-step rate of the bursts during which at least one front-end job was in flight
+(frame_steps_beside / burst_ms_beside, the loop thread's own times) against the rate of the other bursts, and the time from
+create_voice to ready. Every result is checked bit for bit against the
+closed form, one q3tts_generate_queued_voices call over voices made by q3tts_voice_create.
 """
 from __future__ import annotations
 
@@ -305,6 +317,118 @@ def run_text_rate_bench(model, args, reqs, warm, sampling):
         print(f"run {rep} bit-identical codes + pcm, open text against whole submits: {same(res['open'], res['whole'])}", flush=True)
 
 
+def run_live_voices(model, args):
+    """--session --live-voices K --new-voice-every N: see the module's docstring."""
+    from qwen3tts import GenerationRequest, synth
+    n, every, known_n = args.requests, args.new_voice_every, 4
+    base = bench.build_requests(args.preset, 0, n, args.n_text, 0)
+    caps = np.random.default_rng(1234).integers(50, 401, size=n)
+    new_at = [i for i in range(n) if every > 0 and i % every == every - 1]
+    clip_of = {i: known_n + j for j, i in enumerate(new_at)}  # request -> its clip (the others: i % known_n)
+    n_clips = known_n + len(new_at)
+    clips = [synth.synthetic_reference_audio(k, 3.0) for k in range(n_clips)]
+    texts = [base[k % n].ref_text_ids for k in range(n_clips)]
+    kw = dict(temperature=0.9, top_k=50, top_p=1.0, repetition_penalty=1.5, seed=1234)
+    if args.stream:
+        c, w, l = (int(x) for x in args.stream.split(","))
+        kw.update(audio_chunk_frames=c, audio_window_frames=w, audio_lookahead_frames=l, audio_stream_reference=1)
+    first_kind = "audio_chunk" if args.stream else "audio"
+    rate = float(args.arrivals)
+    gaps = np.random.default_rng(4321).exponential(1.0 / rate, size=n) if np.isfinite(rate) else np.zeros(n)
+    req = lambda i, v, cap=None: GenerationRequest(base[i].text_ids, 100, None, None, base[i].language, int(caps[i] if cap is None else cap), voice=v)
+    same = lambda a, b: all(x.status == y.status and np.array_equal(x.codes, y.codes) and np.array_equal(x.audio, y.audio) for x, y in zip(a, b))
+    ref = {"max": 0}  # the longest reference in frames (known once the closed form's voices exist)
+
+    def serve(live):
+        first, spans, lock = {}, [], threading.Lock()
+
+        def on_event(i, kind, payload):
+            if kind == first_kind:
+                first.setdefault(i, time.perf_counter())
+
+        voices = [model.create_voice(clips[k], texts[k]) for k in range(known_n if live else n_clips)]
+        front_new = 0.0  # (the known clips' voices exist before the service starts, either way)
+        if not live:  # the new clips' share of the time in front: measured on its own
+            t1 = time.perf_counter()
+            for v in [model.create_voice(clips[k], texts[k]) for k in range(known_n, n_clips)]:
+                v.close()
+            front_new = time.perf_counter() - t1
+        s = model.open_session(slots=args.slots, max_pending=n, max_ref_frames=ref["max"], on_event=on_event,
+                               live_voices=args.live_voices if live else 0, max_voices=(n_clips if live else 0), **kw)
+        arrive, watchers, made = {}, [], []
+        try:
+            t0 = time.perf_counter()
+            due = t0
+            for i in range(n):
+                due += gaps[i]
+                while time.perf_counter() < due:
+                    time.sleep(min(max(due - time.perf_counter(), 0), 0.002))
+                arrive[i] = time.perf_counter()
+                if i in clip_of and live:
+                    while True:
+                        try:
+                            v = s.create_voice(clips[clip_of[i]], texts[clip_of[i]])
+                            break
+                        except Exception as e:  # BUSY: live_voices jobs in flight
+                            if getattr(e, "status", 0) != 9:
+                                raise
+                            time.sleep(0.001)
+                    made.append(v)
+
+                    def watch(v=v, t=arrive[i]):
+                        v.wait(timeout=600)
+                        with lock:
+                            spans.append((t, time.perf_counter()))
+
+                    watchers.append(threading.Thread(target=watch))
+                    watchers[-1].start()
+                else:
+                    v = voices[clip_of[i]] if i in clip_of else voices[i % known_n]
+                assert s.submit(req(i, v)) == i
+            out = [s.result(i, timeout=600) for i in range(n)]
+            dt = time.perf_counter() - t0
+            for th in watchers:
+                th.join()
+            st, vs = s.stats(), (s.voice_stats() if live else None)
+            s.close()
+        finally:
+            s.close(drain=False)
+        for v in voices + made:
+            v.close()
+        lat = np.asarray([first[i] - arrive[i] + front_new for i in new_at if i in first])
+        beside = None
+        if live and vs.burst_ms_beside > 0 and vs.burst_ms_alone > 0:  # the loop thread's own burst times
+            ready = np.asarray([b - a for a, b in spans])
+            beside = (vs.frame_steps_beside / vs.burst_ms_beside * 1e3, (st.frame_steps - vs.frame_steps_beside) / vs.burst_ms_alone * 1e3,
+                      vs.burst_ms_beside, ready)
+        wall = dt + front_new
+        return out, wall, lat, vs, beside
+
+    print(f"# {args.preset} bf16, {n} voice requests, slots {args.slots}, arrivals {args.arrivals}/s, "
+          f"{'--stream ' + args.stream if args.stream else 'whole audio'}, every {every}th arrival a new 3 s clip "
+          f"({len(new_at)} of them), live_voices {args.live_voices}", flush=True)
+    # the closed form: voices made by create_voice, one generate_queued call
+    voices = [model.create_voice(clips[k], texts[k]) for k in range(n_clips)]
+    ref["max"] = max(v.info.ref_frames for v in voices)
+    model.generate_queued([req(i, voices[i % known_n], 8) for i in range(2 * args.slots)], slots=args.slots, **kw)  # warm-up
+    closed = model.generate_queued([req(i, voices[clip_of.get(i, i % known_n)]) for i in range(n)], slots=args.slots, **kw)
+    for v in voices:
+        v.close()
+    for rep_i in range(args.repeat):
+        for name, live in (("live", True), ("before", False)):
+            out, wall, lat, vs, beside = serve(live)
+            frames = sum(int(r.codes.shape[0]) for r in out)
+            print(f"run {rep_i} {name:6s} frames {frames:7d}  wall {wall:8.3f} s  frames/s {frames / wall:9.1f}  "
+                  f"new clip -> first {first_kind.upper()}: {_pct(lat)}  failed {sum(1 for r in out if r.status != 0)}  "
+                  f"bit-identical to the closed form: {same(out, closed)}", flush=True)
+            if vs is not None:
+                print(f"run {rep_i} {name:6s} frontend_ms_sum {vs.frontend_ms_sum:8.1f} ms over {vs.created} voices  frame_steps_beside "
+                      f"{vs.frame_steps_beside}", flush=True)
+            if beside is not None:
+                print(f"run {rep_i} {name:6s} frame steps/s in bursts with a job in flight {beside[0]:8.1f} (over {beside[2]:7.1f} ms)   "
+                      f"in the others {beside[1]:8.1f}   ratio {beside[0] / beside[1]:.3f}   create_voice -> ready: {_pct(beside[3])}", flush=True)
+
+
 def run_voices(model, args):
     """The ragged workload as voice-clone requests: static ref_audio batches against the queue with voices."""
     from qwen3tts import GenerationRequest, synth
@@ -396,6 +520,9 @@ def main():
     ap.add_argument("--arrivals", default="inf", metavar="RATE", help="--session: requests per second, exponential gaps; inf: all at once")
     ap.add_argument("--text-rate", default=None, metavar="TOK_PER_S",
                     help="--session: every request's content arrives at this rate; open-text requests against whole submits")
+    ap.add_argument("--live-voices", type=int, default=0, metavar="K",
+                    help="--session on a Base checkpoint: a session with K front-end lanes against voices created before open")
+    ap.add_argument("--new-voice-every", type=int, default=8, metavar="N", help="--live-voices: every N-th arrival brings a new clip")
     ap.add_argument("--output-sample-rate", type=int, default=0, metavar="R",
                     help="load the model with q3tts_load_opts.output_sample_rate = R (0: the decoder's own 24000)")
     ap.add_argument("--speed", type=float, default=0.0, metavar="S",
@@ -422,6 +549,11 @@ def main():
         rate_kw["request_speeds"] = True
 
     ckpt = bench.ensure_checkpoint(args.preset, 0, None)
+    if args.session and args.live_voices > 0:
+        model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=192, **rate_kw)
+        run_live_voices(model, args)
+        model.close()
+        return
     if args.voices > 0:  # (an ICL prompt carries the reference text and one row per reference frame: 3 s are 38 frames)
         model = Qwen3TTSModel.from_pretrained(ckpt, max_batch=args.slots, max_frames=408, max_prompt=192, **rate_kw)
         run_voices(model, args)
